@@ -60,7 +60,8 @@ bin/demodMulti: $(PKG)/host/demod_multi.c include/pdt.h include/pdt_gather.h $(L
 	mkdir -p bin
 	$(CC) $(CFLAGS) -Iinclude -o $@ $(PKG)/host/demod_multi.c -L$(CSRC) -lpdtgather -lpdt -lpthread -Wl,-rpath,'$$ORIGIN/../$(CSRC)'
 
-oracle:
+# (after the compat libraries: oracle/Makefile decides at start-up whether to link its compat_demod* drivers against them)
+oracle: $(LIBCOMPAT)
 	$(MAKE) -C oracle
 
 clean:

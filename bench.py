@@ -24,13 +24,25 @@ time stamps) over one capture that is ALREADY RESIDENT IN HBM when the timed reg
 rank demodulates its own independent capture (different seed): weak scaling, no data-path collective; the decoded frame
 records are gathered on rank 0 with one padded all_gather (RCCL) after the timed region and checked there.
 
+A plain run (no ``--full``) does only what the headline needs: it generates the capture into HBM, runs W warm-up and K timed
+steps, writes the outputs of the last timed step when ``--dump-outputs DIR`` is given, and prints the line with the figures
+of the timed steps themselves (``roofline``, ``stages``, ``fir_pll_stage``).  ``--full`` adds every other leg -- the
+transmitted-frame check, ``e2e`` / ``e2e_multi`` / ``e2e_cli``, the CPU baselines and their parity checks, the batched mode's
+per-slot CPU check and the ``secondary`` workloads -- and exits 1 on a parity failure, as before.
+
+``--dump-outputs DIR`` (see dump_outputs): the frame records and the result statistics the timed path hands its caller after
+its last step, as DIR/<name>.npy in float32 / float64 (at most 64 MB: a fixed, seeded sample of the frames beyond that).  The
+captures are pure functions of (workload, seconds, seed), so two builds run with the same arguments can be compared output
+for output.
+
 The JSON line carries, besides the contract keys:
   roofline     the kernel group that dominates the step: algorithmic bytes / live HIP-event duration (libpdt's profile
                mode, events on the stream the kernels run on) against 8 TB/s; ``traffic`` from the committed rocprofv3
                counter passes, printed only when that file was measured with the build that is running (``build`` tags)
   stages       every kernel group: ms per step, algorithmic bytes per step, GB/s, fraction of 8 TB/s
   fir_pll_stage  the north star's stage figure: 4 B in + 4 * interp B out per sample over the PLL + FIR critical path
-  parity       what was compared with what in THIS run (a failure is fatal: exit code 1, no JSON line)
+  parity       what was compared with what in THIS run (a failure is fatal: exit code 1, no JSON line); empty without --full
+  (--full only, below)
   e2e          what the reference program does, timed: open the WAV (tmpfs) -> header -> pdt_demod_fd (threaded read into
                pinned memory, copy to HBM, all kernels, frame records back) -> text -> output file written and closed
   e2e_cli      wall time of the C host program bin/demodPOES|demodARGOS on the same file (process start and HIP
@@ -427,6 +439,50 @@ def cpu_baseline(kind: int, wavs: list[str], n_sample: int, tmp: str):
     return dsp, max(walls), texts, what
 
 
+DUMP_LIMIT = 64 << 20                  # bytes of array data that --dump-outputs writes at most
+DUMP_SEED = 20261016                   # the seed of the frame sample when every frame would not fit
+STATS_DUMPED = ("samples", "out_samples", "symbols", "bits", "frames", "lock_sample", "lock_freq_hz", "norm_factor", "avg_phase")
+
+
+def dump_outputs(path: str, captures, limit: int = DUMP_LIMIT) -> dict:
+    """--dump-outputs: what the timed path hands its caller after its last step, as path/<name>.npy.
+
+    `captures` is a list of (capture index, frame records as pdt.FRAME_DTYPE, pdt.Stats or None); the index is the one the
+    capture's seed is made from (1234 + index).  Files, one row per frame, captures in the order given:
+      frames_capture, frames_time, frames_bit_index, frames_time_src  float64 (rows,)
+      frames_inverted, frames_nbytes, frames_complete                  float32 (rows,)
+      frames_bytes                                                     float32 (rows, 104)
+      stats   float64 (captures with statistics, 1 + len(STATS_DUMPED)): the capture index, then STATS_DUMPED (timings left out)
+    Every frame when they fit in `limit` bytes, otherwise a fixed, seeded sample of them (rows kept in order).
+    Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    frames = [f for _, f, _ in captures]
+    allf = np.concatenate(frames) if frames else np.zeros(0)
+    cap = np.concatenate([np.full(len(f), float(i)) for i, f, _ in captures]) if frames else np.zeros(0)
+    stats = np.array([[float(i)] + [float(getattr(s, k)) for k in STATS_DUMPED] for i, _, s in captures if s is not None],
+                     dtype=np.float64).reshape(-1, 1 + len(STATS_DUMPED))
+    nb = len(allf["bytes"][0]) if len(allf) else 104
+    row = 4 * 8 + 3 * 4 + nb * 4                                        # bytes per frame: 4 float64, 3 + nb float32
+    keep = max(0, (limit - stats.nbytes) // row)
+    if len(allf) > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(allf), size=keep, replace=False))
+        allf, cap = allf[rows], cap[rows]
+    out = {"frames_capture": cap.astype(np.float64)}
+    if len(allf):
+        out.update({"frames_time": allf["time"].astype(np.float64), "frames_bit_index": allf["bit_index"].astype(np.float64),
+                    "frames_time_src": allf["time_src"].astype(np.float64),
+                    "frames_inverted": allf["inverted"].astype(np.float32), "frames_nbytes": allf["nbytes"].astype(np.float32),
+                    "frames_complete": allf["complete"].astype(np.float32), "frames_bytes": allf["bytes"].astype(np.float32)})
+    else:
+        out.update({k: np.zeros(0, np.float64) for k in ("frames_time", "frames_bit_index", "frames_time_src")})
+        out.update({k: np.zeros(0, np.float32) for k in ("frames_inverted", "frames_nbytes", "frames_complete")})
+        out["frames_bytes"] = np.zeros((0, nb), np.float32)
+    out["stats"] = stats
+    for k, a in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    return {k: list(a.shape) for k, a in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -441,7 +497,14 @@ def main():
     ap.add_argument("--captures", type=int, default=1,
                     help="captures demodulated together per GPU and step through pdt_demod_batch_device (default 1 = the "
                          "BASELINE workload; >1 is the batched many-capture mode, reported as such)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the transmitted-frame check, the end-to-end and CLI legs, the CPU "
+                         "baselines with their parity checks and (default workload, N = 1) the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame records and result statistics of the last timed step to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args.gpus)                                # does not return
@@ -478,14 +541,15 @@ def main():
         cpu_seconds = min(cpu_seconds, seconds)
     mode = 1 if kind else 0
     dt_name, fbytes = ("double", 8) if kind else ("float", 4)
-    legs = (not args.no_cpu) and world == 1 and args.captures == 1       # e2e / CLI / CPU legs belong to the N = 1 line
+    legs = args.full and (not args.no_cpu) and world == 1 and args.captures == 1     # e2e / CLI / CPU legs belong to the N = 1 line
 
     pdt = importlib.import_module("project-desert-tortoise_amd")
     build_tag = pdt.build_tag()
     n = int(round(seconds * fs))
     threads = max(1, min(32, (os.cpu_count() or 8) // max(1, world)))
     shm = "/dev/shm" if os.path.isdir("/dev/shm") else None
-    tmp = tempfile.mkdtemp(dir=shm, prefix="pdt_bench_") if ((legs or (args.captures > 1 and not args.no_cpu and world == 1)) and rank == 0) else None
+    batch_check = args.full and args.captures > 1 and not args.no_cpu and world == 1
+    tmp = tempfile.mkdtemp(dir=shm, prefix="pdt_bench_") if ((legs or batch_check) and rank == 0) else None
     try:
         run(args, pdt, torch, dist, rank, local, world, dev, cdev, cfg, kind, fs, seconds, cpu_seconds, baseline_cfg, mode, dt_name,
             fbytes, legs, build_tag, n, threads, tmp)
@@ -543,11 +607,17 @@ def run(args, pdt, torch, dist, rank, local, world, dev, cdev, cfg, kind, fs, se
     frames = dm.frames_array()
     gpu_text = dm.text()
     gathered = gather_frames(frames, cdev) if world > 1 else [frames]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results: every rank's capture (slot 0, gathered) and this rank's other slots of a batch
+        caps = [(r * ncap, gathered[r], st if r == 0 else None) for r in range(world)]
+        caps += [(i, d.frames_array(), d.stats()) for i, d in enumerate(extra, start=1)]
+        dumped = dump_outputs(args.dump_outputs, caps)
     # ---- BASELINE's metric at N GPUs: N capture files through the product launcher (bin/demodMulti), gather inside the clock
     multi = None
     multi_same = None
     exe_multi = os.path.join(ROOT, "bin", "demodMulti")
-    if not args.no_cpu and ncap == 1 and kind == 0 and os.path.exists(exe_multi) and not args.e2e_only:
+    if args.full and not args.no_cpu and ncap == 1 and kind == 0 and os.path.exists(exe_multi) and not args.e2e_only:
         mdir = None
         if rank == 0:
             mdir = tmp if tmp else tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None, prefix="pdt_bench_m_")
@@ -636,7 +706,7 @@ def run(args, pdt, torch, dist, rank, local, world, dev, cdev, cfg, kind, fs, se
             "value_is": f"the bench contract's `value`: the whole hot path over a {cfg} capture ALREADY RESIDENT IN HBM when the timed "
                         "region starts (capture -> minor-frame records, K timed steps); the PCIe-inclusive figure the metric's name "
                         "describes -- WAV file on tmpfs -> minorframes file closed -- is `value_e2e` / `ms_e2e` in this same line "
-                        "(N = 1), and the C host program from process start is `e2e_cli`",
+                        "(N = 1, --full), and the C host program from process start is `e2e_cli`",
             "value": round(value, 3),
             "unit": "Msamples/s",
             "n_gpus": world,
@@ -681,7 +751,10 @@ def run(args, pdt, torch, dist, rank, local, world, dev, cdev, cfg, kind, fs, se
             "pll_seam_fixes": int(st.pll_seam_fixes), "agc_seam_fixes": int(st.agc_seam_fixes),
             "gardner_walked": int(st.gardner_walked), "gardner_candidates": int(st.gardner_candidates),
             "lock_sample": int(st.lock_sample),
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if multi is not None:
             # the figure BASELINE.json's metric names, at this N: files -> frame files through bin/demodMulti, RCCL gather inside
             out["e2e_multi"] = multi
@@ -694,7 +767,7 @@ def run(args, pdt, torch, dist, rank, local, world, dev, cdev, cfg, kind, fs, se
         # ---- full size, every rank: the decoded frames are the transmitted ones (POES; a size-independent property)
         # (a weak signal loses frames, and at 18.75 ksps -- 1.13 samples per Manchester symbol -- the reference itself decodes two
         # frames in three with bit errors once the symbol clock has drifted against the sampling grid: the CPU sample is their gate)
-        if kind == 0 and CONFIGS[cfg]["noise_x"] == 1.0 and not CONFIGS[cfg]["env_floor"] and fs >= 50000:
+        if args.full and kind == 0 and CONFIGS[cfg]["noise_x"] == 1.0 and not CONFIGS[cfg]["env_floor"] and fs >= 50000:
             tx = [transmitted_check(pdt, capture_params(pdt, cfg, 1234 + r, seconds), gathered[r], n, fs) for r in range(world)]
             parity["frames_equal_transmitted_full_size"] = [t["ok"] for t in tx]
             parity["frames_complete_matched_expected"] = [[t["complete"], t["matched"], t["expected_about"]] for t in tx]
@@ -838,7 +911,8 @@ def run(args, pdt, torch, dist, rank, local, world, dev, cdev, cfg, kind, fs, se
                                 ("i8", ["--config", "i8", "--steps", "5", "--warmup", "2", "--no-cpu"]),
                                 ("argos_x64", ["--config", "argos", "--captures", "64", "--steps", "3", "--warmup", "1", "--no-cpu"])):
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-secondary"] + extra, capture_output=True, text=True, timeout=900)
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-secondary"] + extra, capture_output=True, text=True,
+                                       timeout=900)
                     ref = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                     out["secondary"][name] = {k: ref.get(k) for k in ("value", "unit", "ms_per_step", "dtype", "roofline", "fir_pll_stage",
                                                                        "e2e", "e2e_cli", "value_e2e", "ms_e2e", "cpu_baseline", "parity")}

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -26,7 +27,7 @@ def run_bench(*args, env=None, timeout=900):
 
 
 def test_default_workload_shortened_one_gpu():
-    d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--seconds", "40", "--no-secondary")
+    d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--seconds", "40", "--full", "--no-secondary")
     for k in CONTRACT + ["cpu_baseline", "e2e", "parity"]:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["config"]["workload"].startswith("c3 = BASELINE configs[2]")
@@ -45,11 +46,33 @@ def test_default_workload_shortened_one_gpu():
     assert set(d["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
 
 
+def test_plain_run_is_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line holds the contract keys and the figures of the timed steps, none of the legs beside them;
+    --dump-outputs writes the last timed step's frame records and statistics, and a second run with the same arguments writes
+    the same arrays."""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--seconds", "20"]
+    d = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    for k in CONTRACT + ["stages", "fir_pll_stage", "dump_outputs"]:
+        assert k in d, k
+    assert d["steps"] == 3 and d["full"] is False and d["parity"] == {}
+    for k in ("e2e", "e2e_multi", "e2e_cli", "value_e2e", "cpu_baseline", "secondary"):
+        assert k not in d, k
+    run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "frames_bytes.npy" in names and "stats.npy" in names
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and a.tobytes() == b.tobytes(), name
+    fb = np.load(tmp_path / "a" / "frames_bytes.npy")
+    assert fb.shape == (d["frames_per_capture"][0], 104) and fb.shape[0] > 100
+    assert np.load(tmp_path / "a" / "stats.npy")[0, 6] == d["lock_sample"]
+
+
 @pytest.mark.parametrize("cfg", ["aos", "weak"])
 def test_prelock_and_weak_signal_workloads(cfg):
     """The captures the reference meets at both ends of a pass: a minute of noise before the signal rises (the PLL sweeps,
     CarrierTrackingPLL.c:232-246, then its one-time lock), and a low signal-to-noise ratio -- same parity gate."""
-    d = run_bench("--config", cfg, "--steps", "1", "--warmup", "1", "--seconds", "90", "--no-secondary")
+    d = run_bench("--config", cfg, "--steps", "1", "--warmup", "1", "--seconds", "90", "--full", "--no-secondary")
     assert d["parity"]["sample_text_equals_cpu_baseline"] is True
     if cfg == "aos":
         assert d["lock_sample"] >= 60 * 250000
@@ -58,7 +81,7 @@ def test_prelock_and_weak_signal_workloads(cfg):
 def test_two_ranks_share_one_gpu_dry_run():
     """The multi-rank code path (barriers, max over ranks, ragged gather, per-rank check) with the collectives on gloo:
     two ranks, both on GPU 0."""
-    d = run_bench("--gpus", "2", "--steps", "1", "--warmup", "1", "--seconds", "30", env={"PDT_BENCH_BACKEND": "gloo"})
+    d = run_bench("--gpus", "2", "--steps", "1", "--warmup", "1", "--seconds", "30", "--full", env={"PDT_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and len(d["per_rank_ms"]) == 2 and len(d["frames_per_capture"]) == 2
     assert d["parity"]["frames_equal_transmitted_full_size"] == [True, True]
     assert d["parity"]["gathered_rank0_equals_own"] is True
@@ -77,7 +100,7 @@ def test_multi_gpu_bench_over_rccl():
     n = n_gpus()
     if n < 2:
         pytest.skip("one GPU on this box: RCCL with more than one rank cannot run here")
-    d = run_bench("--gpus", str(n), "--steps", "2", "--warmup", "1", "--seconds", "60")
+    d = run_bench("--gpus", str(n), "--steps", "2", "--warmup", "1", "--seconds", "60", "--full")
     assert d["n_gpus"] == n and len(d["per_rank_ms"]) == n
     assert d["parity"]["frames_equal_transmitted_full_size"] == [True] * n
 

@@ -15,15 +15,15 @@ timeout -s ABRT 1500 python -X faulthandler tests/tools/fuzz.py 300 $SEED > $OUT
 timeout -s ABRT 900 python -X faulthandler tests/tools/fuzz_live.py 200 $((SEED + 100)) > $OUT/logs/fuzz_live_200_seed$((SEED + 100)).log 2>&1; tail -1 $OUT/logs/fuzz_live_200_seed$((SEED + 100)).log
 timeout -s ABRT 900 python -X faulthandler tests/tools/fuzz_segments.py 60 $((SEED + 200)) > $OUT/logs/fuzz_segments_60_seed$((SEED + 200)).log 2>&1; tail -1 $OUT/logs/fuzz_segments_60_seed$((SEED + 200)).log
 timeout -s ABRT 900 python -X faulthandler tests/tools/fuzz_quality.py 100 $((SEED + 300)) > $OUT/logs/fuzz_quality_100_seed$((SEED + 300)).log 2>&1; tail -1 $OUT/logs/fuzz_quality_100_seed$((SEED + 300)).log
-( time timeout 1800 python bench.py --gpus 1 ) > $OUT/bench_default_1gpu.json 2> $OUT/logs/bench_default.err; tail -2 $OUT/logs/bench_default.err | cut -c1-300
+( time timeout 1800 python bench.py --gpus 1 --full ) > $OUT/bench_default_1gpu.json 2> $OUT/logs/bench_default.err; tail -2 $OUT/logs/bench_default.err | cut -c1-300
 for cfg in c2 argos aos weak pass i8 c2h; do
-  timeout 900 python bench.py --config $cfg --steps 5 --warmup 2 --no-secondary > $OUT/bench_${cfg}_1gpu.json 2> $OUT/logs/bench_$cfg.err; echo "$cfg rc=$?"
+  timeout 900 python bench.py --config $cfg --steps 5 --warmup 2 --full --no-secondary > $OUT/bench_${cfg}_1gpu.json 2> $OUT/logs/bench_$cfg.err; echo "$cfg rc=$?"
 done
-timeout 600 python bench.py --config c2 --steps 6 --warmup 2 --captures 8 --no-secondary > $OUT/bench_c2_batch8_1gpu.json 2>> $OUT/logs/bench_c2.err
+timeout 600 python bench.py --config c2 --steps 6 --warmup 2 --captures 8 --full --no-secondary > $OUT/bench_c2_batch8_1gpu.json 2>> $OUT/logs/bench_c2.err
 for nc in 32 64; do
-  timeout 900 python bench.py --config argos --captures $nc --steps 5 --warmup 2 --no-secondary > $OUT/bench_argos_batch${nc}_1gpu.json 2> $OUT/logs/bench_argos_batch$nc.err; echo "argos x$nc rc=$?"
+  timeout 900 python bench.py --config argos --captures $nc --steps 5 --warmup 2 --full --no-secondary > $OUT/bench_argos_batch${nc}_1gpu.json 2> $OUT/logs/bench_argos_batch$nc.err; echo "argos x$nc rc=$?"
 done
-timeout 900 python bench.py --config pass --captures 16 --steps 2 --warmup 1 --no-secondary > $OUT/bench_pass_batch16_1gpu.json 2> $OUT/logs/bench_pass_batch16.err; echo "pass x16 rc=$?"
+timeout 900 python bench.py --config pass --captures 16 --steps 2 --warmup 1 --full --no-secondary > $OUT/bench_pass_batch16_1gpu.json 2> $OUT/logs/bench_pass_batch16.err; echo "pass x16 rc=$?"
 timeout 600 python tools/span_hist.py c3 2>&1 | grep -v amdgpu.ids > $OUT/gardner_row_exits_c3.txt
 timeout 600 python tools/span_hist.py c2h 2>&1 | grep -v amdgpu.ids > $OUT/gardner_row_exits_c2h.txt
 bash tools/jobs/cli_cold.sh > /dev/null 2>&1; cp gpurun_out/cli/cli_cold.txt $OUT/cli_cold.txt 2>/dev/null

@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4 (round 6): a capture that does not fit the device's free memory is demodulated through a bounded window (the streaming
+/* 4, additions without a bump (round 7): single-channel (real) captures through a Hilbert front end -- the sample formats
+ * PDT_FMT_REAL_PCM16 / PDT_FMT_REAL_F32, the stage PDT_ST_ANALYTIC, pdt_set_real_input, pdt_demod_real, pdt_demod_device_real,
+ * pdt_stream_push_real, pdt_host_analytic; pdt_demod_fd / pdt_demod_file accept the two real formats.
+ * 4 (round 6): a capture that does not fit the device's free memory is demodulated through a bounded window (the streaming
  * path, fed from the file or the caller's memory piece by piece) instead of failing with PDT_ERR_NOMEM -- the reference's chunk
  * loop needs O(chunk) memory whatever the file's length (POESTIPdemod/main.c:373); pdt_stats.segments / .windowed say how a
  * capture was taken; pdt_loop_params.zero_mask; a context whose caller asked for the PLL stream (pdt_keep_pll(ctx, 1)) is
@@ -100,11 +103,14 @@ enum {
     PDT_ST_BITSYM,      /* global symbol index each bit's time stamp comes from, uint32         */
     PDT_ST_AGC_RAW,     /* NormalizingAGC output BEFORE Squelch (only after pdt_keep_presquelch): what ARGOSdemod -r
                            writes to output.raw (ARGOSdemod/main.c:273-274); equal to PDT_ST_AGC for POES     */
+    PDT_ST_ANALYTIC,    /* real captures only: the analytic stream the chain demodulated, float32 I,Q per input sample
+                           (pdt_demod_real / pdt_demod_device_real / pdt_demod_fd of a real format in one piece); 0 otherwise */
     PDT_ST_COUNT
 };
 
 enum { PDT_CHAIN_FILE = 0, PDT_CHAIN_LIVE = 1 };
 enum { PDT_FMT_PCM16 = 0, PDT_FMT_F32 = 1 };   /* interleaved little-endian int16 I,Q pairs / IEEE float32 I,Q pairs */
+enum { PDT_FMT_REAL_PCM16 = 2, PDT_FMT_REAL_F32 = 3 };   /* single channel: one little-endian int16 / float32 sample per frame */
 
 typedef struct pdt_config {
     int32_t  mode;            /* PDT_MODE_POES / PDT_MODE_ARGOS                                   */
@@ -295,6 +301,7 @@ int  pdt_demod_pcm16(pdt_ctx *ctx, const int16_t *iq_host, uint64_t nframes);
  * exceed the device's free memory, the capture goes through a bounded window instead (pieces of the file pushed through the
  * streaming path with carried state: same frames, text, counts and reports; pdt_stats.windowed = 1).  The reference's loop
  * takes a file of any length (POESTIPdemod/main.c:373, while(!feof)); so do pdt_demod_fd / _file / _pcm16 / _f32.            */
+/* sample_format PDT_FMT_REAL_PCM16 / _F32 (2 / 4 bytes per frame): a single-channel capture (pdt_demod_real below).         */
 int  pdt_demod_fd(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, int sample_format);
 /* The whole job of POESTIPdemod/main.c:373-492 / ARGOSdemod/main.c:250-306 in one call: capture file in (as pdt_demod_fd), the
  * minor-frame / packet text out to the descriptor text_fd, from its position on -- the reference's ByteSync.c:62-101 writes
@@ -346,6 +353,31 @@ int      pdt_stream_push_f32(pdt_ctx *ctx, const float *iq_host, uint64_t nframe
 int      pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames);
 uint64_t pdt_stream_frames(const pdt_ctx *ctx, pdt_frame *out, uint64_t max_frames);
 uint64_t pdt_stream_retained(const pdt_ctx *ctx);
+
+/* Single-channel (real) captures: SatNOGS audio, an SDR in USB mode, a sound card with one input.  A real capture x[n] at
+ * the context's sample rate becomes one float32 I,Q pair per sample on the GPU -- z[n] = (x[n] + j H{x}[n]) e^{-j 2 pi p[n] / 2^32},
+ * H a 63-tap Blackman-windowed Hilbert transformer (centred, no delay; x = 0 outside the capture), p[n] = step n mod 2^32 on the
+ * global sample index, step = round(centre 2^32 / Fs) -- and the chain demodulates that stream exactly as it would a RAW float
+ * capture of the same length (POES: pdt_demod_f32, StaticGain of the first chunk included; ARGOS: the double chain reading the
+ * float pairs).  Int16 samples are s / 32768, float32 samples are used as they are.  The arithmetic is fixed:
+ * pdt_host_analytic restates it bit for bit on the host.
+ *   pdt_set_real_input     the centre frequency the real captures of this context are mixed down from: 0 < centre_hz < Fs / 2,
+ *                          0 = Fs / 4 (also the default); PDT_ERR_ARG otherwise, PDT_ERR_STATE while a stream is open
+ *   pdt_demod_real         a whole real capture in host memory, n samples of sample_format (PDT_FMT_REAL_PCM16 / _F32, else
+ *                          PDT_ERR_ARG); results through pdt_frames / pdt_get_stats / pdt_format_frames / pdt_read_stage
+ *                          (PDT_ST_ANALYTIC = the converted stream), reports and progress as for I,Q captures.  One that does not
+ *                          fit the device goes through the bounded window (pdt_stats.windowed); never in overlapped segments
+ *   pdt_demod_device_real  the same with the samples resident in device memory (only read)
+ *   pdt_stream_push_real   append n real samples to the open stream: the last 31 samples are held back until their right-hand
+ *                          neighbours arrive (pdt_stream_end closes them with zeros; pdt_stream_retained counts them); the frames
+ *                          of the pushes and of the end are those of one pdt_demod_real call.  A stream takes real pushes of one
+ *                          format or I,Q pushes: mixing them returns PDT_ERR_ARG
+ *   pdt_host_analytic      test hook, host only: out[2 n], out[2 n + 1] = the I,Q pair of sample n, as the kernel computes it   */
+int  pdt_set_real_input(pdt_ctx *ctx, double center_hz);
+int  pdt_demod_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format);
+int  pdt_demod_device_real(pdt_ctx *ctx, const void *x_device, uint64_t n, int sample_format);
+int  pdt_stream_push_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format, uint64_t *new_frames);
+int  pdt_host_analytic(uint32_t sample_rate, double center_hz, const void *x, uint64_t n, int sample_format, float *out);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

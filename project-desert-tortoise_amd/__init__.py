@@ -30,7 +30,8 @@ LIBSYNTH_PATH = os.path.join(_HERE, "synth", "libpdtsynth.so")
 MODE_POES, MODE_ARGOS = 0, 1
 SAMPLER_GARDNER, SAMPLER_MM = 0, 1
 CHAIN_FILE, CHAIN_LIVE = 0, 1          # CHAIN_LIVE: the sound-card twin's constants and stage order (POES)
-ST_PLL, ST_LOCK, ST_FIR, ST_AGC, ST_SYM, ST_SYMIDX, ST_BITS, ST_BITSYM, ST_AGC_RAW = range(9)
+ST_PLL, ST_LOCK, ST_FIR, ST_AGC, ST_SYM, ST_SYMIDX, ST_BITS, ST_BITSYM, ST_AGC_RAW, ST_ANALYTIC = range(10)
+FMT_PCM16, FMT_F32, FMT_REAL_PCM16, FMT_REAL_F32 = range(4)    # I,Q int16 / I,Q float32 / one int16 / one float32 per frame
 
 
 class PdtError(RuntimeError):
@@ -170,6 +171,7 @@ ABI_SYMBOLS = [
     "pdt_keep_quality", "pdt_chunk_reports", "pdt_stage_manchester", "pdt_stage_fir", "pdt_stage_agc", "pdt_stage_squelch", "pdt_stage_pll", "pdt_stage_gardner", "pdt_stage_static_gain", "pdt_stage_mm",
     "pdt_keep_presquelch", "pdt_keep_pll", "pdt_stage_bytesync_from", "pdt_demod_fd", "pdt_format_records", "pdt_stream_retained", "pdt_host_math", "pdt_get_device",
     "pdt_write_frames", "pdt_write_records", "pdt_demod_file", "pdt_set_loop_params", "pdt_set_progress",
+    "pdt_set_real_input", "pdt_demod_real", "pdt_demod_device_real", "pdt_stream_push_real", "pdt_host_analytic",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows"]        # include/pdt_dev.h (test-only)
 
@@ -288,6 +290,11 @@ def lib():
     L.pdt_dev_set.argtypes = [C.c_char_p, C.c_char_p]
     L.pdt_set_loop_params.argtypes = [C.c_void_p, C.POINTER(LoopParams)]
     L.pdt_demod_file.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+    L.pdt_set_real_input.argtypes = [C.c_void_p, C.c_double]
+    L.pdt_demod_real.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+    L.pdt_demod_device_real.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+    L.pdt_stream_push_real.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    L.pdt_host_analytic.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
     if L.pdt_abi_version() != 4:
         raise PdtError("libpdt.so ABI version mismatch")
     _lib = L
@@ -321,6 +328,23 @@ def host_math(fn: int, x: np.ndarray):
     o0, o1 = np.zeros(n), np.zeros(n)
     _check(lib().pdt_host_math(fn, a.ctypes.data, n, o0.ctypes.data, o1.ctypes.data), "pdt_host_math")
     return o0, o1
+
+
+def _real_samples(x: np.ndarray) -> tuple[np.ndarray, int]:
+    """A single-channel capture as the library takes it: float arrays as little-endian float32 (FMT_REAL_F32), anything else
+    as little-endian int16 (FMT_REAL_PCM16)."""
+    if np.asarray(x).dtype.kind == "f":
+        return np.ascontiguousarray(x, dtype="<f4").reshape(-1), FMT_REAL_F32
+    return np.ascontiguousarray(x, dtype="<i2").reshape(-1), FMT_REAL_PCM16
+
+
+def host_analytic(sample_rate: int, center_hz: float, x: np.ndarray) -> np.ndarray:
+    """pdt_host_analytic: the Hilbert front end of real captures restated on the host (no GPU), bit for bit what the kernel
+    computes.  Returns float32[n, 2] I,Q pairs."""
+    a, fmt = _real_samples(x)
+    out = np.zeros((a.size, 2), dtype=np.float32)
+    _check(lib().pdt_host_analytic(sample_rate, float(center_hz), a.ctypes.data, a.size, fmt, out.ctypes.data), "pdt_host_analytic")
+    return out
 
 
 def time_axis(mode: int, sample_rate: int, m: int) -> float:
@@ -459,6 +483,22 @@ class Demodulator:
         """The capture straight from an open file (descriptor `fd`): nframes I,Q pairs from byte_offset (44 after the
         canonical WAV header, 0 for RAW); fmt 0 = int16 pairs, 1 = float32 pairs."""
         _check(self._L.pdt_demod_fd(self._h, fd, byte_offset, nframes, fmt), "pdt_demod_fd")
+        return self
+
+    def set_real_input(self, center_hz: float = 0.0):
+        """Centre frequency single-channel captures are mixed down from (0 = Fs / 4, the default)."""
+        _check(self._L.pdt_set_real_input(self._h, float(center_hz)), "pdt_set_real_input")
+        return self
+
+    def demod_real(self, x: np.ndarray):
+        """Single-channel capture in host memory: int16 samples (s / 32768) or float32 samples (as they are)."""
+        a, fmt = _real_samples(x)
+        _check(self._L.pdt_demod_real(self._h, a.ctypes.data, a.size, fmt), "pdt_demod_real")
+        return self
+
+    def demod_device_real(self, dev_ptr: int, n: int, fmt: int = FMT_REAL_PCM16):
+        """Single-channel capture resident in HBM (n samples of FMT_REAL_PCM16 / FMT_REAL_F32)."""
+        _check(self._L.pdt_demod_device_real(self._h, C.c_void_p(dev_ptr), n, fmt), "pdt_demod_device_real")
         return self
 
     def demod_device(self, dev_ptr: int, nframes: int):
@@ -606,6 +646,14 @@ class Demodulator:
         if count is None:
             count = max(total - first, 0)
         dt = {ST_SYMIDX: np.int64, ST_BITS: np.uint8, ST_BITSYM: np.uint32}.get(st, self.dtype)
+        if st == ST_ANALYTIC:
+            out = np.zeros((count, 2), dtype=np.float32)
+            if count:
+                got = self._L.pdt_read_stage(self._h, st, first, count, out.ctypes.data)
+                if got < 0:
+                    _check(int(got), "pdt_read_stage")
+                out = out[:got]
+            return out
         out = np.zeros(count, dtype=dt)
         if count:
             got = self._L.pdt_read_stage(self._h, st, first, count, out.ctypes.data)
@@ -634,6 +682,13 @@ class Demodulator:
         else:
             a = np.ascontiguousarray(iq, dtype="<i2").reshape(-1)
             _check(self._L.pdt_stream_push_pcm16(self._h, a.ctypes.data, a.size // 2, C.byref(n)), "pdt_stream_push_pcm16")
+        return self._stream_new(n.value)
+
+    def stream_push_real(self, x: np.ndarray) -> np.ndarray:
+        """Append single-channel samples (int16 or float32); returns the frames that became final with them."""
+        n = C.c_uint64(0)
+        a, fmt = _real_samples(x)
+        _check(self._L.pdt_stream_push_real(self._h, a.ctypes.data, a.size, fmt, C.byref(n)), "pdt_stream_push_real")
         return self._stream_new(n.value)
 
     def stream_end(self) -> np.ndarray:

@@ -1,6 +1,7 @@
 // pdt_api.hip -- libpdt.so: context management, kernel orchestration and the C ABI of
 // include/pdt.h.  Compiled for gfx950 only, with -ffp-contract=off (see pdt_device_math.h).
 #include "pdt_rt.h"
+#include "pdt_analytic.h"
 
 #include <pthread.h>
 #include <sched.h>
@@ -12,6 +13,9 @@ namespace pdtrt {
 PDT_CHAIN_INSTANCES(extern, float)
 PDT_CHAIN_INSTANCES(extern, double)
 std::atomic<long long> g_alloc_ns{0};
+// pdt_analytic.hip
+hipError_t analytic_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
+                           uint32_t step, const float *tab_dev, void *out);
 }  // namespace pdtrt
 
 static std::atomic<int> g_open_contexts{0};          // contexts alive in this process (pdt_open / pdt_close)
@@ -924,7 +928,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->hits, &ctx->frames, &ctx->taps, &ctx->mag, &ctx->seams_pll, &ctx->seams_agc, &ctx->scal, &ctx->lockinfo,
                        &ctx->term, &ctx->seams_ema, &ctx->gtable, &ctx->gentries, &ctx->gcand,
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
-                       &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo };
+                       &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->rbuf[0], &ctx->rbuf[1] };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1034,6 +1038,8 @@ static int demod_common(pdt_ctx *ctx, uint64_t nframes, int phase = RUN_ALL)
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     ctx->n_samples = nframes;
     ctx->n_out = nframes * ctx->interp;
+    ctx->stage_len[PDT_ST_ANALYTIC] = ctx->analytic_len;             // (a real capture's entry sets it just before; 0 otherwise)
+    ctx->analytic_len = 0;
     if (ctx->elem == 8) return run_capture<double>(ctx, nframes, phase);
     return run_capture<float>(ctx, nframes, phase);                 // POES, both twins
 }
@@ -1041,6 +1047,68 @@ static int demod_common(pdt_ctx *ctx, uint64_t nframes, int phase = RUN_ALL)
 static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes);
 static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes, uint64_t piece);
 static uint64_t stream_history(const pdt_ctx *ctx);
+static int demod_real_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt);
+
+// ---------------------------------------------------------------- real (single-channel) input (pdt_analytic.h)
+static bool real_fmt(int fmt) { return fmt == PDT_FMT_REAL_PCM16 || fmt == PDT_FMT_REAL_F32; }
+static size_t real_bytes(int fmt) { return fmt == PDT_FMT_REAL_PCM16 ? 2 : 4; }
+
+// the rotation table on the device (once per context)
+static int real_table(pdt_ctx *ctx)
+{
+    if (ctx->an_tab.p) return PDT_OK;
+    float tab[2 * AN_TAB];
+    analytic_table(tab);
+    int rc = ctx->an_tab.ensure(sizeof tab);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(ctx->an_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
+    return PDT_OK;
+}
+
+// x (device, n samples of fmt) -> analytic pairs, outputs [0, n) of a whole capture
+static int real_whole(pdt_ctx *ctx, const void *x, uint64_t n, int fmt, void *out)
+{
+    int rc = real_table(ctx);
+    if (rc) return rc;
+    HIP_TRY(analytic_launch(ctx->stream, fmt, x, 0, (long long)n, n, 0, ctx->real_step, (const float *)ctx->an_tab.p, out));
+    return PDT_OK;
+}
+
+// room for n more samples behind the ones a real stream keeps (rbuf[rcur] = rl converted | rp pending | new)
+static int real_reserve(pdt_ctx *ctx, uint64_t n)
+{
+    const size_t rb = real_bytes(ctx->stream_real);
+    return ctx->rbuf[ctx->rcur].ensure_keep((size_t)(ctx->rl + ctx->rp + n + 64) * rb, (size_t)(ctx->rl + ctx->rp) * rb);
+}
+
+// n_new samples have landed behind the kept ones: convert every sample whose right halo is there (all of them when the stream
+// ends: zeros beyond), append the pairs to the stream's window, keep the last 31 converted and the unconverted ones
+static int real_convert(pdt_ctx *ctx, uint64_t n_new, bool final_piece)
+{
+    int rc = real_table(ctx);
+    if (rc) return rc;
+    const size_t rb = real_bytes(ctx->stream_real);
+    const uint64_t avail = ctx->rp + n_new;
+    const uint64_t m = final_piece ? avail : (avail > (uint64_t)AN_HALF ? avail - AN_HALF : 0);
+    if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + m) + 64) * 8, (size_t)ctx->stream_have * 8))) return rc;
+    const unsigned char *x = (const unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)ctx->rl * rb;
+    HIP_TRY(analytic_launch(ctx->stream, ctx->stream_real, x, -(long long)ctx->rl, (long long)avail, m, ctx->real_done, ctx->real_step,
+                            (const float *)ctx->an_tab.p, (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * 8));
+    const uint64_t keep_left = std::min<uint64_t>(AN_HALF, ctx->rl + m), total = ctx->rl + avail, keep = keep_left + (avail - m);
+    if (keep && keep < total) {
+        DevBuf &dst = ctx->rbuf[ctx->rcur ^ 1];
+        if ((rc = dst.ensure((size_t)(keep + 64) * rb))) return rc;
+        HIP_TRY(hipMemcpyAsync(dst.p, (const unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)(total - keep) * rb, (size_t)keep * rb,
+                               hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->rcur ^= 1;
+    }
+    ctx->rl = keep_left;
+    ctx->rp = avail - m;
+    ctx->real_done += m;
+    ctx->stream_have += m;
+    ctx->stream_total += m;
+    return PDT_OK;
+}
 
 // Does a capture of nframes fit the device in one piece?  The reference's chunk loop takes a file of any length in O(chunk)
 // memory (POESTIPdemod/main.c:373, while(!feof)); the one-piece path here keeps every stage's stream of the whole capture
@@ -1059,7 +1127,7 @@ static long long window_piece_for(pdt_ctx *ctx, uint64_t nframes, size_t fb)
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
     // what the context already holds is its to re-use
     const DevBuf *held[] = { &ctx->pcm, &ctx->pll, &ctx->lock, &ctx->fir, &ctx->agc, &ctx->term, &ctx->stream_in, &ctx->lt_theta, &ctx->lt_phi,
-                             &ctx->avgph, &ctx->term_ap, &ctx->agc_raw, &ctx->gtable, &ctx->sym, &ctx->symidx };
+                             &ctx->avgph, &ctx->term_ap, &ctx->agc_raw, &ctx->gtable, &ctx->sym, &ctx->symidx, &ctx->analytic };
     double avail = (double)free_b;
     for (const DevBuf *b : held) avail += (double)b->cap;
     if (ctx->tune.hbm_limit_mb > 0) avail = (double)ctx->tune.hbm_limit_mb * 1048576.0;
@@ -1113,6 +1181,14 @@ static bool overlap_ingest(const pdt_ctx *ctx, uint64_t nframes, size_t fb)
 
 int pdt_demod_fd(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, int sample_format)
 {
+    if (ctx && fd >= 0 && real_fmt(sample_format)) {                 // single channel: never in overlapped segments
+        if (ctx->stream_open) return PDT_ERR_STATE;
+        HIP_TRY(hipSetDevice(ctx->cfg.device));
+        IngestSrc src;
+        src.fd = fd;
+        src.off = byte_offset;
+        return demod_real_src(ctx, src, nframes, sample_format);
+    }
     if (!ctx || fd < 0 || (sample_format != PDT_FMT_PCM16 && sample_format != PDT_FMT_F32)) return PDT_ERR_ARG;
     if (sample_format == PDT_FMT_F32 && ctx->elem != 4) return PDT_ERR_FORMAT;   // ARGOSdemod/main.c:238-241
     HIP_TRY(hipSetDevice(ctx->cfg.device));
@@ -1178,6 +1254,64 @@ int pdt_demod_device_f32(pdt_ctx *ctx, const void *iq_device, uint64_t nframes)
     ctx->pcm_dev = iq_device;
     ctx->pcm_fmt = 1;
     return demod_common(ctx, nframes);
+}
+
+int pdt_set_real_input(pdt_ctx *ctx, double center_hz)
+{
+    if (!ctx) return PDT_ERR_ARG;
+    if (!(std::isfinite(center_hz) && center_hz >= 0.0 && center_hz < 0.5 * (double)ctx->cfg.sample_rate)) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    ctx->real_center = center_hz;
+    ctx->real_step = analytic_step(ctx->cfg.sample_rate, center_hz);
+    return PDT_OK;
+}
+
+// a whole real capture whose samples are resident at x: convert, then the RAW float path
+static int demod_real_resident(pdt_ctx *ctx, const void *x, uint64_t n, int fmt)
+{
+    int rc = ctx->analytic.ensure((size_t)n * 8 + 16);
+    if (rc) return rc;
+    if ((rc = real_whole(ctx, x, n, fmt, ctx->analytic.p))) return rc;
+    ctx->pcm_dev = ctx->analytic.p;
+    ctx->pcm_fmt = 1;
+    ctx->analytic_len = n;
+    return demod_common(ctx, n);
+}
+
+// host memory or a file: the bounded window when the capture does not fit, else ingest + convert + chain
+static int demod_real_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt)
+{
+    const size_t rb = real_bytes(fmt);
+    if (const long long piece = window_piece_for(ctx, n, rb + 8))         // (the analytic stream is a buffer of the capture's length)
+        return piece < 0 ? (int)piece : demod_windowed(ctx, src, n, fmt, -1, nullptr, (uint64_t)piece);
+    int rc = ctx->pcm.ensure((size_t)n * rb + 16);
+    if (rc) return rc;
+    const auto t_in = std::chrono::steady_clock::now();
+    if ((rc = ingest_capture(ctx, src, (size_t)n * rb, ctx->pcm.p))) return rc;
+    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+    rc = demod_real_resident(ctx, ctx->pcm.p, n, fmt);
+    ctx->stats.ingest_ms = ctx->ingest_ms;
+    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
+    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
+    return rc;
+}
+
+int pdt_demod_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format)
+{
+    if (!ctx || (!x_host && n) || !real_fmt(sample_format)) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    IngestSrc src;
+    src.mem = (const unsigned char *)x_host;
+    return demod_real_src(ctx, src, n, sample_format);
+}
+
+int pdt_demod_device_real(pdt_ctx *ctx, const void *x_device, uint64_t n, int sample_format)
+{
+    if (!ctx || (!x_device && n) || !real_fmt(sample_format)) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    return demod_real_resident(ctx, x_device, n, sample_format);
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)
@@ -1395,6 +1529,8 @@ int pdt_stream_begin(pdt_ctx *ctx)
     ctx->stream_done = 0;
     ctx->stream_total = 0;
     ctx->stream_fmt = -1;
+    ctx->stream_real = 0;
+    ctx->rl = ctx->rp = ctx->real_done = 0;
     ctx->stream_open = false;
     ctx->stream_new.clear();
     ctx->frames_host.clear();
@@ -1745,11 +1881,13 @@ static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes
 static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes, uint64_t piece)
 {
     if (ctx->keep_agc_raw) return PDT_ERR_NOMEM;      // (the pre-Squelch stream of the WHOLE capture was asked for: that does not fit)
-    const size_t fb = fmt ? 8 : 4;
+    const bool real = fmt == PDT_FMT_REAL_PCM16 || fmt == PDT_FMT_REAL_F32;
+    const size_t fb = real ? (fmt == PDT_FMT_REAL_PCM16 ? 2 : 4) : fmt ? 8 : 4;     // bytes per frame of the source
     const auto t_call = std::chrono::steady_clock::now();
     int rc = pdt_stream_begin(ctx);
     if (rc) return rc;
-    ctx->stream_fmt = fmt;
+    ctx->stream_fmt = real ? 1 : fmt;
+    ctx->stream_real = real ? fmt : 0;
     ctx->sc.quality = ctx->keep_quality;              // (every cut below is a chunk boundary)
     ctx->report_samples = nframes;
     const uint64_t chunk = ctx->cfg.chunk;
@@ -1776,15 +1914,25 @@ static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, 
     for (bool last = false; !last && !rc;) {
         const uint64_t cnt = std::min<uint64_t>(piece, nframes - pushed);
         last = pushed + cnt == nframes;
-        if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + cnt) + 64) * fb, (size_t)ctx->stream_have * fb))) break;
         IngestSrc s = src;
         if (s.mem) s.mem += (size_t)pushed * fb; else s.off += pushed * fb;
-        const auto t0 = std::chrono::steady_clock::now();
-        if ((rc = ingest_capture(ctx, s, (size_t)cnt * fb, (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * fb))) break;
-        ingest_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        ctx->stream_have += cnt;
-        ctx->stream_total += cnt;
-        pushed += cnt;
+        if (real) {
+            // the piece lands behind the samples the real stream keeps, and is converted into the window (real_convert)
+            if ((rc = real_reserve(ctx, cnt))) break;
+            const auto t0 = std::chrono::steady_clock::now();
+            if ((rc = ingest_capture(ctx, s, (size_t)cnt * fb, (unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)(ctx->rl + ctx->rp) * fb))) break;
+            ingest_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if ((rc = real_convert(ctx, cnt, last))) break;
+            pushed += cnt;
+        } else {
+            if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + cnt) + 64) * fb, (size_t)ctx->stream_have * fb))) break;
+            const auto t0 = std::chrono::steady_clock::now();
+            if ((rc = ingest_capture(ctx, s, (size_t)cnt * fb, (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * fb))) break;
+            ingest_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            ctx->stream_have += cnt;
+            ctx->stream_total += cnt;
+            pushed += cnt;
+        }
         const uint64_t upto = last ? ctx->stream_have : (ctx->sc.origin + ctx->stream_have) / chunk * chunk - ctx->sc.origin;
         if (upto <= ctx->stream_done && !last) continue;
         if ((rc = stream_segment(ctx, upto, last))) break;
@@ -1809,6 +1957,8 @@ static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, 
     ctx->sc = StreamCarry();
     ctx->stream_have = ctx->stream_done = ctx->stream_total = 0;
     ctx->stream_fmt = -1;
+    ctx->stream_real = 0;
+    ctx->rl = ctx->rp = ctx->real_done = 0;
     ctx->stream_open = false;
     return rc;
 }
@@ -1816,6 +1966,20 @@ static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, 
 int pdt_demod_file(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, int sample_format, int text_fd, uint64_t *text_bytes)
 {
     if (text_bytes) *text_bytes = 0;
+    if (ctx && fd >= 0 && text_fd >= 0 && real_fmt(sample_format)) {
+        if (ctx->stream_open) return PDT_ERR_STATE;
+        HIP_TRY(hipSetDevice(ctx->cfg.device));
+        const size_t rb = real_bytes(sample_format);
+        if (const long long piece = window_piece_for(ctx, nframes, rb + 8)) {
+            IngestSrc src;
+            src.fd = fd;
+            src.off = byte_offset;
+            return piece < 0 ? (int)piece : demod_windowed(ctx, src, nframes, sample_format, text_fd, text_bytes, (uint64_t)piece);
+        }
+        const int rc = pdt_demod_fd(ctx, fd, byte_offset, nframes, sample_format);
+        if (rc) return rc;
+        return pdt_write_frames(ctx, text_fd, text_bytes);
+    }
     if (!ctx || fd < 0 || text_fd < 0 || (sample_format != PDT_FMT_PCM16 && sample_format != PDT_FMT_F32)) return PDT_ERR_ARG;
     if (sample_format == PDT_FMT_F32 && ctx->elem != 4) return PDT_ERR_FORMAT;
     if (ctx->stream_open) return PDT_ERR_STATE;
@@ -1838,6 +2002,8 @@ int pdt_demod_file(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes,
     return pdt_write_frames(ctx, text_fd, text_bytes);
 }
 
+static int stream_advance(pdt_ctx *ctx, uint64_t pushed, uint64_t *new_frames);
+
 static int stream_push(pdt_ctx *ctx, const void *host, uint64_t nframes, int fmt, uint64_t *new_frames)
 {
     if (!ctx || (!host && nframes)) return PDT_ERR_ARG;
@@ -1847,6 +2013,7 @@ static int stream_push(pdt_ctx *ctx, const void *host, uint64_t nframes, int fmt
         if (rb) return rb;
         ctx->stream_open = true;
     }
+    if (ctx->stream_real) return PDT_ERR_ARG;        // (a stream of real pushes)
     if (ctx->stream_fmt >= 0 && ctx->stream_fmt != fmt) return PDT_ERR_STATE;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     ctx->stream_fmt = fmt;
@@ -1861,16 +2028,46 @@ static int stream_push(pdt_ctx *ctx, const void *host, uint64_t nframes, int fmt
                                hipMemcpyHostToDevice, ctx->stream));
     ctx->stream_have += nframes;
     ctx->stream_total += nframes;
+    return stream_advance(ctx, nframes, new_frames);
+}
+
+// demodulate the complete chunks the window holds now
+static int stream_advance(pdt_ctx *ctx, uint64_t pushed, uint64_t *new_frames)
+{
     const uint64_t chunk = ctx->cfg.chunk;
     const uint64_t whole = (ctx->sc.origin + ctx->stream_have) / chunk * chunk - ctx->sc.origin;   // local end of the complete chunks
     if (whole > ctx->stream_done) {
-        rc = stream_segment(ctx, whole, false);
+        const int rc = stream_segment(ctx, whole, false);
         if (rc) return rc;
-    } else if (nframes) {
+    } else if (pushed) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));      // the caller's buffer is free to be reused when this returns
     }
     if (new_frames) *new_frames = ctx->stream_new.size();
     return PDT_OK;
+}
+
+static int stream_push_real(pdt_ctx *ctx, const void *host, uint64_t n, int fmt, uint64_t *new_frames)
+{
+    if (new_frames) *new_frames = 0;
+    if (!ctx || (!host && n) || (fmt != PDT_FMT_REAL_PCM16 && fmt != PDT_FMT_REAL_F32)) return PDT_ERR_ARG;
+    if (!ctx->stream_open) {
+        int rb = pdt_stream_begin(ctx);
+        if (rb) return rb;
+        ctx->stream_open = true;
+    }
+    if (ctx->stream_fmt >= 0 && ctx->stream_real != fmt) return PDT_ERR_ARG;     // I,Q pushes, or real ones of the other format
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    ctx->stream_fmt = 1;
+    ctx->stream_real = fmt;
+    ctx->stream_new.clear();
+    int rc = real_reserve(ctx, n);
+    if (rc) return rc;
+    const size_t rb = fmt == PDT_FMT_REAL_PCM16 ? 2 : 4;
+    if (n)
+        HIP_TRY(hipMemcpyAsync((unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)(ctx->rl + ctx->rp) * rb, host, (size_t)n * rb,
+                               hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = real_convert(ctx, n, false))) return rc;
+    return stream_advance(ctx, n, new_frames);
 }
 
 int pdt_stream_push_pcm16(pdt_ctx *ctx, const int16_t *iq_host, uint64_t nframes, uint64_t *new_frames)
@@ -1883,11 +2080,20 @@ int pdt_stream_push_f32(pdt_ctx *ctx, const float *iq_host, uint64_t nframes, ui
     return stream_push(ctx, iq_host, nframes, 1, new_frames);
 }
 
+int pdt_stream_push_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format, uint64_t *new_frames)
+{
+    return stream_push_real(ctx, x_host, n, sample_format, new_frames);
+}
+
 int pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames)
 {
     if (!ctx) return PDT_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     ctx->stream_open = false;                        // (whatever happens below, the stream is over)
+    if (ctx->stream_real) {                          // the held-back samples, closed with zeros
+        const int rr = real_convert(ctx, 0, true);
+        if (rr) return rr;
+    }
     if (ctx->stream_fmt < 0) {                       // nothing was pushed: an empty capture
         ctx->stream_fmt = 0;
         int rc = ctx->stream_in.ensure(64);
@@ -1908,7 +2114,7 @@ int pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames)
     return rc;
 }
 
-uint64_t pdt_stream_retained(const pdt_ctx *ctx) { return ctx ? ctx->stream_have : 0; }
+uint64_t pdt_stream_retained(const pdt_ctx *ctx) { return ctx ? ctx->stream_have + ctx->rp : 0; }
 
 uint64_t pdt_stream_frames(const pdt_ctx *ctx, pdt_frame *out, uint64_t max_frames)
 {
@@ -2178,6 +2384,7 @@ int64_t pdt_read_stage(const pdt_ctx *ctx, int stage, uint64_t first, uint64_t c
     case PDT_ST_SYMIDX: src = ctx->symidx.p; es = 8; break;
     case PDT_ST_BITS: src = ctx->bits.p; es = 1; break;
     case PDT_ST_BITSYM: src = ctx->bitsym.p; es = 4; break;
+    case PDT_ST_ANALYTIC: src = ctx->analytic.p; es = 8; break;
     }
     if (!src) return PDT_ERR_STATE;
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;

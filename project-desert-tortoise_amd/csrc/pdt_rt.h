@@ -388,6 +388,16 @@ struct pdt_ctx {
     int stream_fmt = -1;                // -1 = no push yet, 0 = pcm16, 1 = float32
     bool stream_open = false;           // between the first push and pdt_stream_end / _begin: the stage buffers hold the tails the next push continues from
     std::vector<pdt_frame> stream_new;
+    // real (single-channel) input (pdt_analytic.h): the centre's phase step, the rotation table, the analytic stream of a whole
+    // capture; a stream of real pushes keeps its last samples in rbuf[rcur]: rl converted ones (the next samples' left halo) and rp
+    // not yet converted (waiting for their right halo), then the new ones
+    uint32_t real_step = 1u << 30;
+    double real_center = 0;
+    DevBuf an_tab, analytic, rbuf[2];
+    int rcur = 0;
+    int stream_real = 0;                // 0 = I,Q stream (or none), PDT_FMT_REAL_PCM16 / _F32 = the stream takes real pushes
+    uint64_t rl = 0, rp = 0, real_done = 0;
+    uint64_t analytic_len = 0;          // length of PDT_ST_ANALYTIC the next demod_common reports
     unsigned char *seg_pin = nullptr;   // pinned staging for the small per-segment transfers (part of the pend_sc block)
     pdt_stats stats;
     std::vector<pdt_kernel_time> ktimes;

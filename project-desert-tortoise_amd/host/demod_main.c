@@ -30,6 +30,11 @@
  * run, chunk by chunk from the library's per-chunk reports (pdt_keep_quality), with the reference's arithmetic and under the
  * reference's condition (progress of more than 0.15 %, or end of file); one summary line follows.  RAW float32 input (".raw", -s mandatory) is supported for POES
  * exactly as in POESTIPdemod/main.c:313-339.
+ * -f <kHz> (an addition): the input is a single-channel recording (SatNOGS audio, an SDR in USB mode, a one-input sound card)
+ * whose signal sits around that audio frequency; the library turns it into I,Q through its Hilbert front end
+ * (pdt_set_real_input / pdt_demod_file with PDT_FMT_REAL_*): a mono 16-bit WAV, for POES also a mono float32 .raw
+ * (-s), and with -l and the file name "-" mono float32 blocks from standard input.  A 2-channel file is refused under -f;
+ * without -f a mono file is refused as before.
  */
 #include <ctype.h>
 #include <math.h>
@@ -46,14 +51,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:"      /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:"    /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -167,7 +172,7 @@ static void put_frames(FILE *out, const pdt_frame *f, uint64_t n)
 /* The twin's loop (POESTIPdemodPortAudio/main.c:324-393, ARGOSdemodPortAudio/main.c:266-329) with standard input as the sound card: blocks of `chunk`
  * float32 I,Q frames until end of file (there: until a key is hit); frames are appended as they become final. */
 static int live_loop(FILE *in, FILE *out, const char *outFileName, double sampleRate, unsigned long chunk, double normFactor,
-                     int device, int sampler)
+                     int device, int sampler, int real, double realCenterHz)
 {
     if (sampleRate < 1) sampleRate = 48.0;                            /* twin: SAMPLE_RATE 48000 (main.c:27) */
     pdt_config cfg;
@@ -191,6 +196,10 @@ static int live_loop(FILE *in, FILE *out, const char *outFileName, double sample
         remove(outFileName);
         return 1;
     }
+    if (real && pdt_set_real_input(ctx, realCenterHz) != PDT_OK) {
+        printf("Centre frequency %0.3f kHz must lie between 0 and half the sample rate\n", realCenterHz / 1000.0);
+        return 1;
+    }
     float *block = (float *)malloc(sizeof(float) * 2 * chunk);
     pdt_frame *fr = NULL;
     uint64_t cap = 0, total = 0, samples = 0, fresh = 0;
@@ -199,9 +208,9 @@ static int live_loop(FILE *in, FILE *out, const char *outFileName, double sample
         return 1;
     }
     for (;;) {
-        const size_t got = fread(block, 2 * sizeof(float), chunk, in);
+        const size_t got = fread(block, (real ? 1 : 2) * sizeof(float), chunk, in);     /* -f: mono float32 samples */
         if (got) {
-            rc = pdt_stream_push_f32(ctx, block, got, &fresh);
+            rc = real ? pdt_stream_push_real(ctx, block, got, PDT_FMT_REAL_F32, &fresh) : pdt_stream_push_f32(ctx, block, got, &fresh);
         } else {
             rc = pdt_stream_end(ctx, &fresh);
         }
@@ -247,7 +256,8 @@ int main(int argc, char **argv)
     int timing = 0;
     unsigned long chunkSize = DEFAULT_CHUNKSIZE;
     double normFactor = 0, sampleRate = 0;
-    int outputRawFiles = 0, device = 0, quality = 0, sampler = 0, live = 0, chunkGiven = 0, noProgress = 0, c;
+    int outputRawFiles = 0, device = 0, quality = 0, sampler = 0, live = 0, chunkGiven = 0, noProgress = 0, real = 0, c;
+    double realCenterHz = 0;
     const char *outOverride = NULL;
     char outFileName[1100];
 
@@ -300,6 +310,11 @@ int main(int argc, char **argv)
             live = 1;
             printf("Using the live (sound card) chain\n");
             break;
+        case 'f':                                       /* single-channel input centred at this audio frequency */
+            real = 1;
+            realCenterHz = atof(optarg) * 1000.0;
+            printf("Single-channel input centred at %f Khz\n", atof(optarg));
+            break;
         case 'm':                                       /* MMClockRecovery instead of Gardner (ARGOSdemod/main.c:277) */
             sampler = PDT_SAMPLER_MM;
             printf("Using M&M clock recovery\n");
@@ -349,7 +364,7 @@ int main(int argc, char **argv)
         fclose(raw);
     }
 
-    if (from_stdin) return live_loop(in, out, outFileName, sampleRate, chunkSize, normFactor, device, sampler);
+    if (from_stdin) return live_loop(in, out, outFileName, sampleRate, chunkSize, normFactor, device, sampler, real, realCenterHz);
     int is_raw = 0;
     if (strcasecmp(get_filename_ext(inFileName), "wav") != 0) {
 #ifdef PDT_ARGOS
@@ -361,7 +376,7 @@ int main(int argc, char **argv)
                 printf("Sample Rate (in Khz) must be specified when using RAW files\n");
                 exit(1);
             }
-            printf("Assuming 32-bit IEEE Floating Point RAW input\n");
+            printf(real ? "Assuming single-channel 32-bit IEEE Floating Point RAW input\n" : "Assuming 32-bit IEEE Floating Point RAW input\n");
             is_raw = 1;
         } else {
             printf("Unrecognized file format %s\n", get_filename_ext(inFileName));
@@ -381,7 +396,11 @@ int main(int argc, char **argv)
         }
         pdt_wav_parse_header(hdr, &rate, &channels, &bits, &format, &data_bytes);
         data_offset = 44;
-        if (channels != 2) {
+        if (real && channels != 1) {
+            printf("Single-channel input (-f) requires a mono file, this one has %u channels\n", channels);
+            exit(1);
+        }
+        if (!real && channels != 2) {
             printf("Complex read requires 2 channels (I and Q)\n");
             exit(1);
         }
@@ -410,7 +429,8 @@ int main(int argc, char **argv)
      * memory overlapped with the copy to the GPU: pdt_demod_fd) */
     fseek(in, 0, SEEK_END);
     long fsz = ftell(in);
-    const size_t frame_bytes = is_raw ? 8 : 4;
+    const size_t frame_bytes = (is_raw ? 8 : 4) / (real ? 2 : 1);
+    const int sample_format = real ? (is_raw ? PDT_FMT_REAL_F32 : PDT_FMT_REAL_PCM16) : (is_raw ? PDT_FMT_F32 : PDT_FMT_PCM16);
     uint64_t nframes = fsz > data_offset ? (uint64_t)(fsz - data_offset) / frame_bytes : 0;
 
     pdt_config cfg;
@@ -435,6 +455,12 @@ int main(int argc, char **argv)
 #ifdef PDT_ARGOS
     if (outputRawFiles) pdt_keep_presquelch(ctx, 1);                 /* -r: the AGC output before Squelch, ARGOSdemod/main.c:273-274 */
 #endif
+    if (real && pdt_set_real_input(ctx, realCenterHz) != PDT_OK) {
+        printf("Centre frequency %0.3f kHz must lie between 0 and half the sample rate\n", realCenterHz / 1000.0);
+        fclose(out);
+        remove(outFileName);
+        exit(1);
+    }
     pdt_keep_pll(ctx, 0);                                            /* nothing here reads the PLL output stream */
     progress_state prog;
     memset(&prog, 0, sizeof prog);
@@ -453,10 +479,10 @@ int main(int argc, char **argv)
     int text_written = 0;
     fflush(out);
 #ifndef PDT_ARGOS
-    rc = pdt_demod_file(ctx, fileno(in), (uint64_t)data_offset, nframes, is_raw ? PDT_FMT_F32 : PDT_FMT_PCM16, fileno(out), NULL);
+    rc = pdt_demod_file(ctx, fileno(in), (uint64_t)data_offset, nframes, sample_format, fileno(out), NULL);
     text_written = 1;
 #else
-    rc = pdt_demod_fd(ctx, fileno(in), (uint64_t)data_offset, nframes, is_raw ? PDT_FMT_F32 : PDT_FMT_PCM16);
+    rc = pdt_demod_fd(ctx, fileno(in), (uint64_t)data_offset, nframes, sample_format);
 #endif
     const double t_demod1 = now_ms();
     fclose(in);

@@ -57,6 +57,8 @@ void Tuning::load()
     gardner_nostride = get("PDT_GARDNER_NOSTRIDE") != nullptr;
     gemit_groups = get("PDT_GEMIT_GROUPS") != nullptr;
     agc_unfused = get("PDT_AGC_UNFUSED") != nullptr;
+    manch_3pass = get("PDT_MANCH_3PASS") != nullptr;        // Manchester as tile summaries, one-workgroup scan, emission
+    sync_serial = get("PDT_SYNC_SERIAL") != nullptr;        // frame filter in one workgroup (k_sync_frames_tiles)
     agc_lanes = get("PDT_AGC_LANES") != nullptr;           // the per-lane walkers of rounds 1 - 3 (k_agc_block)
     no_excl = get("PDT_NO_EXCL") != nullptr;
     gardner_onebuf = get("PDT_GARDNER_ONEBUF") != nullptr;
@@ -186,16 +188,30 @@ void launch_bytesync(pdt_ctx *ctx, Plan &PL, hipStream_t st, const SyncParams &S
     SyncTile *d_stiles = (SyncTile *)ctx->stiles.p;
     PDT_LAUNCH(256, k_sync_hits_tile, dim3((unsigned)n_stiles), dim3(256), 0, st, d_bits, &d_sc->nbits, SP, d_stiles,
                        &d_sc->sync_overflow, min_pos);
-    PDT_LAUNCH(PDT_SYNC_THREADS, k_sync_frames_tiles, dim3(1), dim3(PDT_SYNC_THREADS), 0, st, (const SyncTile *)d_stiles, &d_sc->nbits, SP, d_hits, hit_cap,
-                       d_frames, &d_sc->nframes, frame_cap, &d_sc->sync_overflow, (unsigned *)ctx->sync_scr.p);
-    // generic path (atomic append + sort), only when a tile overflowed
-    const long long grid = (bit_cap + 255) / 256;
+    unsigned *d_scr = (unsigned *)ctx->sync_scr.p;
+    if (ctx->tune.sync_serial) {
+        PDT_LAUNCH(PDT_SYNC_THREADS, k_sync_frames_tiles, dim3(1), dim3(PDT_SYNC_THREADS), 0, st, (const SyncTile *)d_stiles, &d_sc->nbits, SP, d_hits,
+                           hit_cap, d_frames, &d_sc->nframes, frame_cap, &d_sc->sync_overflow, d_scr);
+    } else {
+        // the batches are counted on the device: a grid of fixed size walks them (at most the capacity's)
+        const unsigned n_batch = (unsigned)std::min<long long>(256, ((long long)hit_cap + PDT_SYNC_PB - 1) / PDT_SYNC_PB);
+        PDT_LAUNCH(PDT_SYNC_THREADS, k_sync_dense, dim3(1), dim3(PDT_SYNC_THREADS), 0, st, (const SyncTile *)d_stiles, &d_sc->nbits, n_stiles,
+                           hit_cap, &d_sc->sync_overflow, d_scr);
+        PDT_LAUNCH(256, k_sync_gather, dim3((unsigned)std::min<long long>(1024, (n_stiles + 255) / 256)), dim3(256), 0, st,
+                           (const SyncTile *)d_stiles, &d_sc->nbits, n_stiles, d_hits, hit_cap, &d_sc->sync_overflow, (const unsigned *)d_scr);
+        PDT_LAUNCH(PDT_SYNC_PT, k_sync_links, dim3(n_batch), dim3(PDT_SYNC_PT), 0, st, SP, (const unsigned *)d_hits, &d_sc->sync_overflow, d_scr,
+                           hit_cap);
+        PDT_LAUNCH(PDT_SYNC_PT, k_sync_mark, dim3(n_batch), dim3(PDT_SYNC_PT), 0, st, SP, (const unsigned *)d_hits, d_frames, &d_sc->nframes,
+                           frame_cap, &d_sc->sync_overflow, (const unsigned *)d_scr, hit_cap);
+    }
+    // generic path (atomic append + sort), only when a tile overflowed; the fixed grids below walk what the device counted
+    const long long grid = std::min<long long>(2048, (bit_cap + 255) / 256);
     PDT_LAUNCH(256, k_sync_hits, dim3((unsigned)grid), dim3(256), 0, st, d_bits, &d_sc->nbits, SP, d_hits, &d_sc->nhits, hit_cap,
                        &d_sc->sync_overflow, min_pos);
     PDT_LAUNCH(256, k_sync_frames, dim3(1), dim3(256), 0, st, d_hits, &d_sc->nhits, hit_cap, SP, d_frames, &d_sc->nframes,
                        frame_cap, &d_sc->sync_overflow);
-    PDT_LAUNCH(128, k_frame_pack, dim3(frame_cap), dim3(128), 0, st, d_bits, &d_sc->nbits, d_bitsym, d_symidx, SP, d_frames,
-                       &d_sc->nframes, frame_cap);
+    PDT_LAUNCH(128, k_frame_pack, dim3(std::min<uint32_t>(frame_cap, 16384)), dim3(128), 0, st, d_bits, &d_sc->nbits, d_bitsym, d_symidx, SP,
+                       d_frames, &d_sc->nframes, frame_cap);
 }
 
 // reports of chunks [c0, c1) of the capture (c1 <= chunk_host.size()); `total`: the capture's length as far as it is known

@@ -1566,12 +1566,24 @@ template <typename T> struct Chain {
         (void)rc;
         // ---- Manchester
         L.begin("manchester");
-        PDT_LAUNCH(PDT_TILE_THREADS, k_manch_tile<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, &d_sc->nsym, manch_thr,
-                           d_tiles, sym_pad);
-        PDT_LAUNCH(1024, k_manch_scan, dim3(1), dim3(1024), 0, st, d_tiles, &d_sc->nsym, &d_sc->nbits, sym_pad, clock0, bit0,
-                           seg ? &d_tail->clock : (unsigned *)nullptr);
-        PDT_LAUNCH(PDT_TILE_THREADS, k_manch_emit<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, &d_sc->nsym, manch_thr,
-                           d_tiles, d_bits, d_bitsym, bit_cap, sym_pad);
+        if (ctx->tune.manch_3pass) {
+            PDT_LAUNCH(PDT_TILE_THREADS, k_manch_tile<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, &d_sc->nsym, manch_thr,
+                               d_tiles, sym_pad);
+            PDT_LAUNCH(1024, k_manch_scan, dim3(1), dim3(1024), 0, st, d_tiles, &d_sc->nsym, &d_sc->nbits, sym_pad, clock0, bit0,
+                               seg ? &d_tail->clock : (unsigned *)nullptr);
+            PDT_LAUNCH(PDT_TILE_THREADS, k_manch_emit<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, &d_sc->nsym, manch_thr,
+                               d_tiles, d_bits, d_bitsym, bit_cap, sym_pad);
+        } else {
+            // one pass with look-back; its status words live where the tile summaries of the three passes would
+            // (n_tiles records of 32 bytes hold the n_one + 1 <= n_tiles + 1 words)
+            constexpr int ONE_NT = ManchOnePass<T>::NT, ONE_TILE = ManchOnePass<T>::TILE;
+            const long long n_one = (sym_cap + ONE_TILE - 1) / ONE_TILE;
+            unsigned long long *d_mstat = (unsigned long long *)d_tiles;
+            PL.memset_async(d_mstat, 0, (size_t)(n_one + 1) * sizeof(unsigned long long), PL.side_of(st));
+            PDT_LAUNCH(ONE_NT, k_manch_onepass<T>, dim3((unsigned)n_one), dim3(ONE_NT), 0, st, d_sym, &d_sc->nsym,
+                               manch_thr, d_mstat, d_bits, d_bitsym, bit_cap, sym_pad, clock0, bit0, &d_sc->nbits,
+                               seg ? &d_tail->clock : (unsigned *)nullptr, sym_cap);
+        }
         L.end();
 
         // ---- byte sync

@@ -2151,10 +2151,10 @@ template <typename T> __device__ __forceinline__ bool manch_resync(const T *sym,
 #define PDT_MANCH_LDS ((PDT_TILE + 2) + (PDT_TILE + 2) / 16 + 1)
 __device__ __forceinline__ int manch_at(int k) { return k + (k >> 4); }
 // s_sym[manch_at(k)] = sym[t0 - 2 + k], k in [0, PDT_TILE + 2); 0 outside [0, nsym)
-template <typename T>
+template <typename T, int TILE = PDT_TILE, int NT = PDT_TILE_THREADS>
 __device__ __forceinline__ void manch_stage(const T *__restrict__ sym, long long t0, long long nsym, T *s_sym)
 {
-    for (int k = threadIdx.x; k < PDT_TILE + 2; k += PDT_TILE_THREADS) {
+    for (int k = threadIdx.x; k < TILE + 2; k += NT) {
         const long long gi = t0 - 2 + k;
         s_sym[manch_at(k)] = (gi >= 0 && gi < nsym) ? sym[gi] : (T)0;
     }
@@ -2166,7 +2166,7 @@ template <typename T> __device__ __forceinline__ bool manch_resync_lds(const T *
     const T p = s_sym[manch_at(j + 1)];
     return sgn(pp) == sgn(p) && Real<T>::abs(pp) > thr && Real<T>::abs(p) > thr;
 }
-// exclusive block scans over the 256 threads (4 wavefronts); s_w: 4 ints of LDS
+// exclusive block scans over the workgroup (256 threads, 4 wavefronts, in the tile kernels); s_w: an int per wavefront of LDS
 __device__ __forceinline__ int manch_scan_max_excl(int v, int *s_w)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2418,6 +2418,175 @@ __device__ __forceinline__ void k_manch_emit(const T *__restrict__ sym,
     }
 }
 
+// The three passes above in one (decoupled look-back): every workgroup takes its tile in ticket order, decides the tile
+// for both incoming clockmods, publishes the tile's map (ManchMap), finds the state entering it from the words its
+// predecessors published, publishes the state leaving it and writes its bits.  The symbols are read once.
+//   status[0]      ticket counter;   status[1 + t]  tile t: bits 63..62 = 0 nothing yet, 1 map, 2 state after the tile
+//   map:    o0 | o1 << 1 | a0 << 2 | a1 << 22          (a0, a1 <= the tile's symbols < 2^20)
+//   state:  clock | bit count << 1
+// The whole record is one 8-byte word written and read with agent-scope atomics: nothing else is handed over.  status
+// must be zero when the kernel starts (one memset per call).
+#define PDT_MANCH_MAP (1ull << 62)
+#define PDT_MANCH_INC (2ull << 62)
+__device__ __forceinline__ unsigned long long manch_map_word(const ManchMap &m)
+{
+    return PDT_MANCH_MAP | (unsigned long long)m.o0 | ((unsigned long long)m.o1 << 1) | (m.a0 << 2) | (m.a1 << 22);
+}
+__device__ __forceinline__ ManchMap manch_word_map(unsigned long long w)
+{
+    ManchMap m;
+    m.o0 = (unsigned)(w & 1u);
+    m.o1 = (unsigned)((w >> 1) & 1u);
+    m.a0 = (w >> 2) & 0xfffffu;
+    m.a1 = (w >> 22) & 0xfffffu;
+    return m;
+}
+
+// Tiles of 16 symbols per thread: 1024 threads (16 384 symbols, 70 KB of LDS) in the float build, where a tile of 4 096 paid
+// one look-back and one ticket per 4 096 symbols; 256 in the double build.
+template <typename T> struct ManchOnePass {
+    static constexpr int NT = sizeof(T) == 4 ? 1024 : PDT_TILE_THREADS;
+    static constexpr int TILE = 16 * NT;
+    static constexpr int LDS = (TILE + 2) + (TILE + 2) / 16 + 1;
+};
+template <typename T>
+__device__ __forceinline__ void k_manch_onepass(const T *__restrict__ sym, const unsigned long long *__restrict__ nsym_p, T thr,
+                                                unsigned long long *__restrict__ status, unsigned char *__restrict__ bits,
+                                                unsigned *__restrict__ bitsym, long long bit_cap, long long i0, unsigned clock0,
+                                                unsigned long long bit0, unsigned long long *__restrict__ nbits_out,
+                                                unsigned *__restrict__ clock_out, long long sym_cap)
+{
+    constexpr int TILE = ManchOnePass<T>::TILE, NT = ManchOnePass<T>::NT;
+    __shared__ T s_sym[ManchOnePass<T>::LDS];
+    __shared__ int s_wi[NT / 64];
+    __shared__ unsigned s_wu[NT / 64];
+    __shared__ unsigned s_tile, s_tot;
+    __shared__ int s_tlast;
+    __shared__ unsigned s_clock;
+    __shared__ unsigned long long s_base;
+    __shared__ unsigned long long s_look[64];
+    if (threadIdx.x == 0) s_tile = atomicAdd(reinterpret_cast<unsigned *>(status), 1u);
+    __syncthreads();
+    const long long tile = (long long)s_tile;
+    const long long nsym = ((long long)*nsym_p < sym_cap) ? (long long)*nsym_p : sym_cap;     // (more: the host reports the overflow)
+    const long long nt = (nsym > i0) ? (nsym - i0 + TILE - 1) / TILE : 0;
+    if (tile == 0 && nt == 0 && threadIdx.x == 0) {                 // nothing to decide: the carried state passes through
+        *nbits_out = bit0;
+        if (clock_out) *clock_out = clock0;
+    }
+    if (tile >= nt) return;
+    const long long t0 = i0 + tile * TILE;
+    manch_stage<T, TILE, NT>(sym, t0, nsym, s_sym);
+    __syncthreads();
+    const int per = TILE / NT;
+    const int lo = threadIdx.x * per;
+    int last = -1;
+    unsigned rs_mask = 0;
+    for (int u = 0; u < per; u++) {
+        const long long i = t0 + lo + u;
+        if (i < nsym && manch_resync_lds(s_sym, lo + u, thr)) { last = lo + u; rs_mask |= 1u << u; }
+    }
+    const int carry = manch_scan_max_excl(last, s_wi);
+    if (threadIdx.x == NT - 1) s_tlast = (last > carry) ? last : carry;    // last resync of the tile, -1 none
+    // emitted symbols for an incoming clockmod of 0 and of 1 (the same masks once the tile has resynchronised in front)
+    unsigned em[2] = { 0u, 0u };
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        unsigned clock = (carry >= 0) ? (unsigned)((t0 + carry) & 1) : (unsigned)c;
+        for (int u = 0; u < per; u++) {
+            const long long i = t0 + lo + u;
+            if (i >= nsym) break;
+            const unsigned q = (unsigned)(i & 1);
+            if (rs_mask & (1u << u)) clock = q;
+            if (q == clock) em[c] |= 1u << u;
+        }
+    }
+    // one scan of both counts (each <= TILE fits 16 bits)
+    const unsigned both = (unsigned)__popc(em[0]) | ((unsigned)__popc(em[1]) << 16);
+    const unsigned ex = manch_scan_add_excl(both, s_wu);
+    if (threadIdx.x == NT - 1) s_tot = ex + both;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        ManchMap mine;
+        mine.o0 = 0; mine.o1 = 1;
+        if (s_tlast >= 0) mine.o0 = mine.o1 = (unsigned)((t0 + s_tlast) & 1);
+        mine.a0 = s_tot & 0xffffu;
+        mine.a1 = s_tot >> 16;
+        unsigned clock = clock0;
+        unsigned long long base = bit0;
+        if (tile > 0) {
+            if (threadIdx.x == 0) __hip_atomic_store(&status[1 + tile], manch_map_word(mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // look back in windows of 64 tiles (lane k: tile j - k) until one holds a state; every earlier tile has its ticket,
+            // and publishes its map without waiting for anything
+            ManchMap near;                                             // the maps between the window and this tile, composed
+            near.o0 = 0; near.o1 = 1; near.a0 = 0; near.a1 = 0;
+            long long j = tile - 1;
+            for (;;) {
+                const long long t = j - (long long)threadIdx.x;
+                unsigned long long w = PDT_MANCH_MAP;                   // (before tile 0: identity maps, never reached)
+                if (t >= 0)
+                    while ((w = __hip_atomic_load(&status[1 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0ull)
+                        __builtin_amdgcn_s_sleep(1);
+                if (t < 0) w = PDT_MANCH_MAP | 2ull;                    // identity map
+                s_look[threadIdx.x] = w;
+                const unsigned long long inc = __ballot((w >> 62) == 2ull);
+                __builtin_amdgcn_wave_barrier();
+                if (inc) {
+                    const int k = __builtin_ctzll(inc);                 // the nearest state
+                    const unsigned long long ws = s_look[k];
+                    clock = (unsigned)(ws & 1u);
+                    base = (ws & ~(3ull << 62)) >> 1;
+                    for (int q = k - 1; q >= 0; q--) {
+                        const ManchMap m = manch_word_map(s_look[q]);
+                        base += clock ? m.a1 : m.a0;
+                        clock = clock ? m.o1 : m.o0;
+                    }
+                    base += clock ? near.a1 : near.a0;
+                    clock = clock ? near.o1 : near.o0;
+                    break;
+                }
+                ManchMap win;
+                win.o0 = 0; win.o1 = 1; win.a0 = 0; win.a1 = 0;
+                for (int q = 63; q >= 0; q--) win = manch_compose(win, manch_word_map(s_look[q]));
+                near = manch_compose(win, near);
+                __builtin_amdgcn_wave_barrier();
+                j -= 64;
+            }
+        }
+        if (threadIdx.x == 0) {
+            const unsigned c_out = clock ? mine.o1 : mine.o0;
+            const unsigned long long b_out = base + (clock ? mine.a1 : mine.a0);
+            __hip_atomic_store(&status[1 + tile], PDT_MANCH_INC | (b_out << 1) | c_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tile == nt - 1) {
+                *nbits_out = b_out;
+                if (clock_out) *clock_out = c_out;
+            }
+            s_clock = clock;
+            s_base = base;
+        }
+    }
+    __syncthreads();
+    const unsigned cin = s_clock;
+    const unsigned emit_mask = cin ? em[1] : em[0];
+    unsigned long long o = s_base + (cin ? (ex >> 16) : (ex & 0xffffu));
+    for (int u = 0; u < per; u++) {
+        if (!(emit_mask & (1u << u))) continue;
+        const long long i = t0 + lo + u;
+        const T p = s_sym[manch_at(lo + u + 1)];
+        const T cur = s_sym[manch_at(lo + u + 2)];
+        unsigned char bit;
+        if (Real<T>::abs(p) > Real<T>::abs(cur))
+            bit = (p > 0) ? '1' : '0';
+        else
+            bit = (cur > 0) ? '0' : '1';
+        if ((long long)o < bit_cap) {
+            bits[o] = bit;
+            bitsym[o] = (unsigned)i;
+        }
+        o++;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Sync-word search + frame extraction
 // (reference: POESTIPdemod/ByteSync.c:16-150, ARGOSdemod/ByteSync.c:17-150)
@@ -2446,23 +2615,25 @@ __device__ __forceinline__ void k_sync_hits(const unsigned char *__restrict__ bi
 {
     if (only_if && *only_if == 0) return;            // generic path: only when the tile path overflowed
     const long long nbits = (long long)*nbits_p;
-    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nbits || b < min_pos) return;           // (min_pos: a stream segment's window begins inside a frame already reported)
-    unsigned long long w = 0;
-    for (unsigned k = 0; k < P.len; k++) {
-        const long long idx = b - (long long)(P.len - 1) + k;
-        const unsigned v = (idx >= 0) ? (unsigned)(bits[idx] != '0') : 0u;
-        w = (w << 1) | v;
-    }
-    const unsigned long long mask = (P.len >= 64) ? ~0ull : ((1ull << P.len) - 1ull);
-    unsigned kind = 0;
-    if (w == P.pattern)
-        kind = 1;
-    else if (P.allow_inverse && w == (~P.pattern & mask))
-        kind = 2;
-    if (kind) {
-        const unsigned slot = atomicAdd(nhits, 1u);
-        if (slot < hit_cap) hits[slot] = ((unsigned)b << 1) | (kind - 1);   // bit index < 2^31
+    // (a grid of fixed size walks the bits: the grid is recorded before the bit count exists)
+    for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < nbits; b += (long long)gridDim.x * blockDim.x) {
+        if (b < min_pos) continue;                   // (min_pos: a stream segment's window begins inside a frame already reported)
+        unsigned long long w = 0;
+        for (unsigned k = 0; k < P.len; k++) {
+            const long long idx = b - (long long)(P.len - 1) + k;
+            const unsigned v = (idx >= 0) ? (unsigned)(bits[idx] != '0') : 0u;
+            w = (w << 1) | v;
+        }
+        const unsigned long long mask = (P.len >= 64) ? ~0ull : ((1ull << P.len) - 1ull);
+        unsigned kind = 0;
+        if (w == P.pattern)
+            kind = 1;
+        else if (P.allow_inverse && w == (~P.pattern & mask))
+            kind = 2;
+        if (kind) {
+            const unsigned slot = atomicAdd(nhits, 1u);
+            if (slot < hit_cap) hits[slot] = ((unsigned)b << 1) | (kind - 1);   // bit index < 2^31
+        }
     }
 }
 
@@ -2746,18 +2917,242 @@ __device__ __forceinline__ void k_sync_frames_tiles(const SyncTile *__restrict__
     (void)gscr;
 }
 
-__device__ __forceinline__ void k_frame_pack(const unsigned char *__restrict__ bits,
-                                                     const unsigned long long *__restrict__ nbits_p,
-                                                     const unsigned *__restrict__ bitsym,
-                                                     const long long *__restrict__ symidx, SyncParams P,
-                                                     FrameRec *__restrict__ frames, const unsigned *__restrict__ nframes_p,
-                                                     unsigned frame_cap)
+// The same filter chip-wide (k_sync_frames_tiles stays behind the switch PDT_SYNC_SERIAL).  Four kernels:
+//  k_sync_dense   one workgroup: where each tile's hits go in the dense list (scan of the counts, 8 tiles per thread and round);
+//  k_sync_gather  a thread per tile: the ordered compaction (A) itself;
+//  k_sync_links   one workgroup per batch of PDT_SYNC_PB dense hits: the successor links (binary search in LDS, and in
+//                 the dense list past the batch's end), then by pointer doubling, for every hit i of the batch, how many
+//                 frames the walk entered at i opens inside the batch (depth) and the first hit behind the batch it
+//                 reaches (exit);
+//  k_sync_mark    one workgroup per batch: the batch's entry and frame base from the chain entry(b + 1) = exit(entry(b)),
+//                 base(b + 1) = base(b) + depth(entry(b)) -- one hop per batch, walked by every workgroup --, then the
+//                 walk from the entry marked by pointer doubling and the marked hits compacted into the frame records.
+// gscr: [0] dense hits, [2, 2 + cap) exit, [2 + cap, 2 + 2 cap) depth (cap = dense_cap).
+#define PDT_SYNC_PB 4096
+#define PDT_SYNC_PT 1024
+__device__ __forceinline__ void k_sync_dense(const SyncTile *__restrict__ tiles, const unsigned long long *__restrict__ nbits_p,
+                                             long long tile_cap, unsigned dense_cap, const unsigned *__restrict__ overflow,
+                                             unsigned *__restrict__ gscr)
 {
-    unsigned nf = *nframes_p;
-    if (nf > frame_cap) nf = frame_cap;
-    const unsigned f = blockIdx.x;
-    if (f >= nf) return;
+    if (*overflow) return;
     const long long nbits = (long long)*nbits_p;
+    long long nt = (nbits + 4095) / 4096;
+    if (nt > tile_cap) nt = tile_cap;                       // (more bits than the capacity: the host reports it)
+    if (nt > (long long)dense_cap) nt = dense_cap;
+    unsigned *toff = gscr + 2;                              // (the exit table's space: k_sync_links writes it afterwards)
+    __shared__ unsigned s_scan[PDT_SYNC_THREADS];
+    __shared__ unsigned s_base;
+    if (threadIdx.x == 0) s_base = 0;
+    constexpr int TPT = 8;                                  // tiles per thread and round
+    for (long long r0 = 0; r0 < nt; r0 += (long long)TPT * PDT_SYNC_THREADS) {
+        const long long first = r0 + (long long)threadIdx.x * TPT;
+        unsigned cnt[TPT], sum = 0;
+#pragma unroll
+        for (int k = 0; k < TPT; k++) {
+            cnt[k] = (first + k < nt) ? tiles[first + k].count : 0u;
+            sum += cnt[k];
+        }
+        const unsigned incl = sync_block_scan(sum, s_scan);      // (its barriers also order s_base)
+        unsigned off = s_base + incl - sum;
+        const unsigned total = s_scan[PDT_SYNC_THREADS - 1];
+#pragma unroll
+        for (int k = 0; k < TPT; k++) {
+            if (first + k < nt) toff[first + k] = off;
+            off += cnt[k];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_base += total;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) gscr[0] = (s_base < dense_cap) ? s_base : dense_cap;
+}
+
+// the tiles' hits to their places in the dense list, a thread per tile (the 128-byte record in eight 16-byte loads)
+__device__ __forceinline__ void k_sync_gather(const SyncTile *__restrict__ tiles, const unsigned long long *__restrict__ nbits_p,
+                                              long long tile_cap, unsigned *__restrict__ dense, unsigned dense_cap,
+                                              const unsigned *__restrict__ overflow, const unsigned *__restrict__ gscr)
+{
+    if (*overflow) return;
+    long long nt = ((long long)*nbits_p + 4095) / 4096;
+    if (nt > tile_cap) nt = tile_cap;
+    if (nt > (long long)dense_cap) nt = dense_cap;
+    const unsigned *toff = gscr + 2;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += (long long)gridDim.x * blockDim.x) {
+        static_assert(sizeof(SyncTile) == 128, "a tile record is eight 16-byte words");
+        const uint4 *rec = reinterpret_cast<const uint4 *>(tiles + t);
+        uint4 w[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) w[k] = rec[k];
+        const unsigned *v = reinterpret_cast<const unsigned *>(w);      // v[0] = count, v[1 + q] = hit q
+        const unsigned cnt = v[0], off = toff[t];
+#pragma unroll
+        for (unsigned q = 0; q < 31; q++)
+            if (q < cnt && off + q < dense_cap) dense[off + q] = v[1 + q];
+    }
+}
+
+// first index k >= from of the dense list with position >= want (nh_all if none): galloping, then binary search
+__device__ __forceinline__ unsigned sync_lower_bound(const unsigned *__restrict__ dense, unsigned nh_all, unsigned from, unsigned want)
+{
+    unsigned lo = from, hi = from, step = 1;
+    for (;;) {                                              // every index below lo holds a position < want
+        if (hi >= nh_all) { hi = nh_all; break; }
+        if ((dense[hi] >> 1) >= want) break;
+        lo = hi + 1;
+        hi = lo + step;
+        step <<= 1;
+    }
+    while (lo < hi) {
+        const unsigned mid = (lo + hi) >> 1;
+        if ((dense[mid] >> 1) >= want) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// the batch's positions into s_pos and its successor links into nxt (batch-local; nh = leaves the batch, then *ext_out
+// receives the global index); returns the batch's hit count
+__device__ __forceinline__ unsigned sync_batch_links(const unsigned *__restrict__ dense, unsigned nh_all, unsigned h0, unsigned span,
+                                                     unsigned *s_pos, unsigned short *nxt, unsigned *ext)
+{
+    const unsigned nh = (nh_all - h0 < PDT_SYNC_PB) ? nh_all - h0 : PDT_SYNC_PB;
+    for (unsigned i = threadIdx.x; i < nh; i += PDT_SYNC_PT) s_pos[i] = dense[h0 + i] >> 1;
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < nh; i += PDT_SYNC_PT) {
+        const unsigned want = s_pos[i] + span;
+        unsigned lo = i + 1, hi = nh;
+        while (lo < hi) {
+            const unsigned mid = (lo + hi) >> 1;
+            if (s_pos[mid] >= want) hi = mid; else lo = mid + 1;
+        }
+        nxt[i] = (unsigned short)lo;
+        ext[i] = (lo < nh) ? 0u : sync_lower_bound(dense, nh_all, h0 + nh, want);
+    }
+    __syncthreads();
+    return nh;
+}
+
+__device__ __forceinline__ void k_sync_links(SyncParams P, const unsigned *__restrict__ dense, const unsigned *__restrict__ overflow,
+                                             unsigned *__restrict__ gscr, unsigned dense_cap)
+{
+    if (*overflow) return;
+    const unsigned nh_all = gscr[0];
+    unsigned *g_exit = gscr + 2, *g_depth = gscr + 2 + dense_cap;
+    __shared__ unsigned s_pos[PDT_SYNC_PB];
+    __shared__ unsigned s_ext[PDT_SYNC_PB];
+    __shared__ unsigned short s_nxt[PDT_SYNC_PB], s_dep[PDT_SYNC_PB];
+    constexpr int PER = PDT_SYNC_PB / PDT_SYNC_PT;
+    for (unsigned h0 = blockIdx.x * PDT_SYNC_PB; h0 < nh_all; h0 += gridDim.x * PDT_SYNC_PB) {
+        const unsigned nh = sync_batch_links(dense, nh_all, h0, P.span, s_pos, s_nxt, s_ext);
+        for (unsigned i = threadIdx.x; i < nh; i += PDT_SYNC_PT) s_dep[i] = 1;
+        __syncthreads();
+        // doubling: after k rounds nxt(i) = succ^(2^k)(i) or nh, dep(i) = frames of the walk from i before nxt(i), ext(i) =
+        // where the walk leaves the batch once nxt(i) = nh
+        for (unsigned reach = 1; reach < nh; reach <<= 1) {
+            unsigned short nn[PER], nd[PER];
+            unsigned ne[PER];
+#pragma unroll
+            for (int k = 0; k < PER; k++) {
+                const unsigned i = threadIdx.x + (unsigned)k * PDT_SYNC_PT;
+                nn[k] = nh; nd[k] = 0; ne[k] = 0;
+                if (i < nh) {
+                    const unsigned j = s_nxt[i];
+                    nn[k] = (unsigned short)j; nd[k] = s_dep[i]; ne[k] = s_ext[i];
+                    if (j < nh) { nn[k] = s_nxt[j]; nd[k] = (unsigned short)(nd[k] + s_dep[j]); ne[k] = s_ext[j]; }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < PER; k++) {
+                const unsigned i = threadIdx.x + (unsigned)k * PDT_SYNC_PT;
+                if (i < nh) { s_nxt[i] = nn[k]; s_dep[i] = nd[k]; s_ext[i] = ne[k]; }
+            }
+            __syncthreads();
+        }
+        for (unsigned i = threadIdx.x; i < nh; i += PDT_SYNC_PT) {
+            g_exit[h0 + i] = s_ext[i];
+            g_depth[h0 + i] = s_dep[i];
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void k_sync_mark(SyncParams P, const unsigned *__restrict__ dense, FrameRec *__restrict__ frames,
+                                            unsigned *__restrict__ nframes, unsigned frame_cap, const unsigned *__restrict__ overflow,
+                                            const unsigned *__restrict__ gscr, unsigned dense_cap)
+{
+    if (*overflow) return;
+    const unsigned nh_all = gscr[0];
+    const unsigned *g_exit = gscr + 2, *g_depth = gscr + 2 + dense_cap;
+    __shared__ unsigned s_pos[PDT_SYNC_PB];
+    __shared__ unsigned s_ext[PDT_SYNC_PB];
+    __shared__ unsigned short s_nxt[2][PDT_SYNC_PB];
+    __shared__ unsigned s_mark[PDT_SYNC_PB / 32];
+    __shared__ unsigned s_scan[PDT_SYNC_PT];
+    __shared__ unsigned s_entry, s_fbase;
+    constexpr int PER = PDT_SYNC_PB / PDT_SYNC_PT;
+    if (blockIdx.x == 0 && nh_all == 0 && threadIdx.x == 0) *nframes = 0;
+    for (unsigned h0 = blockIdx.x * PDT_SYNC_PB; h0 < nh_all; h0 += gridDim.x * PDT_SYNC_PB) {
+        if (threadIdx.x == 0) {                              // the chain of batch entries up to this batch
+            unsigned e = 0, base = 0;
+            for (unsigned b0 = 0; b0 < h0; b0 += PDT_SYNC_PB)
+                if (e < b0 + PDT_SYNC_PB) { base += g_depth[e]; e = g_exit[e]; }     // (else the batch lies inside an open frame)
+            s_entry = e;
+            s_fbase = base;
+            if (h0 + PDT_SYNC_PB >= nh_all) *nframes = base + ((e < nh_all) ? g_depth[e] : 0u);    // the last batch
+        }
+        const unsigned nh = sync_batch_links(dense, nh_all, h0, P.span, s_pos, s_nxt[0], s_ext);   // (its barriers order s_entry)
+        const unsigned entry = s_entry;
+        if (entry >= h0 + nh) { __syncthreads(); continue; }              // (uniform) no frame opens in this batch
+        for (unsigned i = threadIdx.x; i < PDT_SYNC_PB / 32; i += PDT_SYNC_PT) s_mark[i] = 0u;
+        __syncthreads();
+        if (threadIdx.x == 0) s_mark[(entry - h0) >> 5] = 1u << ((entry - h0) & 31);
+        __syncthreads();
+        int cur = 0;
+        for (unsigned reach = 1; reach < nh; reach <<= 1) {
+#pragma unroll
+            for (int k = 0; k < PER; k++) {
+                const unsigned i = threadIdx.x + (unsigned)k * PDT_SYNC_PT;
+                if (i < nh) {
+                    const unsigned jm = s_nxt[cur][i];
+                    if (jm < nh) {
+                        if ((s_mark[i >> 5] >> (i & 31)) & 1u) atomicOr(&s_mark[jm >> 5], 1u << (jm & 31));
+                        s_nxt[cur ^ 1][i] = s_nxt[cur][jm];
+                    } else
+                        s_nxt[cur ^ 1][i] = (unsigned short)nh;
+                }
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        // ordered compaction of the marked hits (thread t owns hits [PER t, PER t + PER))
+        const unsigned i0 = threadIdx.x * PER;
+        unsigned mine = 0;
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const unsigned i = i0 + k;
+            if (i < nh && ((s_mark[i >> 5] >> (i & 31)) & 1u)) mine++;
+        }
+        const unsigned incl = sync_block_scan(mine, s_scan);
+        unsigned at = s_fbase + incl - mine;
+        for (int k = 0; k < PER; k++) {
+            const unsigned i = i0 + k;
+            if (i < nh && ((s_mark[i >> 5] >> (i & 31)) & 1u)) {
+                if (at < frame_cap) {
+                    const unsigned v = dense[h0 + i];
+                    frames[at].bit_index = (long long)(v >> 1);
+                    frames[at].inverted = (unsigned char)(v & 1u);
+                }
+                at++;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void frame_pack_one(const unsigned char *__restrict__ bits, long long nbits,
+                                               const unsigned *__restrict__ bitsym, const long long *__restrict__ symidx,
+                                               const SyncParams &P, FrameRec *__restrict__ frames, unsigned f)
+{
     const long long pos = frames[f].bit_index;
     const unsigned inv = frames[f].inverted;
     const unsigned t = threadIdx.x;
@@ -2790,6 +3185,20 @@ __device__ __forceinline__ void k_frame_pack(const unsigned char *__restrict__ b
         frames[f].pad = 0;
         frames[f].time_src = symidx[bitsym[pos]];
     }
+}
+
+__device__ __forceinline__ void k_frame_pack(const unsigned char *__restrict__ bits,
+                                                     const unsigned long long *__restrict__ nbits_p,
+                                                     const unsigned *__restrict__ bitsym,
+                                                     const long long *__restrict__ symidx, SyncParams P,
+                                                     FrameRec *__restrict__ frames, const unsigned *__restrict__ nframes_p,
+                                                     unsigned frame_cap)
+{
+    unsigned nf = *nframes_p;
+    if (nf > frame_cap) nf = frame_cap;
+    const long long nbits = (long long)*nbits_p;
+    for (unsigned f = blockIdx.x; f < nf; f += gridDim.x)          // (a grid of fixed size: recorded before the frames are counted)
+        frame_pack_one(bits, nbits, bitsym, symidx, P, frames, f);
 }
 
 // What a stream segment hands to the next one, gathered at the end of the segment's kernels into one record (one copy back).

@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 7): single-channel (real) captures through a Hilbert front end -- the sample formats
+/* 4, additions without a bump (round 8): wideband SDR captures through a digital down-converter -- the sample formats
+ * PDT_FMT_WB_PCM16 / _F32 / _CU8 / _CS8, the stage PDT_ST_CHANNEL, pdt_set_channel, pdt_demod_channel, pdt_demod_device_channel,
+ * pdt_demod_channels_device, pdt_demod_channels, pdt_stream_push_channel, pdt_host_ddc; pdt_demod_fd / pdt_demod_file accept the wideband formats.
+ * 4, additions without a bump (round 7): single-channel (real) captures through a Hilbert front end -- the sample formats
  * PDT_FMT_REAL_PCM16 / PDT_FMT_REAL_F32, the stage PDT_ST_ANALYTIC, pdt_set_real_input, pdt_demod_real, pdt_demod_device_real,
  * pdt_stream_push_real, pdt_host_analytic; pdt_demod_fd / pdt_demod_file accept the two real formats.
  * 4 (round 6): a capture that does not fit the device's free memory is demodulated through a bounded window (the streaming
@@ -105,12 +108,17 @@ enum {
                            writes to output.raw (ARGOSdemod/main.c:273-274); equal to PDT_ST_AGC for POES     */
     PDT_ST_ANALYTIC,    /* real captures only: the analytic stream the chain demodulated, float32 I,Q per input sample
                            (pdt_demod_real / pdt_demod_device_real / pdt_demod_fd of a real format in one piece); 0 otherwise */
+    PDT_ST_CHANNEL,     /* wideband captures only: the channel stream the chain demodulated, float32 I,Q per channel sample,
+                           ceil(N / decim) of them (pdt_demod_channel and its kin); 0 otherwise */
     PDT_ST_COUNT
 };
 
 enum { PDT_CHAIN_FILE = 0, PDT_CHAIN_LIVE = 1 };
 enum { PDT_FMT_PCM16 = 0, PDT_FMT_F32 = 1 };   /* interleaved little-endian int16 I,Q pairs / IEEE float32 I,Q pairs */
 enum { PDT_FMT_REAL_PCM16 = 2, PDT_FMT_REAL_F32 = 3 };   /* single channel: one little-endian int16 / float32 sample per frame */
+/* wideband I,Q captures (pdt_set_channel): int16 pairs, float32 pairs, unsigned 8-bit pairs (RTL-SDR), signed 8-bit pairs (HackRF);
+ * the 8-bit formats exist only as wideband formats */
+enum { PDT_FMT_WB_PCM16 = 16, PDT_FMT_WB_F32 = 17, PDT_FMT_WB_CU8 = 18, PDT_FMT_WB_CS8 = 19 };
 
 typedef struct pdt_config {
     int32_t  mode;            /* PDT_MODE_POES / PDT_MODE_ARGOS                                   */
@@ -302,6 +310,9 @@ int  pdt_demod_pcm16(pdt_ctx *ctx, const int16_t *iq_host, uint64_t nframes);
  * streaming path with carried state: same frames, text, counts and reports; pdt_stats.windowed = 1).  The reference's loop
  * takes a file of any length (POESTIPdemod/main.c:373, while(!feof)); so do pdt_demod_fd / _file / _pcm16 / _f32.            */
 /* sample_format PDT_FMT_REAL_PCM16 / _F32 (2 / 4 bytes per frame): a single-channel capture (pdt_demod_real below).         */
+/* sample_format PDT_FMT_WB_* (4 / 8 / 2 / 2 bytes per frame), once pdt_set_channel has been called: a wideband capture of
+ * nframes input frames (pdt_demod_channel below); it is ingested whole, then converted -- never in overlapped segments, and one
+ * that does not fit the device's memory returns PDT_ERR_NOMEM (the bounded window for wideband input does not exist yet).    */
 int  pdt_demod_fd(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, int sample_format);
 /* The whole job of POESTIPdemod/main.c:373-492 / ARGOSdemod/main.c:250-306 in one call: capture file in (as pdt_demod_fd), the
  * minor-frame / packet text out to the descriptor text_fd, from its position on -- the reference's ByteSync.c:62-101 writes
@@ -378,6 +389,45 @@ int  pdt_demod_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_for
 int  pdt_demod_device_real(pdt_ctx *ctx, const void *x_device, uint64_t n, int sample_format);
 int  pdt_stream_push_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format, uint64_t *new_frames);
 int  pdt_host_analytic(uint32_t sample_rate, double center_hz, const void *x, uint64_t n, int sample_format, float *out);
+
+/* Wideband SDR captures: an RTL-SDR, a HackRF or any receiver that records complex samples at Fs_in with the beacon some
+ * hundreds of kHz off centre, perhaps several carriers at once.  The context is opened at the CHANNEL rate; the wideband input is
+ * at Fs_in = decim x sample_rate.  On the GPU the capture x[n] becomes the channel stream
+ *   y[m] = sum_{k = -8 decim .. 8 decim} h[k] x[m decim + k] e^{-j 2 pi p[m decim + k] / 2^32},   0 <= m < ceil(N / decim),
+ * p[n] = step n mod 2^32 on the global sample index, step = round(offset_hz 2^32 / Fs_in), h the Blackman-windowed sinc of
+ * 16 decim + 1 taps with its cut-off at 0.4 of the channel rate (x = 0 outside the capture), and the chain demodulates that stream
+ * exactly as it would a RAW float capture of the same length (POES: pdt_demod_f32; ARGOS: the double chain reading the float
+ * pairs).  Samples are scaled by format: int16 s / 32768, float32 as they are, unsigned 8-bit (u - 127.5) / 128, signed 8-bit
+ * s / 128.  Time stamps are seconds of the channel stream.  The arithmetic is fixed: pdt_host_ddc restates it bit
+ * for bit on the host.
+ *   pdt_set_channel            the channel of this context's wideband captures: PDT_ERR_ARG unless 2 <= decim <= 64 and
+ *                              |offset_hz| < Fs_in / 2; PDT_ERR_STATE while a stream is open
+ *   pdt_demod_channel          a whole wideband capture in host memory, nframes input frames of sample_format (PDT_FMT_WB_*, else
+ *                              PDT_ERR_ARG; PDT_ERR_STATE before pdt_set_channel); results, reports, progress and statistics as for
+ *                              any capture; PDT_ST_CHANNEL = the converted stream.  One that does not fit the device's memory
+ *                              returns PDT_ERR_NOMEM: the bounded window for wideband input does not exist yet
+ *   pdt_demod_device_channel   the same with the samples resident in device memory (only read)
+ *   pdt_demod_channels_device  ONE wideband capture in device memory, `count` contexts with a channel each: the capture is read
+ *                              once by one conversion launch that fills every context's channel stream, then the contexts go
+ *                              through the batched chain (pdt_demod_batch_device's, on float input).  All contexts must have the
+ *                              same decim and live on the same device (else PDT_ERR_ARG); their modes may differ.  Each context
+ *                              ends up holding exactly what pdt_demod_device_channel alone would have produced
+ *   pdt_demod_channels         pdt_demod_channels_device for a capture in host memory: it is copied to the device once, into
+ *                              the first context's input buffer (PDT_ERR_NOMEM when it does not fit)
+ *   pdt_stream_push_channel    append nframes wideband frames to the open stream: the last 8 decim + (pushed mod decim) input
+ *                              samples are held back until their neighbours arrive (pdt_stream_end closes them with zeros;
+ *                              pdt_stream_retained counts them); the frames of the pushes and of the end are those of one
+ *                              pdt_demod_channel call.  A stream takes pushes of one kind and format: mixing them returns
+ *                              PDT_ERR_ARG
+ *   pdt_host_ddc               test hook, host only: out[2 m], out[2 m + 1] = the I,Q pair of channel sample m, as the kernel
+ *                              computes it; in_rate is Fs_in                                                                   */
+int  pdt_set_channel(pdt_ctx *ctx, int decim, double offset_hz);
+int  pdt_demod_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format);
+int  pdt_demod_device_channel(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format);
+int  pdt_demod_channels_device(pdt_ctx *const *ctxs, int count, const void *iq_device, uint64_t nframes, int sample_format);
+int  pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uint64_t nframes, int sample_format);
+int  pdt_stream_push_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, uint64_t *new_frames);
+int  pdt_host_ddc(uint32_t in_rate, int decim, double offset_hz, const void *x, uint64_t n, int sample_format, float *out);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

@@ -30,8 +30,12 @@ LIBSYNTH_PATH = os.path.join(_HERE, "synth", "libpdtsynth.so")
 MODE_POES, MODE_ARGOS = 0, 1
 SAMPLER_GARDNER, SAMPLER_MM = 0, 1
 CHAIN_FILE, CHAIN_LIVE = 0, 1          # CHAIN_LIVE: the sound-card twin's constants and stage order (POES)
-ST_PLL, ST_LOCK, ST_FIR, ST_AGC, ST_SYM, ST_SYMIDX, ST_BITS, ST_BITSYM, ST_AGC_RAW, ST_ANALYTIC = range(10)
+ST_PLL, ST_LOCK, ST_FIR, ST_AGC, ST_SYM, ST_SYMIDX, ST_BITS, ST_BITSYM, ST_AGC_RAW, ST_ANALYTIC, ST_CHANNEL = range(11)
 FMT_PCM16, FMT_F32, FMT_REAL_PCM16, FMT_REAL_F32 = range(4)    # I,Q int16 / I,Q float32 / one int16 / one float32 per frame
+
+
+# wideband I,Q captures (set_channel): int16 pairs / float32 pairs / unsigned 8-bit pairs / signed 8-bit pairs
+FMT_WB_PCM16, FMT_WB_F32, FMT_WB_CU8, FMT_WB_CS8 = range(16, 20)
 
 
 class PdtError(RuntimeError):
@@ -172,6 +176,7 @@ ABI_SYMBOLS = [
     "pdt_keep_presquelch", "pdt_keep_pll", "pdt_stage_bytesync_from", "pdt_demod_fd", "pdt_format_records", "pdt_stream_retained", "pdt_host_math", "pdt_get_device",
     "pdt_write_frames", "pdt_write_records", "pdt_demod_file", "pdt_set_loop_params", "pdt_set_progress",
     "pdt_set_real_input", "pdt_demod_real", "pdt_demod_device_real", "pdt_stream_push_real", "pdt_host_analytic",
+    "pdt_set_channel", "pdt_demod_channel", "pdt_demod_device_channel", "pdt_demod_channels_device", "pdt_demod_channels", "pdt_stream_push_channel", "pdt_host_ddc",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows"]        # include/pdt_dev.h (test-only)
 
@@ -295,6 +300,13 @@ def lib():
     L.pdt_demod_device_real.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
     L.pdt_stream_push_real.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_host_analytic.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+    L.pdt_set_channel.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    L.pdt_demod_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+    L.pdt_demod_device_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+    L.pdt_demod_channels_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_uint64, C.c_int]
+    L.pdt_demod_channels.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_uint64, C.c_int]
+    L.pdt_stream_push_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    L.pdt_host_ddc.argtypes = [C.c_uint32, C.c_int, C.c_double, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
     if L.pdt_abi_version() != 4:
         raise PdtError("libpdt.so ABI version mismatch")
     _lib = L
@@ -344,6 +356,29 @@ def host_analytic(sample_rate: int, center_hz: float, x: np.ndarray) -> np.ndarr
     a, fmt = _real_samples(x)
     out = np.zeros((a.size, 2), dtype=np.float32)
     _check(lib().pdt_host_analytic(sample_rate, float(center_hz), a.ctypes.data, a.size, fmt, out.ctypes.data), "pdt_host_analytic")
+    return out
+
+
+def _wb_samples(x: np.ndarray) -> tuple[np.ndarray, int]:
+    """A wideband I,Q capture as the library takes it, by dtype: uint8 pairs (FMT_WB_CU8), int8 pairs (FMT_WB_CS8), float pairs as
+    little-endian float32 (FMT_WB_F32), anything else as little-endian int16 pairs (FMT_WB_PCM16).  Returns the flat array."""
+    dt = np.asarray(x).dtype
+    if dt == np.uint8:
+        return np.ascontiguousarray(x).reshape(-1), FMT_WB_CU8
+    if dt == np.int8:
+        return np.ascontiguousarray(x).reshape(-1), FMT_WB_CS8
+    if dt.kind == "f":
+        return np.ascontiguousarray(x, dtype="<f4").reshape(-1), FMT_WB_F32
+    return np.ascontiguousarray(x, dtype="<i2").reshape(-1), FMT_WB_PCM16
+
+
+def host_ddc(in_rate: int, decim: int, offset_hz: float, x: np.ndarray) -> np.ndarray:
+    """pdt_host_ddc: the down-converter of wideband captures restated on the host (no GPU), bit for bit what the kernel computes.
+    x: I,Q pairs at in_rate (uint8, int8, int16 or float32).  Returns float32[ceil(n / decim), 2] at in_rate / decim."""
+    a, fmt = _wb_samples(x)
+    n = a.size // 2
+    out = np.zeros(((n + decim - 1) // decim if decim > 0 else 0, 2), dtype=np.float32)
+    _check(lib().pdt_host_ddc(in_rate, decim, float(offset_hz), a.ctypes.data, n, fmt, out.ctypes.data), "pdt_host_ddc")
     return out
 
 
@@ -501,6 +536,22 @@ class Demodulator:
         _check(self._L.pdt_demod_device_real(self._h, C.c_void_p(dev_ptr), n, fmt), "pdt_demod_device_real")
         return self
 
+    def set_channel(self, decim: int, offset_hz: float):
+        """The channel of this context's wideband captures: input at decim x the context's rate, the carrier offset_hz from centre."""
+        _check(self._L.pdt_set_channel(self._h, int(decim), float(offset_hz)), "pdt_set_channel")
+        return self
+
+    def demod_channel(self, x: np.ndarray):
+        """Wideband I,Q capture in host memory: uint8, int8, int16 or float32 pairs at decim x the context's rate."""
+        a, fmt = _wb_samples(x)
+        _check(self._L.pdt_demod_channel(self._h, a.ctypes.data, a.size // 2, fmt), "pdt_demod_channel")
+        return self
+
+    def demod_device_channel(self, dev_ptr: int, nframes: int, fmt: int = FMT_WB_PCM16):
+        """Wideband capture resident in HBM (nframes I,Q frames of FMT_WB_*)."""
+        _check(self._L.pdt_demod_device_channel(self._h, C.c_void_p(dev_ptr), nframes, fmt), "pdt_demod_device_channel")
+        return self
+
     def demod_device(self, dev_ptr: int, nframes: int):
         """Input already resident in HBM (e.g. ``tensor.data_ptr()`` of an int16 torch tensor)."""
         _check(self._L.pdt_demod_device(self._h, C.c_void_p(dev_ptr), nframes), "pdt_demod_device")
@@ -646,7 +697,7 @@ class Demodulator:
         if count is None:
             count = max(total - first, 0)
         dt = {ST_SYMIDX: np.int64, ST_BITS: np.uint8, ST_BITSYM: np.uint32}.get(st, self.dtype)
-        if st == ST_ANALYTIC:
+        if st in (ST_ANALYTIC, ST_CHANNEL):
             out = np.zeros((count, 2), dtype=np.float32)
             if count:
                 got = self._L.pdt_read_stage(self._h, st, first, count, out.ctypes.data)
@@ -691,6 +742,13 @@ class Demodulator:
         _check(self._L.pdt_stream_push_real(self._h, a.ctypes.data, a.size, fmt, C.byref(n)), "pdt_stream_push_real")
         return self._stream_new(n.value)
 
+    def stream_push_channel(self, x: np.ndarray) -> np.ndarray:
+        """Append wideband I,Q frames (uint8, int8, int16 or float32 pairs); returns the frames that became final with them."""
+        n = C.c_uint64(0)
+        a, fmt = _wb_samples(x)
+        _check(self._L.pdt_stream_push_channel(self._h, a.ctypes.data, a.size // 2, fmt, C.byref(n)), "pdt_stream_push_channel")
+        return self._stream_new(n.value)
+
     def stream_end(self) -> np.ndarray:
         """The capture is over: returns the remaining frames; text()/stats()/frames_array() then describe all of it."""
         n = C.c_uint64(0)
@@ -729,6 +787,19 @@ def demod_batch(demods, dev_ptrs, nframes):
     ps = (C.c_void_p * max(n, 1))(*[C.c_void_p(int(p)) for p in dev_ptrs])
     ns = (C.c_uint64 * max(n, 1))(*[int(v) for v in nframes])
     _check(lib().pdt_demod_batch_device(hs, ps, ns, n), "pdt_demod_batch_device")
+
+
+def demod_channels(demods, dev_ptr, nframes: int = 0, fmt: int = FMT_WB_PCM16):
+    """Several channels of ONE wideband capture: demods[i] (each with its set_channel, all of one decim) demodulates its channel;
+    the capture is read once by one conversion launch, then the contexts share the batched chain.  dev_ptr: the address of the
+    capture in HBM (nframes I,Q frames of fmt), or a numpy array of I,Q pairs in host memory (pdt_demod_channels)."""
+    n = len(demods)
+    hs = (C.c_void_p * max(n, 1))(*[d._h for d in demods])
+    if isinstance(dev_ptr, np.ndarray):
+        a, fmt = _wb_samples(dev_ptr)
+        _check(lib().pdt_demod_channels(hs, n, a.ctypes.data, a.size // 2, fmt), "pdt_demod_channels")
+        return
+    _check(lib().pdt_demod_channels_device(hs, n, C.c_void_p(int(dev_ptr)), int(nframes), fmt), "pdt_demod_channels_device")
 
 
 FRAME_DTYPE = np.dtype([

@@ -2,6 +2,7 @@
 // include/pdt.h.  Compiled for gfx950 only, with -ffp-contract=off (see pdt_device_math.h).
 #include "pdt_rt.h"
 #include "pdt_analytic.h"
+#include "pdt_ddc.h"
 
 #include <pthread.h>
 #include <sched.h>
@@ -16,6 +17,9 @@ std::atomic<long long> g_alloc_ns{0};
 // pdt_analytic.hip
 hipError_t analytic_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
                            uint32_t step, const float *tab_dev, void *out);
+// pdt_ddc.hip
+hipError_t ddc_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
+                      int decim, const float *taps_dev, const float *tab_dev, const uint32_t *steps, void *const *outs, int k);
 }  // namespace pdtrt
 
 static std::atomic<int> g_open_contexts{0};          // contexts alive in this process (pdt_open / pdt_close)
@@ -944,7 +948,8 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->hits, &ctx->frames, &ctx->taps, &ctx->mag, &ctx->seams_pll, &ctx->seams_agc, &ctx->scal, &ctx->lockinfo,
                        &ctx->term, &ctx->seams_ema, &ctx->gtable, &ctx->gentries, &ctx->gcand,
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
-                       &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->rbuf[0], &ctx->rbuf[1] };
+                       &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->rbuf[0], &ctx->rbuf[1],
+                       &ctx->ddc_taps, &ctx->channel, &ctx->cbuf[0], &ctx->cbuf[1] };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1056,6 +1061,10 @@ static int demod_common(pdt_ctx *ctx, uint64_t nframes, int phase = RUN_ALL)
     ctx->n_out = nframes * ctx->interp;
     ctx->stage_len[PDT_ST_ANALYTIC] = ctx->analytic_len;             // (a real capture's entry sets it just before; 0 otherwise)
     ctx->analytic_len = 0;
+    if (phase != RUN_FINISH) {                                       // (a wideband capture's entry sets it just before; 0 otherwise)
+        ctx->stage_len[PDT_ST_CHANNEL] = ctx->channel_len;
+        ctx->channel_len = 0;
+    }
     if (ctx->elem == 8) return run_capture<double>(ctx, nframes, phase);
     return run_capture<float>(ctx, nframes, phase);                 // POES, both twins
 }
@@ -1064,6 +1073,7 @@ static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes
 static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes, uint64_t piece);
 static uint64_t stream_history(const pdt_ctx *ctx);
 static int demod_real_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt);
+static int demod_channel_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt);
 
 // ---------------------------------------------------------------- real (single-channel) input (pdt_analytic.h)
 static bool real_fmt(int fmt) { return fmt == PDT_FMT_REAL_PCM16 || fmt == PDT_FMT_REAL_F32; }
@@ -1205,6 +1215,14 @@ int pdt_demod_fd(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, i
         src.off = byte_offset;
         return demod_real_src(ctx, src, nframes, sample_format);
     }
+    if (ctx && fd >= 0 && ddc_fmt(sample_format)) {                  // wideband: ingested whole, then converted
+        if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
+        HIP_TRY(hipSetDevice(ctx->cfg.device));
+        IngestSrc src;
+        src.fd = fd;
+        src.off = byte_offset;
+        return demod_channel_src(ctx, src, nframes, sample_format);
+    }
     if (!ctx || fd < 0 || (sample_format != PDT_FMT_PCM16 && sample_format != PDT_FMT_F32)) return PDT_ERR_ARG;
     if (sample_format == PDT_FMT_F32 && ctx->elem != 4) return PDT_ERR_FORMAT;   // ARGOSdemod/main.c:238-241
     HIP_TRY(hipSetDevice(ctx->cfg.device));
@@ -1328,6 +1346,187 @@ int pdt_demod_device_real(pdt_ctx *ctx, const void *x_device, uint64_t n, int sa
     if (ctx->stream_open) return PDT_ERR_STATE;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     return demod_real_resident(ctx, x_device, n, sample_format);
+}
+
+// ---------------------------------------------------------------- wideband input (pdt_ddc.h)
+int pdt_set_channel(pdt_ctx *ctx, int decim, double offset_hz)
+{
+    if (!ctx || decim < DDC_MIN_DECIM || decim > DDC_MAX_DECIM) return PDT_ERR_ARG;
+    const double in_rate = (double)decim * (double)ctx->cfg.sample_rate;
+    if (!(std::isfinite(offset_hz) && std::fabs(offset_hz) < 0.5 * in_rate)) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    ctx->ch_decim = decim;
+    ctx->ch_offset = offset_hz;
+    ctx->ch_step = ddc_step(in_rate, offset_hz);
+    return PDT_OK;
+}
+
+// the rotation table and the channel filter's taps on the device (once per context and decimation)
+static int channel_tables(pdt_ctx *ctx)
+{
+    int rc = real_table(ctx);
+    if (rc) return rc;
+    if (ctx->ddc_taps.p && ctx->ddc_taps_decim == ctx->ch_decim) return PDT_OK;
+    const std::vector<float> taps = ddc_taps(ctx->ch_decim);
+    if ((rc = ctx->ddc_taps.ensure(taps.size() * sizeof(float) + 16))) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                      // (a launch that reads the previous taps may be in flight)
+    HIP_TRY(hipMemcpy(ctx->ddc_taps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+    ctx->ddc_taps_decim = ctx->ch_decim;
+    return PDT_OK;
+}
+
+static uint64_t channel_count(const pdt_ctx *ctx, uint64_t n) { return (n + (uint64_t)ctx->ch_decim - 1) / (uint64_t)ctx->ch_decim; }
+
+// n_new input samples have landed behind the kept ones of a wideband stream (cbuf[ccur] = cl left halo | cp pending | new):
+// produce every channel sample whose right halo is there -- floor(pushed / D) - 8 of them so far, ceil(pushed / D) when the
+// stream ends (zeros beyond) --, append them to the stream's window, keep 8 D samples to the left of the next output and
+// everything from it on
+static int channel_convert(pdt_ctx *ctx, uint64_t n_new, bool final_piece)
+{
+    int rc = channel_tables(ctx);
+    if (rc) return rc;
+    const uint64_t D = (uint64_t)ctx->ch_decim, span = (uint64_t)DDC_SPAN * D;
+    const size_t fb = (size_t)ddc_bytes(ctx->stream_wb);
+    const uint64_t base = ctx->ch_out * D;                            // global input index the next output is centred on
+    const uint64_t total_in = ctx->ch_in + n_new;
+    const uint64_t outs = final_piece ? (total_in + D - 1) / D : (total_in / D > (uint64_t)DDC_SPAN ? total_in / D - DDC_SPAN : 0);
+    const uint64_t m = outs > ctx->ch_out ? outs - ctx->ch_out : 0;
+    if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + m) + 64) * 8, (size_t)ctx->stream_have * 8))) return rc;
+    const unsigned char *x = (const unsigned char *)ctx->cbuf[ctx->ccur].p + (size_t)ctx->cl * fb;
+    void *out = (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * 8;
+    HIP_TRY(ddc_launch(ctx->stream, ctx->stream_wb, x, -(long long)ctx->cl, (long long)(ctx->cp + n_new), m, base, ctx->ch_decim,
+                       (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p, &ctx->ch_step, &out, 1));
+    const uint64_t nbase = (ctx->ch_out + m) * D;
+    if (!final_piece) {
+        const uint64_t keep_left = std::min<uint64_t>(span, nbase), start = nbase - keep_left - (base - ctx->cl), keep = total_in - (nbase - keep_left);
+        if (start) {
+            DevBuf &dst = ctx->cbuf[ctx->ccur ^ 1];
+            if ((rc = dst.ensure((size_t)(keep + 64) * fb))) return rc;
+            if (keep)
+                HIP_TRY(hipMemcpyAsync(dst.p, (const unsigned char *)ctx->cbuf[ctx->ccur].p + (size_t)start * fb, (size_t)keep * fb,
+                                       hipMemcpyDeviceToDevice, ctx->stream));
+            ctx->ccur ^= 1;
+        }
+        ctx->cl = keep_left;
+        ctx->cp = total_in - nbase;
+    } else {
+        ctx->cl = ctx->cp = 0;
+    }
+    ctx->ch_in = total_in;
+    ctx->ch_out += m;
+    ctx->stream_have += m;
+    ctx->stream_total += m;
+    return PDT_OK;
+}
+
+// a whole wideband capture whose samples are resident at x: convert into this context's channel buffer
+static int channel_prepare(pdt_ctx *ctx, uint64_t n)
+{
+    int rc = ctx->channel.ensure((size_t)channel_count(ctx, n) * 8 + 16);
+    if (rc) return rc;
+    return channel_tables(ctx);
+}
+
+static int demod_channel_resident(pdt_ctx *ctx, const void *x, uint64_t n, int fmt)
+{
+    int rc = channel_prepare(ctx, n);
+    if (rc) return rc;
+    const uint64_t m = channel_count(ctx, n);
+    void *out = ctx->channel.p;
+    HIP_TRY(ddc_launch(ctx->stream, fmt, x, 0, (long long)n, m, 0, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
+                       &ctx->ch_step, &out, 1));
+    ctx->pcm_dev = ctx->channel.p;
+    ctx->pcm_fmt = 1;
+    ctx->channel_len = m;
+    return demod_common(ctx, m);
+}
+
+// host memory or a file: ingest + convert + chain; PDT_ERR_NOMEM when the capture does not fit (no bounded window yet)
+static int demod_channel_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt)
+{
+    const size_t fb = (size_t)ddc_bytes(fmt);
+    // per channel sample: D input frames and the float pair, beside what the chain keeps
+    if (window_piece_for(ctx, channel_count(ctx, n), fb * (size_t)ctx->ch_decim + 8) != 0) return PDT_ERR_NOMEM;
+    int rc = ctx->pcm.ensure((size_t)n * fb + 16);
+    if (rc) return rc;
+    const auto t_in = std::chrono::steady_clock::now();
+    if ((rc = ingest_capture(ctx, src, (size_t)n * fb, ctx->pcm.p))) return rc;
+    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+    rc = demod_channel_resident(ctx, ctx->pcm.p, n, fmt);
+    ctx->stats.ingest_ms = ctx->ingest_ms;
+    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
+    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
+    return rc;
+}
+
+int pdt_demod_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format)
+{
+    if (!ctx || (!iq_host && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
+    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    IngestSrc src;
+    src.mem = (const unsigned char *)iq_host;
+    return demod_channel_src(ctx, src, nframes, sample_format);
+}
+
+int pdt_demod_device_channel(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format)
+{
+    if (!ctx || (!iq_device && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
+    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    return demod_channel_resident(ctx, iq_device, nframes, sample_format);
+}
+
+static int demod_batch(pdt_ctx *const *ctxs, const void *const *iq_device, const uint64_t *nframes, int count, int fmt);
+
+int pdt_demod_channels_device(pdt_ctx *const *ctxs, int count, const void *iq_device, uint64_t nframes, int sample_format)
+{
+    if (count < 0 || (count && !ctxs) || (!iq_device && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++) {
+        if (!ctxs[i]) return PDT_ERR_ARG;
+        if (ctxs[i]->stream_open || !ctxs[i]->ch_decim) return PDT_ERR_STATE;
+        if (ctxs[i]->ch_decim != ctxs[0]->ch_decim || ctxs[i]->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == ctxs[i]) return PDT_ERR_ARG;               // one context per channel
+    }
+    if (!count) return PDT_OK;
+    pdt_ctx *c0 = ctxs[0];
+    HIP_TRY(hipSetDevice(c0->cfg.device));
+    const uint64_t m = channel_count(c0, nframes);
+    std::vector<uint32_t> steps((size_t)count);
+    std::vector<void *> outs((size_t)count);
+    std::vector<uint64_t> lens((size_t)count, m);
+    for (int i = 0; i < count; i++) {
+        int rc = i ? ctxs[i]->channel.ensure((size_t)m * 8 + 16) : channel_prepare(c0, nframes);
+        if (rc) return rc;
+        steps[(size_t)i] = ctxs[i]->ch_step;
+        outs[(size_t)i] = ctxs[i]->channel.p;
+    }
+    // one read of the wideband capture for every channel, then the batched chain on the float pairs (the groups of the batch run
+    // on their leaders' streams: they start when the conversion is over)
+    HIP_TRY(ddc_launch(c0->stream, sample_format, iq_device, 0, (long long)nframes, m, 0, c0->ch_decim, (const float *)c0->ddc_taps.p,
+                       (const float *)c0->an_tab.p, steps.data(), outs.data(), count));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    for (int i = 0; i < count; i++) ctxs[i]->channel_len = m;
+    return demod_batch(ctxs, (const void *const *)outs.data(), lens.data(), count, 1);
+}
+
+int pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uint64_t nframes, int sample_format)
+{
+    if (count < 0 || (count && !ctxs) || (!iq_host && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
+    if (!count) return PDT_OK;
+    pdt_ctx *c0 = ctxs[0];
+    if (!c0) return PDT_ERR_ARG;
+    if (c0->stream_open || !c0->ch_decim) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(c0->cfg.device));
+    const size_t bytes = (size_t)nframes * (size_t)ddc_bytes(sample_format);
+    if (window_piece_for(c0, channel_count(c0, nframes), (size_t)ddc_bytes(sample_format) * (size_t)c0->ch_decim + 8) != 0) return PDT_ERR_NOMEM;
+    int rc = c0->pcm.ensure(bytes + 16);
+    if (rc) return rc;
+    IngestSrc src;
+    src.mem = (const unsigned char *)iq_host;
+    if ((rc = ingest_capture(c0, src, bytes, c0->pcm.p))) return rc;
+    return pdt_demod_channels_device(ctxs, count, c0->pcm.p, nframes, sample_format);
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)
@@ -1493,6 +1692,12 @@ int pdt_stage_fir(pdt_ctx *ctx, const void *in_host, uint64_t n, pdt_fir_state *
 // ---------------------------------------------------------------- batched many-capture mode
 int pdt_demod_batch_device(pdt_ctx *const *ctxs, const void *const *iq_device, const uint64_t *nframes, int count)
 {
+    return demod_batch(ctxs, iq_device, nframes, count, 0);
+}
+
+// fmt: 0 = int16 pairs, 1 = float32 pairs (the channel streams of pdt_demod_channels_device)
+static int demod_batch(pdt_ctx *const *ctxs, const void *const *iq_device, const uint64_t *nframes, int count, int fmt)
+{
     if (count < 0 || (count && (!ctxs || !iq_device || !nframes))) return PDT_ERR_ARG;
     for (int i = 0; i < count; i++) {
         if (!ctxs[i] || (!iq_device[i] && nframes[i])) return PDT_ERR_ARG;
@@ -1506,7 +1711,7 @@ int pdt_demod_batch_device(pdt_ctx *const *ctxs, const void *const *iq_device, c
         c->batch_hint = 0;
         for (int k = 0; k < count; k++) c->batch_hint += (ctxs[k]->cfg.device == c->cfg.device) ? 1 : 0;
         c->pcm_dev = iq_device[enq];
-        c->pcm_fmt = 0;
+        c->pcm_fmt = fmt;
         const int rc = demod_common(c, nframes[enq], RUN_ENQUEUE);
         if (rc) { first_err = rc; break; }
     }
@@ -1547,6 +1752,8 @@ int pdt_stream_begin(pdt_ctx *ctx)
     ctx->stream_fmt = -1;
     ctx->stream_real = 0;
     ctx->rl = ctx->rp = ctx->real_done = 0;
+    ctx->stream_wb = 0;
+    ctx->cl = ctx->cp = ctx->ch_in = ctx->ch_out = 0;
     ctx->stream_open = false;
     ctx->stream_new.clear();
     ctx->frames_host.clear();
@@ -1975,6 +2182,8 @@ static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, 
     ctx->stream_fmt = -1;
     ctx->stream_real = 0;
     ctx->rl = ctx->rp = ctx->real_done = 0;
+    ctx->stream_wb = 0;
+    ctx->cl = ctx->cp = ctx->ch_in = ctx->ch_out = 0;
     ctx->stream_open = false;
     return rc;
 }
@@ -1992,6 +2201,11 @@ int pdt_demod_file(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes,
             src.off = byte_offset;
             return piece < 0 ? (int)piece : demod_windowed(ctx, src, nframes, sample_format, text_fd, text_bytes, (uint64_t)piece);
         }
+        const int rc = pdt_demod_fd(ctx, fd, byte_offset, nframes, sample_format);
+        if (rc) return rc;
+        return pdt_write_frames(ctx, text_fd, text_bytes);
+    }
+    if (ctx && fd >= 0 && text_fd >= 0 && ddc_fmt(sample_format)) {
         const int rc = pdt_demod_fd(ctx, fd, byte_offset, nframes, sample_format);
         if (rc) return rc;
         return pdt_write_frames(ctx, text_fd, text_bytes);
@@ -2029,7 +2243,7 @@ static int stream_push(pdt_ctx *ctx, const void *host, uint64_t nframes, int fmt
         if (rb) return rb;
         ctx->stream_open = true;
     }
-    if (ctx->stream_real) return PDT_ERR_ARG;        // (a stream of real pushes)
+    if (ctx->stream_real || ctx->stream_wb) return PDT_ERR_ARG;      // (a stream of real or of wideband pushes)
     if (ctx->stream_fmt >= 0 && ctx->stream_fmt != fmt) return PDT_ERR_STATE;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     ctx->stream_fmt = fmt;
@@ -2071,7 +2285,7 @@ static int stream_push_real(pdt_ctx *ctx, const void *host, uint64_t n, int fmt,
         if (rb) return rb;
         ctx->stream_open = true;
     }
-    if (ctx->stream_fmt >= 0 && ctx->stream_real != fmt) return PDT_ERR_ARG;     // I,Q pushes, or real ones of the other format
+    if (ctx->stream_fmt >= 0 && ctx->stream_real != fmt) return PDT_ERR_ARG;     // I,Q or wideband pushes, or real ones of the other format
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     ctx->stream_fmt = 1;
     ctx->stream_real = fmt;
@@ -2101,11 +2315,40 @@ int pdt_stream_push_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sampl
     return stream_push_real(ctx, x_host, n, sample_format, new_frames);
 }
 
+int pdt_stream_push_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, uint64_t *new_frames)
+{
+    if (new_frames) *new_frames = 0;
+    if (!ctx || (!iq_host && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
+    if (!ctx->ch_decim) return PDT_ERR_STATE;
+    if (!ctx->stream_open) {
+        int rb = pdt_stream_begin(ctx);
+        if (rb) return rb;
+        ctx->stream_open = true;
+    }
+    if (ctx->stream_fmt >= 0 && ctx->stream_wb != sample_format) return PDT_ERR_ARG;     // pushes of another kind or format
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    ctx->stream_fmt = 1;
+    ctx->stream_wb = sample_format;
+    ctx->stream_new.clear();
+    const size_t fb = (size_t)ddc_bytes(sample_format);
+    int rc = ctx->cbuf[ctx->ccur].ensure_keep((size_t)(ctx->cl + ctx->cp + nframes + 64) * fb, (size_t)(ctx->cl + ctx->cp) * fb);
+    if (rc) return rc;
+    if (nframes)
+        HIP_TRY(hipMemcpyAsync((unsigned char *)ctx->cbuf[ctx->ccur].p + (size_t)(ctx->cl + ctx->cp) * fb, iq_host, (size_t)nframes * fb,
+                               hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = channel_convert(ctx, nframes, false))) return rc;
+    return stream_advance(ctx, nframes, new_frames);
+}
+
 int pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames)
 {
     if (!ctx) return PDT_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     ctx->stream_open = false;                        // (whatever happens below, the stream is over)
+    if (ctx->stream_wb) {                            // the held-back samples, closed with zeros
+        const int rr = channel_convert(ctx, 0, true);
+        if (rr) return rr;
+    }
     if (ctx->stream_real) {                          // the held-back samples, closed with zeros
         const int rr = real_convert(ctx, 0, true);
         if (rr) return rr;
@@ -2130,7 +2373,7 @@ int pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames)
     return rc;
 }
 
-uint64_t pdt_stream_retained(const pdt_ctx *ctx) { return ctx ? ctx->stream_have + ctx->rp : 0; }
+uint64_t pdt_stream_retained(const pdt_ctx *ctx) { return ctx ? ctx->stream_have + ctx->rp + ctx->cp : 0; }
 
 uint64_t pdt_stream_frames(const pdt_ctx *ctx, pdt_frame *out, uint64_t max_frames)
 {
@@ -2401,6 +2644,7 @@ int64_t pdt_read_stage(const pdt_ctx *ctx, int stage, uint64_t first, uint64_t c
     case PDT_ST_BITS: src = ctx->bits.p; es = 1; break;
     case PDT_ST_BITSYM: src = ctx->bitsym.p; es = 4; break;
     case PDT_ST_ANALYTIC: src = ctx->analytic.p; es = 8; break;
+    case PDT_ST_CHANNEL: src = ctx->channel.p; es = 8; break;
     }
     if (!src) return PDT_ERR_STATE;
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;

@@ -398,6 +398,17 @@ struct pdt_ctx {
     int stream_real = 0;                // 0 = I,Q stream (or none), PDT_FMT_REAL_PCM16 / _F32 = the stream takes real pushes
     uint64_t rl = 0, rp = 0, real_done = 0;
     uint64_t analytic_len = 0;          // length of PDT_ST_ANALYTIC the next demod_common reports
+    // wideband input (pdt_ddc.h): the channel's decimation, offset and phase step, the filter's taps on the device, the channel
+    // stream of a whole capture; a stream of wideband pushes keeps its last input samples in cbuf[ccur]: cl already used ones (the
+    // next output's left halo), then cp pending ones from the sample the next output is centred on, then the new ones
+    int ch_decim = 0;                   // 0 = pdt_set_channel has not been called
+    double ch_offset = 0;
+    uint32_t ch_step = 0;
+    DevBuf ddc_taps, channel, cbuf[2];
+    int ddc_taps_decim = 0, ccur = 0;
+    int stream_wb = 0;                  // 0 = not a wideband stream, PDT_FMT_WB_* = the stream takes wideband pushes of that format
+    uint64_t cl = 0, cp = 0, ch_in = 0, ch_out = 0;     // (ch_in input samples pushed, ch_out channel samples produced)
+    uint64_t channel_len = 0;           // length of PDT_ST_CHANNEL the next demod_common reports
     unsigned char *seg_pin = nullptr;   // pinned staging for the small per-segment transfers (part of the pend_sc block)
     pdt_stats stats;
     std::vector<pdt_kernel_time> ktimes;

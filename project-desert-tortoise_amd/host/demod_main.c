@@ -35,6 +35,13 @@
  * (pdt_set_real_input / pdt_demod_file with PDT_FMT_REAL_*): a mono 16-bit WAV, for POES also a mono float32 .raw
  * (-s), and with -l and the file name "-" mono float32 blocks from standard input.  A 2-channel file is refused under -f;
  * without -f a mono file is refused as before.
+ * -x <decim> with one or more -t <kHz> (an addition): the input is a wideband I,Q capture (RTL-SDR, HackRF, ...) at decim times the
+ * channel rate, the beacon -t kHz (signed) off its centre; the library tunes, filters and decimates on the GPU
+ * (pdt_set_channel / PDT_FMT_WB_*).  The WAV header's rate, or -s in kHz, is the WIDEBAND rate and must be divisible by
+ * decim; files named .cu8 / .cs8 are headerless unsigned / signed 8-bit pairs (-s required).  With several -t the channels share
+ * one read of the capture (pdt_demod_channels) and each writes its own file, the channel's index appended to the usual name
+ * (".0", ".1", ...).  -l -x .. -t .. - reads blocks from standard input through pdt_stream_push_channel, in the format -F names
+ * (cu8, the default, cs8, s16 or f32).  Without -x nothing changes, the refusal of rates above 300 kHz included.
  */
 #include <ctype.h>
 #include <math.h>
@@ -51,14 +58,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:"    /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -172,9 +179,10 @@ static void put_frames(FILE *out, const pdt_frame *f, uint64_t n)
 /* The twin's loop (POESTIPdemodPortAudio/main.c:324-393, ARGOSdemodPortAudio/main.c:266-329) with standard input as the sound card: blocks of `chunk`
  * float32 I,Q frames until end of file (there: until a key is hit); frames are appended as they become final. */
 static int live_loop(FILE *in, FILE *out, const char *outFileName, double sampleRate, unsigned long chunk, double normFactor,
-                     int device, int sampler, int real, double realCenterHz)
+                     int device, int sampler, int real, double realCenterHz, int decim, double offsetHz, int wbFormat)
 {
     if (sampleRate < 1) sampleRate = 48.0;                            /* twin: SAMPLE_RATE 48000 (main.c:27) */
+    if (decim) sampleRate /= decim;                                   /* -x: -s is the wideband rate, the context runs at the channel's */
     pdt_config cfg;
     memset(&cfg, 0, sizeof cfg);
 #ifdef PDT_ARGOS
@@ -200,6 +208,13 @@ static int live_loop(FILE *in, FILE *out, const char *outFileName, double sample
         printf("Centre frequency %0.3f kHz must lie between 0 and half the sample rate\n", realCenterHz / 1000.0);
         return 1;
     }
+    if (decim && pdt_set_channel(ctx, decim, offsetHz) != PDT_OK) {
+        printf("Decimation must be 2 .. 64 and the offset %0.3f kHz below half the wideband rate\n", offsetHz / 1000.0);
+        return 1;
+    }
+    const size_t wbBytes = wbFormat == PDT_FMT_WB_PCM16 ? 4 : wbFormat == PDT_FMT_WB_F32 ? 8 : 2;
+    const size_t inFrame = decim ? wbBytes : (real ? 1 : 2) * sizeof(float);        /* -f: mono float32 samples */
+    if (decim) chunk *= (unsigned long)decim;                         /* (blocks of one chunk of the channel) */
     float *block = (float *)malloc(sizeof(float) * 2 * chunk);
     pdt_frame *fr = NULL;
     uint64_t cap = 0, total = 0, samples = 0, fresh = 0;
@@ -208,9 +223,9 @@ static int live_loop(FILE *in, FILE *out, const char *outFileName, double sample
         return 1;
     }
     for (;;) {
-        const size_t got = fread(block, (real ? 1 : 2) * sizeof(float), chunk, in);     /* -f: mono float32 samples */
+        const size_t got = fread(block, inFrame, chunk, in);
         if (got) {
-            rc = real ? pdt_stream_push_real(ctx, block, got, PDT_FMT_REAL_F32, &fresh) : pdt_stream_push_f32(ctx, block, got, &fresh);
+            rc = decim ? pdt_stream_push_channel(ctx, block, got, wbFormat, &fresh) : real ? pdt_stream_push_real(ctx, block, got, PDT_FMT_REAL_F32, &fresh) : pdt_stream_push_f32(ctx, block, got, &fresh);
         } else {
             rc = pdt_stream_end(ctx, &fresh);
         }
@@ -243,6 +258,58 @@ static int live_loop(FILE *in, FILE *out, const char *outFileName, double sample
     return 0;
 }
 
+/* -x with several -t: one wideband capture, one context per channel, one read of the capture (pdt_demod_channels); every
+ * channel's frames go to a file of its own, outFileName with ".<index>" appended */
+static int multi_channel(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim,
+                         const double *offsetsHz, int nch, const char *outFileName)
+{
+    pdt_ctx *ctxs[16];
+    int rc = PDT_OK;
+    for (int i = 0; i < nch && rc == PDT_OK; i++) {
+        ctxs[i] = NULL;
+        rc = pdt_open(cfg, &ctxs[i]);
+        if (rc != PDT_OK) {
+            printf("GPU demodulator unavailable: %s\n", pdt_strerror(rc));
+            return 1;
+        }
+        if (pdt_set_channel(ctxs[i], decim, offsetsHz[i]) != PDT_OK) {
+            printf("Decimation must be 2 .. 64 and the offset %0.3f kHz below half the wideband rate\n", offsetsHz[i] / 1000.0);
+            return 1;
+        }
+        pdt_keep_pll(ctxs[i], 0);
+    }
+    unsigned char *buf = (unsigned char *)malloc((size_t)nframes * frame_bytes + 16);
+    if (!buf || fseek(in, data_offset, SEEK_SET) != 0 || fread(buf, frame_bytes, (size_t)nframes, in) != (size_t)nframes) {
+        printf("Error reading the capture\n");
+        return 1;
+    }
+    rc = pdt_demod_channels(ctxs, nch, buf, nframes, fmt);
+    free(buf);
+    if (rc != PDT_OK) {
+        printf("Demodulation failed: %s\n", pdt_strerror(rc));
+        return 1;
+    }
+    for (int i = 0; i < nch; i++) {
+        char name[1200];
+        snprintf(name, sizeof name, "%s.%d", outFileName, i);
+        FILE *o = fopen(name, "w+");
+        if (!o || pdt_write_frames(ctxs[i], fileno(o), NULL) != PDT_OK) {
+            printf("Error writing output file\n");
+            return 1;
+        }
+        fclose(o);
+        pdt_stats st;
+        pdt_get_stats(ctxs[i], &st);
+        printf("Channel %d (%+0.3f kHz): ", i, offsetsHz[i] / 1000.0);
+        if (st.lock_sample >= 0) printf("PLL locked at %0.2fHz : ", st.lock_freq_hz);
+        printf("%0.3f Ks : %llu Sym : %llu Bits : %llu " UNIT " -> %s\n", st.samples / 1000.0, (unsigned long long)st.symbols,
+               (unsigned long long)st.bits, (unsigned long long)st.frames, name);
+        if (st.frames == 0) remove(name);
+        pdt_close(ctxs[i]);
+    }
+    return 0;
+}
+
 static double now_ms(void)
 {
     struct timespec ts;
@@ -258,6 +325,8 @@ int main(int argc, char **argv)
     double normFactor = 0, sampleRate = 0;
     int outputRawFiles = 0, device = 0, quality = 0, sampler = 0, live = 0, chunkGiven = 0, noProgress = 0, real = 0, c;
     double realCenterHz = 0;
+    int decim = 0, nOffsets = 0, wbFormat = PDT_FMT_WB_CU8;
+    double offsetsHz[16];
     const char *outOverride = NULL;
     char outFileName[1100];
 
@@ -315,6 +384,28 @@ int main(int argc, char **argv)
             realCenterHz = atof(optarg) * 1000.0;
             printf("Single-channel input centred at %f Khz\n", atof(optarg));
             break;
+        case 'x':                                       /* wideband input at this many times the channel rate */
+            decim = atoi(optarg);
+            printf("Wideband input, decimation %d\n", decim);
+            break;
+        case 't':                                       /* a channel's offset from the capture's centre, signed */
+            if (nOffsets >= 16) {
+                printf("At most 16 channels\n");
+                return 1;
+            }
+            offsetsHz[nOffsets++] = atof(optarg) * 1000.0;
+            printf("Channel %d at %+f Khz\n", nOffsets - 1, atof(optarg));
+            break;
+        case 'F':                                       /* the format of the wideband blocks read from a pipe */
+            if (strcasecmp(optarg, "cu8") == 0) wbFormat = PDT_FMT_WB_CU8;
+            else if (strcasecmp(optarg, "cs8") == 0) wbFormat = PDT_FMT_WB_CS8;
+            else if (strcasecmp(optarg, "s16") == 0) wbFormat = PDT_FMT_WB_PCM16;
+            else if (strcasecmp(optarg, "f32") == 0) wbFormat = PDT_FMT_WB_F32;
+            else {
+                printf("Unknown wideband format %s (cu8, cs8, s16, f32)\n", optarg);
+                return 1;
+            }
+            break;
         case 'm':                                       /* MMClockRecovery instead of Gardner (ARGOSdemod/main.c:277) */
             sampler = PDT_SAMPLER_MM;
             printf("Using M&M clock recovery\n");
@@ -331,6 +422,15 @@ int main(int argc, char **argv)
             abort();
         }
     }
+    if (nOffsets && !decim) {
+        printf("-t requires -x <decimation>\n");
+        return 1;
+    }
+    if (decim && (decim < 2 || decim > 64 || real)) {
+        printf("Decimation (-x) must be 2 .. 64, and cannot be combined with -f\n");
+        return 1;
+    }
+    if (decim && !nOffsets) offsetsHz[nOffsets++] = 0.0;
     if (live && !chunkGiven) chunkSize = 2400;          /* POESTIPdemodPortAudio/main.c:34 */
     if (chunkSize == (live ? 2400 : DEFAULT_CHUNKSIZE)) printf("Using default %ld chunkSize\n", chunkSize);
     if (optind >= argc) {
@@ -350,7 +450,7 @@ int main(int argc, char **argv)
     else
         snprintf(outFileName, sizeof outFileName, PREFIX "_%4d%02d%02d_%02d%02d%02d.txt", tm.tm_year + 1900, tm.tm_mon + 1,
                  tm.tm_mday, tm.tm_hour, tm.tm_min, tm.tm_sec);
-    FILE *out = fopen(outFileName, "w+");
+    FILE *out = nOffsets > 1 ? stdout : fopen(outFileName, "w+");   /* (several channels: a file each, multi_channel) */
     if (!in || !out) {
         printf("Error opening output files\n");
         exit(1);
@@ -364,9 +464,20 @@ int main(int argc, char **argv)
         fclose(raw);
     }
 
-    if (from_stdin) return live_loop(in, out, outFileName, sampleRate, chunkSize, normFactor, device, sampler, real, realCenterHz);
-    int is_raw = 0;
-    if (strcasecmp(get_filename_ext(inFileName), "wav") != 0) {
+    if (from_stdin && nOffsets > 1) {
+        printf("One channel only from a pipe\n");
+        return 1;
+    }
+    if (from_stdin) return live_loop(in, out, outFileName, sampleRate, chunkSize, normFactor, device, sampler, real, realCenterHz, decim, offsetsHz[0], wbFormat);
+    int is_raw = 0, is_8bit = 0;
+    if (decim && (strcasecmp(get_filename_ext(inFileName), "cu8") == 0 || strcasecmp(get_filename_ext(inFileName), "cs8") == 0)) {
+        if (sampleRate < 1) {
+            printf("Sample Rate (in Khz) must be specified when using 8-bit files\n");
+            exit(1);
+        }
+        is_8bit = strcasecmp(get_filename_ext(inFileName), "cu8") == 0 ? PDT_FMT_WB_CU8 : PDT_FMT_WB_CS8;
+        printf("Assuming headerless %s 8-bit I,Q input\n", is_8bit == PDT_FMT_WB_CU8 ? "unsigned" : "signed");
+    } else if (strcasecmp(get_filename_ext(inFileName), "wav") != 0) {
 #ifdef PDT_ARGOS
         printf("RAW files not yet supported :(\n");
         exit(1);
@@ -388,7 +499,7 @@ int main(int argc, char **argv)
     uint32_t rate = 0, channels = 2, bits = 32, format = 1, data_bytes = 0;
     long data_offset = 0;
     long num_samples = 44515000;                                     /* RAW: main.c:337 (progress bar only) */
-    if (!is_raw) {
+    if (!is_raw && !is_8bit) {
         uint8_t hdr[44];
         if (fread(hdr, 1, 44, in) != 44) {
             printf("Error reading WAV header\n");
@@ -413,8 +524,9 @@ int main(int argc, char **argv)
             exit(1);
         }
 #ifndef PDT_ARGOS
-        if (sampleRate > 1) rate = (uint32_t)sampleRate;             /* main.c:343-344 (Q6) */
+        if (sampleRate > 1 && !decim) rate = (uint32_t)sampleRate;   /* main.c:343-344 (Q6) */
 #endif
+        if (sampleRate >= 1 && decim) rate = (uint32_t)(sampleRate * 1000.0);          /* -x: -s is the wideband rate in kHz */
 #ifdef PDT_ARGOS
         num_samples = (long)((uint32_t)(8u * data_bytes) / (channels * bits));   /* ARGOSdemod/main.c:244, unsigned int arithmetic */
 #else
@@ -429,9 +541,24 @@ int main(int argc, char **argv)
      * memory overlapped with the copy to the GPU: pdt_demod_fd) */
     fseek(in, 0, SEEK_END);
     long fsz = ftell(in);
-    const size_t frame_bytes = (is_raw ? 8 : 4) / (real ? 2 : 1);
-    const int sample_format = real ? (is_raw ? PDT_FMT_REAL_F32 : PDT_FMT_REAL_PCM16) : (is_raw ? PDT_FMT_F32 : PDT_FMT_PCM16);
+    const size_t frame_bytes = is_8bit ? 2 : (is_raw ? 8 : 4) / (real ? 2 : 1);
+    const int sample_format = decim ? (is_8bit ? is_8bit : is_raw ? PDT_FMT_WB_F32 : PDT_FMT_WB_PCM16)
+                                    : real ? (is_raw ? PDT_FMT_REAL_F32 : PDT_FMT_REAL_PCM16) : (is_raw ? PDT_FMT_F32 : PDT_FMT_PCM16);
     uint64_t nframes = fsz > data_offset ? (uint64_t)(fsz - data_offset) / frame_bytes : 0;
+    const uint64_t in_frames = nframes;
+    if (decim) {
+        if (rate % (uint32_t)decim) {
+            printf("The wideband rate %u Hz is not divisible by the decimation %d\n", rate, decim);
+            if (out != stdout) {
+                fclose(out);
+                remove(outFileName);
+            }
+            exit(1);
+        }
+        rate /= (uint32_t)decim;
+        num_samples = (long)((nframes + (uint64_t)decim - 1) / (uint64_t)decim);      /* (progress runs over the channel's samples) */
+        printf("Channel rate %.2fKHz\n", (float)rate / 1000.0);
+    }
 
     pdt_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -442,6 +569,7 @@ int main(int argc, char **argv)
     cfg.device = device;
     cfg.sampler = sampler;
     cfg.chain = live ? PDT_CHAIN_LIVE : PDT_CHAIN_FILE;
+    if (nOffsets > 1) return multi_channel(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, offsetsHz, nOffsets, outFileName);
     pdt_ctx *ctx = NULL;
     const double t_open0 = now_ms();
     int rc = pdt_open(&cfg, &ctx);
@@ -461,7 +589,14 @@ int main(int argc, char **argv)
         remove(outFileName);
         exit(1);
     }
+    if (decim && pdt_set_channel(ctx, decim, offsetsHz[0]) != PDT_OK) {
+        printf("The offset %0.3f kHz must lie below half the wideband rate\n", offsetsHz[0] / 1000.0);
+        fclose(out);
+        remove(outFileName);
+        exit(1);
+    }
     pdt_keep_pll(ctx, 0);                                            /* nothing here reads the PLL output stream */
+    if (decim) nframes = (nframes + (uint64_t)decim - 1) / (uint64_t)decim;           /* (the progress lines count channel samples) */
     progress_state prog;
     memset(&prog, 0, sizeof prog);
     prog.num_samples = num_samples;
@@ -479,10 +614,10 @@ int main(int argc, char **argv)
     int text_written = 0;
     fflush(out);
 #ifndef PDT_ARGOS
-    rc = pdt_demod_file(ctx, fileno(in), (uint64_t)data_offset, nframes, sample_format, fileno(out), NULL);
+    rc = pdt_demod_file(ctx, fileno(in), (uint64_t)data_offset, in_frames, sample_format, fileno(out), NULL);
     text_written = 1;
 #else
-    rc = pdt_demod_fd(ctx, fileno(in), (uint64_t)data_offset, nframes, sample_format);
+    rc = pdt_demod_fd(ctx, fileno(in), (uint64_t)data_offset, in_frames, sample_format);
 #endif
     const double t_demod1 = now_ms();
     fclose(in);

@@ -1,0 +1,333 @@
+"""Wideband SDR captures on the GPU: the down-converter's kernel against its host restatement bit for bit, the routing into the
+chain (a wideband capture = the RAW float capture of its channel stream), decoded outcomes against what the synthetic generator
+transmitted, several channels from one read, streaming, files and the command line."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+from test_gpu_real_input import transmitted
+
+pytestmark = pytest.mark.gpu
+
+BIN = os.path.join(ROOT, "bin")
+FORMATS = ("pcm16", "f32", "cu8", "cs8")
+
+
+def random_capture(rng, fmt: str, n: int) -> np.ndarray:
+    if fmt == "pcm16":
+        return rng.integers(-32768, 32768, (n, 2)).astype(np.int16)
+    if fmt == "f32":
+        return rng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
+    if fmt == "cu8":
+        return rng.integers(0, 256, (n, 2)).astype(np.uint8)
+    return rng.integers(-128, 128, (n, 2)).astype(np.int8)
+
+
+def fmt_code(pdt, x: np.ndarray) -> int:
+    return {np.dtype(np.int16): pdt.FMT_WB_PCM16, np.dtype(np.float32): pdt.FMT_WB_F32, np.dtype(np.uint8): pdt.FMT_WB_CU8,
+            np.dtype(np.int8): pdt.FMT_WB_CS8}[x.dtype]
+
+
+def carriers(pdt, kind: int, in_rate: int, secs: float, offsets, seeds, residual: float):
+    """Transmissions summed into one int16 capture at in_rate, each at half amplitude, the carrier of channel i at offsets[i] +
+    residual.  Returns the capture and each transmission's parameters."""
+    n = int(round(secs * in_rate))
+    total = np.zeros((n, 2), dtype=np.int32)
+    params = []
+    for off, seed in zip(offsets, seeds):
+        p = pdt.synth_params(kind, in_rate, off + residual, seed)
+        p.amplitude //= 2
+        p.noise_gain //= 2
+        iq = np.zeros((n, 2), dtype="<i2")
+        pdt.synth_lib().pdt_synth_fill(C.byref(p), 0, n, iq.ctypes.data)
+        total += iq
+        params.append(p)
+    return np.clip(total, -32768, 32767).astype(np.int16), params
+
+
+def to_cu8(x16: np.ndarray) -> np.ndarray:
+    """The unsigned 8-bit rendering of an int16 capture (what an RTL-SDR would have recorded)."""
+    return np.clip(np.floor(x16 / 256.0) + 128, 0, 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("D", (2, 4, 16, 64))
+def test_kernel_equals_host_restatement(pdt, D, fmt):
+    """PDT_ST_CHANNEL is pdt_host_ddc, bit for bit: captures shorter than the halo, around it, around one tile of the kernel and a
+    long one; positive and negative offsets; captures in host memory and at unaligned device addresses."""
+    rng = np.random.default_rng(1000 * D + FORMATS.index(fmt))
+    fs = 250000
+    in_rate = fs * D
+    tile = 2048 // D * D
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        for n in (1, 8 * D - 1, 8 * D + 1, tile - 1, tile + 1, 10 ** 6 + 7):
+            x = random_capture(rng, fmt, n)
+            for offset in ((0.31 * in_rate, -0.123456 * in_rate) if n < 10 ** 6 else (-0.31 * in_rate,)):
+                want = pdt.host_ddc(in_rate, D, offset, x)
+                d.set_channel(D, offset).demod_channel(x)
+                assert d.stage_len(pdt.ST_CHANNEL) == (n + D - 1) // D
+                assert d.stage(pdt.ST_CHANNEL).tobytes() == want.tobytes(), (n, offset)
+                assert d.stats().samples == (n + D - 1) // D
+        # resident captures whose first sample sits 1, 2 and 3 samples behind a 16-byte boundary
+        n = 3 * tile + 5
+        x = random_capture(rng, fmt, n + 3)
+        dev = torch.from_numpy(x.reshape(-1).copy()).to("cuda:0")
+        torch.cuda.synchronize()
+        for skip in (1, 2, 3):
+            want = pdt.host_ddc(in_rate, D, 77777.0, x[skip: skip + n])
+            d.set_channel(D, 77777.0).demod_device_channel(dev.data_ptr() + skip * 2 * x.itemsize, n, fmt_code(pdt, x))
+            assert d.stage(pdt.ST_CHANNEL).tobytes() == want.tobytes(), skip
+
+
+def test_other_captures_have_no_channel_stage(pdt, clip):
+    rate, iq = clip
+    with pdt.Demodulator(pdt.MODE_POES, rate) as d:
+        d.demod(iq[:50000])
+        assert d.stage_len(pdt.ST_CHANNEL) == 0
+
+
+def test_poes_routing_equals_raw_float_path(pdt, orc):
+    """demod_channel(x) and demod_raw(host_ddc(x)) at the channel rate are the same capture: frames, text, counts, per-chunk
+    reports; and the text is the oracle's for that float capture."""
+    fs, D, offset = 250000, 4, 200000.0
+    x, _ = carriers(pdt, 0, fs * D, 8.0, (offset,), (31,), 1000.0)
+    z = pdt.host_ddc(fs * D, D, offset, x)
+    with pdt.Demodulator(pdt.MODE_POES, fs).keep_quality() as d:
+        d.set_channel(D, offset).demod_channel(x)
+        assert d.stage(pdt.ST_CHANNEL).tobytes() == z.tobytes()
+        a = (d.text(), d.frames_array().tobytes(), d.chunk_reports().tobytes())
+        sa = d.stats()
+    with pdt.Demodulator(pdt.MODE_POES, fs).keep_quality() as d:
+        d.demod_raw(z)
+        b = (d.text(), d.frames_array().tobytes(), d.chunk_reports().tobytes())
+        sb = d.stats()
+    assert a == b and len(a[0]) > 10000
+    for k in ("samples", "out_samples", "symbols", "bits", "frames", "lock_sample", "lock_freq_hz", "norm_factor", "avg_phase"):
+        assert getattr(sa, k) == getattr(sb, k), k
+    assert a[0] == orc.Oracle(orc.POES, fs, z).text()
+
+
+SETUPS = [(1000000, 4, (200000.0, -180000.0)), (2400000, 16, (600000.0, -400000.0)), (2048000, 8, (299500.0, -421700.0))]
+
+
+@pytest.mark.parametrize("rendering", ["pcm16", "cu8"])
+@pytest.mark.parametrize("in_rate,D,offsets", SETUPS)
+def test_poes_channels_decode_what_was_sent(pdt, in_rate, D, offsets, rendering):
+    """Two POES transmissions (seeds 11 and 12, 8 s, half amplitude each) in one wideband capture: each channel's complete frames
+    are frames the generator sent (the `transmitted` criterion of the real-input tests), and its PLL locks on the residual 1 kHz."""
+    fs = in_rate // D
+    x, params = carriers(pdt, 0, in_rate, 8.0, offsets, (11, 12), 1000.0)
+    if rendering == "cu8":
+        x = to_cu8(x)
+    for off, p, seed in zip(offsets, params, (11, 12)):
+        with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+            d.set_channel(D, off).demod_channel(x)
+            fr = d.frames_array()
+            st = d.stats()
+        # the transmission runs on the wideband clock: frame k starts at the same time in seconds of the channel stream
+        res = transmitted(pdt, p, fr, len(x), in_rate)
+        print(in_rate, D, off, rendering, res, st.lock_freq_hz)
+        assert res["ok"], res
+        assert st.lock_sample >= 0 and abs(st.lock_freq_hz - 1000.0) < 200.0
+
+
+def test_argos_channel_decodes_every_burst_after_the_lock(pdt):
+    """ARGOS at 1.024 Msps / 32: the double chain reading the channel's float pairs.  The seeds were chosen on the CPU first: for
+    seeds 7, 8 and 9 at both offsets the float64 model of the converter (tests/test_channel_input.py), rendered as int16 -- the
+    oracle's ARGOS chain takes no float captures --, and the oracle alone decode every burst after the lock (9 of 10) and nothing
+    that was not sent; two of those six cases are kept."""
+    in_rate, D, secs = 1024000, 32, 15.0
+    fs = in_rate // D
+    for offset, seed in ((250000.0, 8), (-333300.0, 9)):
+        x, (p,) = carriers(pdt, 1, in_rate, secs, (offset,), (seed,), 120.0)
+        with pdt.Demodulator(pdt.MODE_ARGOS, fs) as d:
+            d.set_channel(D, offset).demod_channel(x)
+            fr = d.frames_array()
+            st = d.stats()
+        assert st.lock_sample >= 0
+        period = in_rate * 3 // 2
+        nb = int(len(x) // period)
+        sent = [bytes(pdt.synth_argos_payload(p, b)) for b in range(nb)]
+        got = [bytes(f["bytes"][:7]) for f in fr if f["complete"]]
+        after = [sent[b] for b in range(nb) if b * period >= st.lock_sample * D]
+        assert len(after) >= nb // 2
+        assert all(s in got for s in after), (len(got), len(after))
+        assert all(g in sent for g in got)
+
+
+def test_several_channels_equal_one_at_a_time(pdt):
+    """demod_channels with 2 and with 4 contexts (one of them ARGOS): each context holds, byte for byte, what it gets alone."""
+    in_rate, D = 1024000, 4
+    fs = in_rate // D
+    x, _ = carriers(pdt, 0, in_rate, 6.0, (200000.0, -180000.0, 390000.0), (11, 12, 13), 1000.0)
+    xa, _ = carriers(pdt, 1, in_rate, 6.0, (-401000.0,), (8,), 120.0)
+    x = np.clip(x.astype(np.int32) + xa, -32768, 32767).astype(np.int16)
+    plan = [(pdt.MODE_POES, 200000.0), (pdt.MODE_POES, -180000.0), (pdt.MODE_ARGOS, -401000.0), (pdt.MODE_POES, 390000.0)]
+    alone = []
+    for mode, off in plan:
+        with pdt.Demodulator(mode, fs) as d:
+            d.set_channel(D, off).demod_channel(x)
+            alone.append((d.text(), d.frames_array().tobytes(), d.stage(pdt.ST_CHANNEL).tobytes()))
+    assert all(len(a[0]) > 100 for a in alone[:2])
+    dev = torch.from_numpy(x.reshape(-1).copy()).to("cuda:0")
+    torch.cuda.synchronize()
+    for count in (2, 4):
+        ds = [pdt.Demodulator(mode, fs).set_channel(D, off) for mode, off in plan[:count]]
+        try:
+            for rep in range(2):
+                pdt.demod_channels(ds, dev.data_ptr(), len(x), pdt.FMT_WB_PCM16)
+                for d, a in zip(ds, alone):
+                    assert (d.text(), d.frames_array().tobytes(), d.stage(pdt.ST_CHANNEL).tobytes()) == a
+            pdt.demod_channels(ds, x)                                   # the capture in host memory
+            for d, a in zip(ds, alone):
+                assert (d.text(), d.frames_array().tobytes()) == a[:2]
+            ds[1].set_channel(8, -180000.0)                             # mixed decimations are refused
+            with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+                pdt.demod_channels(ds, dev.data_ptr(), len(x), pdt.FMT_WB_PCM16)
+            with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+                pdt.demod_channels([ds[0], ds[0]], dev.data_ptr(), len(x), pdt.FMT_WB_PCM16)
+        finally:
+            for d in ds:
+                d.close()
+
+
+@pytest.mark.parametrize("mode,kind,in_rate,D,offset,residual", [(0, 0, 1000000, 4, 200000.0, 1000.0), (1, 1, 1024000, 32, 250000.0, 120.0),
+                                                                (0, 0, 2400000, 16, -400000.0, 1000.0)])
+def test_stream_pushes_equal_the_whole_call(pdt, mode, kind, in_rate, D, offset, residual):
+    fs = in_rate // D
+    x16, _ = carriers(pdt, kind, in_rate, 6.0 if kind == 0 else 12.0, (offset,), (55,), residual)
+    rng = np.random.default_rng(D)
+    for x in (x16, to_cu8(x16)):
+        with pdt.Demodulator(mode, fs) as d:
+            d.set_channel(D, offset).demod_channel(x)
+            want_text, want = d.text(), d.frames_array()
+        assert len(want) > 3
+        with pdt.Demodulator(mode, fs) as d:
+            d.set_channel(D, offset)
+            got, at = [], 0
+            sizes = [1, D - 1, D, 1, 8 * D - 1, 3, 8 * D + 1, 2]
+            while at < len(x):
+                k = sizes.pop(0) if sizes else int(rng.integers(1, 150000 * D))
+                got.append(d.stream_push_channel(x[at: at + k]))
+                at = min(at + k, len(x))
+                held = at if at < 8 * D else 8 * D + at % D
+                assert d.stream_retained() >= held
+            got.append(d.stream_end())
+            assert np.concatenate(got).tobytes() == want.tobytes()
+            assert d.text() == want_text
+
+
+def test_stream_and_context_arguments(pdt):
+    fs = 250000
+    L = pdt.lib()
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        x = np.zeros((1000, 2), dtype=np.int16)
+        with pytest.raises(pdt.PdtError, match=r"\(-6\)"):
+            d.demod_channel(x)                                          # no channel yet
+        for decim, off in ((1, 0.0), (65, 0.0), (0, 0.0), (4, 500000.0), (4, -500000.0), (4, float("nan")), (4, float("inf"))):
+            with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+                d.set_channel(decim, off)
+        d.set_channel(64, 7999999.0).set_channel(4, -499999.0).set_channel(4, 200000.0)
+        for fmt in (0, 1, 2, 3, 15, 20):
+            assert L.pdt_demod_channel(d._h, x.ctypes.data, 1000, fmt) == -1
+        d.stream_push_channel(x)
+        with pytest.raises(pdt.PdtError, match=r"\(-6\)"):
+            d.set_channel(4, 1000.0)                                    # a stream is open
+        with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+            d.stream_push(np.zeros((10, 2), dtype=np.int16))           # I,Q into a wideband stream
+        with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+            d.stream_push_real(np.zeros(10, dtype=np.int16))           # real into a wideband stream
+        with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+            d.stream_push_channel(np.zeros((10, 2), dtype=np.uint8))   # the other wideband format
+        d.stream_end()
+        d.stream_push(np.zeros((10, 2), dtype=np.int16))
+        with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+            d.stream_push_channel(x)                                    # wideband into an I,Q stream
+        d.stream_end()
+    with pytest.raises(pdt.PdtError, match=r"\(-5\)"):
+        pdt.Demodulator(pdt.MODE_POES, 1000000)                         # a wideband rate is still no context rate
+
+
+def test_files_equal_the_in_memory_call(pdt, tmp_path):
+    in_rate, D, offset = 1000000, 4, 200000.0
+    fs = in_rate // D
+    x, _ = carriers(pdt, 0, in_rate, 6.0, (offset,), (61,), 1000.0)
+    u8 = to_cu8(x)
+    s8 = (u8.astype(np.int16) - 128).astype(np.int8)
+    wav = str(tmp_path / "wide.wav")
+    pdt.write_wav(wav, in_rate, x)
+    for path, arr, fmt, off in ((wav, x, pdt.FMT_WB_PCM16, 44), (str(tmp_path / "wide.cu8"), u8, pdt.FMT_WB_CU8, 0),
+                                (str(tmp_path / "wide.cs8"), s8, pdt.FMT_WB_CS8, 0)):
+        if not off:
+            arr.tofile(path)
+        with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+            d.set_channel(D, offset).demod_channel(arr)
+            want = d.text()
+        assert len(want) > 10000
+        fd = os.open(path, os.O_RDONLY)
+        out = str(tmp_path / "out.txt")
+        tfd = os.open(out, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+        try:
+            with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+                nb = d.set_channel(D, offset).demod_file_text(fd, off, len(arr), tfd, fmt=fmt)
+                assert d.stage_len(pdt.ST_CHANNEL) == (len(arr) + D - 1) // D
+        finally:
+            os.close(fd)
+            os.close(tfd)
+        text = open(out, "rb").read()
+        assert nb == len(text) and text == want
+
+
+def test_command_line(pdt, tmp_path):
+    in_rate, D = 1000000, 4
+    fs = in_rate // D
+    x, _ = carriers(pdt, 0, in_rate, 6.0, (200000.0, -180000.0), (11, 12), 1000.0)
+    wav = str(tmp_path / "two_carriers.wav")
+    pdt.write_wav(wav, in_rate, x)
+    want = []
+    for off in (200000.0, -180000.0):
+        with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+            d.set_channel(D, off).demod_channel(x)
+            want.append(d.text())
+    assert all(len(w) > 10000 for w in want)
+    exe = os.path.join(BIN, "demodPOES")
+    out = str(tmp_path / "frames.txt")
+    r = subprocess.run([exe, "-x", "4", "-t", "200", "-t", "-180", "-o", out, wav], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert open(out + ".0", "rb").read() == want[0] and open(out + ".1", "rb").read() == want[1]
+    # one channel: the usual single output file
+    r = subprocess.run([exe, "-x", "4", "-t", "-180", "-o", out, wav], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert open(out, "rb").read() == want[1]
+    # without -x the same file is refused as before: 1 Msps gives interpolation factor 0
+    r = subprocess.run([exe, "-o", out, wav], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 1 and "interpolation factor would be 0" in r.stdout
+    # a rate the decimation does not divide
+    r = subprocess.run([exe, "-x", "7", "-t", "200", "-o", out, wav], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 1 and "not divisible" in r.stdout
+    # headerless 8-bit pairs, -s required
+    cu8 = str(tmp_path / "two_carriers.cu8")
+    u8 = to_cu8(x)
+    u8.tofile(cu8)
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        d.set_channel(D, 200000.0).demod_channel(u8)
+        want8 = d.text()
+    r = subprocess.run([exe, "-x", "4", "-t", "200", "-s", "1000", "-o", out, cu8], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert open(out, "rb").read() == want8
+    r = subprocess.run([exe, "-x", "4", "-t", "200", "-o", out, cu8], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 1 and "must be specified" in r.stdout
+    # -l -x .. -t .. - : blocks of unsigned 8-bit pairs from a pipe through the stream entry
+    with pdt.Demodulator(pdt.MODE_POES, fs, chunk=2400, chain=pdt.CHAIN_LIVE) as d:
+        d.set_channel(D, 200000.0)
+        fr = [d.stream_push_channel(u8[i: i + 2400 * D]) for i in range(0, len(u8), 2400 * D)] + [d.stream_end()]
+        want_live = pdt.format_frames(np.concatenate(fr))
+    assert len(want_live) > 100
+    r = subprocess.run([exe, "-l", "-x", "4", "-t", "200", "-s", "1000", "-o", out, "-"], input=u8.tobytes(), capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert open(out, "rb").read() == want_live

@@ -60,7 +60,9 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 8): wideband SDR captures through a digital down-converter -- the sample formats
+/* 4, additions without a bump (round 9): the carrier survey of wideband captures -- pdt_survey_cfg, pdt_carrier, pdt_survey,
+ * pdt_survey_device, pdt_survey_spectrum, pdt_host_survey: where the carriers of a capture are, for pdt_set_channel.
+ * 4, additions without a bump (round 8): wideband SDR captures through a digital down-converter -- the sample formats
  * PDT_FMT_WB_PCM16 / _F32 / _CU8 / _CS8, the stage PDT_ST_CHANNEL, pdt_set_channel, pdt_demod_channel, pdt_demod_device_channel,
  * pdt_demod_channels_device, pdt_demod_channels, pdt_stream_push_channel, pdt_host_ddc; pdt_demod_fd / pdt_demod_file accept the wideband formats.
  * 4, additions without a bump (round 7): single-channel (real) captures through a Hilbert front end -- the sample formats
@@ -428,6 +430,47 @@ int  pdt_demod_channels_device(pdt_ctx *const *ctxs, int count, const void *iq_d
 int  pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uint64_t nframes, int sample_format);
 int  pdt_stream_push_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, uint64_t *new_frames);
 int  pdt_host_ddc(uint32_t in_rate, int decim, double offset_hz, const void *x, uint64_t n, int sample_format, float *out);
+
+/* The carrier survey of a wideband capture: which offsets to give pdt_set_channel.  The chain's PLL sweeps a few kHz at most (4500 Hz
+ * POES, 550 Hz ARGOS), a cheap receiver's crystal alone is off by more.  The stretch [first_frame, first_frame + nframes) of the
+ * capture is cut into consecutive segments of nfft samples (a last incomplete one is dropped), each is Blackman-windowed and
+ * transformed in float32 on the GPU, the segments' power spectra are averaged in a fixed order, and the host looks for carriers in
+ * the average: noise floor = its median; repeatedly the strongest bin left, as long as it stands threshold_db over the floor, its
+ * frequency the centroid of the power above the floor within merge_hz of it, then the bins within guard_hz of it are blanked.
+ * The arithmetic is fixed: pdt_host_survey restates it bit for bit on the host.
+ * pdt_survey_cfg: a zero in a field means its default -- nfft 16384 (1024, 4096 and 16384 are allowed), max_carriers 16,
+ * threshold_db 15, guard_hz half the channel rate, merge_hz the mode's PLL frequency range (pdt_loop_params.pll_freq_range_hz when
+ * set), first_frame 0, nframes to the end of the capture.
+ *   pdt_survey_device    the capture resident in device memory (only read), nframes frames of sample_format (PDT_FMT_WB_*); the
+ *                        context supplies device, stream, mode and the wideband rate decim x sample_rate (PDT_ERR_STATE before
+ *                        pdt_set_channel, whose offset plays no part).  Up to min(cap, max_carriers) carriers, strongest first, in
+ *                        found[], their number in *count.  PDT_ERR_ARG: another format, an nfft that is not allowed, a stretch
+ *                        outside the capture or shorter than one segment, cap < 1.  The context's demodulation results, stages
+ *                        and statistics are left alone, and a later demodulation is what it would have been without the survey
+ *   pdt_survey           the same for a capture in host memory: copied to the device once, into the context's input buffer
+ *   pdt_survey_spectrum  the averaged spectrum of the context's last survey, n = its nfft floats (else PDT_ERR_ARG; PDT_ERR_STATE
+ *                        before a survey): bin b at b Fs_in / nfft, the upper half the negative frequencies
+ *   pdt_host_survey      test hook, host only: the same spectrum (spectrum_out, nfft floats, may be NULL) and carriers as the
+ *                        kernels and the host search produce; in_rate is Fs_in, mode_range_hz and channel_rate stand for what the
+ *                        context supplies to the defaults of merge_hz and guard_hz                                              */
+typedef struct pdt_survey_cfg {
+    int nfft;
+    int max_carriers;
+    double threshold_db, guard_hz, merge_hz;
+    uint64_t first_frame, nframes;
+} pdt_survey_cfg;
+typedef struct pdt_carrier {
+    double offset_hz;       /* from the capture's centre, [-Fs_in / 2, Fs_in / 2) */
+    float peak_db;          /* the strongest bin over the floor */
+    float floor_power;      /* the median of the averaged spectrum */
+} pdt_carrier;
+int  pdt_survey_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg,
+                       pdt_carrier *found, int cap, int *count);
+int  pdt_survey(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg,
+                pdt_carrier *found, int cap, int *count);
+int  pdt_survey_spectrum(const pdt_ctx *ctx, float *out, int n);
+int  pdt_host_survey(uint32_t in_rate, double mode_range_hz, uint32_t channel_rate, int sample_format, const void *x, uint64_t nframes,
+                     const pdt_survey_cfg *cfg, float *spectrum_out, pdt_carrier *found, int cap, int *count);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

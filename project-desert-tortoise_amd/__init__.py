@@ -17,6 +17,7 @@ Reference behaviour mirrored here (file:line in nebarnix/Project-Desert-Tortoise
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import struct
@@ -165,6 +166,32 @@ class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint32), ("total_ms", C.c_double)]
 
 
+class SurveyCfg(C.Structure):
+    """pdt_survey_cfg: a zero means the default"""
+    _fields_ = [("nfft", C.c_int), ("max_carriers", C.c_int), ("threshold_db", C.c_double), ("guard_hz", C.c_double), ("merge_hz", C.c_double),
+                ("first_frame", C.c_uint64), ("nframes", C.c_uint64)]
+
+
+class CarrierRec(C.Structure):
+    """pdt_carrier"""
+    _fields_ = [("offset_hz", C.c_double), ("peak_db", C.c_float), ("floor_power", C.c_float)]
+
+
+Carrier = collections.namedtuple("Carrier", "offset_hz peak_db floor_power")
+
+
+def _survey_cfg(cfg: dict):
+    """keyword arguments of a survey -> (pdt_survey_cfg or None, capacity of the result)"""
+    unknown = set(cfg) - {f[0] for f in SurveyCfg._fields_}
+    if unknown:
+        raise TypeError(f"unknown survey parameter(s): {sorted(unknown)}")
+    return (SurveyCfg(**cfg) if cfg else None), max(int(cfg.get("max_carriers", 0)) or 16, 1)
+
+
+def _carriers(rec, count: int):
+    return [Carrier(rec[i].offset_hz, rec[i].peak_db, rec[i].floor_power) for i in range(count)]
+
+
 # every symbol include/pdt.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "pdt_abi_version", "pdt_build_tag", "pdt_strerror", "pdt_device_count", "pdt_open", "pdt_close", "pdt_set_stream",
@@ -177,6 +204,7 @@ ABI_SYMBOLS = [
     "pdt_write_frames", "pdt_write_records", "pdt_demod_file", "pdt_set_loop_params", "pdt_set_progress",
     "pdt_set_real_input", "pdt_demod_real", "pdt_demod_device_real", "pdt_stream_push_real", "pdt_host_analytic",
     "pdt_set_channel", "pdt_demod_channel", "pdt_demod_device_channel", "pdt_demod_channels_device", "pdt_demod_channels", "pdt_stream_push_channel", "pdt_host_ddc",
+    "pdt_survey", "pdt_survey_device", "pdt_survey_spectrum", "pdt_host_survey",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows"]        # include/pdt_dev.h (test-only)
 
@@ -307,6 +335,11 @@ def lib():
     L.pdt_demod_channels.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_uint64, C.c_int]
     L.pdt_stream_push_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_host_ddc.argtypes = [C.c_uint32, C.c_int, C.c_double, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+    L.pdt_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(SurveyCfg), C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
+    L.pdt_survey_device.argtypes = L.pdt_survey.argtypes
+    L.pdt_survey_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.pdt_host_survey.argtypes = [C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SurveyCfg), C.c_void_p,
+                                  C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
         raise PdtError("libpdt.so ABI version mismatch")
     _lib = L
@@ -380,6 +413,19 @@ def host_ddc(in_rate: int, decim: int, offset_hz: float, x: np.ndarray) -> np.nd
     out = np.zeros(((n + decim - 1) // decim if decim > 0 else 0, 2), dtype=np.float32)
     _check(lib().pdt_host_ddc(in_rate, decim, float(offset_hz), a.ctypes.data, n, fmt, out.ctypes.data), "pdt_host_ddc")
     return out
+
+
+def host_survey(in_rate: int, mode_range_hz: float, channel_rate: int, x: np.ndarray, **cfg):
+    """pdt_host_survey: the carrier survey of a wideband capture restated on the host (no GPU), bit for bit what the kernels and the
+    host search compute.  x: I,Q pairs at in_rate; mode_range_hz and channel_rate: what a context would supply as the defaults of
+    merge_hz and guard_hz; cfg: fields of pdt_survey_cfg.  Returns (the averaged spectrum float32[nfft], [Carrier, ...])."""
+    a, fmt = _wb_samples(x)
+    c, cap = _survey_cfg(cfg)
+    spec = np.zeros(int(cfg.get("nfft", 0)) or 16384, dtype=np.float32)
+    rec, count = (CarrierRec * cap)(), C.c_int(0)
+    _check(lib().pdt_host_survey(in_rate, float(mode_range_hz), channel_rate, fmt, a.ctypes.data, a.size // 2, C.byref(c) if c else None,
+                                 spec.ctypes.data if spec.size in (1024, 4096, 16384) else None, rec, cap, C.byref(count)), "pdt_host_survey")
+    return spec, _carriers(rec, count.value)
 
 
 def time_axis(mode: int, sample_rate: int, m: int) -> float:
@@ -551,6 +597,32 @@ class Demodulator:
         """Wideband capture resident in HBM (nframes I,Q frames of FMT_WB_*)."""
         _check(self._L.pdt_demod_device_channel(self._h, C.c_void_p(dev_ptr), nframes, fmt), "pdt_demod_device_channel")
         return self
+
+    def survey(self, x: np.ndarray, **cfg):
+        """The carriers of a wideband I,Q capture in host memory (after set_channel, whose offset plays no part): a list of
+        Carrier(offset_hz, peak_db, floor_power), strongest first.  cfg: fields of pdt_survey_cfg (nfft, max_carriers, threshold_db,
+        guard_hz, merge_hz, first_frame, nframes), zero or absent = the default."""
+        a, fmt = _wb_samples(x)
+        c, cap = _survey_cfg(cfg)
+        rec, count = (CarrierRec * cap)(), C.c_int(0)
+        _check(self._L.pdt_survey(self._h, a.ctypes.data, a.size // 2, fmt, C.byref(c) if c else None, rec, cap, C.byref(count)), "pdt_survey")
+        self._survey_nfft = int(cfg.get("nfft", 0)) or 16384
+        return _carriers(rec, count.value)
+
+    def survey_device(self, dev_ptr: int, nframes: int, fmt: int = FMT_WB_PCM16, **cfg):
+        """survey() of a capture resident in HBM (nframes I,Q frames of FMT_WB_*), which is only read."""
+        c, cap = _survey_cfg(cfg)
+        rec, count = (CarrierRec * cap)(), C.c_int(0)
+        _check(self._L.pdt_survey_device(self._h, C.c_void_p(dev_ptr), nframes, fmt, C.byref(c) if c else None, rec, cap, C.byref(count)),
+               "pdt_survey_device")
+        self._survey_nfft = int(cfg.get("nfft", 0)) or 16384
+        return _carriers(rec, count.value)
+
+    def survey_spectrum(self) -> np.ndarray:
+        """The averaged spectrum of the last survey, float32[nfft]: bin b at b Fs_in / nfft, the upper half the negative frequencies."""
+        out = np.zeros(getattr(self, "_survey_nfft", 16384), dtype=np.float32)
+        _check(self._L.pdt_survey_spectrum(self._h, out.ctypes.data, out.size), "pdt_survey_spectrum")
+        return out
 
     def demod_device(self, dev_ptr: int, nframes: int):
         """Input already resident in HBM (e.g. ``tensor.data_ptr()`` of an int16 torch tensor)."""

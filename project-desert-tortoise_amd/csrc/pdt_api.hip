@@ -3,6 +3,7 @@
 #include "pdt_rt.h"
 #include "pdt_analytic.h"
 #include "pdt_ddc.h"
+#include "pdt_survey.h"
 
 #include <pthread.h>
 #include <sched.h>
@@ -17,6 +18,11 @@ std::atomic<long long> g_alloc_ns{0};
 // pdt_analytic.hip
 hipError_t analytic_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
                            uint32_t step, const float *tab_dev, void *out);
+// pdt_survey.hip
+size_t survey_part_floats(uint64_t nseg, int nfft);
+hipError_t survey_launch(hipStream_t st, int fmt, const void *x, uint64_t nseg, int nfft, const float *win, const float *tw, float *part, float *out);
+int survey_plan(const pdt_survey_cfg *cfg, double mode_range_hz, double channel_rate, uint64_t nframes, int cap, pdt::SurveyPlan *p);
+int survey_carriers(const float *P, const pdt::SurveyPlan &p, double in_rate, pdt_carrier *found);
 // pdt_ddc.hip
 hipError_t ddc_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
                       int decim, const float *taps_dev, const float *tab_dev, const uint32_t *steps, void *const *outs, int k);
@@ -949,7 +955,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->term, &ctx->seams_ema, &ctx->gtable, &ctx->gentries, &ctx->gcand,
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->rbuf[0], &ctx->rbuf[1],
-                       &ctx->ddc_taps, &ctx->channel, &ctx->cbuf[0], &ctx->cbuf[1] };
+                       &ctx->ddc_taps, &ctx->channel, &ctx->cbuf[0], &ctx->cbuf[1], &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1527,6 +1533,86 @@ int pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uin
     src.mem = (const unsigned char *)iq_host;
     if ((rc = ingest_capture(c0, src, bytes, c0->pcm.p))) return rc;
     return pdt_demod_channels_device(ctxs, count, c0->pcm.p, nframes, sample_format);
+}
+
+// ---------------------------------------------------------------- carrier survey (pdt_survey.h)
+static int survey_tables(pdt_ctx *ctx, int nfft)
+{
+    if (ctx->survey_tab_nfft == nfft) return PDT_OK;
+    const std::vector<float> win = survey_window(nfft), tw = survey_twiddles(nfft);
+    int rc = ctx->survey_win.ensure(win.size() * sizeof(float) + 16);
+    if (!rc) rc = ctx->survey_tw.ensure(tw.size() * sizeof(float) + 16);
+    if (!rc) rc = ctx->survey_out.ensure((size_t)nfft * sizeof(float));
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                      // (a launch that reads the previous tables may be in flight)
+    HIP_TRY(hipMemcpy(ctx->survey_win.p, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->survey_tw.p, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+    ctx->survey_tab_nfft = nfft;
+    return PDT_OK;
+}
+
+// the plan of a survey by this context: the defaults of merge_hz and guard_hz are the mode's PLL range and half the channel rate
+static int survey_plan_ctx(const pdt_ctx *ctx, const pdt_survey_cfg *cfg, uint64_t nframes, int cap, SurveyPlan *p)
+{
+    const double range = ctx->lp.pll_freq_range_hz != 0 ? ctx->lp.pll_freq_range_hz : ctx->cfg.mode == PDT_MODE_ARGOS ? 550.0 : 4500.0;
+    return survey_plan(cfg, range, (double)ctx->cfg.sample_rate, nframes, cap, p);
+}
+
+// x: the capture, resident.  Nothing of the context's demodulation state is touched.
+static int survey_resident(pdt_ctx *ctx, const void *x, int fmt, const SurveyPlan &p, pdt_carrier *found, int *count)
+{
+    int rc = survey_tables(ctx, p.nfft);
+    if (!rc) rc = ctx->survey_part.ensure(survey_part_floats(p.nseg, p.nfft) * sizeof(float));
+    if (rc) return rc;
+    const unsigned char *first = (const unsigned char *)x + (size_t)p.first * (size_t)ddc_bytes(fmt);
+    HIP_TRY(survey_launch(ctx->stream, fmt, first, p.nseg, p.nfft, (const float *)ctx->survey_win.p, (const float *)ctx->survey_tw.p,
+                          (float *)ctx->survey_part.p, (float *)ctx->survey_out.p));
+    std::vector<float> P((size_t)p.nfft);
+    HIP_TRY(hipMemcpyAsync(P.data(), ctx->survey_out.p, P.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->survey_spec.swap(P);
+    *count = survey_carriers(ctx->survey_spec.data(), p, (double)ctx->ch_decim * (double)ctx->cfg.sample_rate, found);
+    return PDT_OK;
+}
+
+int pdt_survey_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
+                      int cap, int *count)
+{
+    if (!ctx || !iq_device || !ddc_fmt(sample_format) || !found || !count) return PDT_ERR_ARG;
+    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
+    SurveyPlan p;
+    int rc = survey_plan_ctx(ctx, cfg, nframes, cap, &p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    return survey_resident(ctx, iq_device, sample_format, p, found, count);
+}
+
+int pdt_survey(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found, int cap,
+               int *count)
+{
+    if (!ctx || !iq_host || !ddc_fmt(sample_format) || !found || !count) return PDT_ERR_ARG;
+    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
+    SurveyPlan p;
+    int rc = survey_plan_ctx(ctx, cfg, nframes, cap, &p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    // the capture goes where pdt_demod_channel would put it, whole: the same condition on the device's memory
+    const size_t fb = (size_t)ddc_bytes(sample_format);
+    if (window_piece_for(ctx, channel_count(ctx, nframes), fb * (size_t)ctx->ch_decim + 8) != 0) return PDT_ERR_NOMEM;
+    if ((rc = ctx->pcm.ensure((size_t)nframes * fb + 16))) return rc;
+    IngestSrc src;
+    src.mem = (const unsigned char *)iq_host;
+    if ((rc = ingest_capture(ctx, src, (size_t)nframes * fb, ctx->pcm.p))) return rc;
+    return survey_resident(ctx, ctx->pcm.p, sample_format, p, found, count);
+}
+
+int pdt_survey_spectrum(const pdt_ctx *ctx, float *out, int n)
+{
+    if (!ctx || !out) return PDT_ERR_ARG;
+    if (ctx->survey_spec.empty()) return PDT_ERR_STATE;
+    if (n < 0 || (size_t)n != ctx->survey_spec.size()) return PDT_ERR_ARG;
+    memcpy(out, ctx->survey_spec.data(), ctx->survey_spec.size() * sizeof(float));
+    return PDT_OK;
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

@@ -409,6 +409,11 @@ struct pdt_ctx {
     int stream_wb = 0;                  // 0 = not a wideband stream, PDT_FMT_WB_* = the stream takes wideband pushes of that format
     uint64_t cl = 0, cp = 0, ch_in = 0, ch_out = 0;     // (ch_in input samples pushed, ch_out channel samples produced)
     uint64_t channel_len = 0;           // length of PDT_ST_CHANNEL the next demod_common reports
+    // carrier survey (pdt_survey.h): window and twiddle tables of survey_tab_nfft points, the runs' partial rows and the averaged
+    // spectrum on the device, the last survey's spectrum on the host
+    DevBuf survey_win, survey_tw, survey_part, survey_out;
+    int survey_tab_nfft = 0;
+    std::vector<float> survey_spec;
     unsigned char *seg_pin = nullptr;   // pinned staging for the small per-segment transfers (part of the pend_sc block)
     pdt_stats stats;
     std::vector<pdt_kernel_time> ktimes;

@@ -42,6 +42,9 @@
  * one read of the capture (pdt_demod_channels) and each writes its own file, the channel's index appended to the usual name
  * (".0", ".1", ...).  -l -x .. -t .. - reads blocks from standard input through pdt_stream_push_channel, in the format -F names
  * (cu8, the default, cs8, s16 or f32).  Without -x nothing changes, the refusal of rates above 300 kHz included.
+ * -t auto or -t auto:N (an addition, with -x, not beside numeric -t): the carriers are looked for instead of given -- the capture's
+ * averaged spectrum is surveyed on the GPU (pdt_survey), the (N) strongest carriers found are printed like the -t lines
+ * and the run goes on as if their offsets had been given.  No carrier: one line, no output file, exit status 1.  Not from a pipe.
  */
 #include <ctype.h>
 #include <math.h>
@@ -310,6 +313,67 @@ static int multi_channel(FILE *in, long data_offset, uint64_t nframes, size_t fr
     return 0;
 }
 
+static int cmp_float(const void *a, const void *b)
+{
+    const float x = *(const float *)a, y = *(const float *)b;
+    return (x > y) - (x < y);
+}
+
+/* -t auto: survey the capture for its carriers (pdt_survey), at most `want` of them, strongest first.  The offsets come back as the
+ * printed lines show them, so that a run given those numbers with -t is this run.  Returns 0 when there is at least one. */
+static int auto_channels(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, int want,
+                         double *offsetsHz, int *nch)
+{
+    pdt_ctx *ctx = NULL;
+    int rc = pdt_open(cfg, &ctx);
+    if (rc != PDT_OK) {
+        printf("GPU demodulator unavailable: %s\n", pdt_strerror(rc));
+        return 1;
+    }
+    unsigned char *buf = (unsigned char *)malloc((size_t)nframes * frame_bytes + 16);
+    if (!buf || fseek(in, data_offset, SEEK_SET) != 0 || fread(buf, frame_bytes, (size_t)nframes, in) != (size_t)nframes) {
+        printf("Error reading the capture\n");
+        return 1;
+    }
+    pdt_survey_cfg sc;
+    memset(&sc, 0, sizeof sc);
+    sc.max_carriers = want;
+    pdt_carrier found[16];
+    int count = 0;
+    rc = pdt_set_channel(ctx, decim, 0.0);
+    if (rc == PDT_OK) rc = pdt_survey(ctx, buf, nframes, fmt, &sc, found, 16, &count);
+    free(buf);
+    if (rc != PDT_OK) {
+        printf("Survey failed: %s\n", pdt_strerror(rc));
+        pdt_close(ctx);
+        return 1;
+    }
+    if (count == 0) {
+        static float spec[16384];
+        double over = 0.0;
+        if (pdt_survey_spectrum(ctx, spec, 16384) == PDT_OK) {
+            float top = spec[0];
+            for (int i = 1; i < 16384; i++)
+                if (spec[i] > top) top = spec[i];
+            qsort(spec, 16384, sizeof spec[0], cmp_float);
+            const double floor = 0.5 * ((double)spec[8191] + (double)spec[8192]);
+            over = floor > 0 && top > 0 ? 10.0 * log10((double)top / floor) : 0.0;
+        }
+        printf("No carrier found (strongest bin %.1f dB over the floor)\n", over);
+        pdt_close(ctx);
+        return 1;
+    }
+    for (int i = 0; i < count; i++) {
+        char khz[64];
+        snprintf(khz, sizeof khz, "%+f", found[i].offset_hz / 1000.0);
+        offsetsHz[i] = atof(khz) * 1000.0;
+        printf("Channel %d at %s Khz (found, %.1f dB over the floor)\n", i, khz, found[i].peak_db);
+    }
+    *nch = count;
+    pdt_close(ctx);
+    return 0;
+}
+
 static double now_ms(void)
 {
     struct timespec ts;
@@ -325,7 +389,7 @@ int main(int argc, char **argv)
     double normFactor = 0, sampleRate = 0;
     int outputRawFiles = 0, device = 0, quality = 0, sampler = 0, live = 0, chunkGiven = 0, noProgress = 0, real = 0, c;
     double realCenterHz = 0;
-    int decim = 0, nOffsets = 0, wbFormat = PDT_FMT_WB_CU8;
+    int decim = 0, nOffsets = 0, wbFormat = PDT_FMT_WB_CU8, autoCarriers = 0;      /* -t auto[:N]: look for up to N carriers */
     double offsetsHz[16];
     const char *outOverride = NULL;
     char outFileName[1100];
@@ -388,7 +452,16 @@ int main(int argc, char **argv)
             decim = atoi(optarg);
             printf("Wideband input, decimation %d\n", decim);
             break;
-        case 't':                                       /* a channel's offset from the capture's centre, signed */
+        case 't':                                       /* a channel's offset from the capture's centre, signed; or auto[:N] */
+            if (strncmp(optarg, "auto", 4) == 0) {
+                autoCarriers = optarg[4] == ':' ? atoi(optarg + 5) : optarg[4] == 0 ? 16 : 0;
+                if (autoCarriers < 1 || autoCarriers > 16) {
+                    printf("-t auto or -t auto:N with N from 1 to 16\n");
+                    return 1;
+                }
+                printf("Channels: the %d strongest carriers found\n", autoCarriers);
+                break;
+            }
             if (nOffsets >= 16) {
                 printf("At most 16 channels\n");
                 return 1;
@@ -422,7 +495,11 @@ int main(int argc, char **argv)
             abort();
         }
     }
-    if (nOffsets && !decim) {
+    if (autoCarriers && nOffsets) {
+        printf("-t auto cannot be combined with -t <kHz>\n");
+        return 1;
+    }
+    if ((nOffsets || autoCarriers) && !decim) {
         printf("-t requires -x <decimation>\n");
         return 1;
     }
@@ -430,7 +507,7 @@ int main(int argc, char **argv)
         printf("Decimation (-x) must be 2 .. 64, and cannot be combined with -f\n");
         return 1;
     }
-    if (decim && !nOffsets) offsetsHz[nOffsets++] = 0.0;
+    if (decim && !nOffsets && !autoCarriers) offsetsHz[nOffsets++] = 0.0;
     if (live && !chunkGiven) chunkSize = 2400;          /* POESTIPdemodPortAudio/main.c:34 */
     if (chunkSize == (live ? 2400 : DEFAULT_CHUNKSIZE)) printf("Using default %ld chunkSize\n", chunkSize);
     if (optind >= argc) {
@@ -441,6 +518,10 @@ int main(int argc, char **argv)
     printf("%s\n", inFileName);
     printf("Opening IO files..\n");
     const int from_stdin = live && strcmp(inFileName, "-") == 0;
+    if (from_stdin && autoCarriers) {
+        printf("-t auto needs a capture file: the spectrum of a stream is not known in advance\n");
+        return 1;
+    }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
 
     time_t t = time(NULL);
@@ -450,8 +531,9 @@ int main(int argc, char **argv)
     else
         snprintf(outFileName, sizeof outFileName, PREFIX "_%4d%02d%02d_%02d%02d%02d.txt", tm.tm_year + 1900, tm.tm_mon + 1,
                  tm.tm_mday, tm.tm_hour, tm.tm_min, tm.tm_sec);
-    FILE *out = nOffsets > 1 ? stdout : fopen(outFileName, "w+");   /* (several channels: a file each, multi_channel) */
-    if (!in || !out) {
+    /* (several channels: a file each, multi_channel; -t auto: the file is opened once the carriers are known) */
+    FILE *out = autoCarriers ? NULL : nOffsets > 1 ? stdout : fopen(outFileName, "w+");
+    if (!in || (!out && !autoCarriers)) {
         printf("Error opening output files\n");
         exit(1);
     }
@@ -549,7 +631,7 @@ int main(int argc, char **argv)
     if (decim) {
         if (rate % (uint32_t)decim) {
             printf("The wideband rate %u Hz is not divisible by the decimation %d\n", rate, decim);
-            if (out != stdout) {
+            if (out && out != stdout) {
                 fclose(out);
                 remove(outFileName);
             }
@@ -569,6 +651,14 @@ int main(int argc, char **argv)
     cfg.device = device;
     cfg.sampler = sampler;
     cfg.chain = live ? PDT_CHAIN_LIVE : PDT_CHAIN_FILE;
+    if (autoCarriers) {
+        if (auto_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, offsetsHz, &nOffsets)) return 1;
+        out = nOffsets > 1 ? stdout : fopen(outFileName, "w+");
+        if (!out) {
+            printf("Error opening output files\n");
+            exit(1);
+        }
+    }
     if (nOffsets > 1) return multi_channel(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, offsetsHz, nOffsets, outFileName);
     pdt_ctx *ctx = NULL;
     const double t_open0 = now_ms();

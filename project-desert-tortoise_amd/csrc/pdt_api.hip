@@ -873,7 +873,7 @@ int pdt_open(const pdt_config *cfg, pdt_ctx **out)
     if (ctx->tune.agc_warm_s > 0 && !ctx->cfg.agc_warm) ctx->cfg.agc_warm = (uint32_t)(ctx->tune.agc_warm_s * cfg->sample_rate);
     if (!ctx->cfg.chunk) ctx->cfg.chunk = (cfg->mode == PDT_MODE_ARGOS || cfg->chain == PDT_CHAIN_LIVE) ? 2400 : 10000;
     const bool argos_twin = cfg->mode == PDT_MODE_ARGOS && cfg->chain == PDT_CHAIN_LIVE;
-    ctx->elem = (cfg->mode == PDT_MODE_ARGOS && !argos_twin) ? 8 : 4;
+    ctx->elem = (int)((cfg->mode == PDT_MODE_ARGOS && !argos_twin) ? sizeof(double) : sizeof(float));
     int nt = 0, ip = 0;
     int rc = pdt_make_lpf(cfg->mode, cfg->sample_rate, nullptr, &nt, &ip);
     if (rc) { pdt_close(ctx); return rc; }
@@ -954,8 +954,8 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->hits, &ctx->frames, &ctx->taps, &ctx->mag, &ctx->seams_pll, &ctx->seams_agc, &ctx->scal, &ctx->lockinfo,
                        &ctx->term, &ctx->seams_ema, &ctx->gtable, &ctx->gentries, &ctx->gcand,
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
-                       &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->rbuf[0], &ctx->rbuf[1],
-                       &ctx->ddc_taps, &ctx->channel, &ctx->cbuf[0], &ctx->cbuf[1], &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out };
+                       &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
+                       &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1075,71 +1075,78 @@ static int demod_common(pdt_ctx *ctx, uint64_t nframes, int phase = RUN_ALL)
     return run_capture<float>(ctx, nframes, phase);                 // POES, both twins
 }
 
-static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes);
-static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes, uint64_t piece);
+static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, const InFmt &f, int text_fd, uint64_t *text_bytes);
+static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, const InFmt &f, int text_fd, uint64_t *text_bytes, uint64_t piece);
+static int demod_batch(pdt_ctx *const *ctxs, const void *const *iq_device, const uint64_t *nframes, int count, int fmt);
 static uint64_t stream_history(const pdt_ctx *ctx);
-static int demod_real_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt);
-static int demod_channel_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt);
 
-// ---------------------------------------------------------------- real (single-channel) input (pdt_analytic.h)
-static bool real_fmt(int fmt) { return fmt == PDT_FMT_REAL_PCM16 || fmt == PDT_FMT_REAL_F32; }
-static size_t real_bytes(int fmt) { return fmt == PDT_FMT_REAL_PCM16 ? 2 : 4; }
+// ---------------------------------------------------------------- the input front end: I,Q, real and wideband captures
+// A host table on the device, once per key (*slot = the key of what the device holds, 0 = nothing).  A launch that reads the
+// previous table may be in flight: synchronize before overwriting.
+static int table_upload(pdt_ctx *ctx, const std::vector<float> &host, DevBuf &buf, int key, int *slot)
+{
+    *slot = 0;
+    const int rc = buf.ensure(host.size() * sizeof(float) + 16);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(buf.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    *slot = key;
+    return PDT_OK;
+}
 
-// the rotation table on the device (once per context)
+// the rotation table (once per context), and with it the channel filter's taps (once per decimation)
 static int real_table(pdt_ctx *ctx)
 {
-    if (ctx->an_tab.p) return PDT_OK;
-    float tab[2 * AN_TAB];
-    analytic_table(tab);
-    int rc = ctx->an_tab.ensure(sizeof tab);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(ctx->an_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
-    return PDT_OK;
+    if (ctx->an_tab_ready) return PDT_OK;
+    std::vector<float> tab(2 * AN_TAB);
+    analytic_table(tab.data());
+    return table_upload(ctx, tab, ctx->an_tab, 1, &ctx->an_tab_ready);
 }
 
-// x (device, n samples of fmt) -> analytic pairs, outputs [0, n) of a whole capture
-static int real_whole(pdt_ctx *ctx, const void *x, uint64_t n, int fmt, void *out)
+static int channel_tables(pdt_ctx *ctx)
 {
-    int rc = real_table(ctx);
-    if (rc) return rc;
-    HIP_TRY(analytic_launch(ctx->stream, fmt, x, 0, (long long)n, n, 0, ctx->real_step, (const float *)ctx->an_tab.p, out));
-    return PDT_OK;
+    const int rc = real_table(ctx);
+    if (rc || ctx->ddc_taps_decim == ctx->ch_decim) return rc;
+    return table_upload(ctx, ddc_taps(ctx->ch_decim), ctx->ddc_taps, ctx->ch_decim, &ctx->ddc_taps_decim);
 }
 
-// room for n more samples behind the ones a real stream keeps (rbuf[rcur] = rl converted | rp pending | new)
-static int real_reserve(pdt_ctx *ctx, uint64_t n)
+static uint64_t channel_count(const pdt_ctx *ctx, uint64_t n) { return (n + (uint64_t)ctx->ch_decim - 1) / (uint64_t)ctx->ch_decim; }
+
+// room for the channel stream of a whole wideband capture of n frames, and the tables
+static int channel_prepare(pdt_ctx *ctx, uint64_t n)
 {
-    const size_t rb = real_bytes(ctx->stream_real);
-    return ctx->rbuf[ctx->rcur].ensure_keep((size_t)(ctx->rl + ctx->rp + n + 64) * rb, (size_t)(ctx->rl + ctx->rp) * rb);
+    const int rc = ctx->channel.ensure((size_t)channel_count(ctx, n) * 8 + 16);
+    return rc ? rc : channel_tables(ctx);
 }
 
-// n_new samples have landed behind the kept ones: convert every sample whose right halo is there (all of them when the stream
-// ends: zeros beyond), append the pairs to the stream's window, keep the last 31 converted and the unconverted ones
-static int real_convert(pdt_ctx *ctx, uint64_t n_new, bool final_piece)
+// A whole capture resident at x, n frames of f: convert it if its kind has a converter, then the chain (real and wideband
+// input: the RAW float path on the converter's pairs).
+static int demod_resident(pdt_ctx *ctx, const void *x, uint64_t n, const InFmt &f)
 {
-    int rc = real_table(ctx);
-    if (rc) return rc;
-    const size_t rb = real_bytes(ctx->stream_real);
-    const uint64_t avail = ctx->rp + n_new;
-    const uint64_t m = final_piece ? avail : (avail > (uint64_t)AN_HALF ? avail - AN_HALF : 0);
-    if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + m) + 64) * 8, (size_t)ctx->stream_have * 8))) return rc;
-    const unsigned char *x = (const unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)ctx->rl * rb;
-    HIP_TRY(analytic_launch(ctx->stream, ctx->stream_real, x, -(long long)ctx->rl, (long long)avail, m, ctx->real_done, ctx->real_step,
-                            (const float *)ctx->an_tab.p, (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * 8));
-    const uint64_t keep_left = std::min<uint64_t>(AN_HALF, ctx->rl + m), total = ctx->rl + avail, keep = keep_left + (avail - m);
-    if (keep && keep < total) {
-        DevBuf &dst = ctx->rbuf[ctx->rcur ^ 1];
-        if ((rc = dst.ensure((size_t)(keep + 64) * rb))) return rc;
-        HIP_TRY(hipMemcpyAsync(dst.p, (const unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)(total - keep) * rb, (size_t)keep * rb,
-                               hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->rcur ^= 1;
+    int rc;
+    ctx->pcm_fmt = f.pcm_fmt;
+    switch (f.kind) {
+    case IN_IQ:
+        ctx->pcm_dev = x;
+        return demod_common(ctx, n);
+    case IN_REAL:
+        if ((rc = ctx->analytic.ensure((size_t)n * 8 + 16)) || (rc = real_table(ctx))) return rc;
+        HIP_TRY(analytic_launch(ctx->stream, f.code, x, 0, (long long)n, n, 0, ctx->real_step, (const float *)ctx->an_tab.p, ctx->analytic.p));
+        ctx->pcm_dev = ctx->analytic.p;
+        ctx->analytic_len = n;
+        return demod_common(ctx, n);
+    case IN_WB: {
+        if ((rc = channel_prepare(ctx, n))) return rc;
+        const uint64_t m = channel_count(ctx, n);
+        void *out = ctx->channel.p;
+        HIP_TRY(ddc_launch(ctx->stream, f.code, x, 0, (long long)n, m, 0, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
+                           &ctx->ch_step, &out, 1));
+        ctx->pcm_dev = ctx->channel.p;
+        ctx->channel_len = m;
+        return demod_common(ctx, m);
     }
-    ctx->rl = keep_left;
-    ctx->rp = avail - m;
-    ctx->real_done += m;
-    ctx->stream_have += m;
-    ctx->stream_total += m;
-    return PDT_OK;
+    }
+    return PDT_ERR_ARG;
 }
 
 // Does a capture of nframes fit the device in one piece?  The reference's chunk loop takes a file of any length in O(chunk)
@@ -1175,26 +1182,10 @@ static long long window_piece_for(pdt_ctx *ctx, uint64_t nframes, size_t fb)
     return (long long)((uint64_t)piece / chunk * chunk);
 }
 
-int pdt_demod_pcm16(pdt_ctx *ctx, const int16_t *iq_host, uint64_t nframes)
+// a whole wideband capture of n frames beside what the chain keeps -- per channel sample: D input frames and the float pair
+static bool channel_fits(pdt_ctx *ctx, uint64_t n, const InFmt &f)
 {
-    if (!ctx || (!iq_host && nframes)) return PDT_ERR_ARG;
-    if (ctx->stream_open) return PDT_ERR_STATE;                      // pdt_stream_end / pdt_stream_begin first
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    IngestSrc src;
-    src.mem = (const unsigned char *)iq_host;
-    if (const long long piece = window_piece_for(ctx, nframes, 4)) return piece < 0 ? (int)piece : demod_windowed(ctx, src, nframes, 0, -1, nullptr, (uint64_t)piece);
-    int rc = ctx->pcm.ensure((size_t)nframes * 4 + 16);
-    if (rc) return rc;
-    const auto t_in = std::chrono::steady_clock::now();
-    if ((rc = ingest_capture(ctx, src, (size_t)nframes * 4, ctx->pcm.p))) return rc;
-    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-    ctx->pcm_dev = ctx->pcm.p;
-    ctx->pcm_fmt = 0;
-    rc = demod_common(ctx, nframes);
-    ctx->stats.ingest_ms = ctx->ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
-    return rc;
+    return window_piece_for(ctx, channel_count(ctx, n), (size_t)f.bytes * (size_t)ctx->ch_decim + 8) == 0;
 }
 
 // hour-long POES captures: the chain starts on the part of the capture that has arrived (demod_overlapped)
@@ -1211,89 +1202,101 @@ static bool overlap_ingest(const pdt_ctx *ctx, uint64_t nframes, size_t fb)
            nframes / ctx->cfg.chunk >= 64;
 }
 
+// A whole capture into ctx->pcm: room for it, the ingest, its host time in ctx->ingest_ms.  What the statistics say about it
+// is the caller's decision (ingest_publish): a survey leaves the context's results as they are.
+static int ingest_whole(pdt_ctx *ctx, const IngestSrc &src, size_t bytes)
+{
+    int rc = ctx->pcm.ensure(bytes + 16);
+    if (rc) return rc;
+    const auto t_in = std::chrono::steady_clock::now();
+    if ((rc = ingest_capture(ctx, src, bytes, ctx->pcm.p))) return rc;
+    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+    return PDT_OK;
+}
+
+static void ingest_publish(pdt_ctx *ctx)
+{
+    ctx->stats.ingest_ms = ctx->ingest_ms;
+    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
+    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
+}
+
+// One capture from host memory or a file, of any format the entry has let through: the bounded window when it does not fit
+// (wideband input has none yet: PDT_ERR_NOMEM), overlapped segments for a large I,Q file, else ingest + convert + chain; the
+// frame text when a text_fd was given.  PDT_ERR_FORMAT comes before PDT_ERR_STATE here, the order of pdt_demod_fd and
+// pdt_demod_file; the entries from host memory answer an open stream before they come here (demod_host).
+static int demod_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int format, int text_fd, uint64_t *text_bytes)
+{
+    const InFmt f = in_fmt(format);
+    if (f.kind == IN_IQ && f.pcm_fmt && ctx->elem != 4) return PDT_ERR_FORMAT;       // ARGOSdemod/main.c:238-241: "RAW files not yet supported"
+    if (ctx->stream_open || (f.kind == IN_WB && !ctx->ch_decim)) return PDT_ERR_STATE;   // pdt_stream_end / _begin resp. pdt_set_channel first
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    if (f.kind == IN_WB) {
+        if (!channel_fits(ctx, n, f)) return PDT_ERR_NOMEM;
+    } else {
+        // (a real capture's analytic stream is one more buffer of the capture's length; it is never taken in overlapped segments)
+        const long long piece = window_piece_for(ctx, n, (size_t)f.bytes + (f.kind == IN_REAL ? 8 : 0));
+        if (piece) return piece < 0 ? (int)piece : demod_windowed(ctx, src, n, f, text_fd, text_bytes, (uint64_t)piece);
+        if (f.kind == IN_IQ && src.fd >= 0 && overlap_ingest(ctx, n, (size_t)f.bytes)) return demod_overlapped(ctx, src, n, f, text_fd, text_bytes);
+    }
+    int rc = ingest_whole(ctx, src, (size_t)n * (size_t)f.bytes);
+    if (rc) return rc;
+    rc = demod_resident(ctx, ctx->pcm.p, n, f);
+    ingest_publish(ctx);
+    if (rc || text_fd < 0) return rc;
+    return pdt_write_frames(ctx, text_fd, text_bytes);
+}
+
+// the whole-capture entries from host memory and from device memory: each takes the formats of its kind only
+static int demod_host(pdt_ctx *ctx, const void *host, uint64_t n, int format, int kind)
+{
+    if (!ctx || (!host && n) || in_fmt(format).kind != kind) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;                      // (before PDT_ERR_FORMAT: pdt_demod_f32's order)
+    IngestSrc src;
+    src.mem = (const unsigned char *)host;
+    return demod_src(ctx, src, n, format, -1, nullptr);
+}
+
+static int demod_device(pdt_ctx *ctx, const void *dev, uint64_t n, int format, int kind)
+{
+    const InFmt f = in_fmt(format);
+    if (!ctx || (!dev && n) || f.kind != kind) return PDT_ERR_ARG;
+    if (ctx->stream_open || (kind == IN_WB && !ctx->ch_decim)) return PDT_ERR_STATE;     // pdt_stream_end / _begin resp. pdt_set_channel first
+    if (kind == IN_IQ && f.pcm_fmt && ctx->elem != 4) return PDT_ERR_FORMAT;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    return demod_resident(ctx, dev, n, f);
+}
+
+int pdt_demod_pcm16(pdt_ctx *ctx, const int16_t *iq_host, uint64_t nframes) { return demod_host(ctx, iq_host, nframes, PDT_FMT_PCM16, IN_IQ); }
+int pdt_demod_f32(pdt_ctx *ctx, const float *iq_host, uint64_t nframes) { return demod_host(ctx, iq_host, nframes, PDT_FMT_F32, IN_IQ); }
+int pdt_demod_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format) { return demod_host(ctx, x_host, n, sample_format, IN_REAL); }
+int pdt_demod_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format) { return demod_host(ctx, iq_host, nframes, sample_format, IN_WB); }
+
+int pdt_demod_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes) { return demod_device(ctx, iq_device, nframes, PDT_FMT_PCM16, IN_IQ); }
+int pdt_demod_device_f32(pdt_ctx *ctx, const void *iq_device, uint64_t nframes) { return demod_device(ctx, iq_device, nframes, PDT_FMT_F32, IN_IQ); }
+int pdt_demod_device_real(pdt_ctx *ctx, const void *x_device, uint64_t n, int sample_format) { return demod_device(ctx, x_device, n, sample_format, IN_REAL); }
+int pdt_demod_device_channel(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format)
+{
+    return demod_device(ctx, iq_device, nframes, sample_format, IN_WB);
+}
+
 int pdt_demod_fd(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, int sample_format)
 {
-    if (ctx && fd >= 0 && real_fmt(sample_format)) {                 // single channel: never in overlapped segments
-        if (ctx->stream_open) return PDT_ERR_STATE;
-        HIP_TRY(hipSetDevice(ctx->cfg.device));
-        IngestSrc src;
-        src.fd = fd;
-        src.off = byte_offset;
-        return demod_real_src(ctx, src, nframes, sample_format);
-    }
-    if (ctx && fd >= 0 && ddc_fmt(sample_format)) {                  // wideband: ingested whole, then converted
-        if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
-        HIP_TRY(hipSetDevice(ctx->cfg.device));
-        IngestSrc src;
-        src.fd = fd;
-        src.off = byte_offset;
-        return demod_channel_src(ctx, src, nframes, sample_format);
-    }
-    if (!ctx || fd < 0 || (sample_format != PDT_FMT_PCM16 && sample_format != PDT_FMT_F32)) return PDT_ERR_ARG;
-    if (sample_format == PDT_FMT_F32 && ctx->elem != 4) return PDT_ERR_FORMAT;   // ARGOSdemod/main.c:238-241
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    const size_t fb = sample_format == PDT_FMT_F32 ? 8 : 4;
+    if (!ctx || fd < 0 || in_fmt(sample_format).kind == IN_NONE) return PDT_ERR_ARG;
     IngestSrc src;
     src.fd = fd;
     src.off = byte_offset;
-    if (ctx->stream_open) return PDT_ERR_STATE;
-    if (const long long piece = window_piece_for(ctx, nframes, fb))
-        return piece < 0 ? (int)piece : demod_windowed(ctx, src, nframes, sample_format == PDT_FMT_F32 ? 1 : 0, -1, nullptr, (uint64_t)piece);
-    if (overlap_ingest(ctx, nframes, fb)) return demod_overlapped(ctx, src, nframes, sample_format == PDT_FMT_F32 ? 1 : 0, -1, nullptr);
-    int rc = ctx->pcm.ensure((size_t)nframes * fb + 16);
-    if (rc) return rc;
-    const auto t_in = std::chrono::steady_clock::now();
-    if ((rc = ingest_capture(ctx, src, (size_t)nframes * fb, ctx->pcm.p))) return rc;
-    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-    ctx->pcm_dev = ctx->pcm.p;
-    ctx->pcm_fmt = sample_format == PDT_FMT_F32 ? 1 : 0;
-    rc = demod_common(ctx, nframes);
-    ctx->stats.ingest_ms = ctx->ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
-    return rc;
+    return demod_src(ctx, src, nframes, sample_format, -1, nullptr);
 }
 
-int pdt_demod_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes)
+int pdt_demod_file(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, int sample_format, int text_fd, uint64_t *text_bytes)
 {
-    if (!ctx || (!iq_device && nframes)) return PDT_ERR_ARG;
-    if (ctx->stream_open) return PDT_ERR_STATE;                      // pdt_stream_end / pdt_stream_begin first
-    ctx->pcm_dev = iq_device;
-    ctx->pcm_fmt = 0;
-    return demod_common(ctx, nframes);
-}
-
-int pdt_demod_f32(pdt_ctx *ctx, const float *iq_host, uint64_t nframes)
-{
-    if (!ctx || (!iq_host && nframes)) return PDT_ERR_ARG;
-    if (ctx->stream_open) return PDT_ERR_STATE;                      // pdt_stream_end / pdt_stream_begin first
-    if (ctx->elem != 4) return PDT_ERR_FORMAT;       // ARGOSdemod/main.c:238-241: "RAW files not yet supported"
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    if (text_bytes) *text_bytes = 0;
+    if (!ctx || fd < 0 || text_fd < 0 || in_fmt(sample_format).kind == IN_NONE) return PDT_ERR_ARG;
     IngestSrc src;
-    src.mem = (const unsigned char *)iq_host;
-    if (const long long piece = window_piece_for(ctx, nframes, 8)) return piece < 0 ? (int)piece : demod_windowed(ctx, src, nframes, 1, -1, nullptr, (uint64_t)piece);
-    int rc = ctx->pcm.ensure((size_t)nframes * 8 + 16);
-    if (rc) return rc;
-    const auto t_in = std::chrono::steady_clock::now();
-    if ((rc = ingest_capture(ctx, src, (size_t)nframes * 8, ctx->pcm.p))) return rc;
-    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-    ctx->pcm_dev = ctx->pcm.p;
-    ctx->pcm_fmt = 1;
-    rc = demod_common(ctx, nframes);
-    ctx->stats.ingest_ms = ctx->ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
-    return rc;
-}
-
-int pdt_demod_device_f32(pdt_ctx *ctx, const void *iq_device, uint64_t nframes)
-{
-    if (!ctx || (!iq_device && nframes)) return PDT_ERR_ARG;
-    if (ctx->stream_open) return PDT_ERR_STATE;                      // pdt_stream_end / pdt_stream_begin first
-    if (ctx->elem != 4) return PDT_ERR_FORMAT;
-    ctx->pcm_dev = iq_device;
-    ctx->pcm_fmt = 1;
-    return demod_common(ctx, nframes);
+    src.fd = fd;
+    src.off = byte_offset;
+    return demod_src(ctx, src, nframes, sample_format, text_fd, text_bytes);
 }
 
 int pdt_set_real_input(pdt_ctx *ctx, double center_hz)
@@ -1306,55 +1309,6 @@ int pdt_set_real_input(pdt_ctx *ctx, double center_hz)
     return PDT_OK;
 }
 
-// a whole real capture whose samples are resident at x: convert, then the RAW float path
-static int demod_real_resident(pdt_ctx *ctx, const void *x, uint64_t n, int fmt)
-{
-    int rc = ctx->analytic.ensure((size_t)n * 8 + 16);
-    if (rc) return rc;
-    if ((rc = real_whole(ctx, x, n, fmt, ctx->analytic.p))) return rc;
-    ctx->pcm_dev = ctx->analytic.p;
-    ctx->pcm_fmt = 1;
-    ctx->analytic_len = n;
-    return demod_common(ctx, n);
-}
-
-// host memory or a file: the bounded window when the capture does not fit, else ingest + convert + chain
-static int demod_real_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt)
-{
-    const size_t rb = real_bytes(fmt);
-    if (const long long piece = window_piece_for(ctx, n, rb + 8))         // (the analytic stream is a buffer of the capture's length)
-        return piece < 0 ? (int)piece : demod_windowed(ctx, src, n, fmt, -1, nullptr, (uint64_t)piece);
-    int rc = ctx->pcm.ensure((size_t)n * rb + 16);
-    if (rc) return rc;
-    const auto t_in = std::chrono::steady_clock::now();
-    if ((rc = ingest_capture(ctx, src, (size_t)n * rb, ctx->pcm.p))) return rc;
-    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-    rc = demod_real_resident(ctx, ctx->pcm.p, n, fmt);
-    ctx->stats.ingest_ms = ctx->ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
-    return rc;
-}
-
-int pdt_demod_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format)
-{
-    if (!ctx || (!x_host && n) || !real_fmt(sample_format)) return PDT_ERR_ARG;
-    if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    IngestSrc src;
-    src.mem = (const unsigned char *)x_host;
-    return demod_real_src(ctx, src, n, sample_format);
-}
-
-int pdt_demod_device_real(pdt_ctx *ctx, const void *x_device, uint64_t n, int sample_format)
-{
-    if (!ctx || (!x_device && n) || !real_fmt(sample_format)) return PDT_ERR_ARG;
-    if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    return demod_real_resident(ctx, x_device, n, sample_format);
-}
-
-// ---------------------------------------------------------------- wideband input (pdt_ddc.h)
 int pdt_set_channel(pdt_ctx *ctx, int decim, double offset_hz)
 {
     if (!ctx || decim < DDC_MIN_DECIM || decim > DDC_MAX_DECIM) return PDT_ERR_ARG;
@@ -1367,127 +1321,9 @@ int pdt_set_channel(pdt_ctx *ctx, int decim, double offset_hz)
     return PDT_OK;
 }
 
-// the rotation table and the channel filter's taps on the device (once per context and decimation)
-static int channel_tables(pdt_ctx *ctx)
-{
-    int rc = real_table(ctx);
-    if (rc) return rc;
-    if (ctx->ddc_taps.p && ctx->ddc_taps_decim == ctx->ch_decim) return PDT_OK;
-    const std::vector<float> taps = ddc_taps(ctx->ch_decim);
-    if ((rc = ctx->ddc_taps.ensure(taps.size() * sizeof(float) + 16))) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                      // (a launch that reads the previous taps may be in flight)
-    HIP_TRY(hipMemcpy(ctx->ddc_taps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
-    ctx->ddc_taps_decim = ctx->ch_decim;
-    return PDT_OK;
-}
-
-static uint64_t channel_count(const pdt_ctx *ctx, uint64_t n) { return (n + (uint64_t)ctx->ch_decim - 1) / (uint64_t)ctx->ch_decim; }
-
-// n_new input samples have landed behind the kept ones of a wideband stream (cbuf[ccur] = cl left halo | cp pending | new):
-// produce every channel sample whose right halo is there -- floor(pushed / D) - 8 of them so far, ceil(pushed / D) when the
-// stream ends (zeros beyond) --, append them to the stream's window, keep 8 D samples to the left of the next output and
-// everything from it on
-static int channel_convert(pdt_ctx *ctx, uint64_t n_new, bool final_piece)
-{
-    int rc = channel_tables(ctx);
-    if (rc) return rc;
-    const uint64_t D = (uint64_t)ctx->ch_decim, span = (uint64_t)DDC_SPAN * D;
-    const size_t fb = (size_t)ddc_bytes(ctx->stream_wb);
-    const uint64_t base = ctx->ch_out * D;                            // global input index the next output is centred on
-    const uint64_t total_in = ctx->ch_in + n_new;
-    const uint64_t outs = final_piece ? (total_in + D - 1) / D : (total_in / D > (uint64_t)DDC_SPAN ? total_in / D - DDC_SPAN : 0);
-    const uint64_t m = outs > ctx->ch_out ? outs - ctx->ch_out : 0;
-    if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + m) + 64) * 8, (size_t)ctx->stream_have * 8))) return rc;
-    const unsigned char *x = (const unsigned char *)ctx->cbuf[ctx->ccur].p + (size_t)ctx->cl * fb;
-    void *out = (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * 8;
-    HIP_TRY(ddc_launch(ctx->stream, ctx->stream_wb, x, -(long long)ctx->cl, (long long)(ctx->cp + n_new), m, base, ctx->ch_decim,
-                       (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p, &ctx->ch_step, &out, 1));
-    const uint64_t nbase = (ctx->ch_out + m) * D;
-    if (!final_piece) {
-        const uint64_t keep_left = std::min<uint64_t>(span, nbase), start = nbase - keep_left - (base - ctx->cl), keep = total_in - (nbase - keep_left);
-        if (start) {
-            DevBuf &dst = ctx->cbuf[ctx->ccur ^ 1];
-            if ((rc = dst.ensure((size_t)(keep + 64) * fb))) return rc;
-            if (keep)
-                HIP_TRY(hipMemcpyAsync(dst.p, (const unsigned char *)ctx->cbuf[ctx->ccur].p + (size_t)start * fb, (size_t)keep * fb,
-                                       hipMemcpyDeviceToDevice, ctx->stream));
-            ctx->ccur ^= 1;
-        }
-        ctx->cl = keep_left;
-        ctx->cp = total_in - nbase;
-    } else {
-        ctx->cl = ctx->cp = 0;
-    }
-    ctx->ch_in = total_in;
-    ctx->ch_out += m;
-    ctx->stream_have += m;
-    ctx->stream_total += m;
-    return PDT_OK;
-}
-
-// a whole wideband capture whose samples are resident at x: convert into this context's channel buffer
-static int channel_prepare(pdt_ctx *ctx, uint64_t n)
-{
-    int rc = ctx->channel.ensure((size_t)channel_count(ctx, n) * 8 + 16);
-    if (rc) return rc;
-    return channel_tables(ctx);
-}
-
-static int demod_channel_resident(pdt_ctx *ctx, const void *x, uint64_t n, int fmt)
-{
-    int rc = channel_prepare(ctx, n);
-    if (rc) return rc;
-    const uint64_t m = channel_count(ctx, n);
-    void *out = ctx->channel.p;
-    HIP_TRY(ddc_launch(ctx->stream, fmt, x, 0, (long long)n, m, 0, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
-                       &ctx->ch_step, &out, 1));
-    ctx->pcm_dev = ctx->channel.p;
-    ctx->pcm_fmt = 1;
-    ctx->channel_len = m;
-    return demod_common(ctx, m);
-}
-
-// host memory or a file: ingest + convert + chain; PDT_ERR_NOMEM when the capture does not fit (no bounded window yet)
-static int demod_channel_src(pdt_ctx *ctx, const IngestSrc &src, uint64_t n, int fmt)
-{
-    const size_t fb = (size_t)ddc_bytes(fmt);
-    // per channel sample: D input frames and the float pair, beside what the chain keeps
-    if (window_piece_for(ctx, channel_count(ctx, n), fb * (size_t)ctx->ch_decim + 8) != 0) return PDT_ERR_NOMEM;
-    int rc = ctx->pcm.ensure((size_t)n * fb + 16);
-    if (rc) return rc;
-    const auto t_in = std::chrono::steady_clock::now();
-    if ((rc = ingest_capture(ctx, src, (size_t)n * fb, ctx->pcm.p))) return rc;
-    ctx->ingest_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
-    rc = demod_channel_resident(ctx, ctx->pcm.p, n, fmt);
-    ctx->stats.ingest_ms = ctx->ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
-    return rc;
-}
-
-int pdt_demod_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format)
-{
-    if (!ctx || (!iq_host && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
-    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    IngestSrc src;
-    src.mem = (const unsigned char *)iq_host;
-    return demod_channel_src(ctx, src, nframes, sample_format);
-}
-
-int pdt_demod_device_channel(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format)
-{
-    if (!ctx || (!iq_device && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
-    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    return demod_channel_resident(ctx, iq_device, nframes, sample_format);
-}
-
-static int demod_batch(pdt_ctx *const *ctxs, const void *const *iq_device, const uint64_t *nframes, int count, int fmt);
-
 int pdt_demod_channels_device(pdt_ctx *const *ctxs, int count, const void *iq_device, uint64_t nframes, int sample_format)
 {
-    if (count < 0 || (count && !ctxs) || (!iq_device && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
+    if (count < 0 || (count && !ctxs) || (!iq_device && nframes) || in_fmt(sample_format).kind != IN_WB) return PDT_ERR_ARG;
     for (int i = 0; i < count; i++) {
         if (!ctxs[i]) return PDT_ERR_ARG;
         if (ctxs[i]->stream_open || !ctxs[i]->ch_decim) return PDT_ERR_STATE;
@@ -1514,41 +1350,35 @@ int pdt_demod_channels_device(pdt_ctx *const *ctxs, int count, const void *iq_de
                        (const float *)c0->an_tab.p, steps.data(), outs.data(), count));
     HIP_TRY(hipStreamSynchronize(c0->stream));
     for (int i = 0; i < count; i++) ctxs[i]->channel_len = m;
-    return demod_batch(ctxs, (const void *const *)outs.data(), lens.data(), count, 1);
+    return demod_batch(ctxs, (const void *const *)outs.data(), lens.data(), count, PDT_FMT_F32);
 }
 
 int pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uint64_t nframes, int sample_format)
 {
-    if (count < 0 || (count && !ctxs) || (!iq_host && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
+    const InFmt f = in_fmt(sample_format);
+    if (count < 0 || (count && !ctxs) || (!iq_host && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
     if (!count) return PDT_OK;
     pdt_ctx *c0 = ctxs[0];
     if (!c0) return PDT_ERR_ARG;
     if (c0->stream_open || !c0->ch_decim) return PDT_ERR_STATE;
     HIP_TRY(hipSetDevice(c0->cfg.device));
-    const size_t bytes = (size_t)nframes * (size_t)ddc_bytes(sample_format);
-    if (window_piece_for(c0, channel_count(c0, nframes), (size_t)ddc_bytes(sample_format) * (size_t)c0->ch_decim + 8) != 0) return PDT_ERR_NOMEM;
-    int rc = c0->pcm.ensure(bytes + 16);
-    if (rc) return rc;
+    if (!channel_fits(c0, nframes, f)) return PDT_ERR_NOMEM;
     IngestSrc src;
     src.mem = (const unsigned char *)iq_host;
-    if ((rc = ingest_capture(c0, src, bytes, c0->pcm.p))) return rc;
-    return pdt_demod_channels_device(ctxs, count, c0->pcm.p, nframes, sample_format);
+    // (the first context's ingest is timed but not published: the contexts of a batch report no ingest, as they never have -- DESIGN 4.11)
+    const int rc = ingest_whole(c0, src, (size_t)nframes * (size_t)f.bytes);
+    return rc ? rc : pdt_demod_channels_device(ctxs, count, c0->pcm.p, nframes, sample_format);
 }
 
 // ---------------------------------------------------------------- carrier survey (pdt_survey.h)
+// window and twiddles under one key: it is set when both are on the device
 static int survey_tables(pdt_ctx *ctx, int nfft)
 {
     if (ctx->survey_tab_nfft == nfft) return PDT_OK;
-    const std::vector<float> win = survey_window(nfft), tw = survey_twiddles(nfft);
-    int rc = ctx->survey_win.ensure(win.size() * sizeof(float) + 16);
-    if (!rc) rc = ctx->survey_tw.ensure(tw.size() * sizeof(float) + 16);
-    if (!rc) rc = ctx->survey_out.ensure((size_t)nfft * sizeof(float));
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                      // (a launch that reads the previous tables may be in flight)
-    HIP_TRY(hipMemcpy(ctx->survey_win.p, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->survey_tw.p, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-    ctx->survey_tab_nfft = nfft;
-    return PDT_OK;
+    ctx->survey_tab_nfft = 0;
+    int rc = ctx->survey_out.ensure((size_t)nfft * sizeof(float)), win_key = 0;
+    if (!rc) rc = table_upload(ctx, survey_window(nfft), ctx->survey_win, nfft, &win_key);
+    return rc ? rc : table_upload(ctx, survey_twiddles(nfft), ctx->survey_tw, nfft, &ctx->survey_tab_nfft);
 }
 
 // the plan of a survey by this context: the defaults of merge_hz and guard_hz are the mode's PLL range and half the channel rate
@@ -1559,13 +1389,13 @@ static int survey_plan_ctx(const pdt_ctx *ctx, const pdt_survey_cfg *cfg, uint64
 }
 
 // x: the capture, resident.  Nothing of the context's demodulation state is touched.
-static int survey_resident(pdt_ctx *ctx, const void *x, int fmt, const SurveyPlan &p, pdt_carrier *found, int *count)
+static int survey_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const SurveyPlan &p, pdt_carrier *found, int *count)
 {
     int rc = survey_tables(ctx, p.nfft);
     if (!rc) rc = ctx->survey_part.ensure(survey_part_floats(p.nseg, p.nfft) * sizeof(float));
     if (rc) return rc;
-    const unsigned char *first = (const unsigned char *)x + (size_t)p.first * (size_t)ddc_bytes(fmt);
-    HIP_TRY(survey_launch(ctx->stream, fmt, first, p.nseg, p.nfft, (const float *)ctx->survey_win.p, (const float *)ctx->survey_tw.p,
+    const unsigned char *first = (const unsigned char *)x + (size_t)p.first * (size_t)f.bytes;
+    HIP_TRY(survey_launch(ctx->stream, f.code, first, p.nseg, p.nfft, (const float *)ctx->survey_win.p, (const float *)ctx->survey_tw.p,
                           (float *)ctx->survey_part.p, (float *)ctx->survey_out.p));
     std::vector<float> P((size_t)p.nfft);
     HIP_TRY(hipMemcpyAsync(P.data(), ctx->survey_out.p, P.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -1575,35 +1405,38 @@ static int survey_resident(pdt_ctx *ctx, const void *x, int fmt, const SurveyPla
     return PDT_OK;
 }
 
-int pdt_survey_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
+// both survey entries: the capture in host memory goes where pdt_demod_channel would put it, whole -- the same condition on the
+// device's memory -- and its ingest is not published: a survey leaves the context's results and statistics unchanged
+static int survey_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
                       int cap, int *count)
 {
-    if (!ctx || !iq_device || !ddc_fmt(sample_format) || !found || !count) return PDT_ERR_ARG;
+    const InFmt f = in_fmt(sample_format);
+    if (!ctx || !iq || f.kind != IN_WB || !found || !count) return PDT_ERR_ARG;
     if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
     SurveyPlan p;
     int rc = survey_plan_ctx(ctx, cfg, nframes, cap, &p);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
-    return survey_resident(ctx, iq_device, sample_format, p, found, count);
+    if (!resident) {
+        if (!channel_fits(ctx, nframes, f)) return PDT_ERR_NOMEM;
+        IngestSrc src;
+        src.mem = (const unsigned char *)iq;
+        if ((rc = ingest_whole(ctx, src, (size_t)nframes * (size_t)f.bytes))) return rc;
+        iq = ctx->pcm.p;
+    }
+    return survey_resident(ctx, iq, f, p, found, count);
+}
+
+int pdt_survey_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
+                      int cap, int *count)
+{
+    return survey_any(ctx, iq_device, true, nframes, sample_format, cfg, found, cap, count);
 }
 
 int pdt_survey(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found, int cap,
                int *count)
 {
-    if (!ctx || !iq_host || !ddc_fmt(sample_format) || !found || !count) return PDT_ERR_ARG;
-    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
-    SurveyPlan p;
-    int rc = survey_plan_ctx(ctx, cfg, nframes, cap, &p);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    // the capture goes where pdt_demod_channel would put it, whole: the same condition on the device's memory
-    const size_t fb = (size_t)ddc_bytes(sample_format);
-    if (window_piece_for(ctx, channel_count(ctx, nframes), fb * (size_t)ctx->ch_decim + 8) != 0) return PDT_ERR_NOMEM;
-    if ((rc = ctx->pcm.ensure((size_t)nframes * fb + 16))) return rc;
-    IngestSrc src;
-    src.mem = (const unsigned char *)iq_host;
-    if ((rc = ingest_capture(ctx, src, (size_t)nframes * fb, ctx->pcm.p))) return rc;
-    return survey_resident(ctx, ctx->pcm.p, sample_format, p, found, count);
+    return survey_any(ctx, iq_host, false, nframes, sample_format, cfg, found, cap, count);
 }
 
 int pdt_survey_spectrum(const pdt_ctx *ctx, float *out, int n)
@@ -1778,10 +1611,10 @@ int pdt_stage_fir(pdt_ctx *ctx, const void *in_host, uint64_t n, pdt_fir_state *
 // ---------------------------------------------------------------- batched many-capture mode
 int pdt_demod_batch_device(pdt_ctx *const *ctxs, const void *const *iq_device, const uint64_t *nframes, int count)
 {
-    return demod_batch(ctxs, iq_device, nframes, count, 0);
+    return demod_batch(ctxs, iq_device, nframes, count, PDT_FMT_PCM16);
 }
 
-// fmt: 0 = int16 pairs, 1 = float32 pairs (the channel streams of pdt_demod_channels_device)
+// fmt: PDT_FMT_PCM16, or PDT_FMT_F32 for the channel streams of pdt_demod_channels_device
 static int demod_batch(pdt_ctx *const *ctxs, const void *const *iq_device, const uint64_t *nframes, int count, int fmt)
 {
     if (count < 0 || (count && (!ctxs || !iq_device || !nframes))) return PDT_ERR_ARG;
@@ -1797,7 +1630,7 @@ static int demod_batch(pdt_ctx *const *ctxs, const void *const *iq_device, const
         c->batch_hint = 0;
         for (int k = 0; k < count; k++) c->batch_hint += (ctxs[k]->cfg.device == c->cfg.device) ? 1 : 0;
         c->pcm_dev = iq_device[enq];
-        c->pcm_fmt = fmt;
+        c->pcm_fmt = in_fmt(fmt).pcm_fmt;
         const int rc = demod_common(c, nframes[enq], RUN_ENQUEUE);
         if (rc) { first_err = rc; break; }
     }
@@ -1828,19 +1661,21 @@ static int demod_batch(pdt_ctx *const *ctxs, const void *const *iq_device, const
 }
 
 // ---------------------------------------------------------------- streaming front end
+// No stream: what pdt_stream_begin starts from, and what the whole-capture paths that borrow the stream machinery leave behind
+// (demod_overlapped, demod_windowed: a later push starts a new stream).  Results and statistics are not touched.
+static void stream_reset(pdt_ctx *ctx)
+{
+    ctx->sc = StreamCarry();
+    ctx->stream_have = ctx->stream_done = ctx->stream_total = 0;
+    ctx->stream_fmt = -1;
+    ctx->halo.left = ctx->halo.pending = ctx->halo.in = ctx->halo.out = 0;
+    ctx->stream_open = false;
+}
+
 int pdt_stream_begin(pdt_ctx *ctx)
 {
     if (!ctx) return PDT_ERR_ARG;
-    ctx->sc = StreamCarry();
-    ctx->stream_have = 0;
-    ctx->stream_done = 0;
-    ctx->stream_total = 0;
-    ctx->stream_fmt = -1;
-    ctx->stream_real = 0;
-    ctx->rl = ctx->rp = ctx->real_done = 0;
-    ctx->stream_wb = 0;
-    ctx->cl = ctx->cp = ctx->ch_in = ctx->ch_out = 0;
-    ctx->stream_open = false;
+    stream_reset(ctx);
     ctx->stream_new.clear();
     ctx->frames_host.clear();
     ctx->chunk_host.clear();
@@ -1881,12 +1716,13 @@ static uint64_t stream_align(const pdt_ctx *ctx)
 static void segment_begin(pdt_ctx *ctx, bool final_seg)
 {
     StreamCarry &C = ctx->sc;
+    const InFmt f = in_fmt(ctx->stream_fmt);
     C.active = true;
     C.final_seg = final_seg;
     C.first = (long long)ctx->stream_done;
     // (in place: the window is a view into the resident capture -- it "slides" by moving its base, not its samples)
-    ctx->pcm_dev = (const unsigned char *)ctx->stream_in.p + (C.in_place ? (size_t)C.origin * (ctx->stream_fmt ? 8 : 4) : 0);
-    ctx->pcm_fmt = ctx->stream_fmt;
+    ctx->pcm_dev = (const unsigned char *)ctx->stream_in.p + (C.in_place ? (size_t)C.origin * (size_t)f.pcm_bytes : 0);
+    ctx->pcm_fmt = f.pcm_fmt;
 }
 
 static int segment_end(pdt_ctx *ctx, uint64_t upto, bool final_seg);
@@ -1938,7 +1774,7 @@ static int segment_end(pdt_ctx *ctx, uint64_t upto, bool final_seg)
     const uint64_t new_origin = done_g > hist ? (done_g - hist) / align * align : 0;
     if (new_origin > C.origin) {
         const uint64_t d = new_origin - C.origin;
-        const size_t fb = ctx->stream_fmt ? 8 : 4, es = (size_t)ctx->elem;
+        const size_t fb = (size_t)in_fmt(ctx->stream_fmt).pcm_bytes, es = (size_t)ctx->elem;
         const uint32_t ip = ctx->interp;
         const bool need_lock = ctx->cfg.mode == PDT_MODE_ARGOS || ctx->cfg.chain == PDT_CHAIN_LIVE;
         const uint64_t chunk = ctx->cfg.chunk;
@@ -1979,6 +1815,81 @@ static int segment_end(pdt_ctx *ctx, uint64_t upto, bool final_seg)
     return PDT_OK;
 }
 
+// n_new input samples have landed behind the kept ones of a real or wideband stream (HaloCarry): produce every output whose
+// right halo is there (all of them when the stream ends: zeros beyond), append them to the stream's window, keep the next
+// output's left halo and everything from the sample it is centred on.  A converter makes one output per D inputs and reads
+// `span` inputs on either side of an output's centre: the Hilbert front end is D = 1, span = AN_HALF (31 samples held back),
+// the down-converter D = ch_decim, span = DDC_SPAN D (floor(in / D) - 8 outputs so far).  base = out D is the input the next
+// output is centred on, and buf[cur] begins at input base - left.  That D = 1 is the real front end as it used to be written:
+//   m          = floor(in / D) - span / D - out; with D = 1, pending = in - out before the push, so m = pending + n_new - AN_HALF;
+//   keep_left  = min(span, nbase), nbase = (out + m) D; with D = 1, left = min(AN_HALF, out) by induction, so it is min(AN_HALF, left + m);
+//   kept tail  : from buffer offset nbase - keep_left - (base - left) = left + m - keep_left, of in - (nbase - keep_left) =
+//                keep_left + pending + n_new - m samples; g0, the index of the first output, is base / D = out.
+// After the final piece nothing is kept (no copy): the counters stay until pdt_stream_begin, nothing reads them.
+static int front_convert(pdt_ctx *ctx, uint64_t n_new, bool final_piece)
+{
+    const InFmt f = in_fmt(ctx->stream_fmt);
+    const bool wb = f.kind == IN_WB;
+    int rc = wb ? channel_tables(ctx) : real_table(ctx);
+    if (rc) return rc;
+    HaloCarry &h = ctx->halo;
+    const uint64_t D = wb ? (uint64_t)ctx->ch_decim : 1, span = wb ? (uint64_t)DDC_SPAN * D : (uint64_t)AN_HALF;
+    const size_t fb = (size_t)f.bytes;
+    const uint64_t base = h.out * D, total_in = h.in + n_new;
+    const uint64_t outs = final_piece ? (total_in + D - 1) / D : (total_in / D > span / D ? total_in / D - span / D : 0);
+    const uint64_t m = outs > h.out ? outs - h.out : 0;
+    if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + m) + 64) * 8, (size_t)ctx->stream_have * 8))) return rc;
+    const unsigned char *x = (const unsigned char *)h.buf[h.cur].p + (size_t)h.left * fb;
+    void *out = (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * 8;
+    const long long lo = -(long long)h.left, hi = (long long)(h.pending + n_new);
+    if (wb)
+        HIP_TRY(ddc_launch(ctx->stream, f.code, x, lo, hi, m, base, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
+                           &ctx->ch_step, &out, 1));
+    else
+        HIP_TRY(analytic_launch(ctx->stream, f.code, x, lo, hi, m, base, ctx->real_step, (const float *)ctx->an_tab.p, out));
+    const uint64_t nbase = (h.out + m) * D;
+    if (!final_piece) {
+        const uint64_t keep_left = std::min<uint64_t>(span, nbase), start = nbase - keep_left - (base - h.left), keep = total_in - (nbase - keep_left);
+        if (start) {
+            DevBuf &dst = h.buf[h.cur ^ 1];
+            if ((rc = dst.ensure((size_t)(keep + 64) * fb))) return rc;
+            if (keep)
+                HIP_TRY(hipMemcpyAsync(dst.p, (const unsigned char *)h.buf[h.cur].p + (size_t)start * fb, (size_t)keep * fb, hipMemcpyDeviceToDevice,
+                                       ctx->stream));
+            h.cur ^= 1;
+        }
+        h.left = keep_left;
+        h.pending = total_in - nbase;
+    } else {
+        h.left = h.pending = 0;
+    }
+    h.in = total_in;
+    h.out += m;
+    ctx->stream_have += m;
+    ctx->stream_total += m;
+    return PDT_OK;
+}
+
+// Where the next n frames of the stream's input land: behind the window's samples (I,Q: the window grows only with the size
+// of the pushes, not with the length of the stream), resp. behind the samples the converter keeps ...
+static int stream_room(pdt_ctx *ctx, const InFmt &f, uint64_t n, unsigned char **at)
+{
+    const bool iq = f.kind == IN_IQ;
+    DevBuf &buf = iq ? ctx->stream_in : ctx->halo.buf[ctx->halo.cur];
+    const size_t held = (size_t)(iq ? ctx->stream_have : ctx->halo.left + ctx->halo.pending) * (size_t)f.bytes;
+    const int rc = buf.ensure_keep(held + ((size_t)n + 64) * (size_t)f.bytes, held);
+    *at = (unsigned char *)buf.p + held;
+    return rc;
+}
+
+// ... and they are there: part of the window, resp. converted into it
+static int stream_landed(pdt_ctx *ctx, const InFmt &f, uint64_t n, bool final_piece)
+{
+    if (f.kind != IN_IQ) return front_convert(ctx, n, final_piece);
+    ctx->stream_have += n;
+    ctx->stream_total += n;
+    return PDT_OK;
+}
 // A large capture from a file: the spans arrive in the background (ingest_capture with a job) straight into the stream window,
 // which holds the whole capture (its origin moves, its samples never do); the chain runs over it in a few segments with carried
 // state -- the streaming path -- each as soon as its samples are there.  What the call leaves behind is what pdt_stream_end
@@ -2049,13 +1960,13 @@ static uint64_t lcm_u64(uint64_t a, uint64_t b)
     return a / x * b;
 }
 
-static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes)
+static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, const InFmt &f, int text_fd, uint64_t *text_bytes)
 {
-    const size_t fb = fmt ? 8 : 4;
+    const size_t fb = (size_t)f.bytes;
     const auto t_call = std::chrono::steady_clock::now();
     int rc = pdt_stream_begin(ctx);
     if (rc) return rc;
-    ctx->stream_fmt = fmt;
+    ctx->stream_fmt = f.code;
     if ((rc = ctx->stream_in.ensure(((size_t)nframes + 64) * fb))) return rc;
     IngestJob job;
     ctx->sc.in_place = true;
@@ -2169,14 +2080,8 @@ static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes
         }
     }
     if (text_bytes) *text_bytes = sink.bytes;
-    ctx->stats.ingest_ms = ctx->ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
-    // the stream machinery was borrowed: leave no stream behind (a later push starts a new one), keep frames and statistics
-    ctx->sc = StreamCarry();
-    ctx->stream_have = ctx->stream_done = ctx->stream_total = 0;
-    ctx->stream_fmt = -1;
-    ctx->stream_open = false;
+    ingest_publish(ctx);
+    stream_reset(ctx);          // the stream machinery was borrowed: leave no stream behind, keep frames and statistics
     return rc ? rc : rj;
 }
 
@@ -2187,16 +2092,13 @@ static int demod_overlapped(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes
 // stays on the grid where a segment may take the whole-capture kernels (run_capture: seg_fast) when the pieces are large
 // enough for that to matter.  The state it leaves is demod_overlapped's: frames, text, statistics and reports of the whole
 // capture, stage arrays of the last piece.
-static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, int fmt, int text_fd, uint64_t *text_bytes, uint64_t piece)
+static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, const InFmt &f, int text_fd, uint64_t *text_bytes, uint64_t piece)
 {
     if (ctx->keep_agc_raw) return PDT_ERR_NOMEM;      // (the pre-Squelch stream of the WHOLE capture was asked for: that does not fit)
-    const bool real = fmt == PDT_FMT_REAL_PCM16 || fmt == PDT_FMT_REAL_F32;
-    const size_t fb = real ? (fmt == PDT_FMT_REAL_PCM16 ? 2 : 4) : fmt ? 8 : 4;     // bytes per frame of the source
-    const auto t_call = std::chrono::steady_clock::now();
+    const size_t fb = (size_t)f.bytes;                // per frame of the source
     int rc = pdt_stream_begin(ctx);
     if (rc) return rc;
-    ctx->stream_fmt = real ? 1 : fmt;
-    ctx->stream_real = real ? fmt : 0;
+    ctx->stream_fmt = f.code;
     ctx->sc.quality = ctx->keep_quality;              // (every cut below is a chunk boundary)
     ctx->report_samples = nframes;
     const uint64_t chunk = ctx->cfg.chunk;
@@ -2225,23 +2127,14 @@ static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, 
         last = pushed + cnt == nframes;
         IngestSrc s = src;
         if (s.mem) s.mem += (size_t)pushed * fb; else s.off += pushed * fb;
-        if (real) {
-            // the piece lands behind the samples the real stream keeps, and is converted into the window (real_convert)
-            if ((rc = real_reserve(ctx, cnt))) break;
-            const auto t0 = std::chrono::steady_clock::now();
-            if ((rc = ingest_capture(ctx, s, (size_t)cnt * fb, (unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)(ctx->rl + ctx->rp) * fb))) break;
-            ingest_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            if ((rc = real_convert(ctx, cnt, last))) break;
-            pushed += cnt;
-        } else {
-            if ((rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + cnt) + 64) * fb, (size_t)ctx->stream_have * fb))) break;
-            const auto t0 = std::chrono::steady_clock::now();
-            if ((rc = ingest_capture(ctx, s, (size_t)cnt * fb, (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * fb))) break;
-            ingest_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            ctx->stream_have += cnt;
-            ctx->stream_total += cnt;
-            pushed += cnt;
-        }
+        // the piece lands behind the window's samples, or behind the ones a real stream keeps and is converted into the window
+        unsigned char *at = nullptr;
+        if ((rc = stream_room(ctx, f, cnt, &at))) break;
+        const auto t0 = std::chrono::steady_clock::now();
+        if ((rc = ingest_capture(ctx, s, (size_t)cnt * fb, at))) break;
+        ingest_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = stream_landed(ctx, f, cnt, last))) break;
+        pushed += cnt;
         const uint64_t upto = last ? ctx->stream_have : (ctx->sc.origin + ctx->stream_have) / chunk * chunk - ctx->sc.origin;
         if (upto <= ctx->stream_done && !last) continue;
         if ((rc = stream_segment(ctx, upto, last))) break;
@@ -2257,94 +2150,40 @@ static int demod_windowed(pdt_ctx *ctx, const IngestSrc &src, uint64_t nframes, 
     sink.wait();
     if (!rc && sink.rc) rc = sink.rc;
     if (text_bytes) *text_bytes = sink.bytes;
-    (void)t_call;
     ctx->ingest_ms = ingest_ms;
-    ctx->stats.ingest_ms = ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
+    ingest_publish(ctx);
     ctx->stats.windowed = 1;
-    ctx->sc = StreamCarry();
-    ctx->stream_have = ctx->stream_done = ctx->stream_total = 0;
-    ctx->stream_fmt = -1;
-    ctx->stream_real = 0;
-    ctx->rl = ctx->rp = ctx->real_done = 0;
-    ctx->stream_wb = 0;
-    ctx->cl = ctx->cp = ctx->ch_in = ctx->ch_out = 0;
-    ctx->stream_open = false;
+    stream_reset(ctx);
     return rc;
-}
-
-int pdt_demod_file(pdt_ctx *ctx, int fd, uint64_t byte_offset, uint64_t nframes, int sample_format, int text_fd, uint64_t *text_bytes)
-{
-    if (text_bytes) *text_bytes = 0;
-    if (ctx && fd >= 0 && text_fd >= 0 && real_fmt(sample_format)) {
-        if (ctx->stream_open) return PDT_ERR_STATE;
-        HIP_TRY(hipSetDevice(ctx->cfg.device));
-        const size_t rb = real_bytes(sample_format);
-        if (const long long piece = window_piece_for(ctx, nframes, rb + 8)) {
-            IngestSrc src;
-            src.fd = fd;
-            src.off = byte_offset;
-            return piece < 0 ? (int)piece : demod_windowed(ctx, src, nframes, sample_format, text_fd, text_bytes, (uint64_t)piece);
-        }
-        const int rc = pdt_demod_fd(ctx, fd, byte_offset, nframes, sample_format);
-        if (rc) return rc;
-        return pdt_write_frames(ctx, text_fd, text_bytes);
-    }
-    if (ctx && fd >= 0 && text_fd >= 0 && ddc_fmt(sample_format)) {
-        const int rc = pdt_demod_fd(ctx, fd, byte_offset, nframes, sample_format);
-        if (rc) return rc;
-        return pdt_write_frames(ctx, text_fd, text_bytes);
-    }
-    if (!ctx || fd < 0 || text_fd < 0 || (sample_format != PDT_FMT_PCM16 && sample_format != PDT_FMT_F32)) return PDT_ERR_ARG;
-    if (sample_format == PDT_FMT_F32 && ctx->elem != 4) return PDT_ERR_FORMAT;
-    if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    const size_t fb = sample_format == PDT_FMT_F32 ? 8 : 4;
-    if (const long long piece = window_piece_for(ctx, nframes, fb)) {
-        IngestSrc src;
-        src.fd = fd;
-        src.off = byte_offset;
-        return piece < 0 ? (int)piece : demod_windowed(ctx, src, nframes, sample_format == PDT_FMT_F32 ? 1 : 0, text_fd, text_bytes, (uint64_t)piece);
-    }
-    if (overlap_ingest(ctx, nframes, fb)) {
-        IngestSrc src;
-        src.fd = fd;
-        src.off = byte_offset;
-        return demod_overlapped(ctx, src, nframes, sample_format == PDT_FMT_F32 ? 1 : 0, text_fd, text_bytes);
-    }
-    const int rc = pdt_demod_fd(ctx, fd, byte_offset, nframes, sample_format);
-    if (rc) return rc;
-    return pdt_write_frames(ctx, text_fd, text_bytes);
 }
 
 static int stream_advance(pdt_ctx *ctx, uint64_t pushed, uint64_t *new_frames);
 
-static int stream_push(pdt_ctx *ctx, const void *host, uint64_t nframes, int fmt, uint64_t *new_frames)
+// All four push entries.  The first push opens a stream (as if pdt_stream_begin had been called), and the stream has the kind
+// and format of its first push: a push of another one is refused -- PDT_ERR_STATE between the two I,Q formats, PDT_ERR_ARG
+// wherever real or wideband input is involved (the codes the three front ends have always given).
+static int stream_push(pdt_ctx *ctx, const void *host, uint64_t n, int format, uint64_t *new_frames)
 {
-    if (!ctx || (!host && nframes)) return PDT_ERR_ARG;
-    if (fmt == 1 && ctx->elem != 4) return PDT_ERR_FORMAT;
-    if (!ctx->stream_open) {                         // the first push opens a stream (as if pdt_stream_begin had been called)
+    const InFmt f = in_fmt(format);
+    if (!ctx || (!host && n) || f.kind == IN_NONE) return PDT_ERR_ARG;
+    if (f.kind == IN_IQ && f.pcm_fmt && ctx->elem != 4) return PDT_ERR_FORMAT;
+    if (f.kind == IN_WB && !ctx->ch_decim) return PDT_ERR_STATE;
+    if (!ctx->stream_open) {
         int rb = pdt_stream_begin(ctx);
         if (rb) return rb;
         ctx->stream_open = true;
     }
-    if (ctx->stream_real || ctx->stream_wb) return PDT_ERR_ARG;      // (a stream of real or of wideband pushes)
-    if (ctx->stream_fmt >= 0 && ctx->stream_fmt != fmt) return PDT_ERR_STATE;
+    if (ctx->stream_fmt >= 0 && ctx->stream_fmt != format) return f.kind == IN_IQ && in_fmt(ctx->stream_fmt).kind == IN_IQ ? PDT_ERR_STATE : PDT_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
-    ctx->stream_fmt = fmt;
-    const size_t fb = fmt ? 8 : 4;
+    ctx->stream_fmt = format;
     ctx->stream_new.clear();
     if (new_frames) *new_frames = 0;
-    // append to the window (it grows only with the size of the pushes, not with the length of the stream)
-    int rc = ctx->stream_in.ensure_keep(((size_t)(ctx->stream_have + nframes) + 64) * fb, (size_t)ctx->stream_have * fb);
+    unsigned char *at = nullptr;
+    int rc = stream_room(ctx, f, n, &at);
     if (rc) return rc;
-    if (nframes)
-        HIP_TRY(hipMemcpyAsync((unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * fb, host, (size_t)nframes * fb,
-                               hipMemcpyHostToDevice, ctx->stream));
-    ctx->stream_have += nframes;
-    ctx->stream_total += nframes;
-    return stream_advance(ctx, nframes, new_frames);
+    if (n) HIP_TRY(hipMemcpyAsync(at, host, (size_t)n * (size_t)f.bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = stream_landed(ctx, f, n, false))) return rc;
+    return stream_advance(ctx, n, new_frames);
 }
 
 // demodulate the complete chunks the window holds now
@@ -2362,68 +2201,27 @@ static int stream_advance(pdt_ctx *ctx, uint64_t pushed, uint64_t *new_frames)
     return PDT_OK;
 }
 
-static int stream_push_real(pdt_ctx *ctx, const void *host, uint64_t n, int fmt, uint64_t *new_frames)
-{
-    if (new_frames) *new_frames = 0;
-    if (!ctx || (!host && n) || (fmt != PDT_FMT_REAL_PCM16 && fmt != PDT_FMT_REAL_F32)) return PDT_ERR_ARG;
-    if (!ctx->stream_open) {
-        int rb = pdt_stream_begin(ctx);
-        if (rb) return rb;
-        ctx->stream_open = true;
-    }
-    if (ctx->stream_fmt >= 0 && ctx->stream_real != fmt) return PDT_ERR_ARG;     // I,Q or wideband pushes, or real ones of the other format
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    ctx->stream_fmt = 1;
-    ctx->stream_real = fmt;
-    ctx->stream_new.clear();
-    int rc = real_reserve(ctx, n);
-    if (rc) return rc;
-    const size_t rb = fmt == PDT_FMT_REAL_PCM16 ? 2 : 4;
-    if (n)
-        HIP_TRY(hipMemcpyAsync((unsigned char *)ctx->rbuf[ctx->rcur].p + (size_t)(ctx->rl + ctx->rp) * rb, host, (size_t)n * rb,
-                               hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = real_convert(ctx, n, false))) return rc;
-    return stream_advance(ctx, n, new_frames);
-}
-
 int pdt_stream_push_pcm16(pdt_ctx *ctx, const int16_t *iq_host, uint64_t nframes, uint64_t *new_frames)
 {
-    return stream_push(ctx, iq_host, nframes, 0, new_frames);
+    return stream_push(ctx, iq_host, nframes, PDT_FMT_PCM16, new_frames);
 }
 
 int pdt_stream_push_f32(pdt_ctx *ctx, const float *iq_host, uint64_t nframes, uint64_t *new_frames)
 {
-    return stream_push(ctx, iq_host, nframes, 1, new_frames);
+    return stream_push(ctx, iq_host, nframes, PDT_FMT_F32, new_frames);
 }
 
+// (the real and the wideband entry report no new frames when they refuse a push; the I,Q entries leave *new_frames alone then)
 int pdt_stream_push_real(pdt_ctx *ctx, const void *x_host, uint64_t n, int sample_format, uint64_t *new_frames)
 {
-    return stream_push_real(ctx, x_host, n, sample_format, new_frames);
+    if (new_frames) *new_frames = 0;
+    return in_fmt(sample_format).kind == IN_REAL ? stream_push(ctx, x_host, n, sample_format, new_frames) : PDT_ERR_ARG;
 }
 
 int pdt_stream_push_channel(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, uint64_t *new_frames)
 {
     if (new_frames) *new_frames = 0;
-    if (!ctx || (!iq_host && nframes) || !ddc_fmt(sample_format)) return PDT_ERR_ARG;
-    if (!ctx->ch_decim) return PDT_ERR_STATE;
-    if (!ctx->stream_open) {
-        int rb = pdt_stream_begin(ctx);
-        if (rb) return rb;
-        ctx->stream_open = true;
-    }
-    if (ctx->stream_fmt >= 0 && ctx->stream_wb != sample_format) return PDT_ERR_ARG;     // pushes of another kind or format
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    ctx->stream_fmt = 1;
-    ctx->stream_wb = sample_format;
-    ctx->stream_new.clear();
-    const size_t fb = (size_t)ddc_bytes(sample_format);
-    int rc = ctx->cbuf[ctx->ccur].ensure_keep((size_t)(ctx->cl + ctx->cp + nframes + 64) * fb, (size_t)(ctx->cl + ctx->cp) * fb);
-    if (rc) return rc;
-    if (nframes)
-        HIP_TRY(hipMemcpyAsync((unsigned char *)ctx->cbuf[ctx->ccur].p + (size_t)(ctx->cl + ctx->cp) * fb, iq_host, (size_t)nframes * fb,
-                               hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = channel_convert(ctx, nframes, false))) return rc;
-    return stream_advance(ctx, nframes, new_frames);
+    return in_fmt(sample_format).kind == IN_WB ? stream_push(ctx, iq_host, nframes, sample_format, new_frames) : PDT_ERR_ARG;
 }
 
 int pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames)
@@ -2431,16 +2229,12 @@ int pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames)
     if (!ctx) return PDT_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     ctx->stream_open = false;                        // (whatever happens below, the stream is over)
-    if (ctx->stream_wb) {                            // the held-back samples, closed with zeros
-        const int rr = channel_convert(ctx, 0, true);
-        if (rr) return rr;
-    }
-    if (ctx->stream_real) {                          // the held-back samples, closed with zeros
-        const int rr = real_convert(ctx, 0, true);
+    if (ctx->stream_fmt >= 0 && in_fmt(ctx->stream_fmt).kind != IN_IQ) {      // the held-back samples, closed with zeros
+        const int rr = front_convert(ctx, 0, true);
         if (rr) return rr;
     }
     if (ctx->stream_fmt < 0) {                       // nothing was pushed: an empty capture
-        ctx->stream_fmt = 0;
+        ctx->stream_fmt = PDT_FMT_PCM16;
         int rc = ctx->stream_in.ensure(64);
         if (rc) return rc;
     }
@@ -2459,7 +2253,7 @@ int pdt_stream_end(pdt_ctx *ctx, uint64_t *new_frames)
     return rc;
 }
 
-uint64_t pdt_stream_retained(const pdt_ctx *ctx) { return ctx ? ctx->stream_have + ctx->rp + ctx->cp : 0; }
+uint64_t pdt_stream_retained(const pdt_ctx *ctx) { return ctx ? ctx->stream_have + ctx->halo.pending : 0; }
 
 uint64_t pdt_stream_frames(const pdt_ctx *ctx, pdt_frame *out, uint64_t max_frames)
 {

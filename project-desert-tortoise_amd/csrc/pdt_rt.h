@@ -319,6 +319,40 @@ struct StreamCarry {
     uint64_t seg_new_symbols = 0, seg_new_bits = 0;
 };
 
+// What a public sample_format is to the input layer: which front end the samples go through, how large a frame of the source
+// is, and what finally reaches run_capture (I,Q as it is; real and wideband input as the float pairs their converters write).
+enum { IN_NONE = 0, IN_IQ, IN_REAL, IN_WB };
+struct InFmt {
+    int kind;           // IN_NONE: not a format (or a stream without a push yet)
+    int code;           // the public PDT_FMT_*: what the converter kernels take
+    int bytes;          // per input frame
+    int pcm_fmt;        // the chain's input: 0 = int16 pairs, 1 = float32 pairs ...
+    int pcm_bytes;      // ... and the bytes of one
+};
+inline InFmt in_fmt(int sample_format)
+{
+    switch (sample_format) {
+    case PDT_FMT_PCM16: return { IN_IQ, sample_format, 4, 0, 4 };
+    case PDT_FMT_F32: return { IN_IQ, sample_format, 8, 1, 8 };
+    case PDT_FMT_REAL_PCM16: return { IN_REAL, sample_format, 2, 1, 8 };
+    case PDT_FMT_REAL_F32: return { IN_REAL, sample_format, 4, 1, 8 };
+    case PDT_FMT_WB_PCM16: return { IN_WB, sample_format, 4, 1, 8 };
+    case PDT_FMT_WB_F32: return { IN_WB, sample_format, 8, 1, 8 };
+    case PDT_FMT_WB_CU8:
+    case PDT_FMT_WB_CS8: return { IN_WB, sample_format, 2, 1, 8 };
+    }
+    return { IN_NONE, sample_format, 0, 0, 0 };
+}
+
+// The input samples a converter (Hilbert front end, down-converter) still needs when a push has been converted: buf[cur] holds
+// `left` samples already used (the next output's left halo), then `pending` ones from the sample the next output is centred
+// on (they wait for their right halo), then the new push.  `in` input samples have arrived, `out` outputs have been produced.
+struct HaloCarry {
+    DevBuf buf[2];
+    int cur = 0;
+    uint64_t left = 0, pending = 0, in = 0, out = 0;
+};
+
 struct pdt_ctx {
     pdt_config cfg;
     pdt_loop_params lp = {};     // pdt_set_loop_params: 0 = the mains' constant
@@ -357,7 +391,7 @@ struct pdt_ctx {
     int gardner_mode = 0;              // 0 sequential, 1 state table (last run)
     long long gspan_nrows = 0;         // table rows of several chunks in the last run (0: none) -- pdt_dev_span_rows
     const void *pcm_dev = nullptr;     // input actually used (own copy or caller's buffer)
-    int pcm_fmt = 0;                   // 0 = int16 pairs, 1 = float32 pairs
+    int pcm_fmt = 0;                   // 0 = int16 pairs, 1 = float32 pairs (InFmt::pcm_fmt)
 
     std::vector<unsigned char> taps_host;
     // results
@@ -385,30 +419,25 @@ struct pdt_ctx {
     DevBuf stream_in, seg_dev, lt_theta, lt_phi;          // input window of the stream; small device block for the segment's carried-out state
     uint64_t stream_have = 0, stream_done = 0;   // samples in the window / of them already demodulated (local indices)
     uint64_t stream_total = 0;          // samples pushed since pdt_stream_begin
-    int stream_fmt = -1;                // -1 = no push yet, 0 = pcm16, 1 = float32
+    int stream_fmt = -1;                // -1 = no push yet, else the PDT_FMT_* of the first push: the stream's kind and format (in_fmt)
     bool stream_open = false;           // between the first push and pdt_stream_end / _begin: the stage buffers hold the tails the next push continues from
     std::vector<pdt_frame> stream_new;
-    // real (single-channel) input (pdt_analytic.h): the centre's phase step, the rotation table, the analytic stream of a whole
-    // capture; a stream of real pushes keeps its last samples in rbuf[rcur]: rl converted ones (the next samples' left halo) and rp
-    // not yet converted (waiting for their right halo), then the new ones
+    // real (single-channel) input (pdt_analytic.h): the centre's phase step, the rotation table (an_tab_ready: it is on the device),
+    // the analytic stream of a whole capture
     uint32_t real_step = 1u << 30;
     double real_center = 0;
-    DevBuf an_tab, analytic, rbuf[2];
-    int rcur = 0;
-    int stream_real = 0;                // 0 = I,Q stream (or none), PDT_FMT_REAL_PCM16 / _F32 = the stream takes real pushes
-    uint64_t rl = 0, rp = 0, real_done = 0;
+    DevBuf an_tab, analytic;
+    int an_tab_ready = 0;
     uint64_t analytic_len = 0;          // length of PDT_ST_ANALYTIC the next demod_common reports
-    // wideband input (pdt_ddc.h): the channel's decimation, offset and phase step, the filter's taps on the device, the channel
-    // stream of a whole capture; a stream of wideband pushes keeps its last input samples in cbuf[ccur]: cl already used ones (the
-    // next output's left halo), then cp pending ones from the sample the next output is centred on, then the new ones
+    // wideband input (pdt_ddc.h): the channel's decimation, offset and phase step, the filter's taps on the device (for the
+    // decimation ddc_taps_decim), the channel stream of a whole capture
     int ch_decim = 0;                   // 0 = pdt_set_channel has not been called
     double ch_offset = 0;
     uint32_t ch_step = 0;
-    DevBuf ddc_taps, channel, cbuf[2];
-    int ddc_taps_decim = 0, ccur = 0;
-    int stream_wb = 0;                  // 0 = not a wideband stream, PDT_FMT_WB_* = the stream takes wideband pushes of that format
-    uint64_t cl = 0, cp = 0, ch_in = 0, ch_out = 0;     // (ch_in input samples pushed, ch_out channel samples produced)
+    DevBuf ddc_taps, channel;
+    int ddc_taps_decim = 0;
     uint64_t channel_len = 0;           // length of PDT_ST_CHANNEL the next demod_common reports
+    HaloCarry halo;                     // the input samples a stream of real or of wideband pushes keeps between pushes
     // carrier survey (pdt_survey.h): window and twiddle tables of survey_tab_nfft points, the runs' partial rows and the averaged
     // spectrum on the device, the last survey's spectrum on the host
     DevBuf survey_win, survey_tw, survey_part, survey_out;

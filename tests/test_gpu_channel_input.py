@@ -210,7 +210,7 @@ def test_stream_pushes_equal_the_whole_call(pdt, mode, kind, in_rate, D, offset,
         with pdt.Demodulator(mode, fs) as d:
             d.set_channel(D, offset)
             got, at = [], 0
-            sizes = [1, D - 1, D, 1, 8 * D - 1, 3, 8 * D + 1, 2]
+            sizes = [1, 0, D - 1, D, 1, 8 * D - 1, 0, 3, 8 * D + 1, 2]       # one frame, empty pushes, fewer than the halo (8 D)
             while at < len(x):
                 k = sizes.pop(0) if sizes else int(rng.integers(1, 150000 * D))
                 got.append(d.stream_push_channel(x[at: at + k]))

@@ -408,7 +408,10 @@ int  pdt_host_analytic(uint32_t sample_rate, double center_hz, const void *x, ui
  *                              PDT_ERR_ARG; PDT_ERR_STATE before pdt_set_channel); results, reports, progress and statistics as for
  *                              any capture; PDT_ST_CHANNEL = the converted stream.  One that does not fit the device's memory
  *                              returns PDT_ERR_NOMEM: the bounded window for wideband input does not exist yet
- *   pdt_demod_device_channel   the same with the samples resident in device memory (only read)
+ *   pdt_demod_device_channel   the same with the samples resident in device memory (only read).  The address must be aligned
+ *                              to the format's element (2 bytes for int16, 4 for float32, 1 for the 8-bit formats), not to
+ *                              the I,Q pair or to 16 bytes: any such address is served, the aligned ones with wider loads;
+ *                              so too for pdt_demod_channels_device and pdt_survey_device
  *   pdt_demod_channels_device  ONE wideband capture in device memory, `count` contexts with a channel each: the capture is read
  *                              once by one conversion launch that fills every context's channel stream, then the contexts go
  *                              through the batched chain (pdt_demod_batch_device's, on float input).  All contexts must have the

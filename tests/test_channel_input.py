@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 DECIMS = (2, 4, 16, 64)
+ALL_DECIMS = tuple(range(2, 65))                                        # everything pdt_set_channel and -x accept
 FORMATS = ("pcm16", "f32", "cu8", "cs8")
 
 
@@ -87,8 +88,10 @@ def as_complex(y: np.ndarray) -> np.ndarray:
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
-@pytest.mark.parametrize("D", DECIMS)
+@pytest.mark.parametrize("D", ALL_DECIMS)
 def test_host_ddc_matches_float64_model(pdt, D, fmt):
+    """Every decimation the entries accept, not the powers of two alone: the host restatement is the kernel's only definition (the
+    GPU tests compare the two bit for bit at every D), so it is held to the model wherever the kernel is held to it."""
     rng = np.random.default_rng(100 * D + FORMATS.index(fmt))
     in_rate = 250000 * D
     for offset in (0.37 * in_rate, -0.21 * in_rate, 1234.5):
@@ -98,11 +101,11 @@ def test_host_ddc_matches_float64_model(pdt, D, fmt):
         assert got.shape == want.shape
         err = max(np.max(np.abs(got.real - want.real)), np.max(np.abs(got.imag - want.imag)))
         lim = bound(D, np.max(np.abs(np.concatenate([scaled(x).real, scaled(x).imag]))))
-        print(f"D {D} {fmt} offset {offset:.1f}: error {err:.3e}, bound {lim:.3e}")
+        print(f"D {D} {fmt} offset {offset:.1f}: error {err:.3e}, bound {lim:.3e}, error / bound {err / lim:.4f}")
         assert err <= lim
 
 
-@pytest.mark.parametrize("D", (4, 16))
+@pytest.mark.parametrize("D", (4, 16, 7))
 def test_tone_at_the_offset_lands_at_dc_with_gain_one(pdt, D):
     """A tone at +offset and at -offset, each converted with its own sign, comes out as its amplitude at 0 Hz."""
     in_rate, amp = 250000 * D, 0.5
@@ -121,7 +124,7 @@ def test_tone_at_the_offset_lands_at_dc_with_gain_one(pdt, D):
         assert np.sqrt(np.mean(np.abs(z) ** 2)) <= amp * 1e-3
 
 
-@pytest.mark.parametrize("D", (4, 16))
+@pytest.mark.parametrize("D", (4, 16, 7, 33))
 def test_stopband(pdt, D):
     """A tone one channel rate or more from the channel's centre comes out at least 60 dB down (the Blackman design gives about
     74 dB); the float64 model is asked first: were it to fail, the taps would be wrong."""
@@ -164,7 +167,7 @@ def test_phase_depends_on_the_global_index_only(pdt):
     assert abs(z - want) <= 1e-6
 
 
-@pytest.mark.parametrize("D", DECIMS)
+@pytest.mark.parametrize("D", ALL_DECIMS)
 def test_output_count(pdt, D):
     rng = np.random.default_rng(D)
     for n in (0, 1, D - 1, D, D + 1, 8 * D - 1, 8 * D, 8 * D + 1, 23 * D - 1, 23 * D, 23 * D + 1):

@@ -84,6 +84,93 @@ def test_kernel_equals_host_restatement(pdt, D, fmt):
             assert d.stage(pdt.ST_CHANNEL).tobytes() == want.tobytes(), skip
 
 
+ALL_DECIMS = tuple(range(2, 65))                                        # everything pdt_set_channel and -x accept
+
+
+def ddc_geometry(D: int):
+    """ddc_launch's geometry for decimation D (csrc/pdt_ddc.hip: DDC_TILE = 2048, DDC_TB = 256): outputs of a tile, lanes of a
+    workgroup, outputs per lane."""
+    TO = 2048 // D
+    tb = min(256, (TO + 63) // 64 * 64)
+    return TO, tb, (TO + tb - 1) // tb
+
+
+@pytest.mark.parametrize("D", ALL_DECIMS)
+def test_kernel_equals_host_restatement_at_every_decimation(pdt, D):
+    """PDT_ST_CHANNEL is pdt_host_ddc, bit for bit, at EVERY decimation and in all four formats.  The kernel's geometry is a function
+    of D -- TO = 2048 // D outputs a tile, tb = min(256, TO rounded up to 64) lanes, nb = ceil(TO / tb) outputs a lane -- and the
+    powers of two of the test above leave most of it unrun.  From DDC_TILE = 2048 and DDC_TB = 256 (re-derive when either changes):
+
+    * nb, the ddc_fir<NB> instantiation: 4 at D = 2; 3 at D = 3 only (TO = 682); 2 at D = 4 .. 7; 1 from D = 8 on.  The last round has
+      lanes clamped by mb[b] = min(.., TO - 1) where tb does not divide TO: D = 3 (nb = 3), D = 5, 6, 7 (nb = 2); for nb = 1 the lanes
+      t >= TO take no part: D = 9, 10 (tb = 256), 11 .. 15 (tb = 192), 17 .. 31 (tb = 128), 33 .. 63 (tb = 64; D = 63 and 64 both have
+      TO = 32, half a wavefront).
+    * the carry of the polyphase rotation (r += tb % D; if (r >= D) { r -= D; q++; }) runs where D does not divide tb: D = 3, 5, 6, 7,
+      9, 10 (tb = 256), 11, 13, 14, 15 (tb = 192), 17 .. 31 (tb = 128), 33 .. 63 (tb = 64) -- at no power of two.
+    * the head / 16-byte vectors / tail split of an inner tile's load: the tile's first input (m0 - 8) D advances by TO D = 2048 - 2048 %
+      D samples a tile, so where D does not divide 2048 the split differs from tile to tile of ONE aligned capture (the lengths of 3
+      and of about 20 tiles here), for every format's samples-per-vector (2, 4, 8); the resident captures 1, 2 and 3 samples behind a
+      16-byte boundary shift it once more.
+    * the worst cases of the LDS images: (TO + 16) D <= DDC_XS = 3072 is tightest at D = 64 (3072) and 63 (3024); D ((TO + 16) | 1) <=
+      DDC_VS = 3136 at D = 64 (3136), 62 (3038), 63 (3087) and 47 (2773 of the 2048 + 17 D = 2847 the formula allows), where TO + 16
+      is even and the row is padded.
+
+    Lengths: a single sample, around one output, around the halo (8 D), around one tile (tile = TO D inputs), tile - D + 1 where
+    the number of outputs is exactly TO, three tiles and some twenty tiles with an odd remainder; a positive and a negative offset;
+    captures from host memory and resident ones at unaligned addresses.  (The 10^6-sample case stays with the test above.)"""
+    fs = 250000
+    in_rate = fs * D
+    TO, tb, nb = ddc_geometry(D)
+    tile = TO * D
+    print(f"D {D}: TO {TO}, tb {tb}, nb {nb}, tb % D {tb % D}, TO % tb {TO % tb}, tile stride % 8 {tile % 8}")
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        for fmt in FORMATS:
+            rng = np.random.default_rng(5000 * D + FORMATS.index(fmt))
+            for n in (1, D - 1, D, 8 * D - 1, 8 * D + 1, tile - 1, tile, tile + 1, tile - D + 1, 3 * tile + 5, 20 * tile + 2 * D + 777):
+                x = random_capture(rng, fmt, n)
+                for offset in (0.31 * in_rate, -0.123456 * in_rate):
+                    want = pdt.host_ddc(in_rate, D, offset, x)
+                    d.set_channel(D, offset).demod_channel(x)
+                    assert d.stage_len(pdt.ST_CHANNEL) == (n + D - 1) // D, (fmt, n, offset)
+                    assert d.stage(pdt.ST_CHANNEL).tobytes() == want.tobytes(), (fmt, n, offset)
+                    assert d.stats().samples == (n + D - 1) // D, (fmt, n, offset)
+            # resident captures whose first sample sits 1, 2 and 3 samples behind a 16-byte boundary
+            n = 3 * tile + 5
+            x = random_capture(rng, fmt, n + 3)
+            dev = torch.from_numpy(x.reshape(-1).copy()).to("cuda:0")
+            torch.cuda.synchronize()
+            for skip in (1, 2, 3):
+                want = pdt.host_ddc(in_rate, D, -77777.0, x[skip: skip + n])
+                d.set_channel(D, -77777.0).demod_device_channel(dev.data_ptr() + skip * 2 * x.itemsize, n, fmt_code(pdt, x))
+                assert d.stage_len(pdt.ST_CHANNEL) == (n + D - 1) // D, (fmt, skip)
+                assert d.stage(pdt.ST_CHANNEL).tobytes() == want.tobytes(), (fmt, skip)
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_capture_aligned_to_its_element_but_not_to_its_pair(pdt, fmt):
+    """A resident capture may begin half a sample off: at an address that is a multiple of the element's size (2 bytes for int16, 4
+    for float, 1 for the 8-bit formats) and not of the I,Q pair's.  No 16-byte boundary then falls between two samples, and k_ddc
+    loads every tile sample by sample (head = len); include/pdt.h asks for no more than that, and the result is pdt_host_ddc's of
+    the same bytes.  Three tiles and a bit, at a power of two and at an odd decimation; 0, 1 and 3 whole samples further on too."""
+    rng = np.random.default_rng(77 + FORMATS.index(fmt))
+    fs = 250000
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        for D in (4, 7):
+            in_rate = fs * D
+            n = 3 * (2048 // D * D) + 5
+            flat = random_capture(rng, fmt, n + 4).reshape(-1)             # elements: I, Q, I, Q, ...
+            dev = torch.from_numpy(flat.view(np.uint8).copy()).to("cuda:0")  # (the bytes; torch allocations are 16-byte aligned)
+            torch.cuda.synchronize()
+            assert dev.data_ptr() % 16 == 0
+            for skip in (0, 1, 3):
+                first = 2 * skip + 1                                       # the capture begins with what was a Q
+                host = flat[first: first + 2 * n].reshape(n, 2)
+                want = pdt.host_ddc(in_rate, D, 0.2 * in_rate, host)
+                d.set_channel(D, 0.2 * in_rate).demod_device_channel(dev.data_ptr() + first * flat.itemsize, n, fmt_code(pdt, flat))
+                assert d.stage_len(pdt.ST_CHANNEL) == (n + D - 1) // D
+                assert d.stage(pdt.ST_CHANNEL).tobytes() == want.tobytes(), (D, skip)
+
+
 def test_other_captures_have_no_channel_stage(pdt, clip):
     rate, iq = clip
     with pdt.Demodulator(pdt.MODE_POES, rate) as d:
@@ -115,16 +202,12 @@ def test_poes_routing_equals_raw_float_path(pdt, orc):
 SETUPS = [(1000000, 4, (200000.0, -180000.0)), (2400000, 16, (600000.0, -400000.0)), (2048000, 8, (299500.0, -421700.0))]
 
 
-@pytest.mark.parametrize("rendering", ["pcm16", "cu8"])
-@pytest.mark.parametrize("in_rate,D,offsets", SETUPS)
-def test_poes_channels_decode_what_was_sent(pdt, in_rate, D, offsets, rendering):
-    """Two POES transmissions (seeds 11 and 12, 8 s, half amplitude each) in one wideband capture: each channel's complete frames
-    are frames the generator sent (the `transmitted` criterion of the real-input tests), and its PLL locks on the residual 1 kHz."""
+def decode_what_was_sent(pdt, in_rate, D, offsets, rendering, seeds):
     fs = in_rate // D
-    x, params = carriers(pdt, 0, in_rate, 8.0, offsets, (11, 12), 1000.0)
+    x, params = carriers(pdt, 0, in_rate, 8.0, offsets, seeds, 1000.0)
     if rendering == "cu8":
         x = to_cu8(x)
-    for off, p, seed in zip(offsets, params, (11, 12)):
+    for off, p in zip(offsets, params):
         with pdt.Demodulator(pdt.MODE_POES, fs) as d:
             d.set_channel(D, off).demod_channel(x)
             fr = d.frames_array()
@@ -134,6 +217,28 @@ def test_poes_channels_decode_what_was_sent(pdt, in_rate, D, offsets, rendering)
         print(in_rate, D, off, rendering, res, st.lock_freq_hz)
         assert res["ok"], res
         assert st.lock_sample >= 0 and abs(st.lock_freq_hz - 1000.0) < 200.0
+
+
+@pytest.mark.parametrize("rendering", ["pcm16", "cu8"])
+@pytest.mark.parametrize("in_rate,D,offsets", SETUPS)
+def test_poes_channels_decode_what_was_sent(pdt, in_rate, D, offsets, rendering):
+    """Two POES transmissions (seeds 11 and 12, 8 s, half amplitude each) in one wideband capture: each channel's complete frames
+    are frames the generator sent (the `transmitted` criterion of the real-input tests), and its PLL locks on the residual 1 kHz."""
+    decode_what_was_sent(pdt, in_rate, D, offsets, rendering, (11, 12))
+
+
+ODD_SETUPS = [(1750000, 7, (300000.0, -412300.0))]                      # (a list of its own: the survey tests take SETUPS)
+
+
+@pytest.mark.parametrize("rendering", ["pcm16", "cu8"])
+@pytest.mark.parametrize("in_rate,D,offsets", ODD_SETUPS)
+def test_poes_channels_decode_what_was_sent_at_an_odd_decimation(pdt, in_rate, D, offsets, rendering):
+    """The same criterion at 1.75 Msps / 7 (nb = 2 with clamped lanes, the rotation's carry, a load split that moves from tile to
+    tile).  The seeds were tried on the CPU first, as for the ARGOS test below: pdt_host_ddc followed by the oracle's POES chain on
+    the float capture (the call of test_poes_routing_equals_raw_float_path).  Seed pairs (11, 12), (21, 22) and (31, 32), both
+    offsets, both renderings: all twelve cases decode 79 of the 80 frames sent, every one a sent frame, and lock within 15 Hz of the
+    1 kHz residual; (11, 12), the pair of the setups above, is kept."""
+    decode_what_was_sent(pdt, in_rate, D, offsets, rendering, (11, 12))
 
 
 def test_argos_channel_decodes_every_burst_after_the_lock(pdt):
@@ -196,8 +301,87 @@ def test_several_channels_equal_one_at_a_time(pdt):
                 d.close()
 
 
+@pytest.mark.parametrize("in_rate,D,tuned", [(1000000, 4, (200000.0, -180000.0, 390000.0)), (1750000, 7, (300000.0, -412300.0, 610000.0))])
+def test_more_channels_than_one_launch_takes(pdt, in_rate, D, tuned):
+    """demod_channels with 17 and with 33 contexts: ddc_launch takes 16 channels a launch (DDC_KMAX), so these are two and three
+    launches, the last of one channel.  Every context has an offset of its own, except that contexts 15 and 16 -- the last of the
+    first launch and the first of the second -- share one (a carrier's); contexts 0 and 32 sit on carriers too.  Each context's
+    channel stream is pdt_host_ddc of ITS offset, and its text and frames are what the same context holds after demod_channel
+    alone.  Before every joint call each context converts the capture at another offset, so that no buffer still holds the answer."""
+    fs = in_rate // D
+    x, _ = carriers(pdt, 0, in_rate, 0.5, tuned, (11, 12, 13), 1000.0)
+    offsets = [-0.42 * in_rate + i * (0.84 * in_rate / 32) + 137.0 for i in range(33)]
+    offsets[0], offsets[15], offsets[16], offsets[32] = tuned[1], tuned[0], tuned[0], tuned[2]
+    assert len(set(offsets)) == 32
+    dev = torch.from_numpy(x.reshape(-1).copy()).to("cuda:0")
+    torch.cuda.synchronize()
+    ds = [pdt.Demodulator(pdt.MODE_POES, fs) for _ in offsets]
+    try:
+        alone = []
+        for d, off in zip(ds, offsets):
+            d.set_channel(D, off).demod_channel(x)
+            ch = d.stage(pdt.ST_CHANNEL).tobytes()
+            assert ch == pdt.host_ddc(in_rate, D, off, x).tobytes(), off
+            alone.append((d.text(), d.frames_array().tobytes(), ch))
+        assert all(len(alone[i][0]) > 100 for i in (0, 15, 16, 32))
+        assert alone[15] == alone[16] and len({a[2] for a in alone}) == 32
+
+        def scrub(count):
+            for d, off in zip(ds[:count], offsets):
+                d.set_channel(D, 0.5 * off + 777.0).demod_channel(x)
+                d.set_channel(D, off)
+
+        for count in (17, 33):
+            for rep in range(2):
+                scrub(count)
+                pdt.demod_channels(ds[:count], dev.data_ptr(), len(x), pdt.FMT_WB_PCM16)
+                for i, (d, a) in enumerate(zip(ds, alone[:count])):
+                    assert d.stage_len(pdt.ST_CHANNEL) == (len(x) + D - 1) // D
+                    assert d.stage(pdt.ST_CHANNEL).tobytes() == a[2], (count, rep, i)
+                    assert (d.text(), d.frames_array().tobytes()) == a[:2], (count, rep, i)
+        scrub(33)
+        pdt.demod_channels(ds, x)                                       # the capture in host memory
+        for i, (d, a) in enumerate(zip(ds, alone)):
+            assert (d.text(), d.frames_array().tobytes(), d.stage(pdt.ST_CHANNEL).tobytes()) == a, i
+    finally:
+        for d in ds:
+            d.close()
+
+
+def test_changing_the_decimation_on_one_context(pdt):
+    """The tap table is kept on the context under its decimation: D = 4, then D = 7, then D = 4 again on ONE context, each channel
+    stream pdt_host_ddc's and the third call's results the first's; then a stream at D = 3 on the same context, whose frames are
+    a fresh context's whole call."""
+    fs = 250000
+    x4, _ = carriers(pdt, 0, 4 * fs, 1.5, (200000.0,), (41,), 1000.0)
+    x7, _ = carriers(pdt, 0, 7 * fs, 1.5, (-412300.0,), (42,), 1000.0)
+    x3, _ = carriers(pdt, 0, 3 * fs, 1.5, (150000.0,), (43,), 1000.0)
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        d.set_channel(3, 150000.0).demod_channel(x3)
+        want3 = (d.text(), d.frames_array())
+    assert len(want3[1]) > 3
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        d.set_channel(4, 200000.0).demod_channel(x4)
+        first = (d.stage(pdt.ST_CHANNEL).tobytes(), d.text(), d.frames_array().tobytes())
+        assert first[0] == pdt.host_ddc(4 * fs, 4, 200000.0, x4).tobytes() and len(first[1]) > 100
+        d.set_channel(7, -412300.0).demod_channel(x7)
+        assert d.stage_len(pdt.ST_CHANNEL) == (len(x7) + 6) // 7
+        assert d.stage(pdt.ST_CHANNEL).tobytes() == pdt.host_ddc(7 * fs, 7, -412300.0, x7).tobytes()
+        assert len(d.text()) > 100
+        d.set_channel(4, 200000.0).demod_channel(x4)
+        assert (d.stage(pdt.ST_CHANNEL).tobytes(), d.text(), d.frames_array().tobytes()) == first
+        d.set_channel(3, 150000.0)
+        got = [d.stream_push_channel(x3[i: i + 100001]) for i in range(0, len(x3), 100001)] + [d.stream_end()]
+        assert np.concatenate(got).tobytes() == want3[1].tobytes()
+        assert d.text() == want3[0]
+
+
 @pytest.mark.parametrize("mode,kind,in_rate,D,offset,residual", [(0, 0, 1000000, 4, 200000.0, 1000.0), (1, 1, 1024000, 32, 250000.0, 120.0),
-                                                                (0, 0, 2400000, 16, -400000.0, 1000.0)])
+                                                                (0, 0, 2400000, 16, -400000.0, 1000.0),
+                                                                # no powers of two: 750 k / 3 and 1.75 M / 7 into 250 ksps contexts,
+                                                                # 1.65 M / 33 into a 50 ksps one
+                                                                (0, 0, 750000, 3, 150000.0, 1000.0), (0, 0, 1750000, 7, -412300.0, 1000.0),
+                                                                (0, 0, 1650000, 33, 400000.0, 1000.0)])
 def test_stream_pushes_equal_the_whole_call(pdt, mode, kind, in_rate, D, offset, residual):
     fs = in_rate // D
     x16, _ = carriers(pdt, kind, in_rate, 6.0 if kind == 0 else 12.0, (offset,), (55,), residual)
@@ -310,6 +494,17 @@ def test_command_line(pdt, tmp_path):
     # a rate the decimation does not divide
     r = subprocess.run([exe, "-x", "7", "-t", "200", "-o", out, wav], capture_output=True, text=True, timeout=300)
     assert r.returncode == 1 and "not divisible" in r.stdout
+    # ... and one it does: -x 3 on a 750 ksps file with one carrier
+    x3, _ = carriers(pdt, 0, 750000, 6.0, (150000.0,), (13,), 1000.0)
+    wav3 = str(tmp_path / "one_carrier_750k.wav")
+    pdt.write_wav(wav3, 750000, x3)
+    with pdt.Demodulator(pdt.MODE_POES, 250000) as d:
+        d.set_channel(3, 150000.0).demod_channel(x3)
+        want3 = d.text()
+    assert len(want3) > 10000
+    r = subprocess.run([exe, "-x", "3", "-t", "150", "-o", out, wav3], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert open(out, "rb").read() == want3
     # headerless 8-bit pairs, -s required
     cu8 = str(tmp_path / "two_carriers.cu8")
     u8 = to_cu8(x)

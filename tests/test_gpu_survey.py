@@ -71,6 +71,44 @@ def test_kernels_equal_host_restatement(pdt, nfft, fmt):
         assert len(d.frames_array()) == 0 and d.stage_len(pdt.ST_CHANNEL) == 0
 
 
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_capture_aligned_to_its_element_but_not_to_its_pair(pdt, fmt):
+    """A resident capture that begins half a sample off a pair boundary (a multiple of the element's size: 2 bytes for int16, 4 for
+    float, 1 for the 8-bit formats): k_survey loads every segment sample by sample (head = N), and the spectrum is pdt_host_survey's
+    of the same bytes.  More than one run of segments, 0, 1 and 3 whole samples further on too."""
+    rng = np.random.default_rng(500 + FORMATS.index(fmt))
+    in_rate, fs, D, nfft = 1000000, 250000, 4, 1024
+    n = (RUN + 1) * nfft + 9
+    flat = noisy_tone(rng, fmt, n + 4).reshape(-1)                         # elements: I, Q, I, Q, ...
+    dev = torch.from_numpy(flat.view(np.uint8).copy()).to("cuda:0")        # (the bytes; torch allocations are 16-byte aligned)
+    torch.cuda.synchronize()
+    assert dev.data_ptr() % 16 == 0
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        d.set_channel(D, 0.0)
+        for skip in (0, 1, 3):
+            first = 2 * skip + 1                                           # the capture begins with what was a Q
+            host = flat[first: first + 2 * n].reshape(n, 2)
+            want, found = pdt.host_survey(in_rate, 4500.0, fs, host, nfft=nfft)
+            got = d.survey_device(dev.data_ptr() + first * flat.itemsize, n, fmt_code(pdt, flat), nfft=nfft)
+            assert d.survey_spectrum().tobytes() == want.tobytes(), skip
+            assert got == found
+
+
+def test_changing_nfft_on_one_context(pdt):
+    """The window and the twiddles are kept on the context under one key, nfft: 1024, then 16384, then 1024 again on ONE context,
+    each spectrum pdt_host_survey's."""
+    rng = np.random.default_rng(99)
+    in_rate, fs, D = 1000000, 250000, 4
+    x = noisy_tone(rng, "pcm16", (RUN + 1) * 16384 + 5)
+    with pdt.Demodulator(pdt.MODE_POES, fs) as d:
+        d.set_channel(D, 0.0)
+        for nfft in (1024, 16384, 1024):
+            want, found = pdt.host_survey(in_rate, 4500.0, fs, x, nfft=nfft)
+            got = d.survey(x, nfft=nfft)
+            assert d.survey_spectrum().tobytes() == want.tobytes(), nfft
+            assert got == found and len(found) >= 1
+
+
 def test_arguments(pdt):
     fs = 250000
     x = np.zeros((2 * 16384, 2), dtype=np.int16)

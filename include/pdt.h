@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 9): the carrier survey of wideband captures -- pdt_survey_cfg, pdt_carrier, pdt_survey,
+/* 4, additions without a bump (round 10): short transmissions in a wideband capture -- pdt_bursts_cfg, pdt_burst, pdt_row_peak,
+ * pdt_bursts, pdt_bursts_device, pdt_burst_carriers, pdt_waterfall_rows, pdt_bursts_shape, pdt_burst_peaks, pdt_host_bursts: when and where the
+ * platforms of a capture send, for pdt_set_channel.
+ * 4, additions without a bump (round 9): the carrier survey of wideband captures -- pdt_survey_cfg, pdt_carrier, pdt_survey,
  * pdt_survey_device, pdt_survey_spectrum, pdt_host_survey: where the carriers of a capture are, for pdt_set_channel.
  * 4, additions without a bump (round 8): wideband SDR captures through a digital down-converter -- the sample formats
  * PDT_FMT_WB_PCM16 / _F32 / _CU8 / _CS8, the stage PDT_ST_CHANNEL, pdt_set_channel, pdt_demod_channel, pdt_demod_device_channel,
@@ -474,6 +477,70 @@ int  pdt_survey(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_
 int  pdt_survey_spectrum(const pdt_ctx *ctx, float *out, int n);
 int  pdt_host_survey(uint32_t in_rate, double mode_range_hz, uint32_t channel_rate, int sample_format, const void *x, uint64_t nframes,
                      const pdt_survey_cfg *cfg, float *spectrum_out, pdt_carrier *found, int cap, int *count);
+
+/* Short transmissions in a wideband capture: the spectrum over time and the bursts in it.  The survey above looks at ONE spectrum
+ * averaged over the stretch: a platform that sends for half a second every two minutes (ARGOS) stands 23 dB lower in it than while
+ * it is on, and a line that is always there (the DC spike of a cheap receiver, a birdie) looks like a carrier.  Here the stretch's
+ * segments -- the survey's, transformed in the same way -- are added in rows of rows_per consecutive ones (a last incomplete row
+ * is dropped), every row is searched for up to 8 bins that stand threshold_db over the survey's floor (the median of the survey's
+ * averaged spectrum of the same stretch at the same nfft; the bins within guard_hz of a peak are blanked for the next), and the host
+ * links the rows' peaks into bursts: a peak continues the open track whose last bin is nearest within merge_hz, a track not
+ * continued for more than gap_rows rows closes, and a closed track whose length lies in [min_s, max_s] is a burst -- max_s is what
+ * drops the lines that are always there.  A strong transmitter's modulation sidebands reach beyond guard_hz: a peak is not linked when
+ * its own row holds a peak at least 25 dB stronger within 4 guard_hz of it (the rows' peak records keep it).  The arithmetic is fixed: pdt_host_bursts restates it bit for bit.
+ * pdt_bursts_cfg: a zero in a field means its default -- nfft 4096 (1024, 4096, 16384), rows_per 8 (1 .. 64), threshold_db 15,
+ * guard_hz half the channel rate, merge_hz the mode's PLL frequency range, gap_rows 1, min_s two rows, max_s no upper limit,
+ * first_frame 0, nframes to the end of the capture.
+ *   pdt_bursts_device    the capture resident in device memory (only read); context, preconditions and error codes as for
+ *                        pdt_survey_device (PDT_ERR_ARG also for rows_per outside 1 .. 64 and a stretch shorter than one row).
+ *                        *count = the number of bursts found, found[] = the first min(cap, *count), ordered by start, then
+ *                        offset.  The rows live on the device a slab at a time, whatever the capture's length.  Like a survey it
+ *                        leaves the context's results, stages, statistics and pdt_survey_spectrum alone
+ *   pdt_bursts           the same for a capture in host memory: copied to the device once, into the context's input buffer
+ *   pdt_burst_carriers   host only: bursts whose offsets lie within merge_hz of each other are one platform, its offset the mean
+ *                        of theirs weighted by their peak power; the platforms strongest first, for pdt_set_channel; *n = their
+ *                        number, carriers[] = the first min(cap, *n)
+ *   pdt_waterfall_rows   rows first_row .. first_row + nrows - 1 of the context's last burst search (for plots and tests), nrows x
+ *                        nfft floats, bin b of a row at b Fs_in / nfft: they are computed again from the capture, which must still
+ *                        be where it was.  PDT_ERR_STATE before a burst search, and after pdt_bursts once the context's input
+ *                        buffer has taken another capture; PDT_ERR_ARG for rows outside the search
+ *   pdt_bursts_shape     nfft, rows_per and the number of rows of the context's last burst search (each pointer may be NULL;
+ *                        PDT_ERR_STATE as for pdt_waterfall_rows): how large the buffers of the two calls around it must be
+ *   pdt_burst_peaks      the peaks of those rows as the search found them: out[8 r + k], k < counts[r] (the rest zero), strongest
+ *                        first; kept on the host, the capture is not needed
+ *   pdt_host_bursts      test hook, host only: rows (rows_out), peaks (peaks_out, 8 a row, and peak_counts_out) and bursts as the
+ *                        kernels and the host linking produce them; each of the three outputs may be NULL                        */
+typedef struct pdt_bursts_cfg {
+    int nfft;
+    int rows_per;
+    int gap_rows;
+    double threshold_db, guard_hz, merge_hz;
+    double min_s, max_s;
+    uint64_t first_frame, nframes;
+} pdt_bursts_cfg;
+typedef struct pdt_burst {
+    uint64_t first_row, rows;       /* rows of the search: rows_per nfft input frames each */
+    double start_s;                 /* (first_frame + first_row rows_per nfft) / Fs_in */
+    double duration_s;              /* rows rows_per nfft / Fs_in */
+    double offset_hz;               /* from the capture's centre, [-Fs_in / 2, Fs_in / 2) */
+    float peak_db;                  /* its strongest row bin over floor x rows_per */
+    float floor_power;              /* the median of the survey's averaged spectrum */
+} pdt_burst;
+typedef struct pdt_row_peak {
+    int32_t bin;
+    float below, power, above;      /* the row at bin - 1, bin, bin + 1 (wrapping at the band's edge) */
+} pdt_row_peak;
+int  pdt_bursts_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg,
+                       pdt_burst *found, int cap, int *count);
+int  pdt_bursts(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg,
+                pdt_burst *found, int cap, int *count);
+int  pdt_burst_carriers(const pdt_burst *bursts, int count, double merge_hz, pdt_carrier *carriers, int cap, int *n);
+int  pdt_waterfall_rows(pdt_ctx *ctx, uint64_t first_row, uint64_t nrows, float *out);
+int  pdt_bursts_shape(const pdt_ctx *ctx, int *nfft, int *rows_per, uint64_t *nrows);
+int  pdt_burst_peaks(const pdt_ctx *ctx, uint64_t first_row, uint64_t nrows, pdt_row_peak *out, int *counts);
+int  pdt_host_bursts(uint32_t in_rate, double mode_range_hz, uint32_t channel_rate, int sample_format, const void *x, uint64_t nframes,
+                     const pdt_bursts_cfg *cfg, float *rows_out, pdt_row_peak *peaks_out, int *peak_counts_out, pdt_burst *found,
+                     int cap, int *count);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

@@ -188,6 +188,46 @@ def _survey_cfg(cfg: dict):
     return (SurveyCfg(**cfg) if cfg else None), max(int(cfg.get("max_carriers", 0)) or 16, 1)
 
 
+class BurstsCfg(C.Structure):
+    """pdt_bursts_cfg: a zero means the default"""
+    _fields_ = [("nfft", C.c_int), ("rows_per", C.c_int), ("gap_rows", C.c_int), ("threshold_db", C.c_double), ("guard_hz", C.c_double),
+                ("merge_hz", C.c_double), ("min_s", C.c_double), ("max_s", C.c_double), ("first_frame", C.c_uint64), ("nframes", C.c_uint64)]
+
+
+class BurstRec(C.Structure):
+    """pdt_burst"""
+    _fields_ = [("first_row", C.c_uint64), ("rows", C.c_uint64), ("start_s", C.c_double), ("duration_s", C.c_double), ("offset_hz", C.c_double),
+                ("peak_db", C.c_float), ("floor_power", C.c_float)]
+
+
+Burst = collections.namedtuple("Burst", "first_row rows start_s duration_s offset_hz peak_db floor_power")
+ROW_PEAK_DTYPE = np.dtype([("bin", "<i4"), ("below", "<f4"), ("power", "<f4"), ("above", "<f4")])      # pdt_row_peak
+BURST_ROW_PEAKS = 8
+
+
+def _bursts_cfg(cfg: dict):
+    """keyword arguments of a burst search -> (pdt_bursts_cfg or None, capacity of the result: `cap`, default 4096)"""
+    cfg = dict(cfg)
+    cap = int(cfg.pop("cap", 4096))
+    unknown = set(cfg) - {f[0] for f in BurstsCfg._fields_}
+    if unknown:
+        raise TypeError(f"unknown burst search parameter(s): {sorted(unknown)}")
+    return (BurstsCfg(**cfg) if cfg else None), cap
+
+
+def _bursts(rec, count: int, cap: int):
+    return [Burst(*(getattr(rec[i], f[0]) for f in BurstRec._fields_)) for i in range(min(count, cap))]
+
+
+def burst_carriers(bursts, merge_hz: float, cap: int = 16):
+    """pdt_burst_carriers: the platforms of a burst list (bursts within merge_hz of each other are one), strongest first, as
+    Carrier(offset_hz, peak_db, floor_power) for set_channel."""
+    rec = (BurstRec * max(len(bursts), 1))(*[BurstRec(*b) for b in bursts])
+    out, n = (CarrierRec * max(cap, 1))(), C.c_int(0)
+    _check(lib().pdt_burst_carriers(rec, len(bursts), float(merge_hz), out, cap, C.byref(n)), "pdt_burst_carriers")
+    return _carriers(out, min(n.value, cap))
+
+
 def _carriers(rec, count: int):
     return [Carrier(rec[i].offset_hz, rec[i].peak_db, rec[i].floor_power) for i in range(count)]
 
@@ -205,6 +245,7 @@ ABI_SYMBOLS = [
     "pdt_set_real_input", "pdt_demod_real", "pdt_demod_device_real", "pdt_stream_push_real", "pdt_host_analytic",
     "pdt_set_channel", "pdt_demod_channel", "pdt_demod_device_channel", "pdt_demod_channels_device", "pdt_demod_channels", "pdt_stream_push_channel", "pdt_host_ddc",
     "pdt_survey", "pdt_survey_device", "pdt_survey_spectrum", "pdt_host_survey",
+    "pdt_bursts", "pdt_bursts_device", "pdt_burst_carriers", "pdt_waterfall_rows", "pdt_bursts_shape", "pdt_burst_peaks", "pdt_host_bursts",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows"]        # include/pdt_dev.h (test-only)
 
@@ -338,6 +379,14 @@ def lib():
     L.pdt_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(SurveyCfg), C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
     L.pdt_survey_device.argtypes = L.pdt_survey.argtypes
     L.pdt_survey_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.pdt_bursts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(BurstsCfg), C.POINTER(BurstRec), C.c_int, C.POINTER(C.c_int)]
+    L.pdt_bursts_device.argtypes = L.pdt_bursts.argtypes
+    L.pdt_burst_carriers.argtypes = [C.POINTER(BurstRec), C.c_int, C.c_double, C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
+    L.pdt_waterfall_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.pdt_bursts_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+    L.pdt_burst_peaks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.pdt_host_bursts.argtypes = [C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(BurstsCfg), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.POINTER(BurstRec), C.c_int, C.POINTER(C.c_int)]
     L.pdt_host_survey.argtypes = [C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SurveyCfg), C.c_void_p,
                                   C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
@@ -426,6 +475,24 @@ def host_survey(in_rate: int, mode_range_hz: float, channel_rate: int, x: np.nda
     _check(lib().pdt_host_survey(in_rate, float(mode_range_hz), channel_rate, fmt, a.ctypes.data, a.size // 2, C.byref(c) if c else None,
                                  spec.ctypes.data if spec.size in (1024, 4096, 16384) else None, rec, cap, C.byref(count)), "pdt_host_survey")
     return spec, _carriers(rec, count.value)
+
+
+def host_bursts(in_rate: int, mode_range_hz: float, channel_rate: int, x: np.ndarray, rows: bool = True, **cfg):
+    """pdt_host_bursts: the burst search of a wideband capture restated on the host (no GPU), bit for bit what the kernels and the
+    host linking compute.  Arguments as host_survey; cfg: fields of pdt_bursts_cfg, and cap (room for that many bursts).  Returns
+    (rows float32[nrows, nfft] or None when rows is False, peaks ROW_PEAK_DTYPE[nrows, 8], counts int32[nrows], [Burst, ...])."""
+    a, fmt = _wb_samples(x)
+    c, cap = _bursts_cfg(cfg)
+    nfft, per = int(cfg.get("nfft", 0)) or 4096, int(cfg.get("rows_per", 0)) or 8
+    stretch = int(cfg.get("nframes", 0)) or max(a.size // 2 - int(cfg.get("first_frame", 0)), 0)
+    nrows = stretch // (nfft * per) if nfft in (1024, 4096, 16384) and 1 <= per <= 64 else 0
+    w = np.zeros((nrows, nfft), dtype=np.float32) if rows else None
+    peaks, counts = np.zeros((nrows, BURST_ROW_PEAKS), dtype=ROW_PEAK_DTYPE), np.zeros(nrows, dtype=np.int32)
+    rec, count = (BurstRec * max(cap, 1))(), C.c_int(0)
+    _check(lib().pdt_host_bursts(in_rate, float(mode_range_hz), channel_rate, fmt, a.ctypes.data, a.size // 2, C.byref(c) if c else None,
+                                 w.ctypes.data if rows and nrows else None, peaks.ctypes.data if nrows else None, counts.ctypes.data if nrows else None,
+                                 rec, cap, C.byref(count)), "pdt_host_bursts")
+    return w, peaks, counts, _bursts(rec, count.value, cap)
 
 
 def time_axis(mode: int, sample_rate: int, m: int) -> float:
@@ -623,6 +690,47 @@ class Demodulator:
         out = np.zeros(getattr(self, "_survey_nfft", 16384), dtype=np.float32)
         _check(self._L.pdt_survey_spectrum(self._h, out.ctypes.data, out.size), "pdt_survey_spectrum")
         return out
+
+    def bursts(self, x: np.ndarray, **cfg):
+        """The short transmissions of a wideband I,Q capture in host memory (after set_channel, whose offset plays no part): a list
+        of Burst(first_row, rows, start_s, duration_s, offset_hz, peak_db, floor_power) ordered by start, then offset.  cfg: fields
+        of pdt_bursts_cfg (nfft, rows_per, gap_rows, threshold_db, guard_hz, merge_hz, min_s, max_s, first_frame, nframes), zero or
+        absent = the default, and cap (room for that many bursts, default 4096)."""
+        a, fmt = _wb_samples(x)
+        c, cap = _bursts_cfg(cfg)
+        rec, count = (BurstRec * max(cap, 1))(), C.c_int(0)
+        _check(self._L.pdt_bursts(self._h, a.ctypes.data, a.size // 2, fmt, C.byref(c) if c else None, rec, cap, C.byref(count)), "pdt_bursts")
+        return _bursts(rec, count.value, cap)
+
+    def bursts_device(self, dev_ptr: int, nframes: int, fmt: int = FMT_WB_PCM16, **cfg):
+        """bursts() of a capture resident in HBM (nframes I,Q frames of FMT_WB_*), which is only read."""
+        c, cap = _bursts_cfg(cfg)
+        rec, count = (BurstRec * max(cap, 1))(), C.c_int(0)
+        _check(self._L.pdt_bursts_device(self._h, C.c_void_p(dev_ptr), nframes, fmt, C.byref(c) if c else None, rec, cap, C.byref(count)),
+               "pdt_bursts_device")
+        return _bursts(rec, count.value, cap)
+
+    def bursts_shape(self):
+        """(nfft, rows_per, rows) of the context's last burst search."""
+        nfft, per, nrows = C.c_int(0), C.c_int(0), C.c_uint64(0)
+        _check(self._L.pdt_bursts_shape(self._h, C.byref(nfft), C.byref(per), C.byref(nrows)), "pdt_bursts_shape")
+        return nfft.value, per.value, nrows.value
+
+    def waterfall_rows(self, first_row: int, nrows: int) -> np.ndarray:
+        """Rows of the last burst search, float32[nrows, nfft] (bin b at b Fs_in / nfft), computed again from the capture, which
+        must still be where it was."""
+        nfft, _, total = self.bursts_shape()
+        if nrows < 1 or first_row < 0 or first_row + nrows > total:
+            raise PdtError(f"rows {first_row} .. {first_row + nrows - 1} are not rows of the last burst search ({total} rows)")
+        out = np.zeros((nrows, nfft), dtype=np.float32)
+        _check(self._L.pdt_waterfall_rows(self._h, first_row, nrows, out.ctypes.data), "pdt_waterfall_rows")
+        return out
+
+    def burst_peaks(self, first_row: int, nrows: int):
+        """The peaks of rows of the last burst search: (ROW_PEAK_DTYPE[nrows, 8], counts int32[nrows])."""
+        peaks, counts = np.zeros((max(nrows, 1), BURST_ROW_PEAKS), dtype=ROW_PEAK_DTYPE), np.zeros(max(nrows, 1), dtype=np.int32)
+        _check(self._L.pdt_burst_peaks(self._h, first_row, nrows, peaks.ctypes.data, counts.ctypes.data), "pdt_burst_peaks")
+        return peaks, counts
 
     def demod_device(self, dev_ptr: int, nframes: int):
         """Input already resident in HBM (e.g. ``tensor.data_ptr()`` of an int16 torch tensor)."""

@@ -4,6 +4,7 @@
 #include "pdt_analytic.h"
 #include "pdt_ddc.h"
 #include "pdt_survey.h"
+#include "pdt_bursts.h"
 
 #include <pthread.h>
 #include <sched.h>
@@ -23,6 +24,12 @@ size_t survey_part_floats(uint64_t nseg, int nfft);
 hipError_t survey_launch(hipStream_t st, int fmt, const void *x, uint64_t nseg, int nfft, const float *win, const float *tw, float *part, float *out);
 int survey_plan(const pdt_survey_cfg *cfg, double mode_range_hz, double channel_rate, uint64_t nframes, int cap, pdt::SurveyPlan *p);
 int survey_carriers(const float *P, const pdt::SurveyPlan &p, double in_rate, pdt_carrier *found);
+// pdt_bursts.hip
+hipError_t waterfall_launch(hipStream_t st, int fmt, const void *x, uint64_t nrows, int rows_per, int nfft, const float *win, const float *tw, float *rows);
+hipError_t row_peaks_launch(hipStream_t st, const float *rows, uint64_t nrows, int nfft, float level, int gb, void *peaks, int *counts);
+int bursts_plan(const pdt_bursts_cfg *cfg, double mode_range_hz, double channel_rate, double in_rate, uint64_t nframes, int cap, pdt::BurstPlan *p);
+pdt::SurveyPlan bursts_survey_plan(const pdt::BurstPlan &p, const pdt_bursts_cfg *cfg, uint64_t nframes);
+int bursts_link(const void *peaks, const int *counts, bool compact, const pdt::BurstPlan &p, double floor, double in_rate, pdt_burst *found, int cap);
 // pdt_ddc.hip
 hipError_t ddc_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
                       int decim, const float *taps_dev, const float *tab_dev, const uint32_t *steps, void *const *outs, int k);
@@ -49,6 +56,7 @@ void Tuning::load()
     if (const char *e = get("PDT_AGC_TPB")) agc_tpb = std::max(1, atoi(e));
     if (const char *e = get("PDT_PLL_BLOCK")) pll_block = atoi(e);
     if (const char *e = get("PDT_HBM_LIMIT_MB")) hbm_limit_mb = std::max(1ll, atoll(e));        // (tests: pretend the device has this much free memory)
+    if (const char *e = get("PDT_BURST_SLAB_ROWS")) burst_slab_rows = std::max(1ll, atoll(e));    // (tests: rows per slab of a burst search, to cross a seam)
     if (const char *e = get("PDT_WINDOW_PIECE")) window_piece = std::max(1ll, atoll(e));          // (tests: samples per piece of the bounded window)
     if (const char *e = get("PDT_SCOUT_SYMS")) scout_syms = std::max(16, atoi(e));
     if (const char *e = get("PDT_FIR_WG_PER_CU")) fir_wg_per_cu = std::min(4096, std::max(1, atoi(e)));
@@ -955,7 +963,8 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->term, &ctx->seams_ema, &ctx->gtable, &ctx->gentries, &ctx->gcand,
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
-                       &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out };
+                       &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
+                       &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1206,6 +1215,7 @@ static bool overlap_ingest(const pdt_ctx *ctx, uint64_t nframes, size_t fb)
 // is the caller's decision (ingest_publish): a survey leaves the context's results as they are.
 static int ingest_whole(pdt_ctx *ctx, const IngestSrc &src, size_t bytes)
 {
+    ctx->bursts_done = ctx->bursts_done && ctx->bursts_src != ctx->pcm.p;     // (a burst search of host memory read this buffer: pdt_waterfall_rows)
     int rc = ctx->pcm.ensure(bytes + 16);
     if (rc) return rc;
     const auto t_in = std::chrono::steady_clock::now();
@@ -1445,6 +1455,155 @@ int pdt_survey_spectrum(const pdt_ctx *ctx, float *out, int n)
     if (ctx->survey_spec.empty()) return PDT_ERR_STATE;
     if (n < 0 || (size_t)n != ctx->survey_spec.size()) return PDT_ERR_ARG;
     memcpy(out, ctx->survey_spec.data(), ctx->survey_spec.size() * sizeof(float));
+    return PDT_OK;
+}
+
+// ---------------------------------------------------------------- burst search (pdt_bursts.h)
+// rows of a slab: what fits BURST_SLAB_BYTES (the developer switch PDT_BURST_SLAB_ROWS: that many)
+static uint64_t bursts_slab_rows(const pdt_ctx *ctx, int nfft)
+{
+    if (ctx->tune.burst_slab_rows > 0) return (uint64_t)ctx->tune.burst_slab_rows;
+    return std::max<uint64_t>(1, BURST_SLAB_BYTES / ((size_t)nfft * sizeof(float)));
+}
+
+// x: the capture, resident.  The survey's kernels first, as they are, for the floor (into the survey's device buffers: the context's
+// last survey spectrum lives on the host and stays); then slab by slab the rows and their peaks.  Nothing of the context's
+// demodulation state is touched.
+static int bursts_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const BurstPlan &p, const SurveyPlan &sp, pdt_burst *found, int cap, int *count)
+{
+    ctx->bursts_done = false;
+    int rc = survey_tables(ctx, p.nfft);
+    if (!rc) rc = ctx->survey_part.ensure(survey_part_floats(sp.nseg, p.nfft) * sizeof(float));
+    const uint64_t slab = std::min(bursts_slab_rows(ctx, p.nfft), p.nrows);
+    if (!rc) rc = ctx->bursts_rows.ensure((size_t)slab * (size_t)p.nfft * sizeof(float));
+    if (!rc) rc = ctx->bursts_peaks.ensure((size_t)slab * BURST_ROW_PEAKS * sizeof(BurstPeak));
+    if (!rc) rc = ctx->bursts_counts.ensure((size_t)slab * sizeof(int));
+    if (rc) return rc;
+    const unsigned char *first = (const unsigned char *)x + (size_t)p.first * (size_t)f.bytes;
+    const float *win = (const float *)ctx->survey_win.p, *tw = (const float *)ctx->survey_tw.p;
+    HIP_TRY(survey_launch(ctx->stream, f.code, first, sp.nseg, p.nfft, win, tw, (float *)ctx->survey_part.p, (float *)ctx->survey_out.p));
+    std::vector<float> P((size_t)p.nfft);
+    HIP_TRY(hipMemcpyAsync(P.data(), ctx->survey_out.p, P.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const double in_rate = (double)ctx->ch_decim * (double)ctx->cfg.sample_rate, floor = survey_floor(P.data(), p.nfft);
+    const float level = burst_level(floor, p.threshold_db, p.rows_per);
+    const int gb = burst_guard_bins(p.guard_hz, in_rate, p.nfft);
+    // the rows' peaks come back a slab at a time and are kept compact on the host: a row's count and its found records only
+    ctx->bursts_pk.clear();
+    ctx->bursts_cnt.assign((size_t)p.nrows, 0);
+    std::vector<pdt_row_peak> back((size_t)slab * BURST_ROW_PEAKS);
+    const size_t row_bytes = (size_t)p.rows_per * (size_t)p.nfft * (size_t)f.bytes;
+    for (uint64_t t0 = 0; t0 < p.nrows; t0 += slab) {
+        const uint64_t nt = std::min(slab, p.nrows - t0);
+        HIP_TRY(waterfall_launch(ctx->stream, f.code, first + (size_t)t0 * row_bytes, nt, p.rows_per, p.nfft, win, tw, (float *)ctx->bursts_rows.p));
+        HIP_TRY(row_peaks_launch(ctx->stream, (const float *)ctx->bursts_rows.p, nt, p.nfft, level, gb, ctx->bursts_peaks.p, (int *)ctx->bursts_counts.p));
+        HIP_TRY(hipMemcpyAsync(back.data(), ctx->bursts_peaks.p, (size_t)nt * BURST_ROW_PEAKS * sizeof(BurstPeak), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(&ctx->bursts_cnt[(size_t)t0], ctx->bursts_counts.p, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (uint64_t t = 0; t < nt; t++) {
+            const int c = ctx->bursts_cnt[(size_t)(t0 + t)];
+            if (c < 0 || c > BURST_ROW_PEAKS) return PDT_ERR_STATE;
+            ctx->bursts_pk.insert(ctx->bursts_pk.end(), back.begin() + (size_t)t * BURST_ROW_PEAKS, back.begin() + (size_t)t * BURST_ROW_PEAKS + c);
+        }
+    }
+    *count = bursts_link(ctx->bursts_pk.data(), ctx->bursts_cnt.data(), true, p, floor, in_rate, found, cap);
+    ctx->bursts_nfft = p.nfft;
+    ctx->bursts_rows_per = p.rows_per;
+    ctx->bursts_first = p.first;
+    ctx->bursts_nrows = p.nrows;
+    ctx->bursts_src = x;
+    ctx->bursts_fmt = f.code;
+    ctx->bursts_done = true;
+    return PDT_OK;
+}
+
+// both entries, as survey_any: a capture in host memory goes into the context's input buffer, its ingest is not published
+static int bursts_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg, pdt_burst *found,
+                      int cap, int *count)
+{
+    const InFmt f = in_fmt(sample_format);
+    if (!ctx || !iq || f.kind != IN_WB || !found || !count) return PDT_ERR_ARG;
+    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
+    const double range = ctx->lp.pll_freq_range_hz != 0 ? ctx->lp.pll_freq_range_hz : ctx->cfg.mode == PDT_MODE_ARGOS ? 550.0 : 4500.0;
+    BurstPlan p;
+    int rc = bursts_plan(cfg, range, (double)ctx->cfg.sample_rate, (double)ctx->ch_decim * (double)ctx->cfg.sample_rate, nframes, cap, &p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    if (!resident) {
+        if (!channel_fits(ctx, nframes, f)) return PDT_ERR_NOMEM;
+        ctx->bursts_done = false;
+        IngestSrc src;
+        src.mem = (const unsigned char *)iq;
+        if ((rc = ingest_whole(ctx, src, (size_t)nframes * (size_t)f.bytes))) return rc;
+        iq = ctx->pcm.p;
+    }
+    return bursts_resident(ctx, iq, f, p, bursts_survey_plan(p, cfg, nframes), found, cap, count);
+}
+
+int pdt_bursts_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg, pdt_burst *found,
+                      int cap, int *count)
+{
+    return bursts_any(ctx, iq_device, true, nframes, sample_format, cfg, found, cap, count);
+}
+
+int pdt_bursts(pdt_ctx *ctx, const void *iq_host, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg, pdt_burst *found, int cap,
+               int *count)
+{
+    return bursts_any(ctx, iq_host, false, nframes, sample_format, cfg, found, cap, count);
+}
+
+int pdt_waterfall_rows(pdt_ctx *ctx, uint64_t first_row, uint64_t nrows, float *out)
+{
+    if (!ctx || !out) return PDT_ERR_ARG;
+    if (!ctx->bursts_done) return PDT_ERR_STATE;
+    struct { int nfft, rows_per; uint64_t first; } p = { ctx->bursts_nfft, ctx->bursts_rows_per, ctx->bursts_first };
+    if (!nrows || first_row >= ctx->bursts_nrows || nrows > ctx->bursts_nrows - first_row) return PDT_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    int rc = survey_tables(ctx, p.nfft);
+    const uint64_t slab = std::min(bursts_slab_rows(ctx, p.nfft), nrows);
+    if (!rc) rc = ctx->bursts_rows.ensure((size_t)slab * (size_t)p.nfft * sizeof(float));
+    if (rc) return rc;
+    const InFmt f = in_fmt(ctx->bursts_fmt);
+    const size_t row_bytes = (size_t)p.rows_per * (size_t)p.nfft * (size_t)f.bytes;
+    const unsigned char *first = (const unsigned char *)ctx->bursts_src + (size_t)p.first * (size_t)f.bytes + (size_t)first_row * row_bytes;
+    const int log4 = survey_log4(p.nfft);
+    std::vector<float> place((size_t)slab * (size_t)p.nfft);
+    for (uint64_t t0 = 0; t0 < nrows; t0 += slab) {
+        const uint64_t nt = std::min(slab, nrows - t0);
+        HIP_TRY(waterfall_launch(ctx->stream, f.code, first + (size_t)t0 * row_bytes, nt, p.rows_per, p.nfft, (const float *)ctx->survey_win.p,
+                                 (const float *)ctx->survey_tw.p, (float *)ctx->bursts_rows.p));
+        HIP_TRY(hipMemcpyAsync(place.data(), ctx->bursts_rows.p, (size_t)nt * (size_t)p.nfft * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (uint64_t t = 0; t < nt; t++)                                   // place i of a row holds bin survey_rev(i)
+            for (int i = 0; i < p.nfft; i++)
+                out[(size_t)(t0 + t) * (size_t)p.nfft + survey_rev((uint32_t)i, log4)] = place[(size_t)t * (size_t)p.nfft + (size_t)i];
+    }
+    return PDT_OK;
+}
+
+int pdt_burst_peaks(const pdt_ctx *ctx, uint64_t first_row, uint64_t nrows, pdt_row_peak *out, int *counts)
+{
+    if (!ctx || !out || !counts) return PDT_ERR_ARG;
+    if (!ctx->bursts_done) return PDT_ERR_STATE;
+    if (!nrows || first_row >= ctx->bursts_nrows || nrows > ctx->bursts_nrows - first_row) return PDT_ERR_ARG;
+    size_t at = 0;
+    for (uint64_t t = 0; t < first_row; t++) at += (size_t)ctx->bursts_cnt[(size_t)t];
+    memset(out, 0, (size_t)nrows * BURST_ROW_PEAKS * sizeof(pdt_row_peak));
+    for (uint64_t t = 0; t < nrows; t++) {
+        const int c = counts[t] = ctx->bursts_cnt[(size_t)(first_row + t)];
+        if (c) memcpy(out + (size_t)t * BURST_ROW_PEAKS, &ctx->bursts_pk[at], (size_t)c * sizeof(pdt_row_peak));
+        at += (size_t)c;
+    }
+    return PDT_OK;
+}
+
+int pdt_bursts_shape(const pdt_ctx *ctx, int *nfft, int *rows_per, uint64_t *nrows)
+{
+    if (!ctx) return PDT_ERR_ARG;
+    if (!ctx->bursts_done) return PDT_ERR_STATE;
+    if (nfft) *nfft = ctx->bursts_nfft;
+    if (rows_per) *rows_per = ctx->bursts_rows_per;
+    if (nrows) *nrows = ctx->bursts_nrows;
     return PDT_OK;
 }
 

@@ -273,7 +273,7 @@ using namespace pdtrt;
 struct Tuning {
     double band_pad = 0.0, pll_warm_scale = 1.0, head_taus = 0.0, agc_k = 0.0, pll_warm_s = 0.0, agc_warm_s = 0.0;
     double overlap_split[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    long long hbm_limit_mb = 0, window_piece = 0;
+    long long hbm_limit_mb = 0, window_piece = 0, burst_slab_rows = 0;
     int ingest_direct = -1, ingest_numa = -1;        // -1 = decide by probing the file (ingest_capture), 0 = never, 1 = always try
     int scout_syms = 0, gspan = 0, gspan_cap = 0, ingest_threads = 0, ingest_span_mb = 0, ingest_streams = 0, overlap_segments = 0, overlap_min_mb = 0, fir_wg_per_cu = 0, agc_tpb = 0, gseg = 0, pll_block = 0, fix_passes = 2;
     bool fir_generic = false, mix_unfused = false, quality_inline = false, gemit_groups = false, agc_unfused = false, no_excl = false, gardner_onebuf = false, gardner_noring = false, gardner_sequential = false, seg_sequential = false, agc_lanes = false, overlap = true, debug_overlap = false, chain_one_range = false, ema_noguess = false, debug_sync = false, pll_noshort = false, pll_nockpt = false, pll_noconsensus = false, pll_notail = false, seg_plain = false, sync_block = false, gardner_nostride = false, manch_3pass = false, sync_serial = false;
@@ -443,6 +443,16 @@ struct pdt_ctx {
     DevBuf survey_win, survey_tw, survey_part, survey_out;
     int survey_tab_nfft = 0;
     std::vector<float> survey_spec;
+    // burst search (pdt_bursts.h): one slab of rows, its peaks and counts on the device; the last search's geometry and source and
+    // every row's peaks on the host (pdt_waterfall_rows, pdt_burst_peaks)
+    DevBuf bursts_rows, bursts_peaks, bursts_counts;
+    int bursts_nfft = 0, bursts_rows_per = 0;
+    uint64_t bursts_first = 0, bursts_nrows = 0;      // the stretch's first frame, its rows
+    bool bursts_done = false;
+    const void *bursts_src = nullptr;        // the stretch's capture on the device (the caller's, or this context's pcm)
+    int bursts_fmt = 0;
+    std::vector<pdt_row_peak> bursts_pk;
+    std::vector<int> bursts_cnt;
     unsigned char *seg_pin = nullptr;   // pinned staging for the small per-segment transfers (part of the pend_sc block)
     pdt_stats stats;
     std::vector<pdt_kernel_time> ktimes;

@@ -104,6 +104,119 @@ __host__ __device__ __forceinline__ float survey_power(const SurveyC &y)
     return a + b;
 }
 
+// One workgroup of N / 16 lanes takes a run of SURVEY_RUN segments.  A segment is converted and windowed on its way into LDS (16-byte
+// loads from the first 16-byte boundary on), N float pairs: all of the 128 KiB at N = 16384.  Every pass gives each lane four
+// butterflies, u = t + k N / 16: consecutive lanes take consecutive j, so for q >= 64 the 32 lanes of a half-wave read 32
+// consecutive pairs, one 256-byte bank row.  In the passes with q = 16, 4 and 1 a half-wave's places are 32 apart in runs of q
+// -- without more ado 2, 4 and 4 of them on every bank --, so place i is kept at survey_at(i): the low four bits of i exchanged by
+// bits 5-6 (times 5: both bit pairs) and bit 4 by bit 6, a permutation inside each bank row that puts those places on 32 different
+// bank pairs and leaves a row's consecutive places a row.  The last pass stays in registers: its four outputs' powers go to the
+// lane's sixteen sums, which leave after the run as four 16-byte stores, in place order (k_survey_sum undoes the digit reversal).
+__device__ __forceinline__ int survey_at(int i)
+{
+    return i ^ (((i >> 5) & 3) * 5) ^ (((i >> 6) & 1) << 4);
+}
+
+template <int FMT> struct SurveyVec;
+template <> struct SurveyVec<PDT_FMT_WB_PCM16> { enum { SPV = 4, BPS = 4 }; };
+template <> struct SurveyVec<PDT_FMT_WB_F32> { enum { SPV = 2, BPS = 8 }; };
+template <> struct SurveyVec<PDT_FMT_WB_CU8> { enum { SPV = 8, BPS = 2 }; };
+template <> struct SurveyVec<PDT_FMT_WB_CS8> { enum { SPV = 8, BPS = 2 }; };
+
+// One segment (number seg of the stretch that starts at x) by the whole workgroup of N / 16 lanes, t = threadIdx.x: converted,
+// windowed, transformed in sv (N float pairs of LDS), its bins' powers added to the lane's sixteen sums.  Ends with a barrier: sv
+// is free again.  k_survey's runs and k_waterfall's rows (pdt_bursts.hip) are sums over calls of this one function.
+template <int FMT, int N>
+__device__ __forceinline__ void survey_segment(float2 *sv, const void *__restrict__ x, long long seg, const float *__restrict__ win,
+                                               const float *__restrict__ tw, int t, float (&acc)[4][4])
+{
+    constexpr int TB = N / 16, LOG4 = N == 1024 ? 5 : N == 4096 ? 6 : 7;
+    constexpr int BPS = SurveyVec<FMT>::BPS, SPV = SurveyVec<FMT>::SPV;
+    const long long first = seg * N;
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(x) + first * BPS;
+    int head = (int)(((16 - ((uintptr_t)src & 15)) & 15) / BPS);      // samples in front of the first 16-byte boundary
+    if (((uintptr_t)src & 15) % BPS) head = N;                         // (never aligned: sample by sample)
+    const int nvec = (N - head) / SPV;
+    for (int j = t; j < head; j += TB) {
+        float re, im;
+        ddc_load<FMT>(src, j, re, im);
+        const float w = win[j];
+        sv[survey_at(j)] = make_float2(re * w, im * w);
+    }
+    for (int v = t; v < nvec; v += TB) {
+        const int4 raw = *reinterpret_cast<const int4 *>(src + (size_t)head * BPS + (size_t)v * 16);
+#pragma unroll
+        for (int e = 0; e < SPV; e++) {
+            float re, im;
+            ddc_load<FMT>(&raw, e, re, im);
+            const int j = head + v * SPV + e;
+            const float w = win[j];
+            sv[survey_at(j)] = make_float2(re * w, im * w);
+        }
+    }
+    for (int j = head + nvec * SPV + t; j < N; j += TB) {
+        float re, im;
+        ddc_load<FMT>(src, j, re, im);
+        const float w = win[j];
+        sv[survey_at(j)] = make_float2(re * w, im * w);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int pass = 0; pass < LOG4 - 1; pass++) {
+        const int q = N >> (2 * pass + 2), stride = 1 << (2 * pass);       // stride = N / L
+#pragma unroll(N == 16384 ? 1 : 4)                                             // (16 wavefronts a workgroup: 128 registers a lane)
+        for (int k = 0; k < 4; k++) {
+            const int u = t + TB * k, j = u & (q - 1), i0 = ((u - j) << 2) + j;
+            const int pa = survey_at(i0), pb = survey_at(i0 + q), pc = survey_at(i0 + 2 * q), pd = survey_at(i0 + 3 * q);
+            const float2 fa = sv[pa], fb = sv[pb], fc = sv[pc], fd = sv[pd];
+            SurveyC a = { fa.x, fa.y }, b = { fb.x, fb.y }, c = { fc.x, fc.y }, d = { fd.x, fd.y };
+            const int k1 = j * stride;
+            survey_bfly<true>(a, b, c, d, tw + 2 * k1, tw + 4 * k1, tw + 6 * k1);
+            sv[pa] = make_float2(a.r, a.i);
+            sv[pb] = make_float2(b.r, b.i);
+            sv[pc] = make_float2(c.r, c.i);
+            sv[pd] = make_float2(d.r, d.i);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int i0 = 4 * (t + TB * k);
+        const float2 fa = sv[survey_at(i0)], fb = sv[survey_at(i0 + 1)], fc = sv[survey_at(i0 + 2)], fd = sv[survey_at(i0 + 3)];
+        SurveyC a = { fa.x, fa.y }, b = { fb.x, fb.y }, c = { fc.x, fc.y }, d = { fd.x, fd.y };
+        survey_bfly<false>(a, b, c, d, nullptr, nullptr, nullptr);
+        acc[k][0] = acc[k][0] + survey_power(a);
+        acc[k][1] = acc[k][1] + survey_power(b);
+        acc[k][2] = acc[k][2] + survey_power(c);
+        acc[k][3] = acc[k][3] + survey_power(d);
+    }
+    __syncthreads();                                                   // (the next segment overwrites what this pass read)
+}
+
+// the same segment on the host: v[i] = place i of its transform (N = win.size() float pairs), first = its first sample's index in x
+template <int FMT>
+inline void survey_host_segment(const void *x, long long first, const std::vector<float> &win, const std::vector<float> &tw, std::vector<SurveyC> &v)
+{
+    const int N = (int)win.size(), log4 = survey_log4(N);
+    for (int j = 0; j < N; j++) {
+        float re, im;
+        ddc_load<FMT>(x, first + j, re, im);
+        v[(size_t)j].r = re * win[(size_t)j];
+        v[(size_t)j].i = im * win[(size_t)j];
+    }
+    for (int pass = 0; pass < log4; pass++) {
+        const int q = N >> (2 * pass + 2), stride = 1 << (2 * pass);
+        for (int u = 0; u < N / 4; u++) {
+            const int j = u & (q - 1), i0 = ((u - j) << 2) + j, k1 = j * stride;
+            if (pass < log4 - 1)
+                survey_bfly<true>(v[(size_t)i0], v[(size_t)(i0 + q)], v[(size_t)(i0 + 2 * q)], v[(size_t)(i0 + 3 * q)], &tw[(size_t)(2 * k1)],
+                                  &tw[(size_t)(4 * k1)], &tw[(size_t)(6 * k1)]);
+            else
+                survey_bfly<false>(v[(size_t)i0], v[(size_t)(i0 + 1)], v[(size_t)(i0 + 2)], v[(size_t)(i0 + 3)], nullptr, nullptr, nullptr);
+        }
+    }
+}
+
 // a survey's parameters with the defaults filled in (pdtrt::survey_plan, pdt_survey.hip)
 struct SurveyPlan {
     int nfft, max_carriers;

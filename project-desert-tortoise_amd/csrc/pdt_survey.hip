@@ -12,33 +12,13 @@ static_assert(sizeof(pdt_carrier) == sizeof(pdt::SurveyCarrier) && sizeof(pdt_ca
 
 namespace pdt {
 
-// One workgroup of N / 16 lanes takes a run of SURVEY_RUN segments.  A segment is converted and windowed on its way into LDS (16-byte
-// loads from the first 16-byte boundary on), N float pairs: all of the 128 KiB at N = 16384.  Every pass gives each lane four
-// butterflies, u = t + k N / 16: consecutive lanes take consecutive j, so for q >= 64 the 32 lanes of a half-wave read 32
-// consecutive pairs, one 256-byte bank row.  In the passes with q = 16, 4 and 1 a half-wave's places are 32 apart in runs of q
-// -- without more ado 2, 4 and 4 of them on every bank --, so place i is kept at survey_at(i): the low four bits of i exchanged by
-// bits 5-6 (times 5: both bit pairs) and bit 4 by bit 6, a permutation inside each bank row that puts those places on 32 different
-// bank pairs and leaves a row's consecutive places a row.  The last pass stays in registers: its four outputs' powers go to the
-// lane's sixteen sums, which leave after the run as four 16-byte stores, in place order (k_survey_sum undoes the digit reversal).
-__device__ __forceinline__ int survey_at(int i)
-{
-    return i ^ (((i >> 5) & 3) * 5) ^ (((i >> 6) & 1) << 4);
-}
-
-template <int FMT> struct SurveyVec;
-template <> struct SurveyVec<PDT_FMT_WB_PCM16> { enum { SPV = 4, BPS = 4 }; };
-template <> struct SurveyVec<PDT_FMT_WB_F32> { enum { SPV = 2, BPS = 8 }; };
-template <> struct SurveyVec<PDT_FMT_WB_CU8> { enum { SPV = 8, BPS = 2 }; };
-template <> struct SurveyVec<PDT_FMT_WB_CS8> { enum { SPV = 8, BPS = 2 }; };
-
 // x: the stretch's first sample; nseg whole segments of N samples follow it.  part: ceil(nseg / SURVEY_RUN) rows of N floats.
 template <int FMT, int N>
 __global__ void __launch_bounds__(N / 16) k_survey(const void *__restrict__ x, long long nseg, const float *__restrict__ win,
                                                    const float *__restrict__ tw, float *__restrict__ part)
 {
     __shared__ __attribute__((aligned(16))) float2 sv[N];
-    constexpr int TB = N / 16, LOG4 = N == 1024 ? 5 : N == 4096 ? 6 : 7;
-    constexpr int BPS = SurveyVec<FMT>::BPS, SPV = SurveyVec<FMT>::SPV;
+    constexpr int TB = N / 16;
     const int t = threadIdx.x;
     const long long s0 = (long long)blockIdx.x * SURVEY_RUN;
     const int ns = (int)min((long long)SURVEY_RUN, nseg - s0);
@@ -47,67 +27,7 @@ __global__ void __launch_bounds__(N / 16) k_survey(const void *__restrict__ x, l
     for (int k = 0; k < 4; k++)
 #pragma unroll
         for (int m = 0; m < 4; m++) acc[k][m] = 0.0f;
-    for (int s = 0; s < ns; s++) {
-        const long long first = (s0 + s) * N;
-        const unsigned char *src = reinterpret_cast<const unsigned char *>(x) + first * BPS;
-        int head = (int)(((16 - ((uintptr_t)src & 15)) & 15) / BPS);      // samples in front of the first 16-byte boundary
-        if (((uintptr_t)src & 15) % BPS) head = N;                         // (never aligned: sample by sample)
-        const int nvec = (N - head) / SPV;
-        for (int j = t; j < head; j += TB) {
-            float re, im;
-            ddc_load<FMT>(src, j, re, im);
-            const float w = win[j];
-            sv[survey_at(j)] = make_float2(re * w, im * w);
-        }
-        for (int v = t; v < nvec; v += TB) {
-            const int4 raw = *reinterpret_cast<const int4 *>(src + (size_t)head * BPS + (size_t)v * 16);
-#pragma unroll
-            for (int e = 0; e < SPV; e++) {
-                float re, im;
-                ddc_load<FMT>(&raw, e, re, im);
-                const int j = head + v * SPV + e;
-                const float w = win[j];
-                sv[survey_at(j)] = make_float2(re * w, im * w);
-            }
-        }
-        for (int j = head + nvec * SPV + t; j < N; j += TB) {
-            float re, im;
-            ddc_load<FMT>(src, j, re, im);
-            const float w = win[j];
-            sv[survey_at(j)] = make_float2(re * w, im * w);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int pass = 0; pass < LOG4 - 1; pass++) {
-            const int q = N >> (2 * pass + 2), stride = 1 << (2 * pass);       // stride = N / L
-#pragma unroll(N == 16384 ? 1 : 4)                                             // (16 wavefronts a workgroup: 128 registers a lane)
-            for (int k = 0; k < 4; k++) {
-                const int u = t + TB * k, j = u & (q - 1), i0 = ((u - j) << 2) + j;
-                const int pa = survey_at(i0), pb = survey_at(i0 + q), pc = survey_at(i0 + 2 * q), pd = survey_at(i0 + 3 * q);
-                const float2 fa = sv[pa], fb = sv[pb], fc = sv[pc], fd = sv[pd];
-                SurveyC a = { fa.x, fa.y }, b = { fb.x, fb.y }, c = { fc.x, fc.y }, d = { fd.x, fd.y };
-                const int k1 = j * stride;
-                survey_bfly<true>(a, b, c, d, tw + 2 * k1, tw + 4 * k1, tw + 6 * k1);
-                sv[pa] = make_float2(a.r, a.i);
-                sv[pb] = make_float2(b.r, b.i);
-                sv[pc] = make_float2(c.r, c.i);
-                sv[pd] = make_float2(d.r, d.i);
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i0 = 4 * (t + TB * k);
-            const float2 fa = sv[survey_at(i0)], fb = sv[survey_at(i0 + 1)], fc = sv[survey_at(i0 + 2)], fd = sv[survey_at(i0 + 3)];
-            SurveyC a = { fa.x, fa.y }, b = { fb.x, fb.y }, c = { fc.x, fc.y }, d = { fd.x, fd.y };
-            survey_bfly<false>(a, b, c, d, nullptr, nullptr, nullptr);
-            acc[k][0] = acc[k][0] + survey_power(a);
-            acc[k][1] = acc[k][1] + survey_power(b);
-            acc[k][2] = acc[k][2] + survey_power(c);
-            acc[k][3] = acc[k][3] + survey_power(d);
-        }
-        __syncthreads();                                                   // (the next segment overwrites what this pass read)
-    }
+    for (int s = 0; s < ns; s++) survey_segment<FMT, N>(sv, x, s0 + s, win, tw, t, acc);
     float *row = part + (size_t)blockIdx.x * N;
 #pragma unroll
     for (int k = 0; k < 4; k++)
@@ -184,6 +104,8 @@ int survey_plan(const pdt_survey_cfg *cfg, double mode_range_hz, double channel_
 }
 
 // the host's share of a survey: the carriers of the averaged spectrum P
+void survey_host_spectrum(int fmt, const void *x, const SurveyPlan &p, float *spectrum);
+
 int survey_carriers(const float *P, const SurveyPlan &p, double in_rate, pdt_carrier *found)
 {
     return survey_detect(P, p.nfft, in_rate, p.threshold_db, p.guard_hz, p.merge_hz, p.max_carriers, reinterpret_cast<SurveyCarrier *>(found));
@@ -201,29 +123,23 @@ template <int FMT> static void host_survey(const void *x, const SurveyPlan &p, f
     for (uint64_t s0 = 0; s0 < p.nseg; s0 += SURVEY_RUN) {
         std::fill(run.begin(), run.end(), 0.0f);
         for (uint64_t s = s0; s < std::min<uint64_t>(s0 + SURVEY_RUN, p.nseg); s++) {
-            const long long first = (long long)(p.first + s * (uint64_t)N);
-            for (int j = 0; j < N; j++) {
-                float re, im;
-                ddc_load<FMT>(x, first + j, re, im);
-                v[(size_t)j].r = re * win[(size_t)j];
-                v[(size_t)j].i = im * win[(size_t)j];
-            }
-            for (int pass = 0; pass < log4; pass++) {
-                const int q = N >> (2 * pass + 2), stride = 1 << (2 * pass);
-                for (int u = 0; u < N / 4; u++) {
-                    const int j = u & (q - 1), i0 = ((u - j) << 2) + j, k1 = j * stride;
-                    if (pass < log4 - 1)
-                        survey_bfly<true>(v[(size_t)i0], v[(size_t)(i0 + q)], v[(size_t)(i0 + 2 * q)], v[(size_t)(i0 + 3 * q)], &tw[(size_t)(2 * k1)],
-                                          &tw[(size_t)(4 * k1)], &tw[(size_t)(6 * k1)]);
-                    else
-                        survey_bfly<false>(v[(size_t)i0], v[(size_t)(i0 + 1)], v[(size_t)(i0 + 2)], v[(size_t)(i0 + 3)], nullptr, nullptr, nullptr);
-                }
-            }
+            survey_host_segment<FMT>(x, (long long)(p.first + s * (uint64_t)N), win, tw, v);
             for (int i = 0; i < N; i++) run[(size_t)i] = run[(size_t)i] + survey_power(v[(size_t)i]);
         }
         for (int i = 0; i < N; i++) total[(size_t)i] = total[(size_t)i] + (double)run[(size_t)i];
     }
     for (int i = 0; i < N; i++) spectrum[survey_rev((uint32_t)i, log4)] = (float)(total[(size_t)i] / (double)p.nseg);
+}
+
+// the averaged spectrum of the plan's stretch as the kernels leave it, on the host (pdt_host_survey, pdt_host_bursts)
+void pdtrt::survey_host_spectrum(int fmt, const void *x, const SurveyPlan &p, float *spectrum)
+{
+    switch (fmt) {
+    case PDT_FMT_WB_PCM16: host_survey<PDT_FMT_WB_PCM16>(x, p, spectrum); break;
+    case PDT_FMT_WB_F32: host_survey<PDT_FMT_WB_F32>(x, p, spectrum); break;
+    case PDT_FMT_WB_CU8: host_survey<PDT_FMT_WB_CU8>(x, p, spectrum); break;
+    default: host_survey<PDT_FMT_WB_CS8>(x, p, spectrum); break;
+    }
 }
 
 extern "C" int pdt_host_survey(uint32_t in_rate, double mode_range_hz, uint32_t channel_rate, int sample_format, const void *x, uint64_t nframes,
@@ -235,12 +151,7 @@ extern "C" int pdt_host_survey(uint32_t in_rate, double mode_range_hz, uint32_t 
     const int rc = pdtrt::survey_plan(cfg, mode_range_hz, (double)channel_rate, nframes, cap, &p);
     if (rc) return rc;
     std::vector<float> P((size_t)p.nfft);
-    switch (sample_format) {
-    case PDT_FMT_WB_PCM16: host_survey<PDT_FMT_WB_PCM16>(x, p, P.data()); break;
-    case PDT_FMT_WB_F32: host_survey<PDT_FMT_WB_F32>(x, p, P.data()); break;
-    case PDT_FMT_WB_CU8: host_survey<PDT_FMT_WB_CU8>(x, p, P.data()); break;
-    default: host_survey<PDT_FMT_WB_CS8>(x, p, P.data()); break;
-    }
+    pdtrt::survey_host_spectrum(sample_format, x, p, P.data());
     if (spectrum_out) memcpy(spectrum_out, P.data(), P.size() * sizeof(float));
     *count = pdtrt::survey_carriers(P.data(), p, (double)in_rate, found);
     return PDT_OK;

@@ -45,6 +45,11 @@
  * -t auto or -t auto:N (an addition, with -x, not beside numeric -t): the carriers are looked for instead of given -- the capture's
  * averaged spectrum is surveyed on the GPU (pdt_survey), the (N) strongest carriers found are printed like the -t lines
  * and the run goes on as if their offsets had been given.  No carrier: one line, no output file, exit status 1.  Not from a pipe.
+ * -t bursts or -t bursts:N (an addition, under -t auto's rules): the platforms are looked for in the spectrum over time -- the
+ * capture's short transmissions are searched for on the GPU (pdt_bursts), one line is printed per burst, the (N)
+ * strongest platforms among them are printed like the -t lines and the run goes on as if their offsets had been given.  No burst:
+ * one line, no output file, exit status 1.  -B <seconds> is the longest transmission that counts as a burst (pdt_bursts_cfg.max_s),
+ * 5 by default: what lasts longer -- a receiver's DC spike, a birdie, a continuous beacon -- is no platform; -B 0 sets no limit.
  */
 #include <ctype.h>
 #include <math.h>
@@ -61,14 +66,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -374,6 +379,70 @@ static int auto_channels(FILE *in, long data_offset, uint64_t nframes, size_t fr
     return 0;
 }
 
+/* -t bursts: search the capture for short transmissions (pdt_bursts) and take the platforms among them (pdt_burst_carriers), at
+ * most `want`, strongest first.  Offsets come back as printed, like auto_channels'.  Returns 0 when there is at least one. */
+static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, int want,
+                          double max_s, double *offsetsHz, int *nch)
+{
+    enum { ROOM = 4096 };                                /* bursts asked for at first; when there are more, all of them in a second call */
+    pdt_ctx *ctx = NULL;
+    int rc = pdt_open(cfg, &ctx);
+    if (rc != PDT_OK) {
+        printf("GPU demodulator unavailable: %s\n", pdt_strerror(rc));
+        return 1;
+    }
+    unsigned char *buf = (unsigned char *)malloc((size_t)nframes * frame_bytes + 16);
+    pdt_burst *found = (pdt_burst *)malloc(ROOM * sizeof *found);
+    if (!buf || !found || fseek(in, data_offset, SEEK_SET) != 0 || fread(buf, frame_bytes, (size_t)nframes, in) != (size_t)nframes) {
+        printf("Error reading the capture\n");
+        return 1;
+    }
+    pdt_bursts_cfg bc;
+    memset(&bc, 0, sizeof bc);
+    bc.max_s = max_s;
+    int count = 0, nplat = 0;
+    pdt_carrier plat[16];
+    rc = pdt_set_channel(ctx, decim, 0.0);
+    if (rc == PDT_OK) rc = pdt_bursts(ctx, buf, nframes, fmt, &bc, found, ROOM, &count);
+    if (rc == PDT_OK && count > ROOM) {                  /* platforms are taken from the whole recording, not from its beginning */
+        const int room = count;
+        free(found);
+        found = (pdt_burst *)malloc((size_t)room * sizeof *found);
+        rc = found ? pdt_bursts(ctx, buf, nframes, fmt, &bc, found, room, &count) : PDT_ERR_NOMEM;
+        if (count > room) count = room;
+    }
+    free(buf);
+    pdt_close(ctx);
+    if (rc != PDT_OK) {
+        printf("Burst search failed: %s\n", pdt_strerror(rc));
+        free(found);
+        return 1;
+    }
+    if (count == 0) {
+        printf("No burst found\n");
+        free(found);
+        return 1;
+    }
+    for (int i = 0; i < count; i++)
+        printf("Burst at %.3f s, %.3f s long, %+f Khz, %.1f dB over the floor\n", found[i].start_s, found[i].duration_s, found[i].offset_hz / 1000.0,
+               found[i].peak_db);
+    rc = pdt_burst_carriers(found, count, MODE == PDT_MODE_ARGOS ? 550.0 : 4500.0, plat, 16, &nplat);
+    free(found);
+    if (rc != PDT_OK) {
+        printf("Burst search failed: %s\n", pdt_strerror(rc));
+        return 1;
+    }
+    if (nplat > want) nplat = want;
+    for (int i = 0; i < nplat; i++) {
+        char khz[64];
+        snprintf(khz, sizeof khz, "%+f", plat[i].offset_hz / 1000.0);
+        offsetsHz[i] = atof(khz) * 1000.0;
+        printf("Channel %d at %s Khz (found, %.1f dB over the floor)\n", i, khz, plat[i].peak_db);
+    }
+    *nch = nplat;
+    return 0;
+}
+
 static double now_ms(void)
 {
     struct timespec ts;
@@ -390,6 +459,8 @@ int main(int argc, char **argv)
     int outputRawFiles = 0, device = 0, quality = 0, sampler = 0, live = 0, chunkGiven = 0, noProgress = 0, real = 0, c;
     double realCenterHz = 0;
     int decim = 0, nOffsets = 0, wbFormat = PDT_FMT_WB_CU8, autoCarriers = 0;      /* -t auto[:N]: look for up to N carriers */
+    double burstMaxS = 5.0;                                                         /* -B: pdt_bursts_cfg.max_s of -t bursts */
+    int autoBursts = 0;                                                             /* -t bursts[:N]: autoCarriers platforms, from the burst search */
     double offsetsHz[16];
     const char *outOverride = NULL;
     char outFileName[1100];
@@ -462,12 +533,29 @@ int main(int argc, char **argv)
                 printf("Channels: the %d strongest carriers found\n", autoCarriers);
                 break;
             }
+            if (strncmp(optarg, "bursts", 6) == 0) {
+                autoCarriers = optarg[6] == ':' ? atoi(optarg + 7) : optarg[6] == 0 ? 16 : 0;
+                if (autoCarriers < 1 || autoCarriers > 16) {
+                    printf("-t bursts or -t bursts:N with N from 1 to 16\n");
+                    return 1;
+                }
+                autoBursts = 1;
+                printf("Channels: the %d strongest platforms found by their bursts\n", autoCarriers);
+                break;
+            }
             if (nOffsets >= 16) {
                 printf("At most 16 channels\n");
                 return 1;
             }
             offsetsHz[nOffsets++] = atof(optarg) * 1000.0;
             printf("Channel %d at %+f Khz\n", nOffsets - 1, atof(optarg));
+            break;
+        case 'B':                                       /* -t bursts: the longest transmission that is a burst, seconds (0: no limit) */
+            burstMaxS = atof(optarg);
+            if (!(burstMaxS >= 0)) {
+                printf("-B <seconds> must not be negative\n");
+                return 1;
+            }
             break;
         case 'F':                                       /* the format of the wideband blocks read from a pipe */
             if (strcasecmp(optarg, "cu8") == 0) wbFormat = PDT_FMT_WB_CU8;
@@ -496,7 +584,7 @@ int main(int argc, char **argv)
         }
     }
     if (autoCarriers && nOffsets) {
-        printf("-t auto cannot be combined with -t <kHz>\n");
+        printf("-t %s cannot be combined with -t <kHz>\n", autoBursts ? "bursts" : "auto");
         return 1;
     }
     if ((nOffsets || autoCarriers) && !decim) {
@@ -519,7 +607,7 @@ int main(int argc, char **argv)
     printf("Opening IO files..\n");
     const int from_stdin = live && strcmp(inFileName, "-") == 0;
     if (from_stdin && autoCarriers) {
-        printf("-t auto needs a capture file: the spectrum of a stream is not known in advance\n");
+        printf("-t %s needs a capture file: the spectrum of a stream is not known in advance\n", autoBursts ? "bursts" : "auto");
         return 1;
     }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
@@ -652,7 +740,9 @@ int main(int argc, char **argv)
     cfg.sampler = sampler;
     cfg.chain = live ? PDT_CHAIN_LIVE : PDT_CHAIN_FILE;
     if (autoCarriers) {
-        if (auto_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, offsetsHz, &nOffsets)) return 1;
+        if (autoBursts ? burst_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, burstMaxS, offsetsHz, &nOffsets)
+                       : auto_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, offsetsHz, &nOffsets))
+            return 1;
         out = nOffsets > 1 ? stdout : fopen(outFileName, "w+");
         if (!out) {
             printf("Error opening output files\n");

@@ -60,7 +60,9 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 10): short transmissions in a wideband capture -- pdt_bursts_cfg, pdt_burst, pdt_row_peak,
+/* 4, additions without a bump (round 11, test hooks only): pdt_device_math and pdt_device_math_layout -- the kernels' scalar
+ * primitives evaluated on the device one record per lane; pdt_host_math codes 9 - 13.
+ * 4, additions without a bump (round 10): short transmissions in a wideband capture -- pdt_bursts_cfg, pdt_burst, pdt_row_peak,
  * pdt_bursts, pdt_bursts_device, pdt_burst_carriers, pdt_waterfall_rows, pdt_bursts_shape, pdt_burst_peaks, pdt_host_bursts: when and where the
  * platforms of a capture send, for pdt_set_channel.
  * 4, additions without a bump (round 9): the carrier survey of wideband captures -- pdt_survey_cfg, pdt_carrier, pdt_survey,
@@ -711,8 +713,57 @@ int  pdt_wav_parse_header(const uint8_t hdr[44], uint32_t *sample_rate, uint32_t
  * sincosf / hypot / hypotf; CarrierTrackingPLL.c:106-107,134-135, LowPassFilter.c:148,163, AGC.c:57-67) evaluated on the host
  * over an array.  fn: 0 sincos -> out0 = sin, out1 = cos; 1 sin; 2 cos; 3 sincosf of (float)x, widened; 4 hypot of the pairs
  * (x[2i], x[2i+1]) -> out0[i]; 5 hypotf of the pairs; 6 the branch-free sincosf of the fused mix + FIR kernel; 7 / 8 the error
- * and phase wraps of one float PLL step (CarrierTrackingPLL.c:168-188) in their fused form.  The kernels run the same code.     */
+ * and phase wraps of one float PLL step (CarrierTrackingPLL.c:168-188) in their fused form; 9 / 10 the error wrap as the plain
+ * expression (compare with M_PI, correct by -+2 M_PI in double, narrow) in float (widened) / double; 11 / 12 arctan2_ref of the
+ * pairs (y, x) = (x[2i], x[2i+1]) in float (widened) / double (CarrierTrackingPLL.c:15-40); 13 q_rsqrt of (float)x (:43-52).
+ * The kernels run the same code (9 / 10: the same expression in another form); pdt_device_math evaluates it on the device.   */
 int  pdt_host_math(int fn, const double *x, uint64_t n, double *out0, double *out1);
+
+/* Test hook, device: the scalar primitives the kernels are made of (csrc/pdt_device_math.h, csrc/pdt_kernels_front.h,
+ * csrc/pdt_kernels_back.h), each evaluated by itself on the GPU -- one record per lane, the very functions (and the very
+ * machine-code blocks) the kernels call.  `n` records of `nin` elements go in, `n` records of `nout` elements come out, record
+ * after record; an element is a float (4 bytes) or a double (8) as the table says, never widened.  Codes 0 - 8 mean what they
+ * mean in pdt_host_math.
+ *
+ *   fn  elem  nin  nout  function                                   record in -> out
+ *    0   f64    1    2   sincos_glibc                               x -> sin, cos
+ *    1   f64    1    1   sin_glibc                                  x -> sin
+ *    2   f64    1    1   cos_glibc                                  x -> cos
+ *    3   f32    1    2   sincosf_glibc                              x -> sin, cos
+ *    4   f64    2    1   hypot_glibc                                x, y -> h
+ *    5   f32    2    1   hypotf_glibc                               x, y -> h
+ *    6   f32    1    2   sincosf_flat                               x -> sin, cos
+ *    7   f32    1    1   pll_wrap_error_f32 (its machine-code form) x -> r
+ *    8   f32    1    1   pll_wrap_phase_f32                         x -> r
+ *    9   f32    1    1   PiAbs::ge_pi(x) ? unwrap_2pi(x) : x        x -> r      (the error wrap of the generic loop-filter step)
+ *   10   f64    1    1   the same in double                         x -> r
+ *   11   f32    2    1   arctan2_ref                                y, x -> angle
+ *   12   f64    2    1   arctan2_ref                                y, x -> angle
+ *   13   f32    1    1   q_rsqrt                                    x -> r
+ *   14   f32    6    2   pll_phase_step<float, false>               th, phase, freq, alpha, beta, maxf -> phase', freq'   (minf = -maxf)
+ *   15   f32    6    2   pll_phase_step<float, true>                 "
+ *   16   f64    6    2   pll_phase_step<double, false>               "
+ *   17   f64    6    2   pll_phase_step<double, true>                "
+ *   18   f32   10    7   acq_vec4_asm<false>                        th0..th3, phase, freq, sweep, alpha, beta, maxf -> pb[0..3], phase', freq', sweep'
+ *   19   f32   10    7   acq_vec4_asm<true>                          "
+ *   20   f32   10    7   pll_vec4_asm                               the same record -> p[0..3], phase' (= p[3]), freq', sweep (as given)
+ *   21   f32    4    2   pll_sweep_sel<float>                       fr, sw, maxf, on (0 = off) -> fr', sw'                (minf = -maxf)
+ *   22   f64    4    2   pll_sweep_sel<double>                       "
+ *   23   f32    1    2   rint_index, Real<float>::rint              x -> the index (an int32 in the element's bytes), rint(x)
+ *   24   f64    1    2   rint_index, Real<double>::rint             x -> the index (an int64 in the element's bytes), rint(x)
+ *   25   f32    2    1   clip_finite                                e, lim -> clipped
+ *   26   f64    2    1   clip_finite                                e, lim -> clipped
+ *   27   f32   19   35   agc_calm<float, 4>, agc_step, agc_step_calm  x[16], gain, attack, decay -> calm (0 / 1), y[16] and the gain
+ *                                                                   after the batch through agc_step, the same through agc_step_calm
+ *
+ * 18 - 20: alpha, beta and maxf are scalar-register operands of the blocks, as in the kernels (launch constants there): they
+ * must be the same in every record of a call (PDT_ERR_ARG otherwise).  20 ends in an LDS-direct load, the refill of a walker's
+ * look-ahead ring: the probe gives every lane 16 bytes of a buffer of its own to fetch and a slot of its own workgroup's LDS.
+ * One ordinary launch per call on the context's stream; returns when the results are in `out`.                              */
+#define PDT_DEVICE_MATH_FNS 28
+int  pdt_device_math(pdt_ctx *ctx, int fn, const void *in, uint64_t n, void *out);
+/* The table above: bytes per element, elements per record in and out (NULL = not wanted); PDT_ERR_ARG for an unknown fn. */
+int  pdt_device_math_layout(int fn, int *elem_bytes, int *nin, int *nout);
 /* The reference's running-sum time axis (wave.c:91,96-97,167-168): value after m additions of Ts. */
 double pdt_time_axis(int mode, uint32_t sample_rate, uint64_t m);
 

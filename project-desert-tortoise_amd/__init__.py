@@ -246,6 +246,7 @@ ABI_SYMBOLS = [
     "pdt_set_channel", "pdt_demod_channel", "pdt_demod_device_channel", "pdt_demod_channels_device", "pdt_demod_channels", "pdt_stream_push_channel", "pdt_host_ddc",
     "pdt_survey", "pdt_survey_device", "pdt_survey_spectrum", "pdt_host_survey",
     "pdt_bursts", "pdt_bursts_device", "pdt_burst_carriers", "pdt_waterfall_rows", "pdt_bursts_shape", "pdt_burst_peaks", "pdt_host_bursts",
+    "pdt_device_math", "pdt_device_math_layout",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows"]        # include/pdt_dev.h (test-only)
 
@@ -389,6 +390,8 @@ def lib():
                                   C.c_void_p, C.POINTER(BurstRec), C.c_int, C.POINTER(C.c_int)]
     L.pdt_host_survey.argtypes = [C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SurveyCfg), C.c_void_p,
                                   C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
+    L.pdt_device_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.pdt_device_math_layout.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
         raise PdtError("libpdt.so ABI version mismatch")
     _lib = L
@@ -416,12 +419,20 @@ def make_lpf(mode: int, sample_rate: int) -> tuple[np.ndarray, int]:
 
 
 def host_math(fn: int, x: np.ndarray):
-    """pdt_host_math: the library's own sincos / sin / cos / sincosf / hypot / hypotf evaluated on the host (test hook)."""
-    a = np.ascontiguousarray(x, dtype=np.float64)
-    n = len(a) // 2 if fn in (4, 5) else len(a)
+    """pdt_host_math: the library's own sincos / sin / cos / sincosf / hypot / hypotf, the PLL's wraps, arctan2_ref and q_rsqrt
+    evaluated on the host (test hook; include/pdt.h lists the codes).  The two-argument codes take the pairs interleaved."""
+    a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    n = len(a) // 2 if fn in (4, 5, 11, 12) else len(a)
     o0, o1 = np.zeros(n), np.zeros(n)
     _check(lib().pdt_host_math(fn, a.ctypes.data, n, o0.ctypes.data, o1.ctypes.data), "pdt_host_math")
     return o0, o1
+
+
+def device_math_layout(fn: int) -> tuple[np.dtype, int, int]:
+    """pdt_device_math_layout: (element type, elements per record in, elements per record out) of a pdt_device_math code."""
+    eb, ni, no = C.c_int(), C.c_int(), C.c_int()
+    _check(lib().pdt_device_math_layout(fn, C.byref(eb), C.byref(ni), C.byref(no)), "pdt_device_math_layout")
+    return np.dtype(np.float32 if eb.value == 4 else np.float64), ni.value, no.value
 
 
 def _real_samples(x: np.ndarray) -> tuple[np.ndarray, int]:
@@ -731,6 +742,18 @@ class Demodulator:
         peaks, counts = np.zeros((max(nrows, 1), BURST_ROW_PEAKS), dtype=ROW_PEAK_DTYPE), np.zeros(max(nrows, 1), dtype=np.int32)
         _check(self._L.pdt_burst_peaks(self._h, first_row, nrows, peaks.ctypes.data, counts.ctypes.data), "pdt_burst_peaks")
         return peaks, counts
+
+    def device_math(self, fn: int, records: np.ndarray) -> np.ndarray:
+        """pdt_device_math (test hook): the kernels' scalar primitive `fn` evaluated on this context's GPU, one record per lane.
+        records: [n, nin] (or [n] where nin is 1) of the code's element type -- it is not converted; returns [n, nout]."""
+        dt, nin, nout = device_math_layout(fn)
+        a = np.ascontiguousarray(records)
+        if a.dtype != dt or a.size % nin:
+            raise PdtError(f"pdt_device_math({fn}): records of {nin} x {dt} wanted, got {a.dtype} x {a.shape}")
+        n = a.size // nin
+        out = np.empty((n, nout), dtype=dt)
+        _check(self._L.pdt_device_math(self._h, fn, a.ctypes.data, n, out.ctypes.data), "pdt_device_math")
+        return out
 
     def demod_device(self, dev_ptr: int, nframes: int):
         """Input already resident in HBM (e.g. ``tensor.data_ptr()`` of an int16 torch tensor)."""

@@ -789,7 +789,9 @@ int pdt_device_count(void)
 // tests compare them with the C library of the machine, bit for bit).  fn: 0 sincos(x) -> out0 sin, out1 cos; 1 sin; 2 cos;
 // 3 sincosf((float)x) widened; 4 hypot(x[2i], x[2i+1]) -> out0[i]; 5 hypotf of the pair, widened; 6 the branch-free form
 // of 3 (sincosf_flat: what the fused mix + FIR kernel evaluates); 7 / 8 the error and phase wraps of one float PLL step
-// (pll_wrap_error_f32 / pll_wrap_phase_f32), widened.
+// (pll_wrap_error_f32 / pll_wrap_phase_f32), widened; 9 / 10 the error wrap as the reference writes it (CarrierTrackingPLL.c:168-173: the
+// difference compared with M_PI as a double, corrected by -+2 M_PI in double, narrowed) for (float)x / x; 11 / 12 arctan2_ref of the
+// pairs (y, x) in float / double; 13 q_rsqrt of (float)x.
 int pdt_host_math(int fn, const double *x, uint64_t n, double *out0, double *out1)
 {
     if (!x || !out0) return PDT_ERR_ARG;
@@ -804,6 +806,11 @@ int pdt_host_math(int fn, const double *x, uint64_t n, double *out0, double *out
         case 6: { float sf, cf; sincosf_flat((float)x[i], sf, cf); out0[i] = sf; if (out1) out1[i] = cf; break; }
         case 7: out0[i] = pll_wrap_error_f32((float)x[i]); break;
         case 8: out0[i] = pll_wrap_phase_f32((float)x[i]); break;
+        case 9: { const float v = (float)x[i]; out0[i] = ((double)v > M_PI) ? (float)((double)v - 2 * M_PI) : ((double)v < -M_PI) ? (float)((double)v + 2 * M_PI) : v; break; }
+        case 10: out0[i] = (x[i] > M_PI) ? x[i] - 2 * M_PI : (x[i] < -M_PI) ? x[i] + 2 * M_PI : x[i]; break;
+        case 11: out0[i] = arctan2_ref((float)x[2 * i], (float)x[2 * i + 1]); break;
+        case 12: out0[i] = arctan2_ref(x[2 * i], x[2 * i + 1]); break;
+        case 13: out0[i] = q_rsqrt((float)x[i]); break;
         default: return PDT_ERR_ARG;
         }
     }

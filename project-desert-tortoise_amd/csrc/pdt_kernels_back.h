@@ -86,9 +86,15 @@ __device__ __forceinline__ bool is_finite_bits(double v) { return (__double2hiin
 // integer position exactly as rint does (float: 0 <= x < 2^22; double: |x| < 2^31)
 __device__ __forceinline__ int rint_index(float x) { return __float_as_int(x + 12582912.0f) - 0x4B400000; }
 __device__ __forceinline__ int rint_index(double x) { return __double2loint(x + 6755399441055744.0); }
-// (e > lim) ? lim : ((e < -lim) ? -lim : e) for every e that is not a NaN
+// (e > lim) ? lim : ((e < -lim) ? -lim : e): the float form for every e that is not a NaN (the median gives a bound for one); the
+// double form for every e -- fmax / fmin alone would hand back the other operand for a NaN where the reference's select returns
+// the NaN, so it is put back (the compare stands beside the chain, one select behind it)
 __device__ __forceinline__ float clip_finite(float e, float lim) { return __builtin_amdgcn_fmed3f(e, -lim, lim); }
-__device__ __forceinline__ double clip_finite(double e, double lim) { return __builtin_fmin(__builtin_fmax(e, -lim), lim); }
+__device__ __forceinline__ double clip_finite(double e, double lim)
+{
+    const double r = __builtin_fmin(__builtin_fmax(e, -lim), lim);
+    return (e != e) ? e : r;
+}
 
 template <typename T> struct GardnerState {
     T ns, prev, half;      // sampler state (identical in every lane of the wavefront)

@@ -321,11 +321,14 @@ __device__ __forceinline__ void pll_phase_step(T th, T &phase, T &freq, T alpha,
     const T err = PiAbs<T>::ge_pi(diff) ? wrapped : diff;
     const T f1 = freq + beta * err;
     T ph = phase + f1 + alpha * err;
-    const T phw = unwrap_2pi(ph);
-    ph = PiAbs<T>::ge_2pi(ph) ? phw : ph;
     if (SLOW_WRAP) {
+        // the reference's loops as they stand, every correction in double: with gains this large the sum can pass 4 pi, where
+        // the float form of unwrap_2pi is no longer exact (x - hi needs a bit more than a float holds from 8 + 2 pi on)
         while (PiCmp<T>::gt_2pi(ph)) ph = (T)((double)ph - 2.0 * PDT_PI);
         while (PiCmp<T>::lt_m2pi(ph)) ph = (T)((double)ph + 2.0 * PDT_PI);
+    } else {
+        const T phw = unwrap_2pi(ph);
+        ph = PiAbs<T>::ge_2pi(ph) ? phw : ph;
     }
     phase = ph;
     freq = PiAbs<T>::clamp(f1, minf, maxf);

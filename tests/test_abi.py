@@ -69,6 +69,21 @@ def test_struct_layouts_match_header(pdt):
         assert subprocess.run([exe]).returncode == 0
 
 
+def test_device_math_layout_is_the_headers_table(pdt):
+    """pdt_device_math (test hook, csrc/pdt_probe.hip): the record layouts the library reports are the rows of the table in
+    include/pdt.h, and the entry refuses what it cannot run before it touches a device."""
+    src = open(os.path.join(ROOT, "include", "pdt.h")).read()
+    rows = re.findall(r"^ \*\s+(\d+)\s+f(32|64)\s+(\d+)\s+(\d+)\s+\S", src, flags=re.M)
+    n = int(re.search(r"#define PDT_DEVICE_MATH_FNS (\d+)", src).group(1))
+    assert [int(r[0]) for r in rows] == list(range(n)) and n == 28
+    for fn, bits, nin, nout in rows:
+        dt, ni, no = pdt.device_math_layout(int(fn))
+        assert (dt.itemsize * 8, ni, no) == (int(bits), int(nin), int(nout)), fn
+    L = pdt.lib()
+    assert L.pdt_device_math_layout(n, None, None, None) == -1 and L.pdt_device_math_layout(-1, None, None, None) == -1
+    assert L.pdt_device_math(None, 0, None, 1, None) == -1          # PDT_ERR_ARG: no context
+
+
 def test_no_gpu_fails_loudly(pdt, gpu_available):
     if gpu_available:
         pytest.skip("a GPU is present")
@@ -153,7 +168,7 @@ def test_hand_issued_lds_loads_are_the_only_users_of_m0(pdt, tmp_path):
             per_kernel.setdefault(kernel, [0, 0])[1] += 1
     assert per_kernel, "no hand-issued LDS loads found: is the ring still there?"
     for k, (loads, movs) in per_kernel.items():
-        assert any(w in k for w in ("k_agc_", "k_pll_phase", "k_pll_head", "k_pll_tail", "k_pll_fix", "k_lock_ema")), f"m0 / LDS-direct load in an unexpected kernel: {k}"
+        assert any(w in k for w in ("k_agc_", "k_pll_phase", "k_pll_head", "k_pll_tail", "k_pll_fix", "k_lock_ema", "k_probe")), f"m0 / LDS-direct load in an unexpected kernel: {k}"
         assert loads == movs and loads > 0, f"{k}: {loads} LDS-direct loads but {movs} writes of m0"
 
 

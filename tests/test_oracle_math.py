@@ -44,15 +44,30 @@ def test_hypotf_matches_glibc_bitwise(orc):
 
 
 def test_q_rsqrt_and_arctan2_known_values(orc):
+    """The oracle's Q_rsqrt and arctan2 (oracle_math.c) equal the numpy transcriptions of CarrierTrackingPLL.c:15-52
+    (tests/math_models.py) bit for bit, on samples of the sets the GPU tests use (tests/test_gpu_math.py) with all their edge
+    inputs: every 9 700th positive float pattern, the coarse int16 grid's a^2 + b^2, +0; the int16 corner grid, the degenerate
+    pairs and 60 000 random ones; and, as before, the known values to 1e-6: an anchor that is not a transcription."""
+    import math_models as mm
     L = orc.lib()
-    # two Newton steps of the 0x5f3759df seed
-    assert abs(L.orc_q_rsqrt(4.0) - 0.5) < 1e-5
-    assert abs(L.orc_q_rsqrt(0.25) - 2.0) < 1e-4
-    # rational approximation: exact at the octant centres
-    assert abs(L.orc_arctan2_f32(1.0, 1.0) - np.pi / 4) < 1e-6
-    assert abs(L.orc_arctan2_f32(1.0, -1.0) - 3 * np.pi / 4) < 1e-6
-    assert L.orc_arctan2_f32(-1.0, 1.0) == -L.orc_arctan2_f32(1.0, 1.0)
-    assert abs(L.orc_arctan2_f32(0.0, 1.0)) < 1e-6
+    # anchors outside the project's own transcriptions: two Newton steps of the 0x5f3759df seed are within 5e-6 relative of
+    # 1 / sqrt(x); the rational approximation is exact at the octant centres and odd in y
+    assert abs(L.orc_q_rsqrt(4.0) - 0.5) < 1e-5 and abs(L.orc_q_rsqrt(0.25) - 2.0) < 1e-4
+    assert abs(L.orc_arctan2_f32(1.0, 1.0) - np.pi / 4) < 1e-6 and abs(L.orc_arctan2_f32(1.0, -1.0) - 3 * np.pi / 4) < 1e-6
+    assert L.orc_arctan2_f32(-1.0, 1.0) == -L.orc_arctan2_f32(1.0, 1.0) and abs(L.orc_arctan2_f32(0.0, 1.0)) < 1e-6
+    L.orc_arctan2_f64.argtypes = [C.c_double, C.c_double]
+    L.orc_arctan2_f64.restype = C.c_double
+    x = mm.q_rsqrt_set()
+    x = np.concatenate([x[::100], x[-65538::7], np.array([4.0, 0.25, 0.0], np.float32)])
+    got = np.array([L.orc_q_rsqrt(float(v)) for v in x], dtype=np.float32)
+    assert got.tobytes() == mm.q_rsqrt(x).tobytes()
+    for T, f in ((np.float32, L.orc_arctan2_f32), (np.float64, L.orc_arctan2_f64)):
+        yx = mm.arctan2_set(T)
+        free = np.nonzero(np.arange(len(yx)) % 33 == 0)[0]
+        keep = np.concatenate([np.arange(0, 258064, 3), free[free >= 258064][:60000], np.arange(len(yx) - 12000, len(yx))])
+        yx = np.concatenate([yx[keep], np.array([[1, 1], [1, -1], [-1, 1], [0, 1]], dtype=T)])
+        got = np.array([f(float(y), float(v)) for y, v in yx], dtype=T)
+        assert got.tobytes() == mm.arctan2(yx[:, 0], yx[:, 1]).tobytes()
 
 
 def test_unwrap_f32_exhaustive():

@@ -1,12 +1,15 @@
 """The library's own restatements of the C-library functions the reference calls (csrc/pdt_device_math.h; the kernels run
 the same code on the device) against the C library of this machine, bit for bit: glibc 2.35's double sincos / sin / cos
 (table-driven IBM routines), sincosf, hypot (cabs) and hypotf (cabsf), over the argument ranges the chain produces and
-well beyond.  Host only (pdt_host_math): runs without a GPU."""
+well beyond.  Host only (pdt_host_math): runs without a GPU; tests/test_gpu_math.py runs the same functions on the device
+(pdt_device_math) over the same sets, which tests/math_models.py builds for both."""
 import ctypes as C
 import ctypes.util
 
 import numpy as np
 import pytest
+
+from math_models import DOUBLE_RANGES, double_special_points, every_float, range_args
 
 libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
 libm.sin.restype = libm.cos.restype = libm.hypot.restype = C.c_double
@@ -18,19 +21,10 @@ libm.hypotf.restype = C.c_float
 libm.hypotf.argtypes = [C.c_float, C.c_float]
 
 
-def args(lo, hi, n, seed):
-    rng = np.random.default_rng(seed)
-    x = rng.uniform(lo, hi, n)
-    x[::2] *= -1
-    return x
 
-
-RANGES = [(0.0, 2.0 ** -26), (1e-9, 0.13), (0.12, 0.86), (0.85, 2.43), (2.42, 6.3), (6.28, 60.0), (50.0, 1e5), (1e5, 1e8)]
-
-
-@pytest.mark.parametrize("lo,hi", RANGES)
+@pytest.mark.parametrize("lo,hi", DOUBLE_RANGES)
 def test_double_sincos_sin_cos_equal_glibc(pdt, lo, hi):
-    x = args(lo, hi, 60000, 11)
+    x = range_args(lo, hi, 60000, 11)
     s0, c0 = pdt.host_math(0, x)
     s1, _ = pdt.host_math(1, x)
     c2, _ = pdt.host_math(2, x)
@@ -45,9 +39,7 @@ def test_double_sincos_sin_cos_equal_glibc(pdt, lo, hi):
 
 
 def test_special_points_of_the_double_routines(pdt):
-    k = np.arange(0, 900)
-    x = np.concatenate([k / 128.0, k / 128.0 + 2.0 ** -8, np.nextafter(k / 128.0 + 2.0 ** -8, 0), [0.126, 0.855469, 2.426265, 0.0, -0.0],
-                        np.arange(1, 400) * (np.pi / 2), np.arange(1, 400) * np.float64(np.float32(np.pi))])
+    x = double_special_points()
     s0, c0 = pdt.host_math(0, x)
     a, b = C.c_double(), C.c_double()
     for i, v in enumerate(x):
@@ -56,7 +48,7 @@ def test_special_points_of_the_double_routines(pdt):
 
 
 def test_sincosf_equals_glibc(pdt):
-    x = np.concatenate([args(0, 7.0, 150000, 5), args(0, 120.0, 50000, 6), args(0, 1e-4, 5000, 7)]).astype(np.float32).astype(np.float64)
+    x = np.concatenate([range_args(0, 7.0, 150000, 5), range_args(0, 120.0, 50000, 6), range_args(0, 1e-4, 5000, 7)]).astype(np.float32).astype(np.float64)
     s, c = pdt.host_math(3, x)
     a, b = C.c_float(), C.c_float()
     for i, v in enumerate(x):
@@ -100,11 +92,6 @@ def test_branch_free_sincosf_equals_the_library_form(pdt):
         assert np.float32(a.value).tobytes() == np.float32(s6[i]).tobytes() and np.float32(b.value).tobytes() == np.float32(c6[i]).tobytes(), x[i]
 
 
-def _every_float(lo, hi):
-    a = np.arange(np.float32(lo).view(np.uint32), np.float32(hi).view(np.uint32) + 1, dtype=np.uint32).view(np.float32)
-    return np.concatenate([a, -a])
-
-
 def test_pll_wraps_in_fused_form_equal_the_reference_expressions(pdt):
     """One float PLL step's two wraps as the walkers evaluate them (pll_wrap_error_f32: one sign transfer + two fused
     multiply-adds; pll_wrap_phase_f32: k = trunc(p / 2pi), two fused multiply-adds, no select) against the reference's
@@ -112,13 +99,13 @@ def test_pll_wraps_in_fused_form_equal_the_reference_expressions(pdt):
     float of the ranges the corrections can fire in, plus a sample of the range they leave alone."""
     rng = np.random.default_rng(5)
     small = np.concatenate([rng.uniform(-3.2, 3.2, 200000).astype(np.float32), np.array([0.0, 1e-30, -1e-30, 3.1415925, -3.1415925], np.float32)])
-    x = np.concatenate([_every_float(3.0, 9.5), small])
+    x = np.concatenate([every_float(3.0, 9.5), small])
     xd = x.astype(np.float64)
     ref = np.where(xd > np.pi, (xd - 2 * np.pi).astype(np.float32), np.where(xd < -np.pi, (xd + 2 * np.pi).astype(np.float32), x))
     got, _ = pdt.host_math(7, xd)
     assert got.astype(np.float32).tobytes() == ref.astype(np.float32).tobytes()
     small = np.concatenate([rng.uniform(-6.3, 6.3, 200000).astype(np.float32), np.array([0.0, 1e-30, -1e-30, 6.283185, -6.283185], np.float32)])
-    x = np.concatenate([_every_float(6.0, 12.5), small])         # (the one-correction variant is selected for |p| < 4pi - 0.05)
+    x = np.concatenate([every_float(6.0, 12.5), small])         # (the one-correction variant is selected for |p| < 4pi - 0.05)
     xd = x.astype(np.float64)
     ref = np.where(xd > 2 * np.pi, (xd - 2 * np.pi).astype(np.float32), np.where(xd < -2 * np.pi, (xd + 2 * np.pi).astype(np.float32), x))
     got, _ = pdt.host_math(8, xd)

@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 11, test hooks only): pdt_device_math and pdt_device_math_layout -- the kernels' scalar
+/* 4, additions without a bump (round 12): every burst of a wideband capture in a window of its own -- pdt_window, pdt_burst_windows,
+ * pdt_demod_windows_device, pdt_demod_windows, pdt_demod_windows_held: the bursts of pdt_bursts, each cut out of the capture at its own
+ * offset, all windows in one conversion launch.
+ * 4, additions without a bump (round 11, test hooks only): pdt_device_math and pdt_device_math_layout -- the kernels' scalar
  * primitives evaluated on the device one record per lane; pdt_host_math codes 9 - 13.
  * 4, additions without a bump (round 10): short transmissions in a wideband capture -- pdt_bursts_cfg, pdt_burst, pdt_row_peak,
  * pdt_bursts, pdt_bursts_device, pdt_burst_carriers, pdt_waterfall_rows, pdt_bursts_shape, pdt_burst_peaks, pdt_host_bursts: when and where the
@@ -543,6 +546,47 @@ int  pdt_burst_peaks(const pdt_ctx *ctx, uint64_t first_row, uint64_t nrows, pdt
 int  pdt_host_bursts(uint32_t in_rate, double mode_range_hz, uint32_t channel_rate, int sample_format, const void *x, uint64_t nframes,
                      const pdt_bursts_cfg *cfg, float *rows_out, pdt_row_peak *peaks_out, int *peak_counts_out, pdt_burst *found,
                      int cap, int *count);
+
+/* Every burst in a window of its own.  pdt_burst_carriers merges the bursts of a capture into platforms and the whole capture is then
+ * demodulated once per platform at one offset.  That fails where it matters: a platform's Doppler moves by kilohertz over a pass while
+ * the ARGOS loop sweeps 550 Hz, and a capture that opens with noise takes its normalisation from noise and winds the acquisition loop
+ * up on it.  Here each burst is cut out of the capture at its own measured offset: a window [first_frame, first_frame +
+ * nframes) of the capture is a capture of its own -- samples outside it count as zero although the capture has neighbours, the
+ * mixer's phase is counted from the window's first sample, time stamps are seconds of the window's channel stream -- and all windows
+ * of a call are converted by ONE launch (k_ddc_windows), then the contexts go through the batched chain.
+ *   pdt_burst_windows          host only: window i from burst i.  first_frame = llround((start_s + skip) Fs_in), the end is
+ *                              min(capture_frames, llround((start_s + duration_s + tail) Fs_in)), offset_hz the burst's; a window whose
+ *                              start reaches its end has nframes 0.  skip_s < 0: the default, one row of that burst (duration_s /
+ *                              rows) -- start_s lies up to a row BEFORE the transmission, and a window must begin inside the carrier,
+ *                              not in the noise in front of it; tail_s < 0: 0.1 s.  PDT_ERR_ARG: a null pointer with count > 0,
+ *                              in_rate 0, a non-finite argument or burst
+ *   pdt_demod_windows_device   ONE wideband capture in device memory (only read), `count` contexts with a window each.  Context i ends
+ *                              up holding byte for byte what
+ *                                  pdt_set_channel(ctxs[i], decim, win[i].offset_hz);
+ *                                  pdt_demod_device_channel(ctxs[i], (const char *)iq_device + win[i].first_frame * frame_bytes,
+ *                                                           win[i].nframes, sample_format);
+ *                              alone would have produced -- frames, text, statistics, PDT_ST_CHANNEL, reports and progress -- and its
+ *                              channel offset is left at its window's.  Preconditions and errors as for pdt_demod_channels_device
+ *                              (every context after pdt_set_channel, same decim and device, all distinct, no open stream; modes may
+ *                              differ); PDT_ERR_ARG also for a window that reaches beyond nframes or whose |offset_hz| >= Fs_in / 2.
+ *                              Windows may overlap, repeat and be empty
+ *   pdt_demod_windows          the same for a capture in host memory: copied to the device once, into the first context's input buffer
+ *                              (PDT_ERR_NOMEM when it does not fit)
+ *   pdt_demod_windows_held     the same for the capture that `holder`'s last pdt_bursts or pdt_survey call (or their _device forms)
+ *                              read, which must still be where it was: search, then demodulate in rounds, with one copy of the
+ *                              capture.  PDT_ERR_STATE before such a call and once the holder's input buffer has taken another
+ *                              capture (pdt_waterfall_rows' rule); PDT_ERR_ARG when holder is among ctxs.  The holder's results,
+ *                              spectrum, burst list and pdt_waterfall_rows are left alone                                          */
+typedef struct pdt_window {
+    uint64_t first_frame, nframes;  /* of the capture */
+    double offset_hz;               /* from the capture's centre */
+} pdt_window;
+int  pdt_burst_windows(const pdt_burst *bursts, int count, uint32_t in_rate, uint64_t capture_frames, double skip_s, double tail_s,
+                       pdt_window *out);
+int  pdt_demod_windows_device(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_device, uint64_t nframes,
+                              int sample_format);
+int  pdt_demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_host, uint64_t nframes, int sample_format);
+int  pdt_demod_windows_held(pdt_ctx *holder, pdt_ctx *const *ctxs, int count, const pdt_window *win);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

@@ -228,6 +228,28 @@ def burst_carriers(bursts, merge_hz: float, cap: int = 16):
     return _carriers(out, min(n.value, cap))
 
 
+class WindowRec(C.Structure):
+    """pdt_window"""
+    _fields_ = [("first_frame", C.c_uint64), ("nframes", C.c_uint64), ("offset_hz", C.c_double)]
+
+
+Window = collections.namedtuple("Window", "first_frame nframes offset_hz")
+
+
+def _window_recs(windows):
+    return (WindowRec * max(len(windows), 1))(*[WindowRec(int(w[0]), int(w[1]), float(w[2])) for w in windows])
+
+
+def burst_windows(bursts, in_rate: int, capture_frames: int, skip_s: float = -1.0, tail_s: float = -1.0):
+    """pdt_burst_windows: window i of burst i, a list of Window(first_frame, nframes, offset_hz) -- from skip_s behind the burst's
+    start (negative: one row of the burst, so that the window begins inside the carrier) to tail_s behind its end (negative: 0.1 s),
+    cut at the capture's end (host only)."""
+    rec = (BurstRec * max(len(bursts), 1))(*[BurstRec(*b) for b in bursts])
+    out = (WindowRec * max(len(bursts), 1))()
+    _check(lib().pdt_burst_windows(rec, len(bursts), in_rate, capture_frames, float(skip_s), float(tail_s), out), "pdt_burst_windows")
+    return [Window(out[i].first_frame, out[i].nframes, out[i].offset_hz) for i in range(len(bursts))]
+
+
 def _carriers(rec, count: int):
     return [Carrier(rec[i].offset_hz, rec[i].peak_db, rec[i].floor_power) for i in range(count)]
 
@@ -247,6 +269,7 @@ ABI_SYMBOLS = [
     "pdt_survey", "pdt_survey_device", "pdt_survey_spectrum", "pdt_host_survey",
     "pdt_bursts", "pdt_bursts_device", "pdt_burst_carriers", "pdt_waterfall_rows", "pdt_bursts_shape", "pdt_burst_peaks", "pdt_host_bursts",
     "pdt_device_math", "pdt_device_math_layout",
+    "pdt_burst_windows", "pdt_demod_windows_device", "pdt_demod_windows", "pdt_demod_windows_held",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows"]        # include/pdt_dev.h (test-only)
 
@@ -390,6 +413,10 @@ def lib():
                                   C.c_void_p, C.POINTER(BurstRec), C.c_int, C.POINTER(C.c_int)]
     L.pdt_host_survey.argtypes = [C.c_uint32, C.c_double, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SurveyCfg), C.c_void_p,
                                   C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
+    L.pdt_burst_windows.argtypes = [C.POINTER(BurstRec), C.c_int, C.c_uint32, C.c_uint64, C.c_double, C.c_double, C.POINTER(WindowRec)]
+    L.pdt_demod_windows_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(WindowRec), C.c_void_p, C.c_uint64, C.c_int]
+    L.pdt_demod_windows.argtypes = L.pdt_demod_windows_device.argtypes
+    L.pdt_demod_windows_held.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(WindowRec)]
     L.pdt_device_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pdt_device_math_layout.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
@@ -743,6 +770,14 @@ class Demodulator:
         _check(self._L.pdt_burst_peaks(self._h, first_row, nrows, peaks.ctypes.data, counts.ctypes.data), "pdt_burst_peaks")
         return peaks, counts
 
+    def demod_windows_held(self, ds, windows):
+        """pdt_demod_windows_held: demod_windows() on the capture this context's last bursts() or survey() call read (it must still
+        be where it was): ds[i] demodulates windows[i].  This context itself may not be among ds; its results are left alone."""
+        if len(ds) != len(windows):
+            raise ValueError("demod_windows_held: lists of different lengths")
+        hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
+        _check(self._L.pdt_demod_windows_held(self._h, hs, len(ds), _window_recs(windows)), "pdt_demod_windows_held")
+
     def device_math(self, fn: int, records: np.ndarray) -> np.ndarray:
         """pdt_device_math (test hook): the kernels' scalar primitive `fn` evaluated on this context's GPU, one record per lane.
         records: [n, nin] (or [n] where nin is 1) of the code's element type -- it is not converted; returns [n, nout]."""
@@ -1003,6 +1038,22 @@ def demod_channels(demods, dev_ptr, nframes: int = 0, fmt: int = FMT_WB_PCM16):
         _check(lib().pdt_demod_channels(hs, n, a.ctypes.data, a.size // 2, fmt), "pdt_demod_channels")
         return
     _check(lib().pdt_demod_channels_device(hs, n, C.c_void_p(int(dev_ptr)), int(nframes), fmt), "pdt_demod_channels_device")
+
+
+def demod_windows(ds, x_or_ptr, nframes: int, fmt: int, windows):
+    """Every window of ONE wideband capture on a context of its own: ds[i] (after set_channel, all of one decim) demodulates
+    windows[i] = (first_frame, nframes, offset_hz) as a capture of its own at that offset -- what set_channel + demod_device_channel
+    on the slice would give -- all windows converted by one launch, then the batched chain.  x_or_ptr: the address of the capture in
+    HBM (nframes I,Q frames of fmt), or a numpy array of I,Q pairs in host memory (pdt_demod_windows; nframes and fmt are the array's)."""
+    if len(ds) != len(windows):
+        raise ValueError("demod_windows: lists of different lengths")
+    n = len(ds)
+    hs = (C.c_void_p * max(n, 1))(*[d._h for d in ds])
+    if isinstance(x_or_ptr, np.ndarray):
+        a, fmt = _wb_samples(x_or_ptr)
+        _check(lib().pdt_demod_windows(hs, n, _window_recs(windows), a.ctypes.data, a.size // 2, fmt), "pdt_demod_windows")
+        return
+    _check(lib().pdt_demod_windows_device(hs, n, _window_recs(windows), C.c_void_p(int(x_or_ptr)), int(nframes), fmt), "pdt_demod_windows_device")
 
 
 FRAME_DTYPE = np.dtype([

@@ -31,6 +31,9 @@ int bursts_plan(const pdt_bursts_cfg *cfg, double mode_range_hz, double channel_
 pdt::SurveyPlan bursts_survey_plan(const pdt::BurstPlan &p, const pdt_bursts_cfg *cfg, uint64_t nframes);
 int bursts_link(const void *peaks, const int *counts, bool compact, const pdt::BurstPlan &p, double floor, double in_rate, pdt_burst *found, int cap);
 // pdt_ddc.hip
+long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
+hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
+                              long long tiles);
 hipError_t ddc_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
                       int decim, const float *taps_dev, const float *tab_dev, const uint32_t *steps, void *const *outs, int k);
 }  // namespace pdtrt
@@ -971,7 +974,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
-                       &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts };
+                       &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1222,7 +1225,7 @@ static bool overlap_ingest(const pdt_ctx *ctx, uint64_t nframes, size_t fb)
 // is the caller's decision (ingest_publish): a survey leaves the context's results as they are.
 static int ingest_whole(pdt_ctx *ctx, const IngestSrc &src, size_t bytes)
 {
-    ctx->bursts_done = ctx->bursts_done && ctx->bursts_src != ctx->pcm.p;     // (a burst search of host memory read this buffer: pdt_waterfall_rows)
+    ctx->pcm_retaken();                                                       // (a search of host memory read this buffer)
     int rc = ctx->pcm.ensure(bytes + 16);
     if (rc) return rc;
     const auto t_in = std::chrono::steady_clock::now();
@@ -1387,6 +1390,88 @@ int pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uin
     return rc ? rc : pdt_demod_channels_device(ctxs, count, c0->pcm.p, nframes, sample_format);
 }
 
+// ---------------------------------------------------------------- windows of a capture
+// Every window a capture of its own on its own context: one conversion launch for all of them (k_ddc_windows), then the batched chain
+// on the channel streams, as pdt_demod_channels_device.  `forbid`: a context that may not be among ctxs (the holder of the capture).
+static int demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_device, uint64_t nframes, int sample_format,
+                         const pdt_ctx *forbid)
+{
+    const InFmt f = in_fmt(sample_format);
+    if (count < 0 || (count && (!ctxs || !win)) || (!iq_device && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++) {
+        if (!ctxs[i] || ctxs[i] == forbid) return PDT_ERR_ARG;
+        if (ctxs[i]->stream_open || !ctxs[i]->ch_decim) return PDT_ERR_STATE;
+        if (ctxs[i]->ch_decim != ctxs[0]->ch_decim || ctxs[i]->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == ctxs[i]) return PDT_ERR_ARG;               // one context per window
+        const double in_rate = (double)ctxs[i]->ch_decim * (double)ctxs[i]->cfg.sample_rate;
+        if (!(std::isfinite(win[i].offset_hz) && std::fabs(win[i].offset_hz) < 0.5 * in_rate)) return PDT_ERR_ARG;
+        if (win[i].nframes && (win[i].first_frame > nframes || win[i].nframes > nframes - win[i].first_frame)) return PDT_ERR_ARG;
+    }
+    if (!count) return PDT_OK;
+    pdt_ctx *c0 = ctxs[0];
+    HIP_TRY(hipSetDevice(c0->cfg.device));
+    std::vector<DdcWindow> recs((size_t)count);
+    std::vector<void *> outs((size_t)count);
+    std::vector<uint64_t> lens((size_t)count);
+    for (int i = 0; i < count; i++) {
+        pdt_ctx *c = ctxs[i];
+        int rc = pdt_set_channel(c, c->ch_decim, win[i].offset_hz);
+        if (!rc) rc = i ? c->channel.ensure((size_t)channel_count(c, win[i].nframes) * 8 + 16) : channel_prepare(c0, win[i].nframes);
+        if (rc) return rc;
+        DdcWindow &r = recs[(size_t)i];
+        r.x = win[i].nframes ? (const unsigned char *)iq_device + (size_t)win[i].first_frame * (size_t)f.bytes : (const unsigned char *)iq_device;
+        r.out = outs[(size_t)i] = c->channel.p;
+        r.n = (long long)win[i].nframes;
+        r.step = c->ch_step;
+        lens[(size_t)i] = channel_count(c, win[i].nframes);
+    }
+    std::vector<unsigned char> table;
+    const long long tiles = ddc_windows_table(c0->ch_decim, recs.data(), count, table);
+    if (tiles < 0) return PDT_ERR_ARG;
+    if (tiles) {
+        // (the table of the previous call is no longer read: every call ends its conversion with a synchronize)
+        const int rc = c0->win_table.ensure(table.size() + 16);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(c0->win_table.p, table.data(), table.size(), hipMemcpyHostToDevice));
+        HIP_TRY(ddc_windows_launch(c0->stream, sample_format, c0->ch_decim, (const float *)c0->ddc_taps.p, (const float *)c0->an_tab.p,
+                                   c0->win_table.p, count, tiles));
+    }
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    for (int i = 0; i < count; i++) ctxs[i]->channel_len = lens[(size_t)i];
+    return demod_batch(ctxs, (const void *const *)outs.data(), lens.data(), count, PDT_FMT_F32);
+}
+
+int pdt_demod_windows_device(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_device, uint64_t nframes, int sample_format)
+{
+    return demod_windows(ctxs, count, win, iq_device, nframes, sample_format, nullptr);
+}
+
+int pdt_demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_host, uint64_t nframes, int sample_format)
+{
+    const InFmt f = in_fmt(sample_format);
+    if (count < 0 || (count && (!ctxs || !win)) || (!iq_host && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
+    if (!count) return PDT_OK;
+    pdt_ctx *c0 = ctxs[0];
+    if (!c0) return PDT_ERR_ARG;
+    if (c0->stream_open || !c0->ch_decim) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(c0->cfg.device));
+    if (!channel_fits(c0, nframes, f)) return PDT_ERR_NOMEM;
+    IngestSrc src;
+    src.mem = (const unsigned char *)iq_host;
+    const int rc = ingest_whole(c0, src, (size_t)nframes * (size_t)f.bytes);     // (timed, not published: pdt_demod_channels)
+    return rc ? rc : demod_windows(ctxs, count, win, c0->pcm.p, nframes, sample_format, nullptr);
+}
+
+int pdt_demod_windows_held(pdt_ctx *holder, pdt_ctx *const *ctxs, int count, const pdt_window *win)
+{
+    if (!holder) return PDT_ERR_ARG;
+    if (!holder->held_src) return PDT_ERR_STATE;
+    for (int i = 0; i < count && ctxs; i++)
+        if (ctxs[i] && ctxs[i]->cfg.device != holder->cfg.device) return PDT_ERR_ARG;    // (the capture lies in the holder's device's memory)
+    return demod_windows(ctxs, count, win, holder->held_src, holder->held_frames, holder->held_fmt, holder);
+}
+
 // ---------------------------------------------------------------- carrier survey (pdt_survey.h)
 // window and twiddles under one key: it is set when both are on the device
 static int survey_tables(pdt_ctx *ctx, int nfft)
@@ -1441,7 +1526,12 @@ static int survey_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nfra
         if ((rc = ingest_whole(ctx, src, (size_t)nframes * (size_t)f.bytes))) return rc;
         iq = ctx->pcm.p;
     }
-    return survey_resident(ctx, iq, f, p, found, count);
+    ctx->held_src = nullptr;
+    if ((rc = survey_resident(ctx, iq, f, p, found, count))) return rc;
+    ctx->held_src = iq;
+    ctx->held_frames = nframes;
+    ctx->held_fmt = f.code;
+    return PDT_OK;
 }
 
 int pdt_survey_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
@@ -1544,7 +1634,12 @@ static int bursts_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nfra
         if ((rc = ingest_whole(ctx, src, (size_t)nframes * (size_t)f.bytes))) return rc;
         iq = ctx->pcm.p;
     }
-    return bursts_resident(ctx, iq, f, p, bursts_survey_plan(p, cfg, nframes), found, cap, count);
+    ctx->held_src = nullptr;
+    if ((rc = bursts_resident(ctx, iq, f, p, bursts_survey_plan(p, cfg, nframes), found, cap, count))) return rc;
+    ctx->held_src = iq;
+    ctx->held_frames = nframes;
+    ctx->held_fmt = f.code;
+    return PDT_OK;
 }
 
 int pdt_bursts_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg, pdt_burst *found,

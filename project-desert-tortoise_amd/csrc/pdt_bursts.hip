@@ -261,3 +261,31 @@ extern "C" int pdt_burst_carriers(const pdt_burst *bursts, int count, double mer
     memcpy(carriers, c.data(), std::min<size_t>(c.size(), (size_t)cap) * sizeof(SurveyCarrier));
     return PDT_OK;
 }
+
+// llround of a time in frames, kept inside what a frame index holds
+static long long window_frame(double frames)
+{
+    return !(frames > 0.0) ? 0LL : frames >= 9.0e18 ? (long long)9.0e18 : llround(frames);
+}
+
+// window i of burst i: from skip_s behind the burst's start to tail_s behind its end, cut at the capture's end
+extern "C" int pdt_burst_windows(const pdt_burst *bursts, int count, uint32_t in_rate, uint64_t capture_frames, double skip_s, double tail_s,
+                                 pdt_window *out)
+{
+    if (count < 0 || (count && (!bursts || !out)) || in_rate == 0 || !std::isfinite(skip_s) || !std::isfinite(tail_s)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++)
+        if (!(std::isfinite(bursts[i].start_s) && std::isfinite(bursts[i].duration_s) && std::isfinite(bursts[i].offset_hz))) return PDT_ERR_ARG;
+    const double rate = (double)in_rate;
+    for (int i = 0; i < count; i++) {
+        const pdt_burst &b = bursts[i];
+        const double skip = skip_s < 0 ? (b.rows ? b.duration_s / (double)b.rows : 0.0) : skip_s;       // the default: one row of the burst
+        const double tail = tail_s < 0 ? 0.1 : tail_s;
+        const long long first = window_frame((b.start_s + skip) * rate);
+        const long long end = std::min<long long>((long long)std::min<uint64_t>(capture_frames, (uint64_t)INT64_MAX),
+                                                  window_frame((b.start_s + b.duration_s + tail) * rate));
+        out[i].first_frame = (uint64_t)first;
+        out[i].nframes = end > first ? (uint64_t)(end - first) : 0;
+        out[i].offset_hz = b.offset_hz;
+    }
+    return PDT_OK;
+}

@@ -1854,7 +1854,7 @@ template <typename T> int stage_pll(pdt_ctx *ctx, const void *iq_host, uint64_t 
     const bool was_locked = state->started && state->locked;
     const uint64_t lead = was_locked ? 1 : 0;                         // a dummy sample in front stands for "locked before sample 0"
     const uint64_t N = n + lead;
-    ctx->bursts_done = ctx->bursts_done && ctx->bursts_src != ctx->pcm.p;     // (a burst search of host memory read this buffer: pdt_waterfall_rows)
+    ctx->pcm_retaken();                                                       // (a search of host memory read this buffer)
     int rc = ctx->pcm.ensure((size_t)N * fb + 16);
     if (rc) return rc;
     HIP_TRY(hipMemset(ctx->pcm.p, 0, 8));
@@ -1993,7 +1993,7 @@ template <typename T> int stage_static_gain(pdt_ctx *ctx, const void *iq_host, u
 {
     const size_t fb = fmt == PDT_FMT_F32 ? 8 : 4;
     int rc;
-    ctx->bursts_done = ctx->bursts_done && ctx->bursts_src != ctx->pcm.p;     // (a burst search of host memory read this buffer: pdt_waterfall_rows)
+    ctx->pcm_retaken();                                                       // (a search of host memory read this buffer)
     if ((rc = ctx->pcm.ensure((size_t)n * fb + 16))) return rc;
     if ((rc = ctx->mag.ensure((size_t)(n + 1) * sizeof(T)))) return rc;
     if ((rc = ctx->scal.ensure(sizeof(DevScalars)))) return rc;

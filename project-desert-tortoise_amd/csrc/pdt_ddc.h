@@ -66,6 +66,17 @@ template <int FMT> __host__ __device__ __forceinline__ void ddc_load(const void 
     }
 }
 
+// One window of a capture for the windows kernel (k_ddc_windows): a capture of its own of n frames at x, its channel
+// stream of n_out = ceil(n / D) pairs at out, its phase counted from its first sample.  tile0: the launch's first tile of this
+// window.  The per-call table on the device: the windows' records, then one int per tile, the tile's window.
+struct DdcWindow {
+    const void *x;
+    void *out;
+    long long n, n_out;
+    uint32_t step;
+    int tile0;
+};
+
 // v = x e^{-j 2 pi p / 2^32}
 __host__ __device__ __forceinline__ void ddc_mix(float xr, float xi, uint32_t p, const float *__restrict__ tab, float &vr, float &vi)
 {

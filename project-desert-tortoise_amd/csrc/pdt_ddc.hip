@@ -178,11 +178,149 @@ __global__ void __launch_bounds__(DDC_TB) k_ddc(const void *__restrict__ x, long
     }
 }
 
+// Input samples first + j, j = j0 + t, j0 + t + tb, ... < j1, of window w, one by one: scaled, mixed with the phase counted from the
+// window's first sample, and put into the polyphase image at [j mod D][j / D].  EDGE: samples outside [0, n) are zeros.
+template <int FMT, bool EDGE>
+__device__ __forceinline__ void ddc_win_samples(const DdcWindow &w, long long first, int j0, int j1, int t, int tb, int D, int ROWP,
+                                                const float *__restrict__ tab, f2v *__restrict__ vs)
+{
+    int j = j0 + t;
+    int r = j % D, q = j / D;
+    const int dr = tb % D, dq = tb / D;
+    uint32_t p = (uint32_t)(unsigned long long)(first + j) * w.step;
+    const uint32_t dp = (uint32_t)tb * w.step;
+    for (; j < j1; j += tb) {
+        const long long i = first + j;
+        float vr = 0.0f, vi = 0.0f;
+        if (!EDGE || (i >= 0 && i < w.n)) {
+            float re, im;
+            ddc_load<FMT>(w.x, i, re, im);
+            ddc_mix(re, im, p, tab, vr, vi);
+        }
+        vs[r * ROWP + q] = (f2v){ vr, vi };
+        p += dp;
+        r += dr;
+        q += dq;
+        if (r >= D) { r -= D; q++; }
+    }
+}
+
+// The windows of one capture, a channel each (pdt_demod_windows_device): blockIdx.x walks the tiles of all windows, tile_win[tile] is
+// the tile's window, wins[] its record.  A window is a capture of its own: k_ddc's tile geometry on the window's own sample index,
+// zeros outside [0, n) whatever the capture holds there.  One channel, so there is no xs stage: a sample goes from the load through
+// ddc_mix straight into the polyphase image, then ddc_fir as it is.  16-byte loads where the window's own address allows them and the
+// tile lies inside the window, sample by sample in front of the first 16-byte boundary, behind the last whole load, and in the
+// tiles that touch the window's ends.
+template <int FMT>
+__global__ void __launch_bounds__(DDC_TB) k_ddc_windows(const DdcWindow *__restrict__ wins, const int *__restrict__ tile_win, int D, int TO, int ROWP,
+                                                        const float *__restrict__ taps, const float *__restrict__ tab)
+{
+    __shared__ __attribute__((aligned(16))) f2v vs[DDC_VS];
+    __shared__ float hs[DDC_HS];
+    const int t = threadIdx.x, tb = blockDim.x;
+    const DdcWindow w = wins[tile_win[blockIdx.x]];
+    const long long m0 = (long long)((int)blockIdx.x - w.tile0) * TO;
+    const long long first = (m0 - DDC_SPAN) * D;                   // the window's input sample at image place 0
+    const int len = (TO + 2 * DDC_SPAN) * D;                       // <= DDC_XS
+    constexpr int BPS = FMT == PDT_FMT_WB_PCM16 ? 4 : FMT == PDT_FMT_WB_F32 ? 8 : 2;
+    constexpr int SPV = DdcVec<FMT>::SPV;
+    for (int j = t; j <= 2 * DDC_SPAN * D; j += tb) hs[j] = taps[j];
+    if (first >= 0 && first + len <= w.n) {
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(w.x) + first * BPS;
+        int head = (int)(((16 - ((uintptr_t)src & 15)) & 15) / BPS);      // samples in front of the first 16-byte boundary
+        if (((uintptr_t)src & 15) % BPS) head = len;                       // (never aligned: sample by sample)
+        head = min(head, len);
+        const int nvec = (len - head) / SPV;
+        ddc_win_samples<FMT, false>(w, first, 0, head, t, tb, D, ROWP, tab, vs);
+        int j = head + t * SPV;
+        int r = j % D, q = j / D;
+        const int dr = (tb * SPV) % D, dq = (tb * SPV) / D;
+        for (int v = t; v < nvec; v += tb) {
+            float2 s[SPV];
+            ddc_unpack<FMT>(src + (size_t)head * BPS + (size_t)v * 16, s);
+            uint32_t p = (uint32_t)(unsigned long long)(first + j) * w.step;
+            int re = r, qe = q;
+#pragma unroll
+            for (int e = 0; e < SPV; e++) {
+                float vr, vi;
+                ddc_mix(s[e].x, s[e].y, p, tab, vr, vi);
+                vs[re * ROWP + qe] = (f2v){ vr, vi };
+                p += w.step;
+                if (++re == D) { re = 0; qe++; }
+            }
+            j += tb * SPV;
+            r += dr;
+            q += dq;
+            if (r >= D) { r -= D; q++; }
+        }
+        ddc_win_samples<FMT, false>(w, first, head + nvec * SPV, len, t, tb, D, ROWP, tab, vs);
+    } else {
+        ddc_win_samples<FMT, true>(w, first, 0, len, t, tb, D, ROWP, tab, vs);
+    }
+    __syncthreads();
+    const long long left = w.n_out - m0;
+    float2 *out = reinterpret_cast<float2 *>(w.out) + m0;
+    if (t < TO) {
+        switch ((TO + tb - 1) / tb) {
+        case 1: ddc_fir<1>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
+        case 2: ddc_fir<2>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
+        case 3: ddc_fir<3>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
+        default: ddc_fir<4>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
+        }
+    }
+}
+
 }  // namespace pdt
 
 using namespace pdt;
 
 namespace pdtrt {
+
+// The per-call table of the windows kernel, as the host builds it: win[i].x, .out, .n and .step are the caller's, .n_out and .tile0
+// are filled in here; `table` receives the records and behind them the tiles' windows.  Returns the number of tiles, -1 when they
+// are more than a launch takes: a grid's lanes must number less than 2^32, workgroups of up to DDC_TB lanes.
+long long ddc_windows_table(int decim, DdcWindow *win, int count, std::vector<unsigned char> &table)
+{
+    const long long TO = DDC_TILE / decim, most = 0xffffffffLL / DDC_TB;
+    long long tiles = 0;
+    for (int i = 0; i < count; i++) {
+        win[i].n_out = (win[i].n + decim - 1) / decim;
+        if (tiles > most) return -1;
+        win[i].tile0 = (int)tiles;
+        tiles += (win[i].n_out + TO - 1) / TO;
+    }
+    if (tiles > most) return -1;
+    table.resize((size_t)count * sizeof(DdcWindow) + (size_t)tiles * sizeof(int));
+    if (count) memcpy(table.data(), win, (size_t)count * sizeof(DdcWindow));
+    int *tile_win = reinterpret_cast<int *>(table.data() + (size_t)count * sizeof(DdcWindow));
+    for (int i = 0; i < count; i++) {
+        const long long nt = (win[i].n_out + TO - 1) / TO;
+        for (long long k = 0; k < nt; k++) tile_win[win[i].tile0 + k] = i;
+    }
+    return tiles;
+}
+
+// the windows kernel over a table that is on the device: `count` records, `tiles` tiles, one launch
+hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
+                              long long tiles)
+{
+    if (tiles <= 0 || count <= 0) return hipSuccess;
+    if (decim < DDC_MIN_DECIM || decim > DDC_MAX_DECIM || !ddc_fmt(fmt)) return hipErrorInvalidValue;
+    const int TO = DDC_TILE / decim, ROWP = (TO + 2 * DDC_SPAN) | 1;
+    const int tb = std::min(DDC_TB, (TO + 63) / 64 * 64);
+    const DdcWindow *wins = reinterpret_cast<const DdcWindow *>(table_dev);
+    const int *tile_win = reinterpret_cast<const int *>(wins + count);
+    const dim3 grid((unsigned)tiles);
+#define PDT_DDC_GO(F) hipLaunchKernelGGL(k_ddc_windows<F>, grid, dim3(tb), 0, st, wins, tile_win, decim, TO, ROWP, taps_dev, tab_dev)
+    switch (fmt) {
+    case PDT_FMT_WB_PCM16: PDT_DDC_GO(PDT_FMT_WB_PCM16); break;
+    case PDT_FMT_WB_F32: PDT_DDC_GO(PDT_FMT_WB_F32); break;
+    case PDT_FMT_WB_CU8: PDT_DDC_GO(PDT_FMT_WB_CU8); break;
+    default: PDT_DDC_GO(PDT_FMT_WB_CS8); break;
+    }
+#undef PDT_DDC_GO
+    return hipGetLastError();
+}
 
 // the kernel over outputs [0, n_out) of k channels (host side of pdt_api.hip's channel paths)
 hipError_t ddc_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,

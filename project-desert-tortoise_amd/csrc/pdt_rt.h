@@ -453,6 +453,19 @@ struct pdt_ctx {
     int bursts_fmt = 0;
     std::vector<pdt_row_peak> bursts_pk;
     std::vector<int> bursts_cnt;
+    // windows of a capture (pdt_demod_windows_*): the conversion launch's table on the device (first context of a call); the capture
+    // this context's last survey or burst search read, for pdt_demod_windows_held -- where it is, its frames and format
+    DevBuf win_table;
+    const void *held_src = nullptr;
+    uint64_t held_frames = 0;
+    int held_fmt = 0;
+    // The input buffer is about to take other samples (or to be reallocated): what a search of host memory left there is gone --
+    // pdt_waterfall_rows and pdt_demod_windows_held answer PDT_ERR_STATE from now on.  Every writer of pcm calls this first.
+    void pcm_retaken()
+    {
+        bursts_done = bursts_done && bursts_src != pcm.p;
+        if (held_src == pcm.p) held_src = nullptr;
+    }
     unsigned char *seg_pin = nullptr;   // pinned staging for the small per-segment transfers (part of the pend_sc block)
     pdt_stats stats;
     std::vector<pdt_kernel_time> ktimes;

@@ -50,6 +50,13 @@
  * strongest platforms among them are printed like the -t lines and the run goes on as if their offsets had been given.  No burst:
  * one line, no output file, exit status 1.  -B <seconds> is the longest transmission that counts as a burst (pdt_bursts_cfg.max_s),
  * 5 by default: what lasts longer -- a receiver's DC spike, a birdie, a continuous beacon -- is no platform; -B 0 sets no limit.
+ * -t each (an addition, under -t bursts' rules, -B included): the same burst search and the same line per burst, but then every burst is
+ * demodulated in a window of its own at its own offset (pdt_burst_windows at its defaults, pdt_demod_windows_held in rounds through a
+ * pool of at most 64 contexts) -- what a platform whose Doppler moves over the pass, and a recording that opens with
+ * noise, need.  ONE output file under the usual name: every window's records in window order, each time increased by the window's
+ * start in the capture; one line per burst with its lock and its packets, then one summary line.  Bursts found but no packet in
+ * any of them: the lines are printed, the file is removed as after any run without packets, exit status 0.  -t each:N (1 .. 64)
+ * makes the pool N contexts: more rounds, less memory, the same file.
  */
 #include <ctype.h>
 #include <math.h>
@@ -379,10 +386,12 @@ static int auto_channels(FILE *in, long data_offset, uint64_t nframes, size_t fr
     return 0;
 }
 
-/* -t bursts: search the capture for short transmissions (pdt_bursts) and take the platforms among them (pdt_burst_carriers), at
- * most `want`, strongest first.  Offsets come back as printed, like auto_channels'.  Returns 0 when there is at least one. */
-static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, int want,
-                          double max_s, double *offsetsHz, int *nch)
+/* The burst search of -t bursts and -t each: one context, the capture read from the file, pdt_bursts (a second call when there are
+ * more bursts than the first had room for: all of them count), one line per burst.  Returns 0 when there is at least one burst, in
+ * *found_out (the caller's to free), *count_out of them; otherwise the message has been printed.  `keep` not NULL: the context is
+ * left open in *keep -- the search left the capture in its input buffer (pdt_demod_windows_held); otherwise it is closed. */
+static int burst_search(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, double max_s,
+                        pdt_burst **found_out, int *count_out, pdt_ctx **keep)
 {
     enum { ROOM = 4096 };                                /* bursts asked for at first; when there are more, all of them in a second call */
     pdt_ctx *ctx = NULL;
@@ -400,8 +409,7 @@ static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t f
     pdt_bursts_cfg bc;
     memset(&bc, 0, sizeof bc);
     bc.max_s = max_s;
-    int count = 0, nplat = 0;
-    pdt_carrier plat[16];
+    int count = 0;
     rc = pdt_set_channel(ctx, decim, 0.0);
     if (rc == PDT_OK) rc = pdt_bursts(ctx, buf, nframes, fmt, &bc, found, ROOM, &count);
     if (rc == PDT_OK && count > ROOM) {                  /* platforms are taken from the whole recording, not from its beginning */
@@ -412,7 +420,10 @@ static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t f
         if (count > room) count = room;
     }
     free(buf);
-    pdt_close(ctx);
+    if (rc != PDT_OK || count == 0 || !keep) {
+        pdt_close(ctx);
+        ctx = NULL;
+    }
     if (rc != PDT_OK) {
         printf("Burst search failed: %s\n", pdt_strerror(rc));
         free(found);
@@ -426,6 +437,21 @@ static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t f
     for (int i = 0; i < count; i++)
         printf("Burst at %.3f s, %.3f s long, %+f Khz, %.1f dB over the floor\n", found[i].start_s, found[i].duration_s, found[i].offset_hz / 1000.0,
                found[i].peak_db);
+    if (keep) *keep = ctx;
+    *found_out = found;
+    *count_out = count;
+    return 0;
+}
+
+/* -t bursts: search the capture for short transmissions (burst_search) and take the platforms among them (pdt_burst_carriers), at
+ * most `want`, strongest first.  Offsets come back as printed, like auto_channels'.  Returns 0 when there is at least one. */
+static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, int want,
+                          double max_s, double *offsetsHz, int *nch)
+{
+    pdt_burst *found = NULL;
+    int count = 0, nplat = 0, rc;
+    pdt_carrier plat[16];
+    if (burst_search(in, data_offset, nframes, frame_bytes, fmt, cfg, decim, max_s, &found, &count, NULL)) return 1;
     rc = pdt_burst_carriers(found, count, MODE == PDT_MODE_ARGOS ? 550.0 : 4500.0, plat, 16, &nplat);
     free(found);
     if (rc != PDT_OK) {
@@ -440,6 +466,80 @@ static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t f
         printf("Channel %d at %s Khz (found, %.1f dB over the floor)\n", i, khz, plat[i].peak_db);
     }
     *nch = nplat;
+    return 0;
+}
+
+/* -t each: search the capture for short transmissions (burst_search), cut a window per burst (pdt_burst_windows) and demodulate the
+ * windows in rounds on a pool of contexts, from the copy of the capture the search left on the device (pdt_demod_windows_held).
+ * Every window's records, their times counted from the capture's start, go to one file. */
+static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, double max_s,
+                      int poolSize, const char *outFileName)
+{
+    enum { POOL = 64 };
+    pdt_ctx *holder = NULL, *pool[POOL];
+    memset(pool, 0, sizeof pool);
+    pdt_burst *found = NULL;
+    int count = 0, rc;
+    if (burst_search(in, data_offset, nframes, frame_bytes, fmt, cfg, decim, max_s, &found, &count, &holder)) return 1;
+    const uint32_t in_rate = cfg->sample_rate * (uint32_t)decim;
+    pdt_window *win = (pdt_window *)malloc((size_t)count * sizeof *win);
+    rc = win ? pdt_burst_windows(found, count, in_rate, nframes, -1.0, -1.0, win) : PDT_ERR_NOMEM;
+    free(found);
+    const int npool = count < poolSize ? count : poolSize;
+    for (int i = 0; i < npool && rc == PDT_OK; i++) {
+        rc = pdt_open(cfg, &pool[i]);
+        if (rc == PDT_OK) rc = pdt_set_channel(pool[i], decim, 0.0);
+        if (rc == PDT_OK) pdt_keep_pll(pool[i], 0);
+    }
+    pdt_frame *all = NULL;
+    uint64_t total = 0, room = 0;
+    int locked = 0;
+    for (int r0 = 0; r0 < count && rc == PDT_OK; r0 += npool) {
+        const int k = count - r0 < npool ? count - r0 : npool;
+        rc = pdt_demod_windows_held(holder, pool, k, win + r0);
+        for (int i = 0; i < k && rc == PDT_OK; i++) {
+            const uint64_t n = pdt_num_frames(pool[i]);
+            if (total + n > room) {
+                room = 2 * (total + n) + 64;
+                pdt_frame *grown = (pdt_frame *)realloc(all, (size_t)room * sizeof *all);
+                if (!grown) {
+                    rc = PDT_ERR_NOMEM;
+                    break;
+                }
+                all = grown;
+            }
+            pdt_frames(pool[i], all + total, n);
+            const double shift = (double)win[r0 + i].first_frame / (double)in_rate;
+            for (uint64_t f = 0; f < n; f++) all[total + f].time += shift;
+            total += n;
+            pdt_stats st;
+            pdt_get_stats(pool[i], &st);
+            char lock[64] = "none";
+            if (st.lock_sample >= 0) {
+                snprintf(lock, sizeof lock, "%+.2f Hz", st.lock_freq_hz);
+                locked++;
+            }
+            printf("Burst %d: lock %s, %d packets\n", r0 + i, lock, (int)n);
+        }
+    }
+    for (int i = 0; i < npool; i++)
+        if (pool[i]) pdt_close(pool[i]);
+    pdt_close(holder);
+    free(win);
+    if (rc != PDT_OK) {
+        printf("Demodulation failed: %s\n", pdt_strerror(rc));
+        free(all);
+        return 1;
+    }
+    printf("Bursts: %d, locked: %d, packets: %d\n", count, locked, (int)total);
+    FILE *o = fopen(outFileName, "w+");
+    if (!o || pdt_write_records(all, total, fileno(o), NULL) != PDT_OK) {
+        printf("Error writing output file\n");
+        return 1;
+    }
+    fclose(o);
+    free(all);
+    if (total == 0) remove(outFileName);                 /* as everywhere: no packet, no file (main.c:508-512) */
     return 0;
 }
 
@@ -461,6 +561,7 @@ int main(int argc, char **argv)
     int decim = 0, nOffsets = 0, wbFormat = PDT_FMT_WB_CU8, autoCarriers = 0;      /* -t auto[:N]: look for up to N carriers */
     double burstMaxS = 5.0;                                                         /* -B: pdt_bursts_cfg.max_s of -t bursts */
     int autoBursts = 0;                                                             /* -t bursts[:N]: autoCarriers platforms, from the burst search */
+    int eachBurst = 0;                                                              /* -t each[:N]: every burst in a window of its own, N contexts */
     double offsetsHz[16];
     const char *outOverride = NULL;
     char outFileName[1100];
@@ -543,6 +644,17 @@ int main(int argc, char **argv)
                 printf("Channels: the %d strongest platforms found by their bursts\n", autoCarriers);
                 break;
             }
+            if (strncmp(optarg, "each", 4) == 0) {
+                eachBurst = optarg[4] == ':' ? atoi(optarg + 5) : optarg[4] == 0 ? 64 : 0;
+                if (eachBurst < 1 || eachBurst > 64) {
+                    printf("-t each or -t each:N with N from 1 to 64\n");
+                    return 1;
+                }
+                autoCarriers = 16;
+                autoBursts = 1;
+                printf("Channels: every burst found, in a window of its own\n");
+                break;
+            }
             if (nOffsets >= 16) {
                 printf("At most 16 channels\n");
                 return 1;
@@ -584,7 +696,7 @@ int main(int argc, char **argv)
         }
     }
     if (autoCarriers && nOffsets) {
-        printf("-t %s cannot be combined with -t <kHz>\n", autoBursts ? "bursts" : "auto");
+        printf("-t %s cannot be combined with -t <kHz>\n", eachBurst ? "each" : autoBursts ? "bursts" : "auto");
         return 1;
     }
     if ((nOffsets || autoCarriers) && !decim) {
@@ -607,7 +719,7 @@ int main(int argc, char **argv)
     printf("Opening IO files..\n");
     const int from_stdin = live && strcmp(inFileName, "-") == 0;
     if (from_stdin && autoCarriers) {
-        printf("-t %s needs a capture file: the spectrum of a stream is not known in advance\n", autoBursts ? "bursts" : "auto");
+        printf("-t %s needs a capture file: the spectrum of a stream is not known in advance\n", eachBurst ? "each" : autoBursts ? "bursts" : "auto");
         return 1;
     }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
@@ -739,6 +851,7 @@ int main(int argc, char **argv)
     cfg.device = device;
     cfg.sampler = sampler;
     cfg.chain = live ? PDT_CHAIN_LIVE : PDT_CHAIN_FILE;
+    if (eachBurst) return each_burst(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, burstMaxS, eachBurst, outFileName);
     if (autoCarriers) {
         if (autoBursts ? burst_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, burstMaxS, offsetsHz, &nOffsets)
                        : auto_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, offsetsHz, &nOffsets))

@@ -420,8 +420,8 @@ int  pdt_host_analytic(uint32_t sample_rate, double center_hz, const void *x, ui
  *                              to the format's element (2 bytes for int16, 4 for float32, 1 for the 8-bit formats), not to
  *                              the I,Q pair or to 16 bytes: any such address is served, the aligned ones with wider loads;
  *                              so too for pdt_demod_channels_device and pdt_survey_device
- *   pdt_demod_channels_device  ONE wideband capture in device memory, `count` contexts with a channel each: the capture is read
- *                              once by one conversion launch that fills every context's channel stream, then the contexts go
+ *   pdt_demod_channels_device  ONE wideband capture in device memory, `count` contexts with a channel each: one conversion
+ *                              launch per context fills that context's channel stream, then the contexts go
  *                              through the batched chain (pdt_demod_batch_device's, on float input).  All contexts must have the
  *                              same decim and live on the same device (else PDT_ERR_ARG); their modes may differ.  Each context
  *                              ends up holding exactly what pdt_demod_device_channel alone would have produced
@@ -553,7 +553,7 @@ int  pdt_host_bursts(uint32_t in_rate, double mode_range_hz, uint32_t channel_ra
  * up on it.  Here each burst is cut out of the capture at its own measured offset: a window [first_frame, first_frame +
  * nframes) of the capture is a capture of its own -- samples outside it count as zero although the capture has neighbours, the
  * mixer's phase is counted from the window's first sample, time stamps are seconds of the window's channel stream -- and all windows
- * of a call are converted by ONE launch (k_ddc_windows), then the contexts go through the batched chain.
+ * of a call are converted by ONE launch (k_ddc over a table of their tiles), then the contexts go through the batched chain.
  *   pdt_burst_windows          host only: window i from burst i.  first_frame = llround((start_s + skip) Fs_in), the end is
  *                              min(capture_frames, llround((start_s + duration_s + tail) Fs_in)), offset_hz the burst's; a window whose
  *                              start reaches its end has nframes 0.  skip_s < 0: the default, one row of that burst (duration_s /

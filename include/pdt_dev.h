@@ -8,6 +8,7 @@
  * include/pdt.h never call it.  The names are listed in tools/README.md. */
 #ifndef PDT_DEV_H
 #define PDT_DEV_H
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -18,6 +19,13 @@ int pdt_dev_set(const char *name, const char *value);
  * left untabulated).  0 when the last run had no such rows.  What tools/span_hist.py turns into profiles/r6/gardner_row_exits_*.  */
 struct pdt_ctx;
 unsigned long long pdt_dev_span_rows(const struct pdt_ctx *ctx, unsigned *n_exits_out, unsigned long long max);
+/* The down-converter's kernel on ONE record, as a piece of a stream hands it over (csrc/pdt_ddc.h): x_dev is the address of input
+ * sample 0 in device memory, the samples lo <= i < hi are present and zeros lie elsewhere, g0 is the global index of input 0
+ * (the phase of input i is (g0 + i) step), and outputs 0 <= m < n_out, each centred on input m decim, go to out_dev as float32
+ * pairs.  The entry uploads the taps and the rotation table, launches once, waits and frees what it allocated; it has no
+ * context.  A stream's converted pairs cannot be read back otherwise: this is how the tests compare a piece with pdt_host_ddc. */
+int pdt_dev_ddc(int device, uint32_t in_rate, int decim, double offset_hz, int sample_format, const void *x_dev, long long lo, long long hi,
+                uint64_t n_out, uint64_t g0, void *out_dev);
 #ifdef __cplusplus
 }
 #endif

@@ -271,7 +271,7 @@ ABI_SYMBOLS = [
     "pdt_device_math", "pdt_device_math_layout",
     "pdt_burst_windows", "pdt_demod_windows_device", "pdt_demod_windows", "pdt_demod_windows_held",
 ]
-DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows"]        # include/pdt_dev.h (test-only)
+DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_ddc"]        # include/pdt_dev.h (test-only)
 
 _lib = None
 
@@ -400,6 +400,7 @@ def lib():
     L.pdt_demod_channels.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_uint64, C.c_int]
     L.pdt_stream_push_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_host_ddc.argtypes = [C.c_uint32, C.c_int, C.c_double, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+    L.pdt_dev_ddc.argtypes = [C.c_int, C.c_uint32, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_uint64, C.c_uint64, C.c_void_p]
     L.pdt_survey.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(SurveyCfg), C.POINTER(CarrierRec), C.c_int, C.POINTER(C.c_int)]
     L.pdt_survey_device.argtypes = L.pdt_survey.argtypes
     L.pdt_survey_spectrum.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -500,6 +501,14 @@ def host_ddc(in_rate: int, decim: int, offset_hz: float, x: np.ndarray) -> np.nd
     out = np.zeros(((n + decim - 1) // decim if decim > 0 else 0, 2), dtype=np.float32)
     _check(lib().pdt_host_ddc(in_rate, decim, float(offset_hz), a.ctypes.data, n, fmt, out.ctypes.data), "pdt_host_ddc")
     return out
+
+
+def dev_ddc(in_rate: int, decim: int, offset_hz: float, fmt: int, x_ptr: int, lo: int, hi: int, n_out: int, g0: int, out_ptr: int, device: int = 0):
+    """pdt_dev_ddc (test-only, include/pdt_dev.h): the down-converter's kernel on one record as a stream piece hands it over -- input
+    sample 0 at the device address x_ptr, samples lo <= i < hi present, g0 the global index of input 0, n_out float32 pairs to the
+    device address out_ptr.  Returns when they are there."""
+    _check(lib().pdt_dev_ddc(device, in_rate, decim, float(offset_hz), fmt, C.c_void_p(int(x_ptr)), lo, hi, n_out, g0, C.c_void_p(int(out_ptr))),
+           "pdt_dev_ddc")
 
 
 def host_survey(in_rate: int, mode_range_hz: float, channel_rate: int, x: np.ndarray, **cfg):
@@ -1029,7 +1038,7 @@ def demod_batch(demods, dev_ptrs, nframes):
 
 def demod_channels(demods, dev_ptr, nframes: int = 0, fmt: int = FMT_WB_PCM16):
     """Several channels of ONE wideband capture: demods[i] (each with its set_channel, all of one decim) demodulates its channel;
-    the capture is read once by one conversion launch, then the contexts share the batched chain.  dev_ptr: the address of the
+    the capture is ingested once and converted by one launch per context, then the contexts share the batched chain.  dev_ptr: the address of the
     capture in HBM (nframes I,Q frames of fmt), or a numpy array of I,Q pairs in host memory (pdt_demod_channels)."""
     n = len(demods)
     hs = (C.c_void_p * max(n, 1))(*[d._h for d in demods])

@@ -34,8 +34,7 @@ int bursts_link(const void *peaks, const int *counts, bool compact, const pdt::B
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
                               long long tiles);
-hipError_t ddc_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
-                      int decim, const float *taps_dev, const float *tab_dev, const uint32_t *steps, void *const *outs, int k);
+hipError_t ddc_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, pdt::DdcWindow w);
 }  // namespace pdtrt
 
 static std::atomic<int> g_open_contexts{0};          // contexts alive in this process (pdt_open / pdt_close)
@@ -761,6 +760,33 @@ unsigned long long pdt_dev_span_rows(const pdt_ctx *ctx, unsigned *n_exits_out, 
     return n;
 }
 
+// test-only (include/pdt_dev.h): the down-converter on exactly this record, one launch by value; no context
+int pdt_dev_ddc(int device, uint32_t in_rate, int decim, double offset_hz, int sample_format, const void *x_dev, long long lo, long long hi,
+                uint64_t n_out, uint64_t g0, void *out_dev)
+{
+    if (in_rate == 0 || decim < DDC_MIN_DECIM || decim > DDC_MAX_DECIM || !ddc_fmt(sample_format) || !x_dev || !out_dev) return PDT_ERR_ARG;
+    if (!(std::isfinite(offset_hz) && std::fabs(offset_hz) < 0.5 * (double)in_rate)) return PDT_ERR_ARG;
+    HIP_TRY(hipSetDevice(device));
+    const std::vector<float> taps = ddc_taps(decim);
+    std::vector<float> tab(2 * AN_TAB);
+    analytic_table(tab.data());
+    DevBuf dtaps, dtab;
+    auto run = [&]() -> int {
+        int rc;
+        if ((rc = dtaps.ensure(taps.size() * sizeof(float) + 16)) || (rc = dtab.ensure(tab.size() * sizeof(float) + 16))) return rc;
+        HIP_TRY(hipMemcpy(dtaps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dtab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        const DdcWindow r = { x_dev, out_dev, lo, hi, (long long)n_out, ddc_step((double)in_rate, offset_hz), (uint32_t)g0, 0 };
+        HIP_TRY(ddc_launch(nullptr, sample_format, decim, (const float *)dtaps.p, (const float *)dtab.p, r));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return PDT_OK;
+    };
+    const int rc = run();
+    dtaps.release();
+    dtab.release();
+    return rc;
+}
+
 const char *pdt_strerror(int code)
 {
     switch (code) {
@@ -1138,6 +1164,12 @@ static int channel_prepare(pdt_ctx *ctx, uint64_t n)
     return rc ? rc : channel_tables(ctx);
 }
 
+// the down-converter's record (pdt_ddc.h) of a conversion at ctx's offset: input 0 at x, [lo, hi) present, n_out pairs to out
+static DdcWindow channel_record(const pdt_ctx *ctx, const void *x, long long lo, long long hi, uint64_t n_out, uint64_t g0, void *out)
+{
+    return DdcWindow{ x, out, lo, hi, (long long)n_out, ctx->ch_step, (uint32_t)g0, 0 };
+}
+
 // A whole capture resident at x, n frames of f: convert it if its kind has a converter, then the chain (real and wideband
 // input: the RAW float path on the converter's pairs).
 static int demod_resident(pdt_ctx *ctx, const void *x, uint64_t n, const InFmt &f)
@@ -1157,9 +1189,8 @@ static int demod_resident(pdt_ctx *ctx, const void *x, uint64_t n, const InFmt &
     case IN_WB: {
         if ((rc = channel_prepare(ctx, n))) return rc;
         const uint64_t m = channel_count(ctx, n);
-        void *out = ctx->channel.p;
-        HIP_TRY(ddc_launch(ctx->stream, f.code, x, 0, (long long)n, m, 0, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
-                           &ctx->ch_step, &out, 1));
+        HIP_TRY(ddc_launch(ctx->stream, f.code, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
+                           channel_record(ctx, x, 0, (long long)n, m, 0, ctx->channel.p)));
         ctx->pcm_dev = ctx->channel.p;
         ctx->channel_len = m;
         return demod_common(ctx, m);
@@ -1341,72 +1372,31 @@ int pdt_set_channel(pdt_ctx *ctx, int decim, double offset_hz)
     return PDT_OK;
 }
 
-int pdt_demod_channels_device(pdt_ctx *const *ctxs, int count, const void *iq_device, uint64_t nframes, int sample_format)
-{
-    if (count < 0 || (count && !ctxs) || (!iq_device && nframes) || in_fmt(sample_format).kind != IN_WB) return PDT_ERR_ARG;
-    for (int i = 0; i < count; i++) {
-        if (!ctxs[i]) return PDT_ERR_ARG;
-        if (ctxs[i]->stream_open || !ctxs[i]->ch_decim) return PDT_ERR_STATE;
-        if (ctxs[i]->ch_decim != ctxs[0]->ch_decim || ctxs[i]->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == ctxs[i]) return PDT_ERR_ARG;               // one context per channel
-    }
-    if (!count) return PDT_OK;
-    pdt_ctx *c0 = ctxs[0];
-    HIP_TRY(hipSetDevice(c0->cfg.device));
-    const uint64_t m = channel_count(c0, nframes);
-    std::vector<uint32_t> steps((size_t)count);
-    std::vector<void *> outs((size_t)count);
-    std::vector<uint64_t> lens((size_t)count, m);
-    for (int i = 0; i < count; i++) {
-        int rc = i ? ctxs[i]->channel.ensure((size_t)m * 8 + 16) : channel_prepare(c0, nframes);
-        if (rc) return rc;
-        steps[(size_t)i] = ctxs[i]->ch_step;
-        outs[(size_t)i] = ctxs[i]->channel.p;
-    }
-    // one read of the wideband capture for every channel, then the batched chain on the float pairs (the groups of the batch run
-    // on their leaders' streams: they start when the conversion is over)
-    HIP_TRY(ddc_launch(c0->stream, sample_format, iq_device, 0, (long long)nframes, m, 0, c0->ch_decim, (const float *)c0->ddc_taps.p,
-                       (const float *)c0->an_tab.p, steps.data(), outs.data(), count));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
-    for (int i = 0; i < count; i++) ctxs[i]->channel_len = m;
-    return demod_batch(ctxs, (const void *const *)outs.data(), lens.data(), count, PDT_FMT_F32);
-}
-
-int pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uint64_t nframes, int sample_format)
+// ---------------------------------------------------------------- several contexts on one capture: channels and windows
+// Every context converts a window of the resident capture at an offset of its own, then the batched chain runs on the channel streams
+// (the groups of the batch run on their leaders' streams: they start when the conversion is over).  windows: win[i] is context
+// i's, which is tuned to its offset; otherwise (the channels entries) every context takes the whole capture at the offset it has.
+// The windows of a call, many and short, are converted by one launch over a table of their tiles; whole captures by a launch
+// each, record by value, on the first context's stream -- a capture has tiles enough to fill the device, and the table's 4 bytes
+// a tile would be built and copied per call.  `forbid`: a context that may not be among ctxs (the holder of the capture).
+static int demod_each(pdt_ctx *const *ctxs, int count, const pdt_window *win, bool windows, const void *iq_device, uint64_t nframes,
+                      int sample_format, const pdt_ctx *forbid)
 {
     const InFmt f = in_fmt(sample_format);
-    if (count < 0 || (count && !ctxs) || (!iq_host && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
-    if (!count) return PDT_OK;
-    pdt_ctx *c0 = ctxs[0];
-    if (!c0) return PDT_ERR_ARG;
-    if (c0->stream_open || !c0->ch_decim) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(c0->cfg.device));
-    if (!channel_fits(c0, nframes, f)) return PDT_ERR_NOMEM;
-    IngestSrc src;
-    src.mem = (const unsigned char *)iq_host;
-    // (the first context's ingest is timed but not published: the contexts of a batch report no ingest, as they never have -- DESIGN 4.11)
-    const int rc = ingest_whole(c0, src, (size_t)nframes * (size_t)f.bytes);
-    return rc ? rc : pdt_demod_channels_device(ctxs, count, c0->pcm.p, nframes, sample_format);
-}
-
-// ---------------------------------------------------------------- windows of a capture
-// Every window a capture of its own on its own context: one conversion launch for all of them (k_ddc_windows), then the batched chain
-// on the channel streams, as pdt_demod_channels_device.  `forbid`: a context that may not be among ctxs (the holder of the capture).
-static int demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_device, uint64_t nframes, int sample_format,
-                         const pdt_ctx *forbid)
-{
-    const InFmt f = in_fmt(sample_format);
-    if (count < 0 || (count && (!ctxs || !win)) || (!iq_device && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
+    if (count < 0 || (count && (!ctxs || (windows && !win))) || (!iq_device && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
+    auto window_of = [&](int i) { return windows ? win[i] : pdt_window{ 0, nframes, ctxs[i]->ch_offset }; };
     for (int i = 0; i < count; i++) {
         if (!ctxs[i] || ctxs[i] == forbid) return PDT_ERR_ARG;
         if (ctxs[i]->stream_open || !ctxs[i]->ch_decim) return PDT_ERR_STATE;
         if (ctxs[i]->ch_decim != ctxs[0]->ch_decim || ctxs[i]->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
         for (int j = 0; j < i; j++)
-            if (ctxs[j] == ctxs[i]) return PDT_ERR_ARG;               // one context per window
+            if (ctxs[j] == ctxs[i]) return PDT_ERR_ARG;               // one context per channel, per window
+        // (channels: deliberately redundant -- a context's own offset has passed pdt_set_channel's test, the same one, the whole
+        // capture is in range, and pdt_set_channel below sets what is set already: one loop for both entries)
+        const pdt_window w = window_of(i);
         const double in_rate = (double)ctxs[i]->ch_decim * (double)ctxs[i]->cfg.sample_rate;
-        if (!(std::isfinite(win[i].offset_hz) && std::fabs(win[i].offset_hz) < 0.5 * in_rate)) return PDT_ERR_ARG;
-        if (win[i].nframes && (win[i].first_frame > nframes || win[i].nframes > nframes - win[i].first_frame)) return PDT_ERR_ARG;
+        if (!(std::isfinite(w.offset_hz) && std::fabs(w.offset_hz) < 0.5 * in_rate)) return PDT_ERR_ARG;
+        if (w.nframes && (w.first_frame > nframes || w.nframes > nframes - w.first_frame)) return PDT_ERR_ARG;
     }
     if (!count) return PDT_OK;
     pdt_ctx *c0 = ctxs[0];
@@ -1416,41 +1406,41 @@ static int demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win,
     std::vector<uint64_t> lens((size_t)count);
     for (int i = 0; i < count; i++) {
         pdt_ctx *c = ctxs[i];
-        int rc = pdt_set_channel(c, c->ch_decim, win[i].offset_hz);
-        if (!rc) rc = i ? c->channel.ensure((size_t)channel_count(c, win[i].nframes) * 8 + 16) : channel_prepare(c0, win[i].nframes);
+        const pdt_window w = window_of(i);
+        int rc = pdt_set_channel(c, c->ch_decim, w.offset_hz);
+        if (!rc) rc = i ? c->channel.ensure((size_t)channel_count(c, w.nframes) * 8 + 16) : channel_prepare(c0, w.nframes);
         if (rc) return rc;
-        DdcWindow &r = recs[(size_t)i];
-        r.x = win[i].nframes ? (const unsigned char *)iq_device + (size_t)win[i].first_frame * (size_t)f.bytes : (const unsigned char *)iq_device;
-        r.out = outs[(size_t)i] = c->channel.p;
-        r.n = (long long)win[i].nframes;
-        r.step = c->ch_step;
-        lens[(size_t)i] = channel_count(c, win[i].nframes);
+        lens[(size_t)i] = channel_count(c, w.nframes);
+        const void *x = w.nframes ? (const unsigned char *)iq_device + (size_t)w.first_frame * (size_t)f.bytes : (const unsigned char *)iq_device;
+        recs[(size_t)i] = channel_record(c, x, 0, (long long)w.nframes, lens[(size_t)i], 0, outs[(size_t)i] = c->channel.p);
     }
-    std::vector<unsigned char> table;
-    const long long tiles = ddc_windows_table(c0->ch_decim, recs.data(), count, table);
-    if (tiles < 0) return PDT_ERR_ARG;
-    if (tiles) {
-        // (the table of the previous call is no longer read: every call ends its conversion with a synchronize)
-        const int rc = c0->win_table.ensure(table.size() + 16);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy(c0->win_table.p, table.data(), table.size(), hipMemcpyHostToDevice));
-        HIP_TRY(ddc_windows_launch(c0->stream, sample_format, c0->ch_decim, (const float *)c0->ddc_taps.p, (const float *)c0->an_tab.p,
-                                   c0->win_table.p, count, tiles));
+    const float *taps = (const float *)c0->ddc_taps.p, *tab = (const float *)c0->an_tab.p;
+    if (windows) {
+        std::vector<unsigned char> table;
+        const long long tiles = ddc_windows_table(c0->ch_decim, recs.data(), count, table);
+        if (tiles < 0) return PDT_ERR_ARG;
+        if (tiles) {
+            // (the table of the previous call is no longer read: every call ends its conversion with a synchronize)
+            const int rc = c0->win_table.ensure(table.size() + 16);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpy(c0->win_table.p, table.data(), table.size(), hipMemcpyHostToDevice));
+            HIP_TRY(ddc_windows_launch(c0->stream, sample_format, c0->ch_decim, taps, tab, c0->win_table.p, count, tiles));
+        }
+    } else {
+        for (int i = 0; i < count; i++) HIP_TRY(ddc_launch(c0->stream, sample_format, c0->ch_decim, taps, tab, recs[(size_t)i]));
     }
     HIP_TRY(hipStreamSynchronize(c0->stream));
     for (int i = 0; i < count; i++) ctxs[i]->channel_len = lens[(size_t)i];
     return demod_batch(ctxs, (const void *const *)outs.data(), lens.data(), count, PDT_FMT_F32);
 }
 
-int pdt_demod_windows_device(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_device, uint64_t nframes, int sample_format)
-{
-    return demod_windows(ctxs, count, win, iq_device, nframes, sample_format, nullptr);
-}
-
-int pdt_demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_host, uint64_t nframes, int sample_format)
+// the same for a capture in host memory: check, fit, ingest into the first context's input buffer -- timed but not published: the
+// contexts of a batch report no ingest, as they never have
+static int demod_each_host(pdt_ctx *const *ctxs, int count, const pdt_window *win, bool windows, const void *iq_host, uint64_t nframes,
+                           int sample_format)
 {
     const InFmt f = in_fmt(sample_format);
-    if (count < 0 || (count && (!ctxs || !win)) || (!iq_host && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
+    if (count < 0 || (count && (!ctxs || (windows && !win))) || (!iq_host && nframes) || f.kind != IN_WB) return PDT_ERR_ARG;
     if (!count) return PDT_OK;
     pdt_ctx *c0 = ctxs[0];
     if (!c0) return PDT_ERR_ARG;
@@ -1459,8 +1449,28 @@ int pdt_demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, co
     if (!channel_fits(c0, nframes, f)) return PDT_ERR_NOMEM;
     IngestSrc src;
     src.mem = (const unsigned char *)iq_host;
-    const int rc = ingest_whole(c0, src, (size_t)nframes * (size_t)f.bytes);     // (timed, not published: pdt_demod_channels)
-    return rc ? rc : demod_windows(ctxs, count, win, c0->pcm.p, nframes, sample_format, nullptr);
+    const int rc = ingest_whole(c0, src, (size_t)nframes * (size_t)f.bytes);
+    return rc ? rc : demod_each(ctxs, count, win, windows, c0->pcm.p, nframes, sample_format, nullptr);
+}
+
+int pdt_demod_channels_device(pdt_ctx *const *ctxs, int count, const void *iq_device, uint64_t nframes, int sample_format)
+{
+    return demod_each(ctxs, count, nullptr, false, iq_device, nframes, sample_format, nullptr);
+}
+
+int pdt_demod_channels(pdt_ctx *const *ctxs, int count, const void *iq_host, uint64_t nframes, int sample_format)
+{
+    return demod_each_host(ctxs, count, nullptr, false, iq_host, nframes, sample_format);
+}
+
+int pdt_demod_windows_device(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_device, uint64_t nframes, int sample_format)
+{
+    return demod_each(ctxs, count, win, true, iq_device, nframes, sample_format, nullptr);
+}
+
+int pdt_demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_host, uint64_t nframes, int sample_format)
+{
+    return demod_each_host(ctxs, count, win, true, iq_host, nframes, sample_format);
 }
 
 int pdt_demod_windows_held(pdt_ctx *holder, pdt_ctx *const *ctxs, int count, const pdt_window *win)
@@ -1469,7 +1479,7 @@ int pdt_demod_windows_held(pdt_ctx *holder, pdt_ctx *const *ctxs, int count, con
     if (!holder->held_src) return PDT_ERR_STATE;
     for (int i = 0; i < count && ctxs; i++)
         if (ctxs[i] && ctxs[i]->cfg.device != holder->cfg.device) return PDT_ERR_ARG;    // (the capture lies in the holder's device's memory)
-    return demod_windows(ctxs, count, win, holder->held_src, holder->held_frames, holder->held_fmt, holder);
+    return demod_each(ctxs, count, win, true, holder->held_src, holder->held_frames, holder->held_fmt, holder);
 }
 
 // ---------------------------------------------------------------- carrier survey (pdt_survey.h)
@@ -2104,8 +2114,8 @@ static int front_convert(pdt_ctx *ctx, uint64_t n_new, bool final_piece)
     void *out = (unsigned char *)ctx->stream_in.p + (size_t)ctx->stream_have * 8;
     const long long lo = -(long long)h.left, hi = (long long)(h.pending + n_new);
     if (wb)
-        HIP_TRY(ddc_launch(ctx->stream, f.code, x, lo, hi, m, base, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
-                           &ctx->ch_step, &out, 1));
+        HIP_TRY(ddc_launch(ctx->stream, f.code, ctx->ch_decim, (const float *)ctx->ddc_taps.p, (const float *)ctx->an_tab.p,
+                           channel_record(ctx, x, lo, hi, m, base, out)));
     else
         HIP_TRY(analytic_launch(ctx->stream, f.code, x, lo, hi, m, base, ctx->real_step, (const float *)ctx->an_tab.p, out));
     const uint64_t nbase = (h.out + m) * D;

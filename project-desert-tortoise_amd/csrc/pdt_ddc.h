@@ -66,14 +66,17 @@ template <int FMT> __host__ __device__ __forceinline__ void ddc_load(const void 
     }
 }
 
-// One window of a capture for the windows kernel (k_ddc_windows): a capture of its own of n frames at x, its channel
-// stream of n_out = ceil(n / D) pairs at out, its phase counted from its first sample.  tile0: the launch's first tile of this
-// window.  The per-call table on the device: the windows' records, then one int per tile, the tile's window.
+// One conversion of the kernel (k_ddc).  x: the address of input sample 0; the samples lo <= i < hi are
+// present, zeros lie elsewhere.  Output m, 0 <= m < n_out, is centred on input m D and goes to out[m]; n_out is the caller's (a
+// stream piece asks for fewer outputs than its view holds).  g0: the global index of input 0, modulo 2^32 -- the phase of input i
+// is (g0 + i) step mod 2^32.  A whole capture or a window of n frames: lo = 0, hi = n, g0 = 0, n_out = ceil(n / D).  A stream
+// piece: lo = -(the left halo kept), g0 = D times the outputs made so far.  tile0: the launch's first tile of this record.  The
+// per-call table of a launch of many records, on the device: the records, then one int per tile, the tile's record.
 struct DdcWindow {
     const void *x;
     void *out;
-    long long n, n_out;
-    uint32_t step;
+    long long lo, hi, n_out;
+    uint32_t step, g0;
     int tile0;
 };
 

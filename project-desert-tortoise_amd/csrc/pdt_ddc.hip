@@ -1,6 +1,6 @@
-// pdt_ddc.hip -- the digital down-converter of wideband captures (pdt_ddc.h): one kernel per input format that reads a tile of
-// the wideband capture once and produces that tile's outputs for every channel of the launch, and its host restatement
-// pdt_host_ddc.  A unit of its own: the chain's units do not change.
+// pdt_ddc.hip -- the digital down-converter of wideband captures (pdt_ddc.h): one kernel per input format, which converts what a
+// record (DdcWindow) describes -- a whole capture, a window of one, a piece of a stream -- and its host restatement pdt_host_ddc.
+// A unit of its own: the chain's units do not change.
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -12,25 +12,17 @@ namespace pdt {
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-// One workgroup takes TO = floor(2048 / D) consecutive outputs of every channel.  The (TO + 16) D input samples they reach (the
-// tile with its +-8 D halo) are converted to float pairs while they are read into LDS, once: 16-byte loads where the tile lies
-// inside the samples present, sample by sample with zeros outside elsewhere (the first and last tiles, stream pieces).  Then, per
-// channel: every lane rotates its share of the tile into a second LDS image laid out by polyphase branch -- input i' at
-// [i' mod D][i' / D], rows of ROWP pairs -- so that the lanes of a wavefront, one output each, read consecutive pairs for every tap
-// (ds_read_b64 without bank conflicts), the tap itself is one broadcast read, and I and Q advance in one packed FMA.  Outputs leave
-// as consecutive 8-byte pairs.  Up to four outputs per lane (D < 8) share the tap reads.
+// One workgroup takes TO = floor(2048 / D) consecutive outputs of one record.  The (TO + 16) D input samples they reach (the tile
+// with its +-8 D halo) go from the load through ddc_mix straight into an LDS image laid out by polyphase branch -- input i' at
+// [i' mod D][i' / D], rows of ROWP pairs: 16-byte loads where the record's own address allows them and the tile lies inside the
+// samples present, sample by sample in front of the first 16-byte boundary and behind the last whole load, and with zeros outside
+// [lo, hi) in the tiles that touch the ends (the first and last tiles, stream pieces).  Then the lanes of a wavefront, one output
+// each, read consecutive pairs for every tap (ds_read_b64 without bank conflicts), the tap itself is one broadcast read, and I and
+// Q advance in one packed FMA.  Outputs leave as consecutive 8-byte pairs.  Up to four outputs per lane (D < 8) share the tap reads.
 constexpr int DDC_TILE = 2048;                                           // input samples of a tile without its halo, at most
-constexpr int DDC_XS = DDC_TILE + 2 * DDC_SPAN * DDC_MAX_DECIM;          // 3072: (TO + 16) D <= 2048 + 16 D
 constexpr int DDC_VS = DDC_TILE + (2 * DDC_SPAN + 1) * DDC_MAX_DECIM;    // 3136: D ROWP <= D (TO + 17)
 constexpr int DDC_HS = 2 * DDC_SPAN * DDC_MAX_DECIM + 4;
 constexpr int DDC_TB = 256;                                              // lanes of a workgroup, at most
-constexpr int DDC_KMAX = 16;                                             // channels of one launch
-
-struct DdcChans {
-    float2 *out[DDC_KMAX];
-    uint32_t step[DDC_KMAX];
-    int k;
-};
 
 template <int FMT> struct DdcVec;
 template <> struct DdcVec<PDT_FMT_WB_PCM16> { enum { SPV = 4 }; };
@@ -98,101 +90,21 @@ __device__ __forceinline__ void ddc_fir(const f2v *__restrict__ vs, const float 
     }
 }
 
-// x: input sample i (relative) is x[i], present for lo <= i < hi, zero elsewhere; output m is centred on input m D.  g0: global
-// index of input 0.  Every channel's buffer takes n_out pairs.  taps: 16 D + 1 floats.  TO = floor(2048 / D), ROWP = (TO + 16) | 1.
-template <int FMT>
-__global__ void __launch_bounds__(DDC_TB) k_ddc(const void *__restrict__ x, long long lo, long long hi, long long n_out, unsigned long long g0,
-                                                int D, int TO, int ROWP, const float *__restrict__ taps, const float *__restrict__ tab, DdcChans ch)
-{
-    __shared__ __attribute__((aligned(16))) float2 xs[DDC_XS];
-    __shared__ __attribute__((aligned(16))) f2v vs[DDC_VS];
-    __shared__ float hs[DDC_HS];
-    const int t = threadIdx.x, tb = blockDim.x;
-    const long long m0 = (long long)blockIdx.x * TO;
-    const long long first = (m0 - DDC_SPAN) * D;                   // input sample of xs[0]
-    const int len = (TO + 2 * DDC_SPAN) * D;                       // <= DDC_XS
-    constexpr int BPS = FMT == PDT_FMT_WB_PCM16 ? 4 : FMT == PDT_FMT_WB_F32 ? 8 : 2;
-    constexpr int SPV = DdcVec<FMT>::SPV;
-    for (int j = t; j <= 2 * DDC_SPAN * D; j += tb) hs[j] = taps[j];
-    const bool inner = first >= lo && first + len <= hi;
-    if (inner) {
-        const unsigned char *src = reinterpret_cast<const unsigned char *>(x) + first * BPS;
-        int head = (int)(((16 - ((uintptr_t)src & 15)) & 15) / BPS);      // samples in front of the first 16-byte boundary
-        if (((uintptr_t)src & 15) % BPS) head = len;                       // (never aligned: sample by sample)
-        head = min(head, len);
-        const int nvec = (len - head) / SPV;
-        for (int j = t; j < head; j += tb) {
-            float re, im;
-            ddc_load<FMT>(x, first + j, re, im);
-            xs[j] = make_float2(re, im);
-        }
-        for (int v = t; v < nvec; v += tb) {
-            float2 s[SPV];
-            ddc_unpack<FMT>(src + (size_t)head * BPS + (size_t)v * 16, s);
-#pragma unroll
-            for (int e = 0; e < SPV; e++) xs[head + v * SPV + e] = s[e];
-        }
-        for (int j = head + nvec * SPV + t; j < len; j += tb) {
-            float re, im;
-            ddc_load<FMT>(x, first + j, re, im);
-            xs[j] = make_float2(re, im);
-        }
-    } else {
-        for (int j = t; j < len; j += tb) {
-            const long long i = first + j;
-            float re = 0.0f, im = 0.0f;
-            if (i >= lo && i < hi) ddc_load<FMT>(x, i, re, im);
-            xs[j] = make_float2(re, im);
-        }
-    }
-    __syncthreads();
-    const long long left = n_out - m0;
-    const int nb = (TO + tb - 1) / tb;
-    const int dr = tb % D, dq = tb / D;
-    for (int c = 0; c < ch.k; c++) {
-        const uint32_t step = ch.step[c];
-        uint32_t p = (uint32_t)(g0 + (unsigned long long)(first + t)) * step;
-        const uint32_t dp = (uint32_t)tb * step;
-        int r = t % D, q = t / D;
-        for (int j = t; j < len; j += tb) {
-            const float2 s = xs[j];
-            float vr, vi;
-            ddc_mix(s.x, s.y, p, tab, vr, vi);
-            vs[r * ROWP + q] = (f2v){ vr, vi };
-            p += dp;
-            r += dr;
-            q += dq;
-            if (r >= D) { r -= D; q++; }
-        }
-        __syncthreads();
-        float2 *out = ch.out[c] + m0;
-        if (t < TO) {
-            switch (nb) {
-            case 1: ddc_fir<1>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
-            case 2: ddc_fir<2>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
-            case 3: ddc_fir<3>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
-            default: ddc_fir<4>(vs, hs, D, TO, ROWP, t, tb, left, out); break;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// Input samples first + j, j = j0 + t, j0 + t + tb, ... < j1, of window w, one by one: scaled, mixed with the phase counted from the
-// window's first sample, and put into the polyphase image at [j mod D][j / D].  EDGE: samples outside [0, n) are zeros.
+// Input samples first + j, j = j0 + t, j0 + t + tb, ... < j1, of record w, one by one: scaled, mixed with the phase of their global
+// index, and put into the polyphase image at [j mod D][j / D].  EDGE: samples outside [lo, hi) are zeros.
 template <int FMT, bool EDGE>
-__device__ __forceinline__ void ddc_win_samples(const DdcWindow &w, long long first, int j0, int j1, int t, int tb, int D, int ROWP,
-                                                const float *__restrict__ tab, f2v *__restrict__ vs)
+__device__ __forceinline__ void ddc_samples(const DdcWindow &w, long long first, int j0, int j1, int t, int tb, int D, int ROWP,
+                                            const float *__restrict__ tab, f2v *__restrict__ vs)
 {
     int j = j0 + t;
     int r = j % D, q = j / D;
     const int dr = tb % D, dq = tb / D;
-    uint32_t p = (uint32_t)(unsigned long long)(first + j) * w.step;
+    uint32_t p = (w.g0 + (uint32_t)(unsigned long long)(first + j)) * w.step;
     const uint32_t dp = (uint32_t)tb * w.step;
     for (; j < j1; j += tb) {
         const long long i = first + j;
         float vr = 0.0f, vi = 0.0f;
-        if (!EDGE || (i >= 0 && i < w.n)) {
+        if (!EDGE || (i >= w.lo && i < w.hi)) {
             float re, im;
             ddc_load<FMT>(w.x, i, re, im);
             ddc_mix(re, im, p, tab, vr, vi);
@@ -205,40 +117,37 @@ __device__ __forceinline__ void ddc_win_samples(const DdcWindow &w, long long fi
     }
 }
 
-// The windows of one capture, a channel each (pdt_demod_windows_device): blockIdx.x walks the tiles of all windows, tile_win[tile] is
-// the tile's window, wins[] its record.  A window is a capture of its own: k_ddc's tile geometry on the window's own sample index,
-// zeros outside [0, n) whatever the capture holds there.  One channel, so there is no xs stage: a sample goes from the load through
-// ddc_mix straight into the polyphase image, then ddc_fir as it is.  16-byte loads where the window's own address allows them and the
-// tile lies inside the window, sample by sample in front of the first 16-byte boundary, behind the last whole load, and in the
-// tiles that touch the window's ends.
+// The record of a workgroup's tile: `one` when there is no table (tile_win == nullptr: a whole capture or a stream piece, blockIdx.x
+// walks its tiles), else wins[tile_win[blockIdx.x]] (the windows of pdt_demod_windows_device: blockIdx.x walks the tiles of all of
+// them).  taps: 16 D + 1 floats.  TO = floor(2048 / D), ROWP = (TO + 16) | 1.
 template <int FMT>
-__global__ void __launch_bounds__(DDC_TB) k_ddc_windows(const DdcWindow *__restrict__ wins, const int *__restrict__ tile_win, int D, int TO, int ROWP,
-                                                        const float *__restrict__ taps, const float *__restrict__ tab)
+__global__ void __launch_bounds__(DDC_TB) k_ddc(const DdcWindow one, const DdcWindow *__restrict__ wins, const int *__restrict__ tile_win, int D,
+                                                int TO, int ROWP, const float *__restrict__ taps, const float *__restrict__ tab)
 {
     __shared__ __attribute__((aligned(16))) f2v vs[DDC_VS];
     __shared__ float hs[DDC_HS];
     const int t = threadIdx.x, tb = blockDim.x;
-    const DdcWindow w = wins[tile_win[blockIdx.x]];
+    const DdcWindow w = tile_win ? wins[tile_win[blockIdx.x]] : one;
     const long long m0 = (long long)((int)blockIdx.x - w.tile0) * TO;
-    const long long first = (m0 - DDC_SPAN) * D;                   // the window's input sample at image place 0
-    const int len = (TO + 2 * DDC_SPAN) * D;                       // <= DDC_XS
+    const long long first = (m0 - DDC_SPAN) * D;                   // the record's input sample at image place 0
+    const int len = (TO + 2 * DDC_SPAN) * D;                       // <= 2048 + 16 D; its image D ROWP <= DDC_VS
     constexpr int BPS = FMT == PDT_FMT_WB_PCM16 ? 4 : FMT == PDT_FMT_WB_F32 ? 8 : 2;
     constexpr int SPV = DdcVec<FMT>::SPV;
     for (int j = t; j <= 2 * DDC_SPAN * D; j += tb) hs[j] = taps[j];
-    if (first >= 0 && first + len <= w.n) {
+    if (first >= w.lo && first + len <= w.hi) {
         const unsigned char *src = reinterpret_cast<const unsigned char *>(w.x) + first * BPS;
         int head = (int)(((16 - ((uintptr_t)src & 15)) & 15) / BPS);      // samples in front of the first 16-byte boundary
         if (((uintptr_t)src & 15) % BPS) head = len;                       // (never aligned: sample by sample)
         head = min(head, len);
         const int nvec = (len - head) / SPV;
-        ddc_win_samples<FMT, false>(w, first, 0, head, t, tb, D, ROWP, tab, vs);
+        ddc_samples<FMT, false>(w, first, 0, head, t, tb, D, ROWP, tab, vs);
         int j = head + t * SPV;
         int r = j % D, q = j / D;
         const int dr = (tb * SPV) % D, dq = (tb * SPV) / D;
         for (int v = t; v < nvec; v += tb) {
             float2 s[SPV];
             ddc_unpack<FMT>(src + (size_t)head * BPS + (size_t)v * 16, s);
-            uint32_t p = (uint32_t)(unsigned long long)(first + j) * w.step;
+            uint32_t p = (w.g0 + (uint32_t)(unsigned long long)(first + j)) * w.step;
             int re = r, qe = q;
 #pragma unroll
             for (int e = 0; e < SPV; e++) {
@@ -253,9 +162,9 @@ __global__ void __launch_bounds__(DDC_TB) k_ddc_windows(const DdcWindow *__restr
             q += dq;
             if (r >= D) { r -= D; q++; }
         }
-        ddc_win_samples<FMT, false>(w, first, head + nvec * SPV, len, t, tb, D, ROWP, tab, vs);
+        ddc_samples<FMT, false>(w, first, head + nvec * SPV, len, t, tb, D, ROWP, tab, vs);
     } else {
-        ddc_win_samples<FMT, true>(w, first, 0, len, t, tb, D, ROWP, tab, vs);
+        ddc_samples<FMT, true>(w, first, 0, len, t, tb, D, ROWP, tab, vs);
     }
     __syncthreads();
     const long long left = w.n_out - m0;
@@ -276,15 +185,37 @@ using namespace pdt;
 
 namespace pdtrt {
 
-// The per-call table of the windows kernel, as the host builds it: win[i].x, .out, .n and .step are the caller's, .n_out and .tile0
-// are filled in here; `table` receives the records and behind them the tiles' windows.  Returns the number of tiles, -1 when they
-// are more than a launch takes: a grid's lanes must number less than 2^32, workgroups of up to DDC_TB lanes.
+// k_ddc over `tiles` tiles: of record `one` when table_dev is null, else of the `count` records of the table
+static hipError_t ddc_go(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, long long tiles, const DdcWindow &one,
+                         const void *table_dev, int count)
+{
+    if (tiles <= 0) return hipSuccess;
+    if (decim < DDC_MIN_DECIM || decim > DDC_MAX_DECIM || !ddc_fmt(fmt)) return hipErrorInvalidValue;
+    const int TO = DDC_TILE / decim, ROWP = (TO + 2 * DDC_SPAN) | 1;
+    const int tb = std::min(DDC_TB, (TO + 63) / 64 * 64);
+    if (tiles > 0xffffffffLL / tb) return hipErrorInvalidValue;        // (a grid's lanes must number less than 2^32)
+    const DdcWindow *wins = reinterpret_cast<const DdcWindow *>(table_dev);
+    const int *tile_win = table_dev ? reinterpret_cast<const int *>(wins + count) : nullptr;
+    const dim3 grid((unsigned)tiles);
+#define PDT_DDC_GO(F) hipLaunchKernelGGL(k_ddc<F>, grid, dim3(tb), 0, st, one, wins, tile_win, decim, TO, ROWP, taps_dev, tab_dev)
+    switch (fmt) {
+    case PDT_FMT_WB_PCM16: PDT_DDC_GO(PDT_FMT_WB_PCM16); break;
+    case PDT_FMT_WB_F32: PDT_DDC_GO(PDT_FMT_WB_F32); break;
+    case PDT_FMT_WB_CU8: PDT_DDC_GO(PDT_FMT_WB_CU8); break;
+    default: PDT_DDC_GO(PDT_FMT_WB_CS8); break;
+    }
+#undef PDT_DDC_GO
+    return hipGetLastError();
+}
+
+// The per-call table of many records, as the host builds it: win[i]'s fields are the caller's but .tile0, which is filled in here;
+// `table` receives the records and behind them the tiles' records.  Returns the number of tiles, -1 when they are more than a
+// launch takes.
 long long ddc_windows_table(int decim, DdcWindow *win, int count, std::vector<unsigned char> &table)
 {
     const long long TO = DDC_TILE / decim, most = 0xffffffffLL / DDC_TB;
     long long tiles = 0;
     for (int i = 0; i < count; i++) {
-        win[i].n_out = (win[i].n + decim - 1) / decim;
         if (tiles > most) return -1;
         win[i].tile0 = (int)tiles;
         tiles += (win[i].n_out + TO - 1) / TO;
@@ -300,57 +231,20 @@ long long ddc_windows_table(int decim, DdcWindow *win, int count, std::vector<un
     return tiles;
 }
 
-// the windows kernel over a table that is on the device: `count` records, `tiles` tiles, one launch
+// the kernel over a table that is on the device: `count` records, `tiles` tiles, one launch
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
                               long long tiles)
 {
-    if (tiles <= 0 || count <= 0) return hipSuccess;
-    if (decim < DDC_MIN_DECIM || decim > DDC_MAX_DECIM || !ddc_fmt(fmt)) return hipErrorInvalidValue;
-    const int TO = DDC_TILE / decim, ROWP = (TO + 2 * DDC_SPAN) | 1;
-    const int tb = std::min(DDC_TB, (TO + 63) / 64 * 64);
-    const DdcWindow *wins = reinterpret_cast<const DdcWindow *>(table_dev);
-    const int *tile_win = reinterpret_cast<const int *>(wins + count);
-    const dim3 grid((unsigned)tiles);
-#define PDT_DDC_GO(F) hipLaunchKernelGGL(k_ddc_windows<F>, grid, dim3(tb), 0, st, wins, tile_win, decim, TO, ROWP, taps_dev, tab_dev)
-    switch (fmt) {
-    case PDT_FMT_WB_PCM16: PDT_DDC_GO(PDT_FMT_WB_PCM16); break;
-    case PDT_FMT_WB_F32: PDT_DDC_GO(PDT_FMT_WB_F32); break;
-    case PDT_FMT_WB_CU8: PDT_DDC_GO(PDT_FMT_WB_CU8); break;
-    default: PDT_DDC_GO(PDT_FMT_WB_CS8); break;
-    }
-#undef PDT_DDC_GO
-    return hipGetLastError();
+    if (count <= 0) return hipSuccess;
+    return ddc_go(st, fmt, decim, taps_dev, tab_dev, tiles, DdcWindow(), table_dev, count);
 }
 
-// the kernel over outputs [0, n_out) of k channels (host side of pdt_api.hip's channel paths)
-hipError_t ddc_launch(hipStream_t st, int fmt, const void *x, long long lo, long long hi, unsigned long long n_out, unsigned long long g0,
-                      int decim, const float *taps_dev, const float *tab_dev, const uint32_t *steps, void *const *outs, int k)
+// the kernel over one record, passed by value: no table, no copy, nothing waited for
+hipError_t ddc_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, DdcWindow w)
 {
-    if (!n_out || k <= 0) return hipSuccess;
-    if (decim < DDC_MIN_DECIM || decim > DDC_MAX_DECIM || !ddc_fmt(fmt)) return hipErrorInvalidValue;
-    const int TO = DDC_TILE / decim, ROWP = (TO + 2 * DDC_SPAN) | 1;
-    const int tb = std::min(DDC_TB, (TO + 63) / 64 * 64);
-    const dim3 grid((unsigned)((n_out + (unsigned long long)TO - 1) / (unsigned long long)TO));
-    for (int c0 = 0; c0 < k; c0 += DDC_KMAX) {
-        DdcChans ch;
-        memset(&ch, 0, sizeof ch);
-        ch.k = std::min(DDC_KMAX, k - c0);
-        for (int c = 0; c < ch.k; c++) {
-            ch.out[c] = (float2 *)outs[c0 + c];
-            ch.step[c] = steps[c0 + c];
-        }
-#define PDT_DDC_GO(F) hipLaunchKernelGGL(k_ddc<F>, grid, dim3(tb), 0, st, x, lo, hi, (long long)n_out, g0, decim, TO, ROWP, taps_dev, tab_dev, ch)
-        switch (fmt) {
-        case PDT_FMT_WB_PCM16: PDT_DDC_GO(PDT_FMT_WB_PCM16); break;
-        case PDT_FMT_WB_F32: PDT_DDC_GO(PDT_FMT_WB_F32); break;
-        case PDT_FMT_WB_CU8: PDT_DDC_GO(PDT_FMT_WB_CU8); break;
-        default: PDT_DDC_GO(PDT_FMT_WB_CS8); break;
-        }
-#undef PDT_DDC_GO
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    const long long TO = DDC_TILE / std::max(decim, 1);
+    w.tile0 = 0;
+    return ddc_go(st, fmt, decim, taps_dev, tab_dev, (w.n_out + TO - 1) / TO, w, nullptr, 0);
 }
 
 }  // namespace pdtrt

@@ -25,7 +25,7 @@
 namespace pdt {
 
 constexpr int SURVEY_RUN = 64;                  // R: segments of a run (one workgroup, one partial row)
-constexpr int SURVEY_MAX_CARRIERS = 16;         // what one k_ddc launch takes
+constexpr int SURVEY_MAX_CARRIERS = 16;         // the channels the host programs take (-t)
 constexpr int SURVEY_DEFAULT_NFFT = 16384;
 constexpr double SURVEY_DEFAULT_THRESHOLD_DB = 15.0;
 

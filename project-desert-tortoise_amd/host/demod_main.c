@@ -38,8 +38,8 @@
  * -x <decim> with one or more -t <kHz> (an addition): the input is a wideband I,Q capture (RTL-SDR, HackRF, ...) at decim times the
  * channel rate, the beacon -t kHz (signed) off its centre; the library tunes, filters and decimates on the GPU
  * (pdt_set_channel / PDT_FMT_WB_*).  The WAV header's rate, or -s in kHz, is the WIDEBAND rate and must be divisible by
- * decim; files named .cu8 / .cs8 are headerless unsigned / signed 8-bit pairs (-s required).  With several -t the channels share
- * one read of the capture (pdt_demod_channels) and each writes its own file, the channel's index appended to the usual name
+ * decim; files named .cu8 / .cs8 are headerless unsigned / signed 8-bit pairs (-s required).  With several -t the capture is
+ * ingested once for all channels (pdt_demod_channels: one conversion launch per channel) and each writes its own file, the channel's index appended to the usual name
  * (".0", ".1", ...).  -l -x .. -t .. - reads blocks from standard input through pdt_stream_push_channel, in the format -F names
  * (cu8, the default, cs8, s16 or f32).  Without -x nothing changes, the refusal of rates above 300 kHz included.
  * -t auto or -t auto:N (an addition, with -x, not beside numeric -t): the carriers are looked for instead of given -- the capture's
@@ -273,7 +273,7 @@ static int live_loop(FILE *in, FILE *out, const char *outFileName, double sample
     return 0;
 }
 
-/* -x with several -t: one wideband capture, one context per channel, one read of the capture (pdt_demod_channels); every
+/* -x with several -t: one wideband capture, one context per channel, the capture ingested once (pdt_demod_channels); every
  * channel's frames go to a file of its own, outFileName with ".<index>" appended */
 static int multi_channel(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim,
                          const double *offsetsHz, int nch, const char *outFileName)

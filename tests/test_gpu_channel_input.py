@@ -1,6 +1,6 @@
 """Wideband SDR captures on the GPU: the down-converter's kernel against its host restatement bit for bit, the routing into the
 chain (a wideband capture = the RAW float capture of its channel stream), decoded outcomes against what the synthetic generator
-transmitted, several channels from one read, streaming, files and the command line."""
+transmitted, several channels of one capture, the records of stream pieces, streaming, files and the command line."""
 import ctypes as C
 import os
 import subprocess
@@ -111,9 +111,8 @@ def test_kernel_equals_host_restatement_at_every_decimation(pdt, D):
       D samples a tile, so where D does not divide 2048 the split differs from tile to tile of ONE aligned capture (the lengths of 3
       and of about 20 tiles here), for every format's samples-per-vector (2, 4, 8); the resident captures 1, 2 and 3 samples behind a
       16-byte boundary shift it once more.
-    * the worst cases of the LDS images: (TO + 16) D <= DDC_XS = 3072 is tightest at D = 64 (3072) and 63 (3024); D ((TO + 16) | 1) <=
-      DDC_VS = 3136 at D = 64 (3136), 62 (3038), 63 (3087) and 47 (2773 of the 2048 + 17 D = 2847 the formula allows), where TO + 16
-      is even and the row is padded.
+    * the worst cases of the LDS image: D ((TO + 16) | 1) <= DDC_VS = 3136 is tightest at D = 64 (3136), 62 (3038), 63 (3087) and 47
+      (2773 of the 2048 + 17 D = 2847 the formula allows), where TO + 16 is even and the row is padded.
 
     Lengths: a single sample, around one output, around the halo (8 D), around one tile (tile = TO D inputs), tile - D + 1 where
     the number of outputs is exactly TO, three tiles and some twenty tiles with an odd remainder; a positive and a negative offset;
@@ -144,6 +143,52 @@ def test_kernel_equals_host_restatement_at_every_decimation(pdt, D):
                 d.set_channel(D, -77777.0).demod_device_channel(dev.data_ptr() + skip * 2 * x.itemsize, n, fmt_code(pdt, x))
                 assert d.stage_len(pdt.ST_CHANNEL) == (n + D - 1) // D, (fmt, skip)
                 assert d.stage(pdt.ST_CHANNEL).tobytes() == want.tobytes(), (fmt, skip)
+
+
+PIECE_DECIMS = (2, 3, 7, 16, 64)          # nb = 4, 3, 2, 1 and 1; the rotation's carry (3, 7) and none; the tightest LDS image (64)
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("D", PIECE_DECIMS)
+def test_a_piece_that_sees_its_neighbours_equals_the_whole_capture(pdt, D, fmt):
+    """A stream's converted pairs cannot be read back, and a frame need not notice one wrong ulp or sample at a push seam.  So the
+    kernel is run (pdt_dev_ddc) on the records a stream hands it: outputs [k0, k0 + m) of a resident capture of 5 tiles + 3 D + 1
+    frames from a view that begins at input k0 D, sees up to 8 D samples to its left (lo < 0) and the rest of the capture to its
+    right, with g0 = k0 D -- and must give pdt_host_ddc(whole capture)[k0 : k0 + m], byte for byte.  The tile grid starts at another
+    alignment in every piece, as in a stream: the stream's first output and its first tile and a bit (no left halo), one output whose
+    view begins exactly 8 D before it (the first tile's inner test at its boundary), two outputs across a tile's end, several
+    tiles, and a piece that runs to the capture's end (zeros beyond).
+    One further piece is truncated on both sides (lo = -3, hi = (m - 1) D + 2) and must equal the same outputs of the capture with
+    every sample outside the view set to zero -- not in cu8, where no byte maps to 0."""
+    fs = 250000
+    in_rate, offset = fs * D, -0.123456 * fs * D
+    TO, _, _ = ddc_geometry(D)
+    n = 5 * TO * D + 3 * D + 1
+    n_out = (n + D - 1) // D
+    rng = np.random.default_rng(9000 * D + FORMATS.index(fmt))
+    x = random_capture(rng, fmt, n)
+    code, bps = fmt_code(pdt, x), 2 * x.itemsize
+    want = pdt.host_ddc(in_rate, D, offset, x)
+    dev = torch.from_numpy(x.reshape(-1).copy()).to("cuda:0")
+    out = torch.empty((n_out + 1, 2), dtype=torch.float32, device="cuda:0")
+
+    def piece(k0, m, lo, hi):
+        out.fill_(float("nan"))
+        torch.cuda.synchronize()
+        pdt.dev_ddc(in_rate, D, offset, code, dev.data_ptr() + k0 * D * bps, lo, hi, m, k0 * D, out.data_ptr())
+        got = out.cpu().numpy()
+        assert np.isnan(got[m:]).all(), (k0, m)                          # nothing behind the outputs asked for
+        return got[:m]
+
+    for k0, m in ((0, 1), (0, TO + 3), (9, 1), (TO - 1, 2), (TO + 5, 2 * TO + 1), (n_out - TO - 2, TO + 2)):
+        got = piece(k0, m, -min(8 * D, k0 * D), n - k0 * D)
+        assert got.tobytes() == want[k0: k0 + m].tobytes(), (k0, m)
+    if fmt != "cu8":
+        k0, m = TO + 5, 2 * TO + 1
+        lo, hi = -3, (m - 1) * D + 2
+        z = np.zeros_like(x)
+        z[k0 * D + lo: k0 * D + hi] = x[k0 * D + lo: k0 * D + hi]
+        assert piece(k0, m, lo, hi).tobytes() == pdt.host_ddc(in_rate, D, offset, z)[k0: k0 + m].tobytes()
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
@@ -302,10 +347,10 @@ def test_several_channels_equal_one_at_a_time(pdt):
 
 
 @pytest.mark.parametrize("in_rate,D,tuned", [(1000000, 4, (200000.0, -180000.0, 390000.0)), (1750000, 7, (300000.0, -412300.0, 610000.0))])
-def test_more_channels_than_one_launch_takes(pdt, in_rate, D, tuned):
-    """demod_channels with 17 and with 33 contexts: ddc_launch takes 16 channels a launch (DDC_KMAX), so these are two and three
-    launches, the last of one channel.  Every context has an offset of its own, except that contexts 15 and 16 -- the last of the
-    first launch and the first of the second -- share one (a carrier's); contexts 0 and 32 sit on carriers too.  Each context's
+def test_seventeen_and_thirty_three_channels(pdt, in_rate, D, tuned):
+    """demod_channels with 17 and with 33 contexts (more than the 16 carriers a survey reports): one conversion launch per context, all
+    on the first context's stream.  Every context has an offset of its own, except that contexts 15 and 16 share one (a carrier's);
+    contexts 0 and 32 sit on carriers too.  Each context's
     channel stream is pdt_host_ddc of ITS offset, and its text and frames are what the same context holds after demod_channel
     alone.  Before every joint call each context converts the capture at another offset, so that no buffer still holds the answer."""
     fs = in_rate // D

@@ -1,4 +1,4 @@
-"""Every burst of a wideband capture in a window of its own, on the GPU: k_ddc_windows against the host restatement
+"""Every burst of a wideband capture in a window of its own, on the GPU: the kernel over a table of windows against the host restatement
 bit for bit, each window against the single call it stands for, the payloads sent against the payloads decoded -- the first burst
 of every platform and a platform that drifts through the loop's range included --, states and arguments, and `-t each` on the
 command line."""

@@ -1,10 +1,11 @@
 """The down-converter of wideband captures: a 15-minute 2.4 Msps unsigned 8-bit capture resident in HBM, decimation 16,
-K channels from one read (pdt_demod_channels_device), wall time of the whole call, median of --reps, and that time per channel.
+K channels of it (pdt_demod_channels_device), wall time of the whole call, median of --reps, and that time per channel.
 
 Run it under `rocprofv3 --kernel-trace --stats -d DIR -o ddc -- python tools/channel_bench.py --channels K` for the conversion
-kernel's own time (k_ddc in DIR/.../ddc_kernel_stats.csv); `--stats FILE --channels K` then turns that file's k_ddc row into bytes
-read over time (2 B per input sample, read once whatever K), as a share of the 6.3 TB/s measured for a float4 copy.  The single-read
-claim is the K = 4 kernel time against 4 x the K = 1 time.  The capture is 30 s of four synthetic POES carriers, repeated on the device.
+kernel's own time (k_ddc in DIR/.../ddc_kernel_stats.csv); `--stats FILE --channels K` then turns that file's k_ddc row into the
+kernel time of one demod_channels call -- K launches, one per channel -- and into bytes read over that time (2 B per input sample
+and channel), as a share of the 6.3 TB/s measured for a float4 copy.  The capture is 30 s of four synthetic POES carriers, repeated
+on the device.
 """
 import argparse
 import csv
@@ -27,11 +28,12 @@ def kernel_share(path: str, n: int, k: int) -> dict:
     with open(path) as f:
         rows = [r for r in csv.DictReader(f) if "k_ddc" in r["Name"]]
     ns = sum(float(r["TotalDurationNs"]) for r in rows)
-    calls = sum(int(r["Calls"]) for r in rows)
+    launches = sum(int(r["Calls"]) for r in rows)
+    calls = launches // k                                  # one launch per channel of a demod_channels call
     per_call_ms = ns / calls / 1e6
-    tb_s = 2.0 * n / (per_call_ms * 1e-3) / 1e12
-    return {"channels": k, "kernel_ms": round(per_call_ms, 3), "calls": calls, "read_TB_s": round(tb_s, 4), "of_6.3": round(tb_s / 6.3, 4),
-            "out_GB": round(8.0 * k * n / 16 / 1e9, 3)}
+    tb_s = 2.0 * n * k / (per_call_ms * 1e-3) / 1e12
+    return {"channels": k, "kernel_ms": round(per_call_ms, 3), "calls": calls, "launches": launches, "read_TB_s": round(tb_s, 4),
+            "of_6.3": round(tb_s / 6.3, 4), "out_GB": round(8.0 * k * n / 16 / 1e9, 3)}
 
 
 def main():

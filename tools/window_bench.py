@@ -1,12 +1,13 @@
 """Every burst in a window of its own: the two-platform ARGOS capture of tests/test_gpu_windows.py (1.024 Msps, int16 or
 --cu8) resident in HBM, its bursts searched for once, the first --windows of their windows demodulated by one demod_windows call on as
 many contexts; wall time of the whole call (one conversion launch and the batched chain), median of --reps.  --single also
-demodulates ONE window as long as all of them together through demod_device_channel in the same process: k_ddc at K = 1 over the
-same number of input samples, for the comparison of k_ddc_windows with k_ddc.
+demodulates ONE window as long as all of them together through demod_device_channel in the same process: the same kernel over the
+same number of input samples, one record by value instead of the table of many.
 
-Run it under `rocprofv3 --kernel-trace --stats -f csv -d DIR -o windows -- python tools/window_bench.py --single` for the kernels' own time
-(no counters); `--stats FILE` then turns that file's rows into launches and time of k_ddc_windows and k_ddc: there must be exactly
-one k_ddc_windows launch per call (reps + 1 of them: the first call allocates).
+Run it under `rocprofv3 --kernel-trace --stats -f csv -d DIR -o windows -- python tools/window_bench.py` for the kernel's own time (no
+counters); `--stats FILE` then turns that file's k_ddc rows into launches and time.  In a run without --single there must be exactly
+one launch per call (reps + 1 of them: the first call allocates); a run with --single has as many launches again, and what it
+adds to the time is the single window's.
 """
 import argparse
 import csv
@@ -30,11 +31,9 @@ def kernel_times(path: str, calls: int) -> dict:
     out = {"calls": calls}
     with open(path) as f:
         for r in csv.DictReader(f):
-            for key in ("k_ddc_windows", "k_ddc"):
-                if key in r["Name"]:
-                    out[key + "_ms"] = round(out.get(key + "_ms", 0.0) + float(r["TotalDurationNs"]) / 1e6, 3)
-                    out[key + "_launches"] = out.get(key + "_launches", 0) + int(r["Calls"])
-                    break
+            if "k_ddc" in r["Name"]:
+                out["k_ddc_ms"] = round(out.get("k_ddc_ms", 0.0) + float(r["TotalDurationNs"]) / 1e6, 3)
+                out["k_ddc_launches"] = out.get("k_ddc_launches", 0) + int(r["Calls"])
     return out
 
 
@@ -44,7 +43,7 @@ def main():
     ap.add_argument("--windows", type=int, default=64, help="at most this many windows (and contexts)")
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--cu8", action="store_true", help="the unsigned 8-bit rendering of the capture")
-    ap.add_argument("--single", action="store_true", help="also one window of the same total length through k_ddc")
+    ap.add_argument("--single", action="store_true", help="also one window of the same total length through demod_device_channel")
     ap.add_argument("--stats", help="rocprofv3 kernel_stats.csv of an earlier run: print the kernels' launches and total time")
     a = ap.parse_args()
     if a.stats:

@@ -1493,55 +1493,75 @@ static int survey_tables(pdt_ctx *ctx, int nfft)
     return rc ? rc : table_upload(ctx, survey_twiddles(nfft), ctx->survey_tw, nfft, &ctx->survey_tab_nfft);
 }
 
-// the plan of a survey by this context: the defaults of merge_hz and guard_hz are the mode's PLL range and half the channel rate
-static int survey_plan_ctx(const pdt_ctx *ctx, const pdt_survey_cfg *cfg, uint64_t nframes, int cap, SurveyPlan *p)
+// the mode's PLL frequency range: the default of a search's merge_hz (that of guard_hz is half the channel rate)
+static double search_range_hz(const pdt_ctx *ctx)
 {
-    const double range = ctx->lp.pll_freq_range_hz != 0 ? ctx->lp.pll_freq_range_hz : ctx->cfg.mode == PDT_MODE_ARGOS ? 550.0 : 4500.0;
-    return survey_plan(cfg, range, (double)ctx->cfg.sample_rate, nframes, cap, p);
+    return ctx->lp.pll_freq_range_hz != 0 ? ctx->lp.pll_freq_range_hz : ctx->cfg.mode == PDT_MODE_ARGOS ? 550.0 : 4500.0;
 }
 
-// x: the capture, resident.  Nothing of the context's demodulation state is touched.
-static int survey_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const SurveyPlan &p, pdt_carrier *found, int *count)
+// P = the averaged spectrum of the nseg whole segments from `first` on, a resident stretch: the survey's kernels into the survey's
+// device buffers, read back.  Nothing of the context's demodulation state is touched.
+static int search_spectrum(pdt_ctx *ctx, const unsigned char *first, const InFmt &f, uint64_t nseg, int nfft, std::vector<float> &P)
 {
-    int rc = survey_tables(ctx, p.nfft);
-    if (!rc) rc = ctx->survey_part.ensure(survey_part_floats(p.nseg, p.nfft) * sizeof(float));
+    int rc = survey_tables(ctx, nfft);
+    if (!rc) rc = ctx->survey_part.ensure(survey_part_floats(nseg, nfft) * sizeof(float));
     if (rc) return rc;
-    const unsigned char *first = (const unsigned char *)x + (size_t)p.first * (size_t)f.bytes;
-    HIP_TRY(survey_launch(ctx->stream, f.code, first, p.nseg, p.nfft, (const float *)ctx->survey_win.p, (const float *)ctx->survey_tw.p,
+    HIP_TRY(survey_launch(ctx->stream, f.code, first, nseg, nfft, (const float *)ctx->survey_win.p, (const float *)ctx->survey_tw.p,
                           (float *)ctx->survey_part.p, (float *)ctx->survey_out.p));
-    std::vector<float> P((size_t)p.nfft);
+    P.resize((size_t)nfft);
     HIP_TRY(hipMemcpyAsync(P.data(), ctx->survey_out.p, P.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PDT_OK;
+}
+
+// x: the capture, resident
+static int survey_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const SurveyPlan &p, pdt_carrier *found, int *count)
+{
+    std::vector<float> P;
+    const int rc = search_spectrum(ctx, (const unsigned char *)x + (size_t)p.first * (size_t)f.bytes, f, p.nseg, p.nfft, P);
+    if (rc) return rc;
     ctx->survey_spec.swap(P);
     *count = survey_carriers(ctx->survey_spec.data(), p, (double)ctx->ch_decim * (double)ctx->cfg.sample_rate, found);
     return PDT_OK;
 }
 
-// both survey entries: the capture in host memory goes where pdt_demod_channel would put it, whole -- the same condition on the
-// device's memory -- and its ingest is not published: a survey leaves the context's results and statistics unchanged
-static int survey_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
-                      int cap, int *count)
+// All four entries of the survey and of the burst search.  plan(range): the search's plan from its cfg, the mode's range for the
+// default of merge_hz; search(x, f): the search itself over the resident capture.  A capture in host memory goes where
+// pdt_demod_channel would put it, whole -- the same condition on the device's memory -- and its ingest is not published: a search
+// leaves the context's results and statistics unchanged.  The capture searched is the one pdt_demod_windows_held reads, once
+// the search has succeeded.
+static int search_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nframes, int sample_format, bool results, bool bursts,
+                      const std::function<int(double)> &plan, const std::function<int(const void *, const InFmt &)> &search)
 {
     const InFmt f = in_fmt(sample_format);
-    if (!ctx || !iq || f.kind != IN_WB || !found || !count) return PDT_ERR_ARG;
+    if (!ctx || !iq || f.kind != IN_WB || !results) return PDT_ERR_ARG;
     if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
-    SurveyPlan p;
-    int rc = survey_plan_ctx(ctx, cfg, nframes, cap, &p);
+    int rc = plan(search_range_hz(ctx));
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     if (!resident) {
         if (!channel_fits(ctx, nframes, f)) return PDT_ERR_NOMEM;
+        if (bursts) ctx->bursts_done = false;                               // (the rows of the last search: their capture may lie elsewhere)
         IngestSrc src;
         src.mem = (const unsigned char *)iq;
         if ((rc = ingest_whole(ctx, src, (size_t)nframes * (size_t)f.bytes))) return rc;
         iq = ctx->pcm.p;
     }
     ctx->held_src = nullptr;
-    if ((rc = survey_resident(ctx, iq, f, p, found, count))) return rc;
+    if ((rc = search(iq, f))) return rc;
     ctx->held_src = iq;
     ctx->held_frames = nframes;
     ctx->held_fmt = f.code;
     return PDT_OK;
+}
+
+static int survey_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
+                      int cap, int *count)
+{
+    SurveyPlan p;
+    return search_any(ctx, iq, resident, nframes, sample_format, found && count, false,
+                      [&](double range) { return survey_plan(cfg, range, (double)ctx->cfg.sample_rate, nframes, cap, &p); },
+                      [&](const void *x, const InFmt &f) { return survey_resident(ctx, x, f, p, found, count); });
 }
 
 int pdt_survey_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_survey_cfg *cfg, pdt_carrier *found,
@@ -1573,25 +1593,36 @@ static uint64_t bursts_slab_rows(const pdt_ctx *ctx, int nfft)
     return std::max<uint64_t>(1, BURST_SLAB_BYTES / ((size_t)nfft * sizeof(float)));
 }
 
+// The waterfall of nrows rows from `first` on, at most `slab` rows at a time in bursts_rows (ensured here): after the launch of rows
+// t0 .. t0 + nt - 1, each(t0, nt) does with them what the caller wants, the wait for the stream included.
+static int waterfall_slabs(pdt_ctx *ctx, const unsigned char *first, const InFmt &f, int nfft, int rows_per, uint64_t nrows, uint64_t slab,
+                           const std::function<int(uint64_t, uint64_t)> &each)
+{
+    int rc = ctx->bursts_rows.ensure((size_t)slab * (size_t)nfft * sizeof(float));
+    if (rc) return rc;
+    const size_t row_bytes = (size_t)rows_per * (size_t)nfft * (size_t)f.bytes;
+    for (uint64_t t0 = 0; t0 < nrows; t0 += slab) {
+        const uint64_t nt = std::min(slab, nrows - t0);
+        HIP_TRY(waterfall_launch(ctx->stream, f.code, first + (size_t)t0 * row_bytes, nt, rows_per, nfft, (const float *)ctx->survey_win.p,
+                                 (const float *)ctx->survey_tw.p, (float *)ctx->bursts_rows.p));
+        if ((rc = each(t0, nt))) return rc;
+    }
+    return PDT_OK;
+}
+
 // x: the capture, resident.  The survey's kernels first, as they are, for the floor (into the survey's device buffers: the context's
 // last survey spectrum lives on the host and stays); then slab by slab the rows and their peaks.  Nothing of the context's
 // demodulation state is touched.
 static int bursts_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const BurstPlan &p, const SurveyPlan &sp, pdt_burst *found, int cap, int *count)
 {
     ctx->bursts_done = false;
-    int rc = survey_tables(ctx, p.nfft);
-    if (!rc) rc = ctx->survey_part.ensure(survey_part_floats(sp.nseg, p.nfft) * sizeof(float));
+    const unsigned char *first = (const unsigned char *)x + (size_t)p.first * (size_t)f.bytes;
+    std::vector<float> P;
+    int rc = search_spectrum(ctx, first, f, sp.nseg, p.nfft, P);
     const uint64_t slab = std::min(bursts_slab_rows(ctx, p.nfft), p.nrows);
-    if (!rc) rc = ctx->bursts_rows.ensure((size_t)slab * (size_t)p.nfft * sizeof(float));
     if (!rc) rc = ctx->bursts_peaks.ensure((size_t)slab * BURST_ROW_PEAKS * sizeof(BurstPeak));
     if (!rc) rc = ctx->bursts_counts.ensure((size_t)slab * sizeof(int));
     if (rc) return rc;
-    const unsigned char *first = (const unsigned char *)x + (size_t)p.first * (size_t)f.bytes;
-    const float *win = (const float *)ctx->survey_win.p, *tw = (const float *)ctx->survey_tw.p;
-    HIP_TRY(survey_launch(ctx->stream, f.code, first, sp.nseg, p.nfft, win, tw, (float *)ctx->survey_part.p, (float *)ctx->survey_out.p));
-    std::vector<float> P((size_t)p.nfft);
-    HIP_TRY(hipMemcpyAsync(P.data(), ctx->survey_out.p, P.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     const double in_rate = (double)ctx->ch_decim * (double)ctx->cfg.sample_rate, floor = survey_floor(P.data(), p.nfft);
     const float level = burst_level(floor, p.threshold_db, p.rows_per);
     const int gb = burst_guard_bins(p.guard_hz, in_rate, p.nfft);
@@ -1599,10 +1630,7 @@ static int bursts_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const Bu
     ctx->bursts_pk.clear();
     ctx->bursts_cnt.assign((size_t)p.nrows, 0);
     std::vector<pdt_row_peak> back((size_t)slab * BURST_ROW_PEAKS);
-    const size_t row_bytes = (size_t)p.rows_per * (size_t)p.nfft * (size_t)f.bytes;
-    for (uint64_t t0 = 0; t0 < p.nrows; t0 += slab) {
-        const uint64_t nt = std::min(slab, p.nrows - t0);
-        HIP_TRY(waterfall_launch(ctx->stream, f.code, first + (size_t)t0 * row_bytes, nt, p.rows_per, p.nfft, win, tw, (float *)ctx->bursts_rows.p));
+    rc = waterfall_slabs(ctx, first, f, p.nfft, p.rows_per, p.nrows, slab, [&](uint64_t t0, uint64_t nt) -> int {
         HIP_TRY(row_peaks_launch(ctx->stream, (const float *)ctx->bursts_rows.p, nt, p.nfft, level, gb, ctx->bursts_peaks.p, (int *)ctx->bursts_counts.p));
         HIP_TRY(hipMemcpyAsync(back.data(), ctx->bursts_peaks.p, (size_t)nt * BURST_ROW_PEAKS * sizeof(BurstPeak), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipMemcpyAsync(&ctx->bursts_cnt[(size_t)t0], ctx->bursts_counts.p, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1612,7 +1640,9 @@ static int bursts_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const Bu
             if (c < 0 || c > BURST_ROW_PEAKS) return PDT_ERR_STATE;
             ctx->bursts_pk.insert(ctx->bursts_pk.end(), back.begin() + (size_t)t * BURST_ROW_PEAKS, back.begin() + (size_t)t * BURST_ROW_PEAKS + c);
         }
-    }
+        return PDT_OK;
+    });
+    if (rc) return rc;
     *count = bursts_link(ctx->bursts_pk.data(), ctx->bursts_cnt.data(), true, p, floor, in_rate, found, cap);
     ctx->bursts_nfft = p.nfft;
     ctx->bursts_rows_per = p.rows_per;
@@ -1624,32 +1654,15 @@ static int bursts_resident(pdt_ctx *ctx, const void *x, const InFmt &f, const Bu
     return PDT_OK;
 }
 
-// both entries, as survey_any: a capture in host memory goes into the context's input buffer, its ingest is not published
 static int bursts_any(pdt_ctx *ctx, const void *iq, bool resident, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg, pdt_burst *found,
                       int cap, int *count)
 {
-    const InFmt f = in_fmt(sample_format);
-    if (!ctx || !iq || f.kind != IN_WB || !found || !count) return PDT_ERR_ARG;
-    if (ctx->stream_open || !ctx->ch_decim) return PDT_ERR_STATE;
-    const double range = ctx->lp.pll_freq_range_hz != 0 ? ctx->lp.pll_freq_range_hz : ctx->cfg.mode == PDT_MODE_ARGOS ? 550.0 : 4500.0;
     BurstPlan p;
-    int rc = bursts_plan(cfg, range, (double)ctx->cfg.sample_rate, (double)ctx->ch_decim * (double)ctx->cfg.sample_rate, nframes, cap, &p);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    if (!resident) {
-        if (!channel_fits(ctx, nframes, f)) return PDT_ERR_NOMEM;
-        ctx->bursts_done = false;
-        IngestSrc src;
-        src.mem = (const unsigned char *)iq;
-        if ((rc = ingest_whole(ctx, src, (size_t)nframes * (size_t)f.bytes))) return rc;
-        iq = ctx->pcm.p;
-    }
-    ctx->held_src = nullptr;
-    if ((rc = bursts_resident(ctx, iq, f, p, bursts_survey_plan(p, cfg, nframes), found, cap, count))) return rc;
-    ctx->held_src = iq;
-    ctx->held_frames = nframes;
-    ctx->held_fmt = f.code;
-    return PDT_OK;
+    return search_any(ctx, iq, resident, nframes, sample_format, found && count, true,
+                      [&](double range) -> int {
+                          return bursts_plan(cfg, range, (double)ctx->cfg.sample_rate, (double)ctx->ch_decim * (double)ctx->cfg.sample_rate, nframes, cap, &p);
+                      },
+                      [&](const void *x, const InFmt &f) { return bursts_resident(ctx, x, f, p, bursts_survey_plan(p, cfg, nframes), found, cap, count); });
 }
 
 int pdt_bursts_device(pdt_ctx *ctx, const void *iq_device, uint64_t nframes, int sample_format, const pdt_bursts_cfg *cfg, pdt_burst *found,
@@ -1671,26 +1684,22 @@ int pdt_waterfall_rows(pdt_ctx *ctx, uint64_t first_row, uint64_t nrows, float *
     struct { int nfft, rows_per; uint64_t first; } p = { ctx->bursts_nfft, ctx->bursts_rows_per, ctx->bursts_first };
     if (!nrows || first_row >= ctx->bursts_nrows || nrows > ctx->bursts_nrows - first_row) return PDT_ERR_ARG;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
-    int rc = survey_tables(ctx, p.nfft);
-    const uint64_t slab = std::min(bursts_slab_rows(ctx, p.nfft), nrows);
-    if (!rc) rc = ctx->bursts_rows.ensure((size_t)slab * (size_t)p.nfft * sizeof(float));
+    const int rc = survey_tables(ctx, p.nfft);
     if (rc) return rc;
     const InFmt f = in_fmt(ctx->bursts_fmt);
     const size_t row_bytes = (size_t)p.rows_per * (size_t)p.nfft * (size_t)f.bytes;
     const unsigned char *first = (const unsigned char *)ctx->bursts_src + (size_t)p.first * (size_t)f.bytes + (size_t)first_row * row_bytes;
     const int log4 = survey_log4(p.nfft);
+    const uint64_t slab = std::min(bursts_slab_rows(ctx, p.nfft), nrows);
     std::vector<float> place((size_t)slab * (size_t)p.nfft);
-    for (uint64_t t0 = 0; t0 < nrows; t0 += slab) {
-        const uint64_t nt = std::min(slab, nrows - t0);
-        HIP_TRY(waterfall_launch(ctx->stream, f.code, first + (size_t)t0 * row_bytes, nt, p.rows_per, p.nfft, (const float *)ctx->survey_win.p,
-                                 (const float *)ctx->survey_tw.p, (float *)ctx->bursts_rows.p));
+    return waterfall_slabs(ctx, first, f, p.nfft, p.rows_per, nrows, slab, [&](uint64_t t0, uint64_t nt) -> int {
         HIP_TRY(hipMemcpyAsync(place.data(), ctx->bursts_rows.p, (size_t)nt * (size_t)p.nfft * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         for (uint64_t t = 0; t < nt; t++)                                   // place i of a row holds bin survey_rev(i)
             for (int i = 0; i < p.nfft; i++)
                 out[(size_t)(t0 + t) * (size_t)p.nfft + survey_rev((uint32_t)i, log4)] = place[(size_t)t * (size_t)p.nfft + (size_t)i];
-    }
-    return PDT_OK;
+        return PDT_OK;
+    });
 }
 
 int pdt_burst_peaks(const pdt_ctx *ctx, uint64_t first_row, uint64_t nrows, pdt_row_peak *out, int *counts)

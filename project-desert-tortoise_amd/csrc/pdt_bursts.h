@@ -51,7 +51,7 @@ constexpr int BURST_DEFAULT_NFFT = 4096;
 constexpr int BURST_DEFAULT_GAP_ROWS = 1;
 constexpr double BURST_SIDEBAND_DB = 25.0;      // a peak beside one this much stronger in its row, at most ...
 constexpr int BURST_SIDEBAND_GUARDS = 4;        // ... this many guards away, is its sideband (burst_link)
-constexpr int BURST_BATCH_SEGS = 64;            // segments one workgroup of k_waterfall takes: max(1, 64 / R) consecutive rows
+constexpr int BURST_BATCH_SEGS = 64;            // segments one workgroup of the waterfall takes: max(1, 64 / R) consecutive rows
 constexpr size_t BURST_SLAB_BYTES = (size_t)64 << 20;       // the rows resident at a time (the developer switch PDT_BURST_SLAB_ROWS: rows)
 
 struct BurstPeak {                 // (= pdt_row_peak of include/pdt.h), 16 bytes

@@ -1,6 +1,7 @@
-// pdt_bursts.hip -- short transmissions in a wideband capture (pdt_bursts.h): the survey's transform with the time axis kept
-// (k_waterfall: one row of power sums per R segments), the peaks of every row (k_row_peaks), and the host restatement
-// pdt_host_bursts with the linking of peaks into bursts and of bursts into platforms.  A unit of its own, beside pdt_survey.hip.
+// pdt_bursts.hip -- short transmissions in a wideband capture (pdt_bursts.h): the survey's transform with the time axis kept (the
+// waterfall: k_spectra of pdt_survey.hip, one row of power sums per R segments), the peaks of every row (k_row_peaks), and the host
+// restatement pdt_host_bursts with the linking of peaks into bursts and of bursts into platforms.  A unit of its own, beside
+// pdt_survey.hip.
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -13,35 +14,11 @@ static_assert(sizeof(pdt_row_peak) == sizeof(pdt::BurstPeak) && sizeof(pdt_row_p
 
 namespace pdt {
 
-// rows of one workgroup: about BURST_BATCH_SEGS segments, so that at small R the window and twiddle traffic and the launch are not
-// paid per row
-__host__ __device__ __forceinline__ int burst_rows_per_group(int rows_per)
+// rows of one workgroup of the waterfall's launch: about BURST_BATCH_SEGS segments, so that at small R the window and twiddle traffic
+// and the launch are not paid per row
+inline int burst_rows_per_group(int rows_per)
 {
     return rows_per >= BURST_BATCH_SEGS ? 1 : BURST_BATCH_SEGS / rows_per;
-}
-
-// x: the first sample of row 0 of this launch; nrows rows of R segments of N samples follow it.  rows: nrows x N floats, row t's
-// place i = the sum of bin survey_rev(i) (k_survey's partial rows are the same sums over SURVEY_RUN segments).
-template <int FMT, int N>
-__global__ void __launch_bounds__(N / 16) k_waterfall(const void *__restrict__ x, long long nrows, int rows_per, const float *__restrict__ win,
-                                                      const float *__restrict__ tw, float *__restrict__ rows)
-{
-    __shared__ __attribute__((aligned(16))) float2 sv[N];
-    constexpr int TB = N / 16;
-    const int t = threadIdx.x, per = burst_rows_per_group(rows_per);
-    const long long r0 = (long long)blockIdx.x * per, r1 = min(r0 + per, nrows);
-    for (long long r = r0; r < r1; r++) {
-        float acc[4][4];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int m = 0; m < 4; m++) acc[k][m] = 0.0f;
-        for (int s = 0; s < rows_per; s++) survey_segment<FMT, N>(sv, x, r * rows_per + s, win, tw, t, acc);
-        float *row = rows + (size_t)r * N;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            *reinterpret_cast<float4 *>(row + 4 * (t + TB * k)) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
-    }
 }
 
 constexpr int PEAKS_TB = 256;
@@ -119,30 +96,17 @@ using namespace pdt;
 
 namespace pdtrt {
 
-void survey_host_spectrum(int fmt, const void *x, const SurveyPlan &p, float *spectrum);      // pdt_survey.hip
+// pdt_survey.hip
+void survey_host_spectrum(int fmt, const void *x, const SurveyPlan &p, float *spectrum);
+hipError_t spectra_launch(hipStream_t st, int fmt, const void *x, uint64_t nseg, int per_row, int per_group, int nfft, const float *win, const float *tw,
+                          float *rows);
 
-// k_waterfall over nrows rows from x on (x: the first sample of the first of them): rows = nrows x nfft floats in place order
+// the waterfall of nrows rows from x on (x: the first sample of the first of them): rows = nrows x nfft floats in place order, row t's
+// place i = the sum of bin survey_rev(i) over its rows_per segments
 hipError_t waterfall_launch(hipStream_t st, int fmt, const void *x, uint64_t nrows, int rows_per, int nfft, const float *win, const float *tw, float *rows)
 {
-    if (!nrows || !survey_nfft(nfft) || !ddc_fmt(fmt) || rows_per < 1 || rows_per > BURST_MAX_ROWS_PER) return hipErrorInvalidValue;
-    const uint64_t per = (uint64_t)burst_rows_per_group(rows_per);
-    const unsigned groups = (unsigned)((nrows + per - 1) / per);
-#define PDT_WF_GO(F, N) hipLaunchKernelGGL((k_waterfall<F, N>), dim3(groups), dim3(N / 16), 0, st, x, (long long)nrows, rows_per, win, tw, rows)
-#define PDT_WF_FMT(F)                                   \
-    switch (nfft) {                                     \
-    case 1024: PDT_WF_GO(F, 1024); break;               \
-    case 4096: PDT_WF_GO(F, 4096); break;               \
-    default: PDT_WF_GO(F, 16384); break;                \
-    }
-    switch (fmt) {
-    case PDT_FMT_WB_PCM16: PDT_WF_FMT(PDT_FMT_WB_PCM16); break;
-    case PDT_FMT_WB_F32: PDT_WF_FMT(PDT_FMT_WB_F32); break;
-    case PDT_FMT_WB_CU8: PDT_WF_FMT(PDT_FMT_WB_CU8); break;
-    default: PDT_WF_FMT(PDT_FMT_WB_CS8); break;
-    }
-#undef PDT_WF_FMT
-#undef PDT_WF_GO
-    return hipGetLastError();
+    if (rows_per < 1 || rows_per > BURST_MAX_ROWS_PER) return hipErrorInvalidValue;
+    return spectra_launch(st, fmt, x, nrows * (uint64_t)rows_per, rows_per, burst_rows_per_group(rows_per) * rows_per, nfft, win, tw, rows);
 }
 
 // k_row_peaks over nrows rows of a slab: peaks = nrows x BURST_ROW_PEAKS records, counts = nrows
@@ -204,20 +168,6 @@ int bursts_link(const void *peaks, const int *counts, bool compact, const BurstP
 
 }  // namespace pdtrt
 
-// row t of the plan's stretch on the host, natural bin order (v, sum: room for N values)
-template <int FMT>
-static void host_row(const void *x, const BurstPlan &p, uint64_t t, const std::vector<float> &win, const std::vector<float> &tw, std::vector<SurveyC> &v,
-                     std::vector<float> &sum, float *row)
-{
-    const int N = p.nfft, log4 = survey_log4(N);
-    std::fill(sum.begin(), sum.end(), 0.0f);
-    for (int s = 0; s < p.rows_per; s++) {
-        survey_host_segment<FMT>(x, (long long)(p.first + (t * (uint64_t)p.rows_per + (uint64_t)s) * (uint64_t)N), win, tw, v);
-        for (int i = 0; i < N; i++) sum[(size_t)i] = sum[(size_t)i] + survey_power(v[(size_t)i]);
-    }
-    for (int i = 0; i < N; i++) row[survey_rev((uint32_t)i, log4)] = sum[(size_t)i];
-}
-
 extern "C" int pdt_host_bursts(uint32_t in_rate, double mode_range_hz, uint32_t channel_rate, int sample_format, const void *x, uint64_t nframes,
                                const pdt_bursts_cfg *cfg, float *rows_out, pdt_row_peak *peaks_out, int *peak_counts_out, pdt_burst *found, int cap,
                                int *count)
@@ -237,14 +187,12 @@ extern "C" int pdt_host_bursts(uint32_t in_rate, double mode_range_hz, uint32_t 
     std::vector<float> row((size_t)p.nfft), sum((size_t)p.nfft);
     std::vector<SurveyC> v((size_t)p.nfft);
     const std::vector<float> win = survey_window(p.nfft), tw = survey_twiddles(p.nfft);
+    const int log4 = survey_log4(p.nfft);
+    const uint64_t row_frames = (uint64_t)p.rows_per * (uint64_t)p.nfft;
     for (uint64_t t = 0; t < p.nrows; t++) {
         float *dst = rows_out ? rows_out + (size_t)t * (size_t)p.nfft : row.data();
-        switch (sample_format) {
-        case PDT_FMT_WB_PCM16: host_row<PDT_FMT_WB_PCM16>(x, p, t, win, tw, v, sum, dst); break;
-        case PDT_FMT_WB_F32: host_row<PDT_FMT_WB_F32>(x, p, t, win, tw, v, sum, dst); break;
-        case PDT_FMT_WB_CU8: host_row<PDT_FMT_WB_CU8>(x, p, t, win, tw, v, sum, dst); break;
-        default: host_row<PDT_FMT_WB_CS8>(x, p, t, win, tw, v, sum, dst); break;
-        }
+        survey_host_sum(sample_format, x, (long long)(p.first + t * row_frames), p.rows_per, win, tw, v, sum.data());
+        for (int i = 0; i < p.nfft; i++) dst[survey_rev((uint32_t)i, log4)] = sum[(size_t)i];        // natural bin order
         counts[(size_t)t] = burst_row_peaks(dst, p.nfft, level, gb, &peaks[(size_t)t * BURST_ROW_PEAKS]);
     }
     if (peaks_out) memcpy(peaks_out, peaks.data(), peaks.size() * sizeof(BurstPeak));

@@ -20,8 +20,11 @@ constexpr int DDC_MIN_DECIM = 2, DDC_MAX_DECIM = 64;
 constexpr int DDC_SPAN = 8;             // the filter reaches 8 D input samples each way: 16 D + 1 taps
 
 inline bool ddc_fmt(int fmt) { return fmt >= 16 && fmt <= 19; }         // PDT_FMT_WB_PCM16 .. PDT_FMT_WB_CS8
-// bytes of one complex input sample of wideband format fmt (PDT_FMT_WB_*)
-__host__ __device__ __forceinline__ int ddc_bytes(int fmt) { return fmt == 16 ? 4 : fmt == 17 ? 8 : 2; }
+// wideband format FMT (PDT_FMT_WB_*): the bytes of one complex input sample and the samples of one 16-byte load, for every kernel
+// that reads a capture (k_ddc, survey_segment of pdt_survey.h)
+template <int FMT> struct DdcFmt {
+    enum { BPS = FMT == 16 ? 4 : FMT == 17 ? 8 : 2, SPV = 16 / BPS };
+};
 
 // h[k + 8 D], 16 D + 1 floats
 inline std::vector<float> ddc_taps(int D)

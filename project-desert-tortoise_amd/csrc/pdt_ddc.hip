@@ -24,12 +24,6 @@ constexpr int DDC_VS = DDC_TILE + (2 * DDC_SPAN + 1) * DDC_MAX_DECIM;    // 3136
 constexpr int DDC_HS = 2 * DDC_SPAN * DDC_MAX_DECIM + 4;
 constexpr int DDC_TB = 256;                                              // lanes of a workgroup, at most
 
-template <int FMT> struct DdcVec;
-template <> struct DdcVec<PDT_FMT_WB_PCM16> { enum { SPV = 4 }; };
-template <> struct DdcVec<PDT_FMT_WB_F32> { enum { SPV = 2 }; };
-template <> struct DdcVec<PDT_FMT_WB_CU8> { enum { SPV = 8 }; };
-template <> struct DdcVec<PDT_FMT_WB_CS8> { enum { SPV = 8 }; };
-
 // the SPV samples of one aligned 16-byte load
 template <int FMT> __device__ __forceinline__ void ddc_unpack(const void *src, float2 *dst)
 {
@@ -131,8 +125,7 @@ __global__ void __launch_bounds__(DDC_TB) k_ddc(const DdcWindow one, const DdcWi
     const long long m0 = (long long)((int)blockIdx.x - w.tile0) * TO;
     const long long first = (m0 - DDC_SPAN) * D;                   // the record's input sample at image place 0
     const int len = (TO + 2 * DDC_SPAN) * D;                       // <= 2048 + 16 D; its image D ROWP <= DDC_VS
-    constexpr int BPS = FMT == PDT_FMT_WB_PCM16 ? 4 : FMT == PDT_FMT_WB_F32 ? 8 : 2;
-    constexpr int SPV = DdcVec<FMT>::SPV;
+    constexpr int BPS = DdcFmt<FMT>::BPS, SPV = DdcFmt<FMT>::SPV;
     for (int j = t; j <= 2 * DDC_SPAN * D; j += tb) hs[j] = taps[j];
     if (first >= w.lo && first + len <= w.hi) {
         const unsigned char *src = reinterpret_cast<const unsigned char *>(w.x) + first * BPS;

@@ -117,21 +117,15 @@ __device__ __forceinline__ int survey_at(int i)
     return i ^ (((i >> 5) & 3) * 5) ^ (((i >> 6) & 1) << 4);
 }
 
-template <int FMT> struct SurveyVec;
-template <> struct SurveyVec<PDT_FMT_WB_PCM16> { enum { SPV = 4, BPS = 4 }; };
-template <> struct SurveyVec<PDT_FMT_WB_F32> { enum { SPV = 2, BPS = 8 }; };
-template <> struct SurveyVec<PDT_FMT_WB_CU8> { enum { SPV = 8, BPS = 2 }; };
-template <> struct SurveyVec<PDT_FMT_WB_CS8> { enum { SPV = 8, BPS = 2 }; };
-
 // One segment (number seg of the stretch that starts at x) by the whole workgroup of N / 16 lanes, t = threadIdx.x: converted,
 // windowed, transformed in sv (N float pairs of LDS), its bins' powers added to the lane's sixteen sums.  Ends with a barrier: sv
-// is free again.  k_survey's runs and k_waterfall's rows (pdt_bursts.hip) are sums over calls of this one function.
+// is free again.  The survey's runs and the waterfall's rows are sums over calls of this one function (k_spectra, pdt_survey.hip).
 template <int FMT, int N>
 __device__ __forceinline__ void survey_segment(float2 *sv, const void *__restrict__ x, long long seg, const float *__restrict__ win,
                                                const float *__restrict__ tw, int t, float (&acc)[4][4])
 {
     constexpr int TB = N / 16, LOG4 = N == 1024 ? 5 : N == 4096 ? 6 : 7;
-    constexpr int BPS = SurveyVec<FMT>::BPS, SPV = SurveyVec<FMT>::SPV;
+    constexpr int BPS = DdcFmt<FMT>::BPS, SPV = DdcFmt<FMT>::SPV;
     const long long first = seg * N;
     const unsigned char *src = reinterpret_cast<const unsigned char *>(x) + first * BPS;
     int head = (int)(((16 - ((uintptr_t)src & 15)) & 15) / BPS);      // samples in front of the first 16-byte boundary
@@ -214,6 +208,31 @@ inline void survey_host_segment(const void *x, long long first, const std::vecto
             else
                 survey_bfly<false>(v[(size_t)i0], v[(size_t)(i0 + 1)], v[(size_t)(i0 + 2)], v[(size_t)(i0 + 3)], nullptr, nullptr, nullptr);
         }
+    }
+}
+
+// The sum of `count` consecutive segments on the host, the first of which begins at sample `first` of x: sum[i] = their powers at
+// place i, added in float in ascending order from 0 -- a run of the survey, a row of the waterfall (v: room for N = win.size() values)
+template <int FMT>
+inline void survey_host_sum_of(const void *x, long long first, int count, const std::vector<float> &win, const std::vector<float> &tw,
+                               std::vector<SurveyC> &v, float *sum)
+{
+    const int N = (int)win.size();
+    std::fill(sum, sum + N, 0.0f);
+    for (int s = 0; s < count; s++) {
+        survey_host_segment<FMT>(x, first + (long long)s * N, win, tw, v);
+        for (int i = 0; i < N; i++) sum[i] = sum[i] + survey_power(v[(size_t)i]);
+    }
+}
+
+inline void survey_host_sum(int fmt, const void *x, long long first, int count, const std::vector<float> &win, const std::vector<float> &tw,
+                            std::vector<SurveyC> &v, float *sum)
+{
+    switch (fmt) {
+    case PDT_FMT_WB_PCM16: survey_host_sum_of<PDT_FMT_WB_PCM16>(x, first, count, win, tw, v, sum); break;
+    case PDT_FMT_WB_F32: survey_host_sum_of<PDT_FMT_WB_F32>(x, first, count, win, tw, v, sum); break;
+    case PDT_FMT_WB_CU8: survey_host_sum_of<PDT_FMT_WB_CU8>(x, first, count, win, tw, v, sum); break;
+    default: survey_host_sum_of<PDT_FMT_WB_CS8>(x, first, count, win, tw, v, sum); break;
     }
 }
 

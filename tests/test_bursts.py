@@ -1,9 +1,14 @@
 """Short transmissions in a wideband capture, host side: pdt_host_bursts -- the waterfall, the rows' peaks and their linking into
 bursts restated on the host, bit for bit what the kernels and the context run -- against a float64 model of the rows
 and against gated tones whose times and offsets are known; no GPU needed."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
 from test_survey import FORMATS, NFFTS, SPECTRUM_BOUND, capture, scaled, window64
 
 ARGOS_RANGE = 550.0
@@ -64,6 +69,24 @@ def test_rows_match_float64_model(pdt, nfft, fmt):
         err = np.max(np.abs(got.astype(np.float64) - want)) / np.max(want)
         print(f"nfft {nfft} {fmt} R {per}: max |W - W64| / max W64 = {err:.3e}")
         assert err <= SPECTRUM_BOUND
+
+
+def test_spectra_digests(pdt):
+    """The bits of pdt_host_survey's spectrum and carriers and of pdt_host_bursts' rows, peaks, counts and bursts are those of the
+    commit that tests/golden/spectra_digests.json names, on the seeded inputs of tests/golden/make_spectra_digests.py: four formats,
+    three NFFT, a survey of 197 segments and 77 samples whole and as a stretch, burst searches at R = 1, 3, 8 and 64 that end with a
+    partial row and a partial segment.  An input whose own digest differs is reported as such: then numpy moved, not the library."""
+    spec = importlib.util.spec_from_file_location("make_spectra_digests", os.path.join(GOLDEN, "make_spectra_digests.py"))
+    make = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make)
+    with open(os.path.join(GOLDEN, "spectra_digests.json")) as f:
+        want = json.load(f)["digests"]
+    got = make.digests(pdt)
+    assert sorted(got) == sorted(want) and len(want) == 12 * (2 + 4)
+    assert [k for k in want if got[k]["input"] != want[k]["input"]] == [], "the test's own inputs differ"
+    assert [k for k in want if got[k] != want[k]] == []
+    assert all(want[k]["ncarriers"] >= 1 for k in want if k.startswith("survey"))
+    assert all(want[k]["npeaks"] >= 1 and want[k]["nbursts"] >= 1 for k in want if k.startswith("bursts"))
 
 
 def test_gated_tones_in_noise(pdt):

@@ -1,6 +1,6 @@
-"""The burst search on the GPU: k_waterfall's rows, k_row_peaks' peaks and the burst list against the host restatement bit for bit,
-captures off their pair boundary, a slab seam, that a burst search leaves no trace in a context, bursts -> burst_carriers ->
-set_channel -> demod_channels on two synthetic ARGOS platforms, and `-t bursts` on the command line."""
+"""The burst search on the GPU: the waterfall's rows (k_spectra), k_row_peaks' peaks and the burst list against the host restatement
+bit for bit, captures off their pair boundary, a slab seam, that a burst search leaves no trace in a context, bursts ->
+burst_carriers -> set_channel -> demod_channels on two synthetic ARGOS platforms, and `-t bursts` on the command line."""
 import os
 import re
 import subprocess
@@ -63,7 +63,9 @@ def same_search(pdt, d, x, dev=None, **cfg):
 def test_kernels_equal_host_restatement(pdt, nfft, fmt):
     """Rows (pdt_waterfall_rows), per-row peaks and the burst list are pdt_host_bursts', bit for bit, at R = 1, 3, 8 and 64; the
     capture ends with an incomplete row and an incomplete segment.  Row 1 has ten lines (the cap of eight is hit), row 2 is a tie
-    of every bin.  threshold_db 3: the floor is the median of the average over five rows, one of which is flat."""
+    of every bin.  threshold_db 3: the floor is the median of the average over five rows, one of which is flat.  At N = 1024 also
+    noise with one gated tone over several workgroups of several rows, the last workgroup short: R = 3, 47 rows (21 a workgroup) and
+    two segments and 11 samples, and R = 1, 130 rows (64 a workgroup) and 11 samples."""
     rng = np.random.default_rng(nfft + FORMATS.index(fmt))
     guard = 3.5 * IN_RATE / nfft
     with pdt.Demodulator(pdt.MODE_ARGOS, FS) as d:
@@ -81,6 +83,17 @@ def test_kernels_equal_host_restatement(pdt, nfft, fmt):
                                    nframes=3 * per * nfft + 9)
             assert d.bursts(x, nfft=nfft, rows_per=per, threshold_db=3.0, guard_hz=guard, first_frame=per * nfft - 5, nframes=3 * per * nfft + 9) == same[3]
             assert d.waterfall_rows(1, 2).tobytes() == same[0][1:3].tobytes()
+        if nfft == 1024:
+            # several workgroups of several rows, the last one short: R = 3 gives a workgroup 21 rows, R = 1 gives it 64
+            for per, nrows, extra in ((3, 47, 2 * nfft + 11), (1, 130, 11)):
+                tone = [(100, tone_amplitude(nfft, 0.05, 1000.0), [(nrows // 3, nrows // 4)])]
+                z = gated(rng, nfft, per, nrows, extra, 0.05, tone)
+                x = render(z[:, 0].astype(np.float64) + 1j * z[:, 1], fmt)
+                rows, _, counts, found = same_search(pdt, d, x, nfft=nfft, rows_per=per)
+                assert len(rows) == nrows and counts.sum() >= nrows // 4 and len(found) >= 1
+                for first in (20, 63):                                     # three rows across the first workgroup's last row
+                    if first + 3 <= nrows:
+                        assert d.waterfall_rows(first, 3).tobytes() == rows[first: first + 3].tobytes()
 
 
 @pytest.mark.parametrize("fmt", FORMATS)

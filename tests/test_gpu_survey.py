@@ -74,7 +74,7 @@ def test_kernels_equal_host_restatement(pdt, nfft, fmt):
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_capture_aligned_to_its_element_but_not_to_its_pair(pdt, fmt):
     """A resident capture that begins half a sample off a pair boundary (a multiple of the element's size: 2 bytes for int16, 4 for
-    float, 1 for the 8-bit formats): k_survey loads every segment sample by sample (head = N), and the spectrum is pdt_host_survey's
+    float, 1 for the 8-bit formats): k_spectra loads every segment sample by sample (head = N), and the spectrum is pdt_host_survey's
     of the same bytes.  More than one run of segments, 0, 1 and 3 whole samples further on too."""
     rng = np.random.default_rng(500 + FORMATS.index(fmt))
     in_rate, fs, D, nfft = 1000000, 250000, 4, 1024

@@ -1,11 +1,11 @@
 """The burst search of wideband captures: the 15-minute 2.4 Msps unsigned 8-bit capture of tools/survey_bench.py resident
 in HBM, searched at --nfft and --rows-per; wall time of the whole call (the survey for the floor, the slabs' kernels, read-back of the
-peaks, the host's linking), median of --reps, and the number of bursts found.  --survey times a survey at the same nfft in the same
-process, for the comparison of k_waterfall with k_survey.
+peaks, the host's linking), median of --reps, and the number of bursts found.
 
-Run it under `rocprofv3 --kernel-trace --stats -d DIR -o bursts -- python tools/burst_bench.py --nfft N --rows-per R --survey` for the
-kernels' own time; `--stats FILE` then turns that file's rows into time per call of k_waterfall, k_row_peaks and k_survey (a burst
-search of S slabs launches each of the first two S times: their times are summed over a call's slabs).
+Run it under `rocprofv3 --kernel-trace --stats -d DIR -o bursts -- python tools/burst_bench.py --nfft N --rows-per R` for the kernels'
+own time; `--stats FILE` then turns that file's rows into the total time and the launches of k_spectra, k_row_peaks and k_survey_sum.
+A burst search of S slabs launches k_spectra 1 + S times -- once over the stretch in runs of 64 segments for the floor, once per slab
+for the rows: one kernel, one name -- and k_row_peaks S times.
 """
 import argparse
 import csv
@@ -29,7 +29,7 @@ def kernel_times(path: str, calls: int) -> dict:
     out = {}
     with open(path) as f:
         for r in csv.DictReader(f):
-            for key in ("k_waterfall", "k_row_peaks", "k_survey_sum", "k_survey"):
+            for key in ("k_spectra", "k_row_peaks", "k_survey_sum"):
                 if key in r["Name"]:
                     out[key + "_ms"] = round(out.get(key + "_ms", 0.0) + float(r["TotalDurationNs"]) / 1e6, 3)
                     out[key + "_launches"] = out.get(key + "_launches", 0) + int(r["Calls"])
@@ -46,7 +46,6 @@ def main():
     ap.add_argument("--nfft", type=int, default=4096)
     ap.add_argument("--rows-per", type=int, default=8)
     ap.add_argument("--reps", type=int, default=4)
-    ap.add_argument("--survey", action="store_true", help="also time a survey at the same nfft")
     ap.add_argument("--stats", help="rocprofv3 kernel_stats.csv of an earlier run: print the kernels' total time and launches")
     a = ap.parse_args()
     n = int(a.seconds * a.rate)
@@ -81,13 +80,6 @@ def main():
             ts.append((time.perf_counter() - t0) * 1e3)
         out["call_ms"] = round(float(np.median(ts)), 2)
         out["bursts"] = len(found)
-        if a.survey:
-            ts = []
-            for _ in range(a.reps + 1):
-                t0 = time.perf_counter()
-                d.survey_device(dev.data_ptr(), n, pdt.FMT_WB_CU8, nfft=a.nfft)
-                ts.append((time.perf_counter() - t0) * 1e3)
-            out["survey_call_ms"] = round(float(np.median(ts[1:])), 2)
     print(json.dumps(out))
 
 

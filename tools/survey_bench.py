@@ -3,7 +3,7 @@ tools/channel_bench.py), surveyed at --nfft; wall time of the whole call (kernel
 median of --reps, and the carriers found.
 
 Run it under `rocprofv3 --kernel-trace --stats -d DIR -o survey -- python tools/survey_bench.py --nfft N` for the kernels' own time
-(k_survey and k_survey_sum in DIR/.../survey_kernel_stats.csv); `--stats FILE --nfft N` then turns that file's rows into time per call
+(k_spectra and k_survey_sum in DIR/.../survey_kernel_stats.csv); `--stats FILE --nfft N` then turns that file's rows into time per call
 and bytes read over time (2 B per input sample, read once), as a share of the 6.3 TB/s measured for a float4 copy.
 """
 import argparse
@@ -25,10 +25,10 @@ OFFSETS = (600000.0, -400000.0, 250000.0, -850000.0)
 
 def kernel_share(path: str, n: int, nfft: int) -> dict:
     with open(path) as f:
-        rows = [r for r in csv.DictReader(f) if "k_survey" in r["Name"]]
+        rows = list(csv.DictReader(f))
     out = {"nfft": nfft}
-    for key, pick in (("survey", lambda r: "k_survey_sum" not in r["Name"]), ("sum", lambda r: "k_survey_sum" in r["Name"])):
-        sel = [r for r in rows if pick(r)]
+    for key, name in (("survey", "k_spectra"), ("sum", "k_survey_sum")):
+        sel = [r for r in rows if name in r["Name"]]
         calls = sum(int(r["Calls"]) for r in sel)
         out[f"{key}_kernel_ms"] = round(sum(float(r["TotalDurationNs"]) for r in sel) / max(calls, 1) / 1e6, 3)
         out[f"{key}_calls"] = calls

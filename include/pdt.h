@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 12): every burst of a wideband capture in a window of its own -- pdt_window, pdt_burst_windows,
+/* 4, additions without a bump (round 13): the carrier of a channel stream as a measurement -- pdt_tone_cfg, pdt_tone, pdt_tones,
+ * pdt_tones_batch, pdt_host_tones: frequency, level and C/N0 of every burst's carrier, or of a channel's carrier at a stride (the
+ * Doppler curve).
+ * 4, additions without a bump (round 12): every burst of a wideband capture in a window of its own -- pdt_window, pdt_burst_windows,
  * pdt_demod_windows_device, pdt_demod_windows, pdt_demod_windows_held: the bursts of pdt_bursts, each cut out of the capture at its own
  * offset, all windows in one conversion launch.
  * 4, additions without a bump (round 11, test hooks only): pdt_device_math and pdt_device_math_layout -- the kernels' scalar
@@ -587,6 +590,55 @@ int  pdt_demod_windows_device(pdt_ctx *const *ctxs, int count, const pdt_window 
                               int sample_format);
 int  pdt_demod_windows(pdt_ctx *const *ctxs, int count, const pdt_window *win, const void *iq_host, uint64_t nframes, int sample_format);
 int  pdt_demod_windows_held(pdt_ctx *holder, pdt_ctx *const *ctxs, int count, const pdt_window *win);
+
+/* The carrier as a measurement: its frequency, its level and its C/N0.  ARGOS locates platforms from the Doppler shift of their carrier;
+ * pdt_burst.offset_hz is a centroid of 250 Hz bins and pdt_stats.lock_freq_hz the loop's integrator at one instant -- neither is a
+ * measurement.  Every ARGOS burst opens with 160 ms of unmodulated carrier and a window of pdt_burst_windows begins inside it; a POES
+ * channel carries a residual carrier all the time.  The channel stream of the context's last whole-capture call (PDT_ST_CHANNEL, in
+ * device memory) is cut into segments of nfft samples, segment i from first + i stride on; only segments wholly inside the stream are
+ * measured.  Each is Blackman-windowed and transformed as a segment of the survey is; the strongest bin with |f_b| <= search_hz is the
+ * peak (of equal ones the lowest bin), a log-parabola through it and its two neighbours gives frequency and level, and the float sum
+ * of the bins at circular distance noise_lo .. noise_hi from the peak gives the noise density.  The arithmetic is fixed (DESIGN 4.15,
+ * csrc/pdt_tone.h): pdt_host_tones restates it bit for bit on the host.
+ * pdt_tone_cfg: a zero in a field means its default -- nfft the largest of 1024, 4096, 16384 with nfft / Fs <= 0.128 s (PDT_ERR_ARG
+ * when there is none), search_hz the mode's PLL frequency range (pdt_loop_params.pll_freq_range_hz when set; pdt_host_tones, which has
+ * no mode: every bin but the band's edge), noise_lo 8 and noise_hi 71 (128 bins), first 0, stride nfft, count to the end of the stream.
+ *   pdt_tones        the context's channel stream: out[i] = segment i, *count = the number measured = min(cap, segments asked for and
+ *                    present) -- 0 for a stream shorter than first + nfft.  PDT_ERR_STATE when the last call left no PDT_ST_CHANNEL
+ *                    (no wideband capture yet, another kind of capture, a stream open or ended, a capture taken in pieces);
+ *                    PDT_ERR_ARG for an nfft that is not allowed, a negative or non-finite search_hz or one >= Fs / 2, noise_lo < 1,
+ *                    noise_lo > noise_hi, noise_hi >= nfft / 2, cap < 1.  Like a survey it leaves the context's results, stages,
+ *                    statistics, pdt_survey_spectrum and burst list exactly as they were (a profiled context's pdt_kernel_times
+ *                    gain the entry k_tones)
+ *   pdt_tones_batch  the same for `count` contexts in ONE launch (the windows of a round of pdt_demod_windows_*): context i's
+ *                    records at out + i cap_each, their number in counts[i].  The contexts must be distinct, live on one device and
+ *                    have one sample rate (else PDT_ERR_ARG); every one is checked as pdt_tones checks its own before anything runs
+ *   pdt_host_tones   test hook, host only: the same records for any float32 I,Q stream of n samples at `rate`; offset_hz stands for
+ *                    the context's channel offset
+ * pdt_tone: time_s = the segment's middle, (first + i stride + (nfft - 1) / 2) / Fs, in seconds of the channel stream; residual_hz
+ * = the carrier's frequency in the channel stream, freq_hz = the channel's offset + residual_hz, from the capture's centre; power = the
+ * carrier's power, |amplitude|^2 of the stream's samples; cn0_dbhz = 10 log10(power / noise density); then the raw record as the
+ * kernel leaves it: the peak's bin, the segment's power spectrum at bin - 1, bin, bin + 1 (wrapping at nfft), the noise bins' sum and
+ * their number.  valid = 0 -- a neighbour that is not > 0, no maximum in the log-parabola, an all-zero search set --: the frequencies
+ * are the bin's centre, power the bin's own, cn0_dbhz NaN.                                                                          */
+typedef struct pdt_tone_cfg {
+    int32_t nfft;
+    int32_t noise_lo, noise_hi;
+    int32_t reserved_;
+    double search_hz;
+    uint64_t first, stride, count;
+} pdt_tone_cfg;
+typedef struct pdt_tone {
+    double time_s, freq_hz, residual_hz, power, cn0_dbhz;
+    int32_t valid;
+    int32_t bin;
+    float below, peak, above, noise_sum;
+    int32_t noise_bins;
+    int32_t reserved_;
+} pdt_tone;
+int  pdt_tones(pdt_ctx *ctx, const pdt_tone_cfg *cfg, pdt_tone *out, int cap, int *count);
+int  pdt_tones_batch(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, pdt_tone *out, int cap_each, int *counts);
+int  pdt_host_tones(uint32_t rate, double offset_hz, const float *iq, uint64_t n, const pdt_tone_cfg *cfg, pdt_tone *out, int cap, int *count);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

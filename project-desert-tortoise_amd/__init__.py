@@ -250,6 +250,57 @@ def burst_windows(bursts, in_rate: int, capture_frames: int, skip_s: float = -1.
     return [Window(out[i].first_frame, out[i].nframes, out[i].offset_hz) for i in range(len(bursts))]
 
 
+class ToneCfg(C.Structure):
+    """pdt_tone_cfg: a zero means the default"""
+    _fields_ = [("nfft", C.c_int32), ("noise_lo", C.c_int32), ("noise_hi", C.c_int32), ("reserved_", C.c_int32), ("search_hz", C.c_double),
+                ("first", C.c_uint64), ("stride", C.c_uint64), ("count", C.c_uint64)]
+
+
+class ToneRec(C.Structure):
+    """pdt_tone"""
+    _fields_ = [("time_s", C.c_double), ("freq_hz", C.c_double), ("residual_hz", C.c_double), ("power", C.c_double), ("cn0_dbhz", C.c_double),
+                ("valid", C.c_int32), ("bin", C.c_int32), ("below", C.c_float), ("peak", C.c_float), ("above", C.c_float), ("noise_sum", C.c_float),
+                ("noise_bins", C.c_int32), ("reserved_", C.c_int32)]
+
+
+# pdt_tone as a numpy record: the derived doubles, the valid flag, then the raw record as the kernel leaves it
+TONE_DTYPE = np.dtype([("time_s", "<f8"), ("freq_hz", "<f8"), ("residual_hz", "<f8"), ("power", "<f8"), ("cn0_dbhz", "<f8"), ("valid", "<i4"),
+                       ("bin", "<i4"), ("below", "<f4"), ("peak", "<f4"), ("above", "<f4"), ("noise_sum", "<f4"), ("noise_bins", "<i4"),
+                       ("reserved_", "<i4")])
+
+
+def _tone_cfg(cfg: dict):
+    """keyword arguments of a carrier measurement -> (pdt_tone_cfg or None, capacity of the result: `cap`, default 4096)"""
+    cfg = dict(cfg)
+    cap = int(cfg.pop("cap", 4096))
+    unknown = set(cfg) - {f[0] for f in ToneCfg._fields_}
+    if unknown:
+        raise TypeError(f"unknown tone parameter(s): {sorted(unknown)}")
+    return (ToneCfg(**cfg) if cfg else None), cap
+
+
+def host_tones(rate: int, offset_hz: float, iq: np.ndarray, **cfg) -> np.ndarray:
+    """pdt_host_tones: the carrier measurement of a float32 I,Q stream at `rate` restated on the host (no GPU), bit for bit what the
+    kernel and the host's derivation compute.  offset_hz: what a context's channel offset would be; cfg: fields of pdt_tone_cfg (nfft,
+    search_hz, noise_lo, noise_hi, first, stride, count), zero or absent = the default, and cap.  Returns TONE_DTYPE[count]."""
+    a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+    c, cap = _tone_cfg(cfg)
+    out, count = np.zeros(max(cap, 1), dtype=TONE_DTYPE), C.c_int(0)
+    _check(lib().pdt_host_tones(rate, float(offset_hz), a.ctypes.data, a.size // 2, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)),
+           "pdt_host_tones")
+    return out[:count.value]
+
+
+def tones_batch(ds, **cfg):
+    """pdt_tones_batch: Demod.tones() of several contexts of one device in ONE launch (the windows of a round of demod_windows_held):
+    a list of TONE_DTYPE arrays, one per context."""
+    c, cap = _tone_cfg(cfg)
+    hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
+    out, counts = np.zeros((max(len(ds), 1), max(cap, 1)), dtype=TONE_DTYPE), (C.c_int * max(len(ds), 1))()
+    _check(lib().pdt_tones_batch(hs, len(ds), C.byref(c) if c else None, out.ctypes.data, cap, counts), "pdt_tones_batch")
+    return [out[i, :counts[i]].copy() for i in range(len(ds))]
+
+
 def _carriers(rec, count: int):
     return [Carrier(rec[i].offset_hz, rec[i].peak_db, rec[i].floor_power) for i in range(count)]
 
@@ -270,6 +321,7 @@ ABI_SYMBOLS = [
     "pdt_bursts", "pdt_bursts_device", "pdt_burst_carriers", "pdt_waterfall_rows", "pdt_bursts_shape", "pdt_burst_peaks", "pdt_host_bursts",
     "pdt_device_math", "pdt_device_math_layout",
     "pdt_burst_windows", "pdt_demod_windows_device", "pdt_demod_windows", "pdt_demod_windows_held",
+    "pdt_tones", "pdt_tones_batch", "pdt_host_tones",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_ddc"]        # include/pdt_dev.h (test-only)
 
@@ -418,6 +470,9 @@ def lib():
     L.pdt_demod_windows_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(WindowRec), C.c_void_p, C.c_uint64, C.c_int]
     L.pdt_demod_windows.argtypes = L.pdt_demod_windows_device.argtypes
     L.pdt_demod_windows_held.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(WindowRec)]
+    L.pdt_tones.argtypes = [C.c_void_p, C.POINTER(ToneCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_tones_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(ToneCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_host_tones.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.POINTER(ToneCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.pdt_device_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pdt_device_math_layout.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
@@ -786,6 +841,15 @@ class Demodulator:
             raise ValueError("demod_windows_held: lists of different lengths")
         hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
         _check(self._L.pdt_demod_windows_held(self._h, hs, len(ds), _window_recs(windows)), "pdt_demod_windows_held")
+
+    def tones(self, **cfg) -> np.ndarray:
+        """pdt_tones: the carrier of this context's channel stream (the last demod_channel / demod_windows call's), segment by segment:
+        TONE_DTYPE[count] with time_s, freq_hz, residual_hz, power, cn0_dbhz, valid and the raw record.  cfg: fields of pdt_tone_cfg
+        (nfft, search_hz, noise_lo, noise_hi, first, stride, count), zero or absent = the default, and cap (room for that many)."""
+        c, cap = _tone_cfg(cfg)
+        out, count = np.zeros(max(cap, 1), dtype=TONE_DTYPE), C.c_int(0)
+        _check(self._L.pdt_tones(self._h, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)), "pdt_tones")
+        return out[:count.value]
 
     def device_math(self, fn: int, records: np.ndarray) -> np.ndarray:
         """pdt_device_math (test hook): the kernels' scalar primitive `fn` evaluated on this context's GPU, one record per lane.

@@ -5,6 +5,7 @@
 #include "pdt_ddc.h"
 #include "pdt_survey.h"
 #include "pdt_bursts.h"
+#include "pdt_tone.h"
 
 #include <pthread.h>
 #include <sched.h>
@@ -30,6 +31,11 @@ hipError_t row_peaks_launch(hipStream_t st, const float *rows, uint64_t nrows, i
 int bursts_plan(const pdt_bursts_cfg *cfg, double mode_range_hz, double channel_rate, double in_rate, uint64_t nframes, int cap, pdt::BurstPlan *p);
 pdt::SurveyPlan bursts_survey_plan(const pdt::BurstPlan &p, const pdt_bursts_cfg *cfg, uint64_t nframes);
 int bursts_link(const void *peaks, const int *counts, bool compact, const pdt::BurstPlan &p, double floor, double in_rate, pdt_burst *found, int cap);
+// pdt_tone.hip
+hipError_t tones_launch(hipStream_t st, int nfft, const void *segs_dev, uint64_t nsegs, int lo, int hi, const float *win, const float *tw, void *out);
+int tone_plan(const pdt_tone_cfg *cfg, double fs, double range_hz, uint64_t len, int cap, pdt::TonePlan *p);
+void tone_sums(int nfft, double *sw, double *sw2);
+void tones_derive(const void *raw, const pdt::TonePlan &p, double fs, double offset_hz, double sw, double sw2, pdt_tone *out);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -1000,7 +1006,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
-                       &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table };
+                       &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1726,6 +1732,94 @@ int pdt_bursts_shape(const pdt_ctx *ctx, int *nfft, int *rows_per, uint64_t *nro
     if (rows_per) *rows_per = ctx->bursts_rows_per;
     if (nrows) *nrows = ctx->bursts_nrows;
     return PDT_OK;
+}
+
+// ---------------------------------------------------------------- carrier measurement (pdt_tone.h)
+// The segments of all contexts of a call in one launch over a table on the device, as the windows of a call are converted
+// (ddc_windows_launch): the first context supplies stream, tables and the two device buffers.  Every context is checked before
+// anything runs.  Nothing of any context's demodulation state is touched; a profiled first context's kernel times gain k_tones.
+static int tones_each(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, pdt_tone *out, int cap_each, int *counts)
+{
+    if (count < 0 || (count && (!ctxs || !out || !counts))) return PDT_ERR_ARG;
+    std::vector<TonePlan> plans((size_t)count);
+    for (int i = 0; i < count; i++) {
+        const pdt_ctx *c = ctxs[i];
+        if (!c) return PDT_ERR_ARG;
+        if (c->cfg.device != ctxs[0]->cfg.device || c->cfg.sample_rate != ctxs[0]->cfg.sample_rate) return PDT_ERR_ARG;
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == c) return PDT_ERR_ARG;
+        if (c->stream_open || !c->stage_len[PDT_ST_CHANNEL] || !c->channel.p) return PDT_ERR_STATE;
+        const int rc = tone_plan(cfg, (double)c->cfg.sample_rate, search_range_hz(c), c->stage_len[PDT_ST_CHANNEL], cap_each, &plans[(size_t)i]);
+        if (rc) return rc;
+    }
+    if (!count) return PDT_OK;
+    pdt_ctx *c0 = ctxs[0];
+    const int nfft = plans[0].nfft;
+    std::vector<ToneSeg> table;
+    for (int i = 0; i < count; i++) {
+        const TonePlan &p = plans[(size_t)i];
+        for (uint64_t k = 0; k < p.nseg; k++)
+            table.push_back(ToneSeg{ ctxs[i]->channel.p, (long long)(p.first + k * p.stride), (int32_t)table.size(), p.kmax });
+    }
+    if (table.size() > 0x7fffffffu) return PDT_ERR_ARG;
+    std::vector<ToneRaw> raw(table.size());
+    if (!table.empty()) {
+        HIP_TRY(hipSetDevice(c0->cfg.device));
+        int rc = survey_tables(c0, nfft);
+        if (!rc) rc = c0->tone_table.ensure(table.size() * sizeof(ToneSeg));
+        if (!rc) rc = c0->tone_out.ensure(table.size() * sizeof(ToneRaw));
+        if (rc) return rc;
+        // (the table of the previous call is no longer read: every call ends with a synchronize)
+        HIP_TRY(hipMemcpy(c0->tone_table.p, table.data(), table.size() * sizeof(ToneSeg), hipMemcpyHostToDevice));
+        hipEvent_t ea = nullptr, eb = nullptr;
+        if (c0->cfg.profile) {
+            HIP_TRY(hipEventCreate(&ea));
+            HIP_TRY(hipEventCreate(&eb));
+            HIP_TRY(hipEventRecord(ea, c0->stream));
+        }
+        HIP_TRY(tones_launch(c0->stream, nfft, c0->tone_table.p, table.size(), plans[0].noise_lo, plans[0].noise_hi, (const float *)c0->survey_win.p,
+                             (const float *)c0->survey_tw.p, c0->tone_out.p));
+        if (c0->cfg.profile) HIP_TRY(hipEventRecord(eb, c0->stream));
+        HIP_TRY(hipMemcpyAsync(raw.data(), c0->tone_out.p, raw.size() * sizeof(ToneRaw), hipMemcpyDeviceToHost, c0->stream));
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        if (c0->cfg.profile) {
+            pdt_kernel_time k;
+            memset(&k, 0, sizeof k);
+            snprintf(k.name, sizeof k.name, "k_tones");
+            k.launches = 1;
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ea, eb);
+            k.total_ms = ms;
+            (void)hipEventDestroy(ea);
+            (void)hipEventDestroy(eb);
+            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [](const pdt_kernel_time &o) { return !strcmp(o.name, "k_tones"); }),
+                             c0->ktimes.end());
+            c0->ktimes.push_back(k);
+        }
+    }
+    if (c0->tone_sum_nfft != nfft) {                                       // (the window's sums, once per context and NFFT)
+        tone_sums(nfft, &c0->tone_sw, &c0->tone_sw2);
+        c0->tone_sum_nfft = nfft;
+    }
+    size_t at = 0;
+    for (int i = 0; i < count; i++) {
+        const TonePlan &p = plans[(size_t)i];
+        tones_derive(raw.data() + at, p, (double)ctxs[i]->cfg.sample_rate, ctxs[i]->ch_offset, c0->tone_sw, c0->tone_sw2, out + (size_t)i * (size_t)cap_each);
+        counts[i] = (int)p.nseg;
+        at += (size_t)p.nseg;
+    }
+    return PDT_OK;
+}
+
+int pdt_tones_batch(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, pdt_tone *out, int cap_each, int *counts)
+{
+    return tones_each(ctxs, count, cfg, out, cap_each, counts);
+}
+
+int pdt_tones(pdt_ctx *ctx, const pdt_tone_cfg *cfg, pdt_tone *out, int cap, int *count)
+{
+    if (!ctx || !out || !count) return PDT_ERR_ARG;
+    return tones_each(&ctx, 1, cfg, out, cap, count);
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

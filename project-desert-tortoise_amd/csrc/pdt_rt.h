@@ -456,6 +456,10 @@ struct pdt_ctx {
     // windows of a capture (pdt_demod_windows_*): the conversion launch's table on the device (first context of a call); the capture
     // this context's last survey or burst search read, for pdt_demod_windows_held -- where it is, its frames and format
     DevBuf win_table;
+    // carrier measurement (pdt_tone.h): the launch's table of segments and its raw records on the device (first context of a call)
+    DevBuf tone_table, tone_out;
+    int tone_sum_nfft = 0;              // the window's sums below are those of this many points (0 = none yet)
+    double tone_sw = 0, tone_sw2 = 0;
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
     int held_fmt = 0;

@@ -57,6 +57,13 @@
  * start in the capture; one line per burst with its lock and its packets, then one summary line.  Bursts found but no packet in
  * any of them: the lines are printed, the file is removed as after any run without packets, exit status 0.  -t each:N (1 .. 64)
  * makes the pool N contexts: more rounds, less memory, the same file.
+ * -M <file> (an addition, with -x and a capture file): the carrier as a measurement (pdt_tones), written to <file>.  With
+ * -t each one line per window after each round, "%d %.5f %.2f %.1f %.1f": the window's index, the capture's seconds at the middle of
+ * the window's first segment, the carrier's frequency from the capture's centre in Hz, its C/N0 in dB-Hz and its power in dB; only the
+ * first segment of a window is measured, the 128 ms of unmodulated carrier a burst opens with.  With -t <kHz>, -t auto or -t bursts one
+ * line per segment at stride N along the channel, without the index: the Doppler curve (several channels: a file each, the index
+ * appended as to the output's name).  Not from a pipe, not with -l, and not for a capture that left no channel stream in one piece: a
+ * message, exit status 1.  Without -M nothing changes.
  */
 #include <ctype.h>
 #include <math.h>
@@ -73,14 +80,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -273,10 +280,33 @@ static int live_loop(FILE *in, FILE *out, const char *outFileName, double sample
     return 0;
 }
 
+/* -M: the carrier of ctx's channel stream, every segment at stride N, one line each (pdt_tones at its defaults).
+ * Returns 0 when the file is written. */
+static int write_tones(pdt_ctx *ctx, const char *name)
+{
+    const int cap = (int)(pdt_stage_len(ctx, PDT_ST_CHANNEL) / 1024 + 1);
+    pdt_tone *tones = (pdt_tone *)malloc((size_t)cap * sizeof *tones);
+    int n = 0;
+    const int rc = tones ? pdt_tones(ctx, NULL, tones, cap, &n) : PDT_ERR_NOMEM;
+    if (rc == PDT_ERR_STATE) printf("-M needs a wideband capture taken in one piece: this one left no channel stream\n");
+    else if (rc != PDT_OK) printf("Carrier measurement failed: %s\n", pdt_strerror(rc));
+    FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !m) printf("Error opening %s\n", name);
+    if (!m) {
+        free(tones);
+        return 1;
+    }
+    for (int i = 0; i < n; i++) fprintf(m, "%.5f %.2f %.1f %.1f\n", tones[i].time_s, tones[i].freq_hz, tones[i].cn0_dbhz, 10.0 * log10(tones[i].power));
+    fclose(m);
+    free(tones);
+    printf("Carrier: %d segments -> %s\n", n, name);
+    return 0;
+}
+
 /* -x with several -t: one wideband capture, one context per channel, the capture ingested once (pdt_demod_channels); every
  * channel's frames go to a file of its own, outFileName with ".<index>" appended */
 static int multi_channel(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim,
-                         const double *offsetsHz, int nch, const char *outFileName)
+                         const double *offsetsHz, int nch, const char *outFileName, const char *measureName)
 {
     pdt_ctx *ctxs[16];
     int rc = PDT_OK;
@@ -320,6 +350,10 @@ static int multi_channel(FILE *in, long data_offset, uint64_t nframes, size_t fr
         printf("%0.3f Ks : %llu Sym : %llu Bits : %llu " UNIT " -> %s\n", st.samples / 1000.0, (unsigned long long)st.symbols,
                (unsigned long long)st.bits, (unsigned long long)st.frames, name);
         if (st.frames == 0) remove(name);
+        if (measureName) {
+            snprintf(name, sizeof name, "%s.%d", measureName, i);
+            if (write_tones(ctxs[i], name)) return 1;
+        }
         pdt_close(ctxs[i]);
     }
     return 0;
@@ -473,7 +507,7 @@ static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t f
  * windows in rounds on a pool of contexts, from the copy of the capture the search left on the device (pdt_demod_windows_held).
  * Every window's records, their times counted from the capture's start, go to one file. */
 static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, double max_s,
-                      int poolSize, const char *outFileName)
+                      int poolSize, const char *outFileName, const char *measureName)
 {
     enum { POOL = 64 };
     pdt_ctx *holder = NULL, *pool[POOL];
@@ -494,9 +528,33 @@ static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame
     pdt_frame *all = NULL;
     uint64_t total = 0, room = 0;
     int locked = 0;
+    FILE *measure = measureName && rc == PDT_OK ? fopen(measureName, "w") : NULL;
+    if (measureName && rc == PDT_OK && !measure) {
+        printf("Error opening %s\n", measureName);
+        return 1;
+    }
     for (int r0 = 0; r0 < count && rc == PDT_OK; r0 += npool) {
         const int k = count - r0 < npool ? count - r0 : npool;
         rc = pdt_demod_windows_held(holder, pool, k, win + r0);
+        if (measure && rc == PDT_OK) {
+            /* -M: the first segment of every window of the round that holds one, all in one launch (pdt_tones_batch) */
+            pdt_ctx *with[POOL];
+            int index[POOL], counts[POOL], m = 0;
+            pdt_tone tones[POOL];
+            pdt_tone_cfg tc;
+            memset(&tc, 0, sizeof tc);
+            tc.count = 1;
+            for (int i = 0; i < k; i++)
+                if (pdt_stage_len(pool[i], PDT_ST_CHANNEL)) {
+                    with[m] = pool[i];
+                    index[m++] = r0 + i;
+                }
+            rc = pdt_tones_batch(with, m, &tc, tones, 1, counts);
+            for (int i = 0; i < m && rc == PDT_OK; i++)
+                if (counts[i])
+                    fprintf(measure, "%d %.5f %.2f %.1f %.1f\n", index[i], (double)win[index[i]].first_frame / (double)in_rate + tones[i].time_s,
+                            tones[i].freq_hz, tones[i].cn0_dbhz, 10.0 * log10(tones[i].power));
+        }
         for (int i = 0; i < k && rc == PDT_OK; i++) {
             const uint64_t n = pdt_num_frames(pool[i]);
             if (total + n > room) {
@@ -526,6 +584,7 @@ static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame
         if (pool[i]) pdt_close(pool[i]);
     pdt_close(holder);
     free(win);
+    if (measure) fclose(measure);
     if (rc != PDT_OK) {
         printf("Demodulation failed: %s\n", pdt_strerror(rc));
         free(all);
@@ -563,7 +622,7 @@ int main(int argc, char **argv)
     int autoBursts = 0;                                                             /* -t bursts[:N]: autoCarriers platforms, from the burst search */
     int eachBurst = 0;                                                              /* -t each[:N]: every burst in a window of its own, N contexts */
     double offsetsHz[16];
-    const char *outOverride = NULL;
+    const char *outOverride = NULL, *measureName = NULL;                            /* -M: the carrier measurement's file */
     char outFileName[1100];
 
     printf(BANNER);
@@ -662,6 +721,9 @@ int main(int argc, char **argv)
             offsetsHz[nOffsets++] = atof(optarg) * 1000.0;
             printf("Channel %d at %+f Khz\n", nOffsets - 1, atof(optarg));
             break;
+        case 'M':                                       /* the carrier of every burst, or of the channel at a stride, to this file */
+            measureName = optarg;
+            break;
         case 'B':                                       /* -t bursts: the longest transmission that is a burst, seconds (0: no limit) */
             burstMaxS = atof(optarg);
             if (!(burstMaxS >= 0)) {
@@ -720,6 +782,10 @@ int main(int argc, char **argv)
     const int from_stdin = live && strcmp(inFileName, "-") == 0;
     if (from_stdin && autoCarriers) {
         printf("-t %s needs a capture file: the spectrum of a stream is not known in advance\n", eachBurst ? "each" : autoBursts ? "bursts" : "auto");
+        return 1;
+    }
+    if (measureName && (from_stdin || live || !decim)) {
+        printf("-M needs a wideband capture file (-x) taken in one piece: not a pipe, not -l\n");
         return 1;
     }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
@@ -851,7 +917,7 @@ int main(int argc, char **argv)
     cfg.device = device;
     cfg.sampler = sampler;
     cfg.chain = live ? PDT_CHAIN_LIVE : PDT_CHAIN_FILE;
-    if (eachBurst) return each_burst(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, burstMaxS, eachBurst, outFileName);
+    if (eachBurst) return each_burst(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, burstMaxS, eachBurst, outFileName, measureName);
     if (autoCarriers) {
         if (autoBursts ? burst_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, burstMaxS, offsetsHz, &nOffsets)
                        : auto_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, offsetsHz, &nOffsets))
@@ -862,7 +928,7 @@ int main(int argc, char **argv)
             exit(1);
         }
     }
-    if (nOffsets > 1) return multi_channel(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, offsetsHz, nOffsets, outFileName);
+    if (nOffsets > 1) return multi_channel(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, offsetsHz, nOffsets, outFileName, measureName);
     pdt_ctx *ctx = NULL;
     const double t_open0 = now_ms();
     int rc = pdt_open(&cfg, &ctx);
@@ -941,6 +1007,11 @@ int main(int argc, char **argv)
         free(tmp);
     }
 #endif
+    if (measureName && write_tones(ctx, measureName)) {
+        fclose(out);
+        remove(outFileName);
+        exit(1);
+    }
     pdt_stats st;
     pdt_get_stats(ctx, &st);
     print_norm_and_lock(&prog, &st);                                 /* (what the progress function has not printed) */

@@ -1852,23 +1852,14 @@ int pdt_stage_bytesync_from(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbi
     DevScalars sc;
     memset(&sc, 0, sizeof sc);
     sc.nbits = nbits;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.copy(OP_H2D, d_sc, &sc, sizeof sc);
     if (nbits) PL.copy(OP_H2D, ctx->bits.p, bits_host, (size_t)nbits);
     PL.memset_async(ctx->frames.p, 0, (size_t)frame_cap * sizeof(FrameRec));
     PDT_LAUNCH(256, k_iota, dim3((unsigned)((bit_cap + 255) / 256)), dim3(256), 0, st, (unsigned *)ctx->bitsym.p,
                (long long *)ctx->symidx.p, bit_cap);
     launch_bytesync(ctx, PL, st, SP, d_sc, bit_cap, hit_cap, frame_cap, (long long)first_sync_end);
-    DevScalars *back = ctx->pend_sc;                                  // pinned
-    PL.copy(OP_D2H, back, d_sc, sizeof sc);
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    sc = *back;
+    if ((rc = oneshot_run(ctx, d_sc, &sc))) return rc;
     if (sc.nframes > frame_cap || (sc.sync_overflow && sc.nhits > hit_cap)) return PDT_ERR_STATE;
     std::vector<FrameRec> recs(sc.nframes);
     if (sc.nframes) HIP_TRY(hipMemcpy(recs.data(), ctx->frames.p, (size_t)sc.nframes * sizeof(FrameRec), hipMemcpyDeviceToHost));
@@ -1931,11 +1922,8 @@ int pdt_stage_mm(pdt_ctx *ctx, const void *in_host, uint64_t n, pdt_mm_state *st
                  uint64_t *nsym_out)
 {
     if (!ctx || (!in_host && n) || n >= (1ull << 30)) return PDT_ERR_ARG;
-    {
-        const double rg = ctx->cfg.mm_step_range != 0 ? ctx->cfg.mm_step_range : 3.0;
-        const double baud = ctx->cfg.mode == PDT_MODE_ARGOS ? 800.0 : 16640.3;
-        if (!(rg >= 0) || rg >= baud * 0.5) return PDT_ERR_ARG;                            // stepMax must stay positive and finite
-    }
+    // (the range the whole-capture entries refuse, against the context's own baud rate)
+    if (ctx->elem == 8 ? make_mm_params<double>(ctx, 0, 0, nullptr) : make_mm_params<float>(ctx, 0, 0, nullptr)) return PDT_ERR_ARG;
     if (ctx->stream_open) return PDT_ERR_STATE;              // (the stage buffers carry an open stream's tails)
     HIP_TRY(hipSetDevice(ctx->cfg.device));
     if (ctx->elem == 8) return stage_mm<double>(ctx, in_host, n, state, out_host, pick_out, nsym_out);
@@ -2658,19 +2646,13 @@ int pdt_tip_check(pdt_ctx *ctx, pdt_tip_summary *out)
     TipCounters *d_cnt = (TipCounters *)ctx->tip.p;
     TipFrame *d_rec = (TipFrame *)(d_cnt + 1);
     hipStream_t st = ctx->stream;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.memset_async(d_cnt, 0, sizeof(TipCounters));
     PDT_LAUNCH(256, k_tip_check, dim3((nf + 255) / 256), dim3(256), 0, st, (const FrameRec *)ctx->frames.p, nf, d_rec, d_cnt);
     TipCounters cnt;
     PL.copy(OP_D2H, &cnt, d_cnt, sizeof cnt);
     PL.copy(OP_D2H, ctx->tip_host.data(), d_rec, (size_t)nf * sizeof(TipFrame));
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = oneshot_run(ctx))) return rc;
     out->frames_checked = cnt.frames_checked;
     out->good_frames = cnt.good_frames;
     out->bad_chunks = cnt.bad_chunks;

@@ -305,6 +305,140 @@ template <typename T> int finish_capture(pdt_ctx *ctx, uint64_t n, const FinishA
     return PDT_OK;
 }
 
+// ---------------------------------------------------------------- launch recipes
+// One stage's launches on explicit pointers, lengths and parameters, recorded into PL.  The chain's rec_* methods call them where a
+// capture takes that path, the stage entries (stage_*, below) call them on caller data: one copy of every grid and LDS rule.
+
+// The AGC walkers' block and the cap of a block's warm-up, the caller's (pdt_config) or the defaults, in whole groups of four
+// samples (any values give the same output; they only move time around).
+// (the cap of a block's warm-up, which is 11 gain time constants = 11 gain / decay samples: weak input -- the noise in front
+// of a pass -- means a high gain and a long memory; capped at one second, every seam of a minute of noise failed its check
+// and was repaired in order, 219 ms; eight seconds cover gains up to ~700)
+inline void agc_block_warm(const pdt_ctx *ctx, long long *Ba, long long *Wa)
+{
+    const bool argos = ctx->cfg.mode == PDT_MODE_ARGOS;
+    const double fs_d = (double)ctx->cfg.sample_rate;
+    const int interp = (int)ctx->interp;
+    auto round4 = [](long long v) { return (v + 3) / 4 * 4; };
+    *Ba = std::max<long long>(64, round4(ctx->cfg.agc_block ? ctx->cfg.agc_block : (long long)((argos ? 0.125 : 0.0625) * fs_d * interp)));
+    *Wa = round4(ctx->cfg.agc_warm ? ctx->cfg.agc_warm : (long long)((argos ? 2.0 : 8.0) * fs_d * interp));
+}
+
+// StaticGain (main.c:384-389)
+template <typename T> void rec_static_gain(Plan &PL, hipStream_t st, IqSrc src, long long n, T *mag, T level, double norm_override, T *d_norm)
+{
+    PDT_LAUNCH(256, k_static_gain<T>, dim3(1), dim3(256), 0, st, src, n, mag, level, norm_override, d_norm);
+}
+
+// Squelch (twin main.c:370)
+template <typename T> void rec_squelch(Plan &PL, hipStream_t st, T *data, const T *lock, long long n, T thr)
+{
+    PDT_LAUNCH(256, k_squelch<T>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, st, data, lock, n, thr);
+}
+
+// the low-pass filter on its own (LowPassFilter.c:13-125): k_fir_plain (ARGOS), the register-tiled interpolating form -- which
+// also writes the AGC's affine tile maps when it is given a place for them -- or the generic one.  True: the register-tiled form.
+template <typename T> bool rec_fir_unfused(pdt_ctx *ctx, Plan &PL, hipStream_t st, const T *d_in, long long N, T *d_out, AgcMap *tile_maps, T agc_decay)
+{
+    const bool argos = ctx->cfg.mode == PDT_MODE_ARGOS;
+    const int interp = (int)ctx->interp, ntaps = (int)ctx->ntaps;
+    const T *d_taps = (const T *)ctx->taps.p;
+    const int opt = 8;
+    const long long tile = (long long)PDT_FIR_THREADS * opt;
+    const long long grid = (N * interp + tile - 1) / tile;
+    if (argos) {
+        const size_t sh = (size_t)(ntaps + tile + ntaps + 8) * sizeof(T);
+        PDT_LAUNCH(PDT_FIR_THREADS, k_fir_plain<T>, dim3((unsigned)grid), dim3(PDT_FIR_THREADS), sh, st, d_in, N, ntaps, d_taps, d_out, opt);
+        return false;
+    }
+    const int K = ntaps / interp;
+    if constexpr (std::is_same<T, float>::value) {                     // (the float chain: POES is never built in double)
+        const size_t sh_rt = (size_t)(65 * (K + 1) + 3 + 64 * K * interp) * sizeof(T);
+        const long long tiles_rt = (N + 64ll * K - 1) / (64ll * K);
+        // workgroups take tiles round robin; 32 per CU measured best (c3: 3.9 / 3.7 / 3.2 / 3.1 / 3.1 ms at 4 / 8 / 16 / 32 / 64):
+        // the taps come by scalar loads per residue, nothing is kept across tiles, and a finer grain balances the tail
+        const long long fir_tpb = ctx->tune.fir_wg_per_cu > 0 ? ctx->tune.fir_wg_per_cu : 32;
+        const unsigned grid_rt = (unsigned)std::min<long long>(tiles_rt, 256ll * fir_tpb);
+        if (K == 26 && sh_rt <= 64000 && ctx->taps_rot.p && !ctx->tune.fir_generic) {
+            switch (interp) {
+#define PDT_FIR_CASE(I)                                                                                                       \
+    case I:                                                                                                                   \
+        PDT_LAUNCH(PDT_FIR_THREADS, (k_fir_interp_rt<T, I, 26>), dim3(grid_rt), dim3(PDT_FIR_THREADS), sh_rt, st, d_in, N, (const T *)ctx->taps_rot.p, d_out, \
+                           tile_maps, agc_decay);                                                                             \
+        return true;
+                PDT_FIR_CASE(1) PDT_FIR_CASE(2) PDT_FIR_CASE(3) PDT_FIR_CASE(4) PDT_FIR_CASE(5) PDT_FIR_CASE(6) PDT_FIR_CASE(7) PDT_FIR_CASE(8)
+#undef PDT_FIR_CASE
+            }
+        }
+    }
+    const size_t sh = (size_t)(ntaps + tile / interp + K + 8) * sizeof(T);   // any other interpolation factor: generic form
+    PDT_LAUNCH(PDT_FIR_THREADS, k_fir_interp<T>, dim3((unsigned)grid), dim3(PDT_FIR_THREADS), sh, st, d_in, N, interp, K, d_taps, d_out, opt);
+    return false;
+}
+
+// NormalizingAGC through the per-lane block walkers (AGC.c:24-46,78-132): the affine block maps and the gain guesses from them
+// (own_maps; else the caller has written d_guess), then the walkers.  *ckpt: the gain checkpoints they left for rec_agc_fix, or none.
+template <typename T> int rec_agc_lanes(pdt_ctx *ctx, Plan &PL, hipStream_t st, const T *a_in, long long na, const AgcParams<T> &AP, T *d_norm,
+                                        long long Ba, long long Wa, bool own_maps, AgcMap *d_maps, double *d_guess, const T *a_lock, T *a_out, T **ckpt)
+{
+    const long long nb = (na + Ba - 1) / Ba;
+    if (own_maps) {
+        PDT_LAUNCH(256, k_agc_affine<T>, dim3((unsigned)nb), dim3(256), 0, st, a_in, na, AP.decay, Ba, d_maps);
+        PDT_LAUNCH(1024, k_agc_guess<T>, dim3(1), dim3(1024), 0, st, (const AgcMap *)d_maps, nb, (const T *)d_norm, d_guess, 1, nb);
+    }
+    // warm-up length in gain time constants: the affine guess is off by the accumulated float rounding of
+    // the true recurrence only, so a few time constants make the trajectories agree to the last bit
+    const double agc_K = ctx->tune.agc_k > 0 ? ctx->tune.agc_k : (sizeof(T) == 4) ? 11.0 : 34.0;
+    // the walkers of the double-precision build leave checkpoints (blocks of at least two of them)
+    *ckpt = nullptr;
+    if (sizeof(T) == 8 && Ba >= 2 * PDT_AGC_CKPT) {
+        const int rc = ctx->agc_ckpt.ensure((size_t)(nb + 64) * (size_t)(Ba / PDT_AGC_CKPT) * sizeof(T));
+        if (rc) return rc;
+        *ckpt = (T *)ctx->agc_ckpt.p;
+    }
+    PDT_LAUNCH(64, k_agc_block<T>, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st, a_in, na, AP, d_norm, Ba, Wa, (const double *)d_guess, a_lock,
+               a_out, (AgcSeam<T> *)ctx->seams_agc.p, agc_K, *ckpt);
+    return PDT_OK;
+}
+
+// ... and the repair of the seams that did not close, in order from the first one
+template <typename T> void rec_agc_fix(pdt_ctx *ctx, Plan &PL, hipStream_t st, const T *a_in, long long na, const AgcParams<T> &AP, long long Ba,
+                                       const T *a_lock, T *a_out, DevScalars *d_sc, T *ckpt)
+{
+    PDT_LAUNCH(1024, k_agc_scan<T>, dim3(1), dim3(1024), 0, st, na, Ba, (const AgcSeam<T> *)ctx->seams_agc.p, &d_sc->agc_first_bad);
+    PDT_LAUNCH(64, k_agc_fix<T>, dim3(1), dim3(64), 0, st, a_in, na, AP, Ba, a_lock, a_out, (AgcSeam<T> *)ctx->seams_agc.p, d_sc->counters,
+               (const long long *)&d_sc->agc_first_bad, ckpt);
+}
+
+// MMClockRecovery: sequential, one wavefront
+template <typename T> void rec_mm(Plan &PL, hipStream_t st, const T *in, const MmParams<T> &MP, T *d_sym, long long *d_symidx, DevScalars *d_sc,
+                                  long long sym_cap, const SamplerCarry<T> &carry_in, int have_carry, SamplerCarry<T> *carry_out)
+{
+    PDT_LAUNCH(PDT_GARDNER_THREADS, (k_mm<T, 8192, 1024>), dim3(1), dim3(PDT_GARDNER_THREADS), 0, st, in, MP, d_sym, d_symidx, &d_sc->nsym, sym_cap,
+               carry_in, have_carry, carry_out);
+}
+
+// GardenerClockRecovery by the sequential walker: one workgroup, chunk after chunk from the carried state
+template <typename T> void rec_gardner_walk(Plan &PL, hipStream_t st, const T *in, const T *lock, const GardnerParams<T> &GP, T *d_sym, long long *d_symidx,
+                                            DevScalars *d_sc, long long sym_cap, const SamplerCarry<T> &carry_in, SamplerCarry<T> *carry_out)
+{
+    PDT_LAUNCH(256, (k_gardner<T, GardnerLds<T>::LEN, GardnerLds<T>::OUT>), dim3(1), dim3(256), 0, st, in, lock, GP, d_sym, d_symidx, &d_sc->nsym,
+               sym_cap, (const GardnerEntry<T> *)nullptr, carry_in, carry_out, 0ll, 1, (const unsigned char *)nullptr);
+}
+
+// ManchesterDecode in three passes: tile summaries, their scan, emission.  pad: the history symbols in front of the first one to
+// decide; clock0 / bit0: the clock and the bits a stream has so far; clock_out: where the clock after the last symbol goes, or null.
+template <typename T> void rec_manch_3pass(Plan &PL, hipStream_t st, const T *d_sym, DevScalars *d_sc, T thr, ManchTile *d_tiles, long long n_tiles,
+                                           long long pad, unsigned clock0, unsigned long long bit0, unsigned *clock_out, unsigned char *d_bits,
+                                           unsigned *d_bitsym, long long bit_cap)
+{
+    const unsigned long long *d_nsym = &d_sc->nsym;
+    PDT_LAUNCH(PDT_TILE_THREADS, k_manch_tile<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, d_nsym, thr, d_tiles, pad);
+    PDT_LAUNCH(1024, k_manch_scan, dim3(1), dim3(1024), 0, st, d_tiles, d_nsym, &d_sc->nbits, pad, clock0, bit0, clock_out);
+    PDT_LAUNCH(PDT_TILE_THREADS, k_manch_emit<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, d_nsym, thr, d_tiles, d_bits, d_bitsym,
+               bit_cap, pad);
+}
+
 // The chain's launch recording for one capture (or one segment of a stream): every stage of POESTIPdemod/main.c:373-492 resp.
 // ARGOSdemod/main.c:250-306 recorded into the context's launch plan.  Round 6: one object per call, a method per stage (run_capture
 // was one function of 1 080 lines); what the stages share -- constants, geometry, capacities, device pointers -- are its members,
@@ -467,21 +601,12 @@ template <typename T> struct Chain {
             PP.phase0 = (T)seg->phase; PP.freq0 = (T)seg->freq; PP.avg0 = (T)seg->avg; PP.locksig0 = (T)seg->locksig;
             PP.sweep0 = (T)seg->sweep; PP.i0 = first;
         }
-        fsi = Fs * (T)interp;                                              // POESTIPdemod/main.c:429
-        AP.attack = ctx->lp.agc_attack != 0 ? (T)ctx->lp.agc_attack : (T)(79.5775 * (2.0 * M_PI / (double)fsi));
-        AP.decay = ctx->lp.agc_decay != 0 ? (T)ctx->lp.agc_decay : (T)(159.1549 * (2.0 * M_PI / (double)fsi));
+        fsi = output_rate<T>(ctx);
+        AP = make_agc_params<T>(ctx);
         AP.squelch = argos ? 1 : 0;
         AP.squelch_thr = (T)0.15;                                                  // ARGOSdemod/main.c:46,276
-        AP.raw_out = nullptr;
-        baud = ctx->lp.gardner_baud != 0 ? (T)ctx->lp.gardner_baud : argos ? (T)(400 * 2.0) : (T)(8320 * 2 + 0.3);   // main.c:90 / ARGOS main.c:64
-        GP.step = (T)(int)fsi / baud;                                              // GardenerClockRecovery.c:19
-        GP.kp = (ctx->lp.gardner_kp != 0 || (ctx->lp.zero_mask & PDT_LP_ZERO_GARDNER_KP)) ? (T)ctx->lp.gardner_kp : (T)3.0;
-        GP.lim = (ctx->lp.gardner_step_range != 0 || (ctx->lp.zero_mask & PDT_LP_ZERO_GARDNER_STEP_RANGE)) ? (T)ctx->lp.gardner_step_range : (T)0.1;
-        GP.n_total = n_out;
-        GP.chunk_out = chunk_out;
-        GP.argos_heap = 0;
-        GP.argos_field_bits = 0;
-        GP.argos_even = 0;
+        baud = sampler_baud<T>(ctx);
+        GP = make_gardner_params<T>(ctx, n_out, chunk_out);
         if (argos && (size_t)chunk * sizeof(T) < 128 * 1024) {                    // Q16, below M_MMAP_THRESHOLD
             // (sizeof(T) = 4: the ARGOS sound-card twin, whose buffers are `chunk` floats, ARGOSdemodPortAudio/main.c:61-63)
             const unsigned long long req = (unsigned long long)sizeof(T) * (unsigned long long)chunk;
@@ -491,7 +616,7 @@ template <typename T> struct Chain {
             GP.argos_even = (int)((csz - 8 - req) / sizeof(T));
         }
         argos_twin = argos && ctx->cfg.chain == PDT_CHAIN_LIVE;
-        manch_thr = (ctx->lp.manchester_threshold != 0 || (ctx->lp.zero_mask & PDT_LP_ZERO_MANCHESTER_THRESHOLD)) ? (T)ctx->lp.manchester_threshold : argos ? (T)0.5 : live ? (T)0.75 : (T)1.0;              // main.c:445 / ARGOS main.c:282 / twin :65,393
+        manch_thr = manchester_threshold<T>(ctx, argos, live);
         SP = make_sync_params(argos, argos_twin);
 
         return PDT_OK;
@@ -527,17 +652,13 @@ template <typename T> struct Chain {
             Wp = (long long)std::min(std::max(w, 0.15 * fs_d), 0.6 * fs_d);
         }
         Wacq = (long long)(0.02 * fs_d);             // acquisition-gain stage of the warm-up
-        Ba = ctx->cfg.agc_block ? ctx->cfg.agc_block : (long long)((argos ? 0.125 : 0.0625) * fs_d * interp);
+        agc_block_warm(ctx, &Ba, &Wa);
         // (Round 6, ARGOS captures demodulated many at a time -- pdt_demod_batch_device: between bursts the AGC's gain is high and its
         // memory, gain / decay samples, long: most walkers replay the whole two-second cap of their warm-up for a block of an eighth
         // of a second, every sample is read 17 times -- 64 captures: 83 GB, 28 ms of the batch's 81.  A single capture needs the many
         // short blocks for their lanes, a batch has lanes to spare: blocks of one second, every sample read three times.)
         // (two-second blocks were measured too, for 32 and 64 captures: 17.8 / 19.7 ms against 11.8 / 15.0 -- too few lanes then)
         if (argos && !ctx->cfg.agc_block && ctx->batch_hint >= 8) Ba = (long long)(1.0 * fs_d * interp);
-        // (the cap of a block's warm-up, which is 11 gain time constants = 11 gain / decay samples: weak input -- the noise in front
-        // of a pass -- means a high gain and a long memory; capped at one second, every seam of a minute of noise failed its check
-        // and was repaired in order, 219 ms; eight seconds cover gains up to ~700)
-        Wa = ctx->cfg.agc_warm ? ctx->cfg.agc_warm : (long long)((argos ? 2.0 : 8.0) * fs_d * interp);
         if (!ctx->cfg.pll_block) {
             // One walker wavefront saturates the vector ALU of its SIMD (a wave64 instruction occupies the 16 lanes for 4 clocks), so
             // a second one on the same SIMD doubles the time of both: keep the walkers of everything that runs together -- this
@@ -615,9 +736,8 @@ template <typename T> struct Chain {
         // ---- capacities
         min_step = (double)GP.step - 0.25;
         if (ctx->cfg.sampler == PDT_SAMPLER_MM) {
-            const double rg = ctx->cfg.mm_step_range != 0 ? ctx->cfg.mm_step_range : 3.0;
-            if (!(rg >= 0) || rg >= (double)baud * 0.5) return PDT_ERR_ARG;        // stepMax must stay positive and finite
-            min_step = (double)(int)fsi / ((double)baud + rg) * 0.999;
+            if ((rc = make_mm_params<T>(ctx, n_out, chunk_out, nullptr))) return rc;     // stepMax must stay positive and finite
+            min_step = (double)(int)fsi / ((double)baud + mm_step_range(ctx)) * 0.999;
         }
         n_chunks = chunk_out > 0 ? (n_out + chunk_out - 1) / chunk_out : 0;
         sym_cap = (long long)((double)n_out / min_step) + n_chunks + 64 + (seg ? 2 * PDT_SEG_KEEP : 0);
@@ -757,8 +877,7 @@ template <typename T> struct Chain {
             PL.copy(OP_H2D, d_norm, spin, sizeof(T));
         } else {
             L.begin("static_gain");
-            PDT_LAUNCH(256, k_static_gain<T>, dim3(1), dim3(256), 0, st, d_pcm, n0, (T *)ctx->mag.p, (T)1.0,
-                               ctx->cfg.norm_override, d_norm);
+            rec_static_gain<T>(PL, st, d_pcm, n0, (T *)ctx->mag.p, (T)1.0, ctx->cfg.norm_override, d_norm);
             L.end();
         }
 
@@ -1014,7 +1133,7 @@ template <typename T> struct Chain {
             quality_after_fir = quality && quality_term_fused;
             if (live) {                                            // twin main.c:370, DSP_SQLCH_THRESH 0.05 (:55)
                 L.begin("squelch");
-                PDT_LAUNCH(256, k_squelch<T>, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, st, d_pll, (const T *)d_lock, N, (T)0.05);
+                rec_squelch<T>(PL, st, d_pll, d_lock, N, (T)0.05);
                 L.end();
             }
         }
@@ -1054,77 +1173,46 @@ template <typename T> struct Chain {
         (void)rc;
         // ---- FIR
         if (n_out > 0) {
-            const int opt = 8;
-            const long long tile = (long long)PDT_FIR_THREADS * opt;
-            const long long grid = (n_out + tile - 1) / tile;
             L.begin(fuse_mix ? "mix_fir" : "fir");
-            if (argos) {
-                const size_t sh = (size_t)(ntaps + tile + ntaps + 8) * sizeof(T);
-                PDT_LAUNCH(PDT_FIR_THREADS, k_fir_plain<T>, dim3((unsigned)grid), dim3(PDT_FIR_THREADS), sh, st, d_pll, N, ntaps, d_taps,
-                                   d_fir, opt);
-            } else {
+            bool done = false;                                 // the kernel that writes the AGC's tile maps was taken
+            AgcMap *fir_tile_maps = nullptr;
+            if (!argos && agc_tiles_per_block > 0) {
+                // the AGC's affine tile maps are folded into the filter when the AGC blocks are whole FIR tiles
                 const int K = ntaps / interp;
-                const size_t sh_rt = (size_t)(65 * (K + 1) + 3 + 64 * K * interp) * sizeof(T);
                 const long long tiles_rt = (N + 64ll * K - 1) / (64ll * K);
-                // the AGC's affine tile maps are folded into this kernel when the AGC blocks are whole FIR tiles
-                AgcMap *fir_tile_maps = nullptr;
-                if (agc_tiles_per_block > 0) {
-                    if ((rc = ctx->agc_maps.ensure((size_t)(tiles_rt + 1) * sizeof(AgcMap) + (size_t)(nb_agc + 2) * (sizeof(double) + sizeof(AgcMap))))) return rc;
-                    fir_tile_maps = (AgcMap *)ctx->agc_maps.p;
-                    fused_tiles = tiles_rt;
-                }
-                // workgroups take tiles round robin; 32 per CU measured best (c3: 3.9 / 3.7 / 3.2 / 3.1 / 3.1 ms at 4 / 8 / 16 / 32 / 64):
-                // the taps come by scalar loads per residue, nothing is kept across tiles, and a finer grain balances the tail
-                const long long fir_tpb = ctx->tune.fir_wg_per_cu > 0 ? ctx->tune.fir_wg_per_cu : 32;
-                const unsigned grid_rt = (unsigned)std::min<long long>(tiles_rt, 256ll * fir_tpb);
-                bool done = false;
-                if constexpr (std::is_same<T, float>::value) if (fuse_mix) {
-                    // one map per run of 208 outputs instead of one per FIR tile of 1 664 (AGC blocks are whole tiles = 8 runs each)
-                    const long long runs_nat = (N + PDT_MF_RUN - 1) / PDT_MF_RUN;
-                    AgcMap *run_maps = nullptr;
-                    if (agc_tiles_per_block > 0) {
-                        if ((rc = ctx->agc_maps.ensure((size_t)(runs_nat + 1) * sizeof(AgcMap) + (size_t)(nb_agc + 2) * (sizeof(double) + sizeof(AgcMap))))) return rc;
-                        run_maps = (AgcMap *)ctx->agc_maps.p;
-                        fused_tiles = runs_nat;
-                        agc_maps_per_block = agc_tiles_per_block * (64 * 26 / PDT_MF_RUN);
-                    }
-                    // eight wavefronts per workgroup (two workgroups per CU = four wavefronts per SIMD)
-                    const unsigned mf_grid = (unsigned)(lt_tiles * (Bp / PDT_MF_RUN));
-                    // (a stream segment keeps the PLL output's tail: the next segment's filter starts from its last 25 samples)
-                    float *mf_pll = (ctx->keep_pll || seg) ? (float *)d_pll : (float *)nullptr;
-                    const long long mf_pll_from = (seg && !ctx->keep_pll) ? std::max<long long>(0, N - 256) : 0ll;
-    #define PDT_MF_ARGS d_pcm, (const float *)d_phi, (const float *)d_pll, N, Bp, (const PllLockInfo<float> *)d_info, (const float *)ctx->taps_rot.p, (float *)d_fir, mf_pll, run_maps, (float)AP.decay
-                    if (quality_after_fir) {
-                        float *d_tap = (float *)ctx->term_ap.p;
-                        if (d_pcm.fmt == 0) PDT_LAUNCH(512, (k_mix_fir<26, 0, 8, true>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, d_tap, mf_pll_from);
-                        else PDT_LAUNCH(512, (k_mix_fir<26, 1, 8, true>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, d_tap, mf_pll_from);
-                    } else {
-                        if (d_pcm.fmt == 0) PDT_LAUNCH(512, (k_mix_fir<26, 0, 8>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, (float *)nullptr, mf_pll_from);
-                        else PDT_LAUNCH(512, (k_mix_fir<26, 1, 8>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, (float *)nullptr, mf_pll_from);
-                    }
-    #undef PDT_MF_ARGS
-                    done = true;
-                }
-                if constexpr (std::is_same<T, float>::value) if (!done && K == 26 && sh_rt <= 64000 && ctx->taps_rot.p && !ctx->tune.fir_generic) {     // (the float chain: POES is never built in double)
-                    done = true;
-                    switch (interp) {
-    #define PDT_FIR_CASE(I)                                                                                                       \
-        case I:                                                                                                                   \
-            PDT_LAUNCH(PDT_FIR_THREADS, (k_fir_interp_rt<T, I, 26>), dim3(grid_rt), dim3(PDT_FIR_THREADS), sh_rt, st, d_pll, N, (const T *)ctx->taps_rot.p, d_fir, \
-                               fir_tile_maps, AP.decay);                                                                                    \
-            break;
-                        PDT_FIR_CASE(1) PDT_FIR_CASE(2) PDT_FIR_CASE(3) PDT_FIR_CASE(4) PDT_FIR_CASE(5) PDT_FIR_CASE(6) PDT_FIR_CASE(7) PDT_FIR_CASE(8)
-    #undef PDT_FIR_CASE
-                    default: done = false;
-                    }
-                }
-                if (!done) fused_tiles = 0;
-                if (!done) {                                       // any other interpolation factor: generic form
-                    const size_t sh = (size_t)(ntaps + tile / interp + K + 8) * sizeof(T);
-                    PDT_LAUNCH(PDT_FIR_THREADS, k_fir_interp<T>, dim3((unsigned)grid), dim3(PDT_FIR_THREADS), sh, st, d_pll, N, interp, K,
-                                       d_taps, d_fir, opt);
-                }
+                if ((rc = ctx->agc_maps.ensure((size_t)(tiles_rt + 1) * sizeof(AgcMap) + (size_t)(nb_agc + 2) * (sizeof(double) + sizeof(AgcMap))))) return rc;
+                fir_tile_maps = (AgcMap *)ctx->agc_maps.p;
+                fused_tiles = tiles_rt;
             }
+            if constexpr (std::is_same<T, float>::value) if (fuse_mix) {
+                // one map per run of 208 outputs instead of one per FIR tile of 1 664 (AGC blocks are whole tiles = 8 runs each)
+                const long long runs_nat = (N + PDT_MF_RUN - 1) / PDT_MF_RUN;
+                AgcMap *run_maps = nullptr;
+                if (agc_tiles_per_block > 0) {
+                    if ((rc = ctx->agc_maps.ensure((size_t)(runs_nat + 1) * sizeof(AgcMap) + (size_t)(nb_agc + 2) * (sizeof(double) + sizeof(AgcMap))))) return rc;
+                    run_maps = (AgcMap *)ctx->agc_maps.p;
+                    fused_tiles = runs_nat;
+                    agc_maps_per_block = agc_tiles_per_block * (64 * 26 / PDT_MF_RUN);
+                }
+                // eight wavefronts per workgroup (two workgroups per CU = four wavefronts per SIMD)
+                const unsigned mf_grid = (unsigned)(lt_tiles * (Bp / PDT_MF_RUN));
+                // (a stream segment keeps the PLL output's tail: the next segment's filter starts from its last 25 samples)
+                float *mf_pll = (ctx->keep_pll || seg) ? (float *)d_pll : (float *)nullptr;
+                const long long mf_pll_from = (seg && !ctx->keep_pll) ? std::max<long long>(0, N - 256) : 0ll;
+#define PDT_MF_ARGS d_pcm, (const float *)d_phi, (const float *)d_pll, N, Bp, (const PllLockInfo<float> *)d_info, (const float *)ctx->taps_rot.p, (float *)d_fir, mf_pll, run_maps, (float)AP.decay
+                if (quality_after_fir) {
+                    float *d_tap = (float *)ctx->term_ap.p;
+                    if (d_pcm.fmt == 0) PDT_LAUNCH(512, (k_mix_fir<26, 0, 8, true>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, d_tap, mf_pll_from);
+                    else PDT_LAUNCH(512, (k_mix_fir<26, 1, 8, true>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, d_tap, mf_pll_from);
+                } else {
+                    if (d_pcm.fmt == 0) PDT_LAUNCH(512, (k_mix_fir<26, 0, 8>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, (float *)nullptr, mf_pll_from);
+                    else PDT_LAUNCH(512, (k_mix_fir<26, 1, 8>), dim3(mf_grid), dim3(512), 0, st, PDT_MF_ARGS, (float *)nullptr, mf_pll_from);
+                }
+#undef PDT_MF_ARGS
+                done = true;
+            }
+            if (!done) done = rec_fir_unfused<T>(ctx, PL, st, (const T *)d_pll, N, d_fir, fir_tile_maps, AP.decay);
+            if (!done) fused_tiles = 0;
             L.end();
         }
 
@@ -1147,7 +1235,6 @@ template <typename T> struct Chain {
             if (APs.raw_out) APs.raw_out += first_out;
             const long long nb = (na + Ba - 1) / Ba;
             agc_last_block = nb - 1;
-            const long long grid = (nb + 63) / 64;
             const bool fused = fused_tiles > 0;                    // tile maps already written by the FIR kernel
             if (!fused && (rc = ctx->agc_maps.ensure((size_t)(nb + 1) * (sizeof(AgcMap) + sizeof(double))))) return rc;
             AgcMap *d_maps = (AgcMap *)ctx->agc_maps.p;
@@ -1158,22 +1245,17 @@ template <typename T> struct Chain {
             const long long map_first = fused ? first_out / map_len_fused : 0;
             const AgcMap *d_maps_in = d_maps + map_first;
             const long long n_maps_in = fused ? fused_tiles - map_first : nb;
-            // warm-up length in gain time constants: the affine guess is off by the accumulated float rounding of
-            // the true recurrence only, so a few time constants make the trajectories agree to the last bit
-            double agc_K = (sizeof(T) == 4) ? 11.0 : 34.0;
-            if (ctx->tune.agc_k > 0) agc_K = ctx->tune.agc_k;
             if (quality_side && !quality_term_fused) PL.simple(OP_JOIN_WAIT);          // the phases (in the AGC output's buffer) have been read
             L.begin("agc_block");
-            if (!fused) PDT_LAUNCH(256, k_agc_affine<T>, dim3((unsigned)nb), dim3(256), 0, st, a_in, na, APs.decay, Ba, d_maps);
             if (agc_maps_per_block == 0) agc_maps_per_block = agc_tiles_per_block;        // (the FIR kernel's maps: one per tile)
+            // the gain guesses from the FIR kernel's maps (not fused: rec_agc_lanes makes its own maps and guesses)
             if (fused && agc_maps_per_block > 1) {
                 AgcMap *d_bmaps = (AgcMap *)(d_guess + nb + 1);
                 PDT_LAUNCH(256, k_agc_blockmaps, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_maps_in, nb,
                                    (int)agc_maps_per_block, n_maps_in, d_bmaps);
                 PDT_LAUNCH(1024, k_agc_guess<T>, dim3(1), dim3(1024), 0, st, (const AgcMap *)d_bmaps, nb, (const T *)d_norm, d_guess, 1, nb);
-            } else
-            PDT_LAUNCH(1024, k_agc_guess<T>, dim3(1), dim3(1024), 0, st, d_maps_in, nb, (const T *)d_norm, d_guess,
-                               fused ? (int)agc_maps_per_block : 1, n_maps_in);
+            } else if (fused)
+                PDT_LAUNCH(1024, k_agc_guess<T>, dim3(1), dim3(1024), 0, st, d_maps_in, nb, (const T *)d_norm, d_guess, (int)agc_maps_per_block, n_maps_in);
             // (Round 3: walkers that store only the gain in front of every 16-sample batch + a streaming kernel that applies them were
             // slower, 4.2 against 3.3 ms at an hour of 250 ksps: the walkers are not held up by their output stores.)
             // Round 4: the walkers move whole lines (k_agc_block_tr) wherever the FIR kernel delivered its tile maps -- float chain,
@@ -1192,31 +1274,21 @@ template <typename T> struct Chain {
                         // -> 4 / 3 / 0 / 0 / 0 / 0 open seams, walkers 1.76 / 1.80 / 1.84 / 1.86 / 1.91 / 2.06 ms; a minute of noise in front:
                         // 3 / 1 / 2 / 1 / 1 / 0 and 12.1 ... 19.1 ms.  A seam that stays open is cheap since the repairs stop at the first
                         // checkpoint they reproduce.)
-                        if (ctx->tune.agc_k <= 0) agc_K = 12.0;
+                        const double agc_K = ctx->tune.agc_k > 0 ? ctx->tune.agc_k : 12.0;
                         const size_t ck_bytes = (size_t)(nb + 64) * (size_t)(Ba / PDT_AGC_CKPT + 1) * sizeof(float);
                         if ((rc = ctx->agc_ckpt.ensure(ck_bytes))) return rc;
                         agc_ckpt = (float *)ctx->agc_ckpt.p;
-                        PDT_LAUNCH(64, (k_agc_block_tr<PDT_AGC_TR_R>), dim3((unsigned)grid), dim3(64), 0, st, (const float *)a_in, na, APs,
+                        PDT_LAUNCH(64, (k_agc_block_tr<PDT_AGC_TR_R>), dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st, (const float *)a_in, na, APs,
                                    (const float *)d_norm, Ba, Wa, (const double *)d_guess, d_maps_in, (int)agc_maps_per_block,
                                    (int)(tile_len / map_len), n_maps_in, tile_len, (float *)a_out, (AgcSeam<float> *)ctx->seams_agc.p, agc_K, agc_ckpt);
                     }
                 }
             }
             T *agc_ckpt_any = (T *)agc_ckpt;
-            if (!agc_tr) {
-                // the per-lane walkers of the double-precision build leave checkpoints too (blocks of at least two of them)
-                if (sizeof(T) == 8 && Ba >= 2 * PDT_AGC_CKPT) {
-                    if ((rc = ctx->agc_ckpt.ensure((size_t)(nb + 64) * (size_t)(Ba / PDT_AGC_CKPT) * sizeof(T)))) return rc;
-                    agc_ckpt_any = (T *)ctx->agc_ckpt.p;
-                }
-                PDT_LAUNCH(64, k_agc_block<T>, dim3((unsigned)grid), dim3(64), 0, st, a_in, na, APs, d_norm, Ba, Wa,
-                                   (const double *)d_guess, a_lock, a_out, (AgcSeam<T> *)ctx->seams_agc.p, agc_K, agc_ckpt_any);
-            }
+            if (!agc_tr && (rc = rec_agc_lanes<T>(ctx, PL, st, a_in, na, APs, d_norm, Ba, Wa, !fused, d_maps, d_guess, a_lock, a_out, &agc_ckpt_any))) return rc;
             L.end();
             L.begin("agc_fix");
-            PDT_LAUNCH(1024, k_agc_scan<T>, dim3(1), dim3(1024), 0, st, na, Ba, (const AgcSeam<T> *)ctx->seams_agc.p, &d_sc->agc_first_bad);
-            PDT_LAUNCH(64, k_agc_fix<T>, dim3(1), dim3(64), 0, st, a_in, na, APs, Ba, a_lock, a_out,
-                               (AgcSeam<T> *)ctx->seams_agc.p, d_sc->counters, (const long long *)&d_sc->agc_first_bad, agc_ckpt_any);
+            rec_agc_fix<T>(ctx, PL, st, a_in, na, APs, Ba, a_lock, a_out, d_sc, agc_ckpt_any);
             L.end();
         }
 
@@ -1508,17 +1580,10 @@ template <typename T> struct Chain {
         } else if (use_mm) {
             // MMClockRecovery at the sampler's call site (SURVEY 8 row a13): sequential, one wavefront
             MmParams<T> MP;
-            const T rangeT = (T)(ctx->cfg.mm_step_range != 0 ? ctx->cfg.mm_step_range : 3.0);     // ARGOSdemod/main.c:277
-            MP.kp = (T)(ctx->cfg.mm_kp != 0 ? ctx->cfg.mm_kp : 0.15);
-            MP.step0 = (T)(int)fsi / baud;                                                        // MMClockRecovery.c:20
-            MP.step_max = (T)(int)fsi / (baud - rangeT);                                          // :9
-            MP.step_min = (T)(int)fsi / (baud + rangeT);                                          // :10
-            MP.n_total = n_out;
-            MP.chunk_out = chunk_out;
+            if ((rc = make_mm_params<T>(ctx, n_out, chunk_out, &MP))) return rc;
             L.begin("gardner");
             if (seg && !seg->have_sampler) carry_in.b = MP.step0;                 // (the M&M state starts at stepSize = Fs / baud, MMClockRecovery.c:20)
-            PDT_LAUNCH(PDT_GARDNER_THREADS, (k_mm<T, 8192, 1024>), dim3(1), dim3(PDT_GARDNER_THREADS), 0, st, (const T *)d_agc, MP, d_sym, d_symidx,
-                               &d_sc->nsym, sym_cap, carry_in, seg ? 1 : 0, d_carry_out);
+            rec_mm<T>(PL, st, d_agc, MP, d_sym, d_symidx, d_sc, sym_cap, carry_in, seg ? 1 : 0, d_carry_out);
             L.end();
         } else {
             L.begin("gardner");
@@ -1551,8 +1616,7 @@ template <typename T> struct Chain {
                 PDT_LAUNCH(256, (k_gardner_small<T, SMALL_LEN, SMALL_OUT>), dim3(1), dim3(256), 0, st, (const T *)d_agc, (const T *)d_lock, GP,
                                    d_sym, d_symidx, &d_sc->nsym, sym_cap);
             else
-                PDT_LAUNCH(256, (k_gardner<T, GardnerLds<T>::LEN, GardnerLds<T>::OUT>), dim3(1), dim3(256), 0, st, d_agc, d_lock, GP, d_sym, d_symidx,
-                                   &d_sc->nsym, sym_cap, (const GardnerEntry<T> *)nullptr, carry_in, d_carry_out, 0ll, 1, (const unsigned char *)nullptr);
+                rec_gardner_walk<T>(PL, st, d_agc, d_lock, GP, d_sym, d_symidx, d_sc, sym_cap, carry_in, d_carry_out);
             L.end();
         }
 
@@ -1567,12 +1631,8 @@ template <typename T> struct Chain {
         // ---- Manchester
         L.begin("manchester");
         if (ctx->tune.manch_3pass) {
-            PDT_LAUNCH(PDT_TILE_THREADS, k_manch_tile<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, &d_sc->nsym, manch_thr,
-                               d_tiles, sym_pad);
-            PDT_LAUNCH(1024, k_manch_scan, dim3(1), dim3(1024), 0, st, d_tiles, &d_sc->nsym, &d_sc->nbits, sym_pad, clock0, bit0,
-                               seg ? &d_tail->clock : (unsigned *)nullptr);
-            PDT_LAUNCH(PDT_TILE_THREADS, k_manch_emit<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, d_sym, &d_sc->nsym, manch_thr,
-                               d_tiles, d_bits, d_bitsym, bit_cap, sym_pad);
+            rec_manch_3pass<T>(PL, st, d_sym, d_sc, manch_thr, d_tiles, n_tiles, sym_pad, clock0, bit0, seg ? &d_tail->clock : (unsigned *)nullptr,
+                               d_bits, d_bitsym, bit_cap);
         } else {
             // one pass with look-back; its status words live where the tile summaries of the three passes would
             // (n_tiles records of 32 bytes hold the n_one + 1 <= n_tiles + 1 words)
@@ -1715,7 +1775,6 @@ template <typename T> int stage_manchester(pdt_ctx *ctx, const void *sym_host, u
     if ((rc = ctx->bitsym.ensure((size_t)bit_cap * sizeof(unsigned)))) return rc;
     if ((rc = ctx->hits.ensure((size_t)n_tiles * sizeof(ManchTile)))) return rc;
     if ((rc = ctx->scal.ensure(sizeof(DevScalars)))) return rc;
-    hipStream_t st = ctx->stream;
     T *d_sym = (T *)ctx->sym.p;
     ManchTile *d_tiles = (ManchTile *)ctx->hits.p;
     DevScalars *d_sc = (DevScalars *)ctx->scal.p;
@@ -1725,27 +1784,13 @@ template <typename T> int stage_manchester(pdt_ctx *ctx, const void *sym_host, u
     T hist[4] = { 0, 0, 0, 0 };
     hist[pad - 2] = (T)state->previous;
     hist[pad - 1] = (T)state->current;
-    const T thr = (T)thr_d;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.copy(OP_H2D, d_sc, &sc, sizeof sc);
     PL.copy(OP_H2D, d_sym, hist, (size_t)pad * sizeof(T));
     if (nsym) PL.copy(OP_H2D, d_sym + pad, sym_host, (size_t)nsym * sizeof(T));
-    PDT_LAUNCH(PDT_TILE_THREADS, k_manch_tile<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, (const T *)d_sym,
-               (const unsigned long long *)&d_sc->nsym, thr, d_tiles, pad);
-    PDT_LAUNCH(1024, k_manch_scan, dim3(1), dim3(1024), 0, st, d_tiles, (const unsigned long long *)&d_sc->nsym, &d_sc->nbits, pad,
-               (unsigned)(state->clockmod & 1u), 0ull, &d_sc->pad0_);
-    PDT_LAUNCH(PDT_TILE_THREADS, k_manch_emit<T>, dim3((unsigned)n_tiles), dim3(PDT_TILE_THREADS), 0, st, (const T *)d_sym,
-               (const unsigned long long *)&d_sc->nsym, thr, d_tiles, (unsigned char *)ctx->bits.p, (unsigned *)ctx->bitsym.p, bit_cap, pad);
-    DevScalars *back = ctx->pend_sc;                                  // pinned
-    PL.copy(OP_D2H, back, d_sc, sizeof sc);
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    sc = *back;
+    rec_manch_3pass<T>(PL, ctx->stream, d_sym, d_sc, (T)thr_d, d_tiles, n_tiles, pad, (unsigned)(state->clockmod & 1u), 0ull, &d_sc->pad0_,
+                       (unsigned char *)ctx->bits.p, (unsigned *)ctx->bitsym.p, bit_cap);
+    if ((rc = oneshot_run(ctx, d_sc, &sc))) return rc;
     if ((long long)sc.nbits > bit_cap) return PDT_ERR_STATE;
     if (sc.nbits && bits_out) HIP_TRY(hipMemcpy(bits_out, ctx->bits.p, (size_t)sc.nbits, hipMemcpyDeviceToHost));
     if (sc.nbits && bit_symbol_out) {
@@ -1776,55 +1821,18 @@ template <typename T> int stage_fir(pdt_ctx *ctx, const void *in_host, uint64_t 
     // so the local index of every input must equal its stream index modulo K: p zeros, the K last inputs, the new ones
     const long long p = argos ? 0 : (long long)(state->count % (uint64_t)K);
     const long long lead = p + K;
-    const long long N = lead + (long long)n, n_out = N * interp;
+    const long long N = lead + (long long)n;
     int rc;
     if ((rc = ctx->pll.ensure((size_t)(N + 1) * sizeof(T)))) return rc;
-    if ((rc = ctx->fir.ensure((size_t)(n_out + 1) * sizeof(T)))) return rc;
-    hipStream_t st = ctx->stream;
-    T *d_in = (T *)ctx->pll.p, *d_out = (T *)ctx->fir.p, *d_taps = (T *)ctx->taps.p;
+    if ((rc = ctx->fir.ensure((size_t)(N * interp + 1) * sizeof(T)))) return rc;
+    T *d_in = (T *)ctx->pll.p, *d_out = (T *)ctx->fir.p;
     std::vector<T> head((size_t)lead, (T)0);
     for (int i = 0; i < K; i++) head[(size_t)(p + i)] = (T)state->history[i];
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.copy(OP_H2D, d_in, head.data(), (size_t)lead * sizeof(T));
     if (n) PL.copy(OP_H2D, d_in + lead, in_host, (size_t)n * sizeof(T));
-    const int opt = 8;
-    const long long tile = (long long)PDT_FIR_THREADS * opt;
-    const long long grid = (n_out + tile - 1) / tile;
-    if (argos) {
-        const size_t sh = (size_t)(ntaps + tile + ntaps + 8) * sizeof(T);
-        PDT_LAUNCH(PDT_FIR_THREADS, k_fir_plain<T>, dim3((unsigned)grid), dim3(PDT_FIR_THREADS), sh, st, (const T *)d_in, N, ntaps,
-                   (const T *)d_taps, d_out, opt);
-    } else {
-        const size_t sh_rt = (size_t)(65 * (K + 1) + 3 + 64 * K * interp) * sizeof(T);
-        const long long tiles_rt = (N + 64ll * K - 1) / (64ll * K);
-        const unsigned grid_rt = (unsigned)std::min<long long>(tiles_rt, 256ll * 32);
-        bool done = false;
-        if constexpr (std::is_same<T, float>::value) if (K == 26 && sh_rt <= 64000 && ctx->taps_rot.p && !ctx->tune.fir_generic) {     // the kernel of the whole-capture path
-            done = true;
-            switch (interp) {
-#define PDT_FIR_CASE(I)                                                                                                       \
-    case I:                                                                                                                   \
-        PDT_LAUNCH(PDT_FIR_THREADS, (k_fir_interp_rt<T, I, 26>), dim3(grid_rt), dim3(PDT_FIR_THREADS), sh_rt, st, (const T *)d_in, N, (const T *)ctx->taps_rot.p, d_out, \
-                           (AgcMap *)nullptr, (T)0);                                                                          \
-        break;
-                PDT_FIR_CASE(1) PDT_FIR_CASE(2) PDT_FIR_CASE(3) PDT_FIR_CASE(4) PDT_FIR_CASE(5) PDT_FIR_CASE(6) PDT_FIR_CASE(7) PDT_FIR_CASE(8)
-#undef PDT_FIR_CASE
-            default: done = false;
-            }
-        }
-        if (!done) {
-            const size_t sh = (size_t)(ntaps + tile / interp + K + 8) * sizeof(T);
-            PDT_LAUNCH(PDT_FIR_THREADS, k_fir_interp<T>, dim3((unsigned)grid), dim3(PDT_FIR_THREADS), sh, st, (const T *)d_in, N, interp, K,
-                       (const T *)d_taps, d_out, opt);
-        }
-    }
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    rec_fir_unfused<T>(ctx, PL, ctx->stream, (const T *)d_in, N, d_out, (AgcMap *)nullptr, (T)0);
+    if ((rc = oneshot_run(ctx))) return rc;
     if (n && out_host)
         HIP_TRY(hipMemcpy(out_host, d_out + lead * interp, (size_t)n * (size_t)interp * sizeof(T), hipMemcpyDeviceToHost));
     // the ring after the call: the last K inputs, oldest first
@@ -1915,24 +1923,12 @@ template <typename T> int stage_gardner(pdt_ctx *ctx, const void *in_host, uint6
     memset(&fresh, 0, sizeof fresh);
     if (!state) state = &fresh;
     const bool argos = ctx->cfg.mode == PDT_MODE_ARGOS;
-    const int interp = (int)ctx->interp;
     const long long C = (long long)capacity, na = (long long)n;
     // The sampler's reads past the chunk (Q3: the mid-point index is not rolled over with nextSample) see what the caller's
     // buffer still holds behind element n -- for the kernels that is "the previous chunk of the stream": a stream of two
     // chunks of C, the buffer as it stands and then its first n elements, walked from chunk 1 on.
     const long long total = C + na;
-    const T Fs = (T)ctx->cfg.sample_rate;
-    const T fsi = Fs * (T)interp;
-    GardnerParams<T> GP;
-    const T baud = ctx->lp.gardner_baud != 0 ? (T)ctx->lp.gardner_baud : argos ? (T)(400 * 2.0) : (T)(8320 * 2 + 0.3);   // main.c:90 / ARGOS main.c:64
-    GP.step = (T)(int)fsi / baud;                                              // GardenerClockRecovery.c:19
-    GP.kp = (ctx->lp.gardner_kp != 0 || (ctx->lp.zero_mask & PDT_LP_ZERO_GARDNER_KP)) ? (T)ctx->lp.gardner_kp : (T)3.0;
-    GP.lim = (ctx->lp.gardner_step_range != 0 || (ctx->lp.zero_mask & PDT_LP_ZERO_GARDNER_STEP_RANGE)) ? (T)ctx->lp.gardner_step_range : (T)0.1;
-    GP.n_total = total;
-    GP.chunk_out = C;
-    GP.argos_heap = 0;
-    GP.argos_field_bits = 0;
-    GP.argos_even = 0;
+    GardnerParams<T> GP = make_gardner_params<T>(ctx, total, C);
     if (argos && neighbour_host && (size_t)C * 8 < 128 * 1024) {              // Q16: the array malloc'd behind this one
         const unsigned long long req = 8ull * (unsigned long long)C;
         GP.argos_heap = 1;
@@ -1947,16 +1943,13 @@ template <typename T> int stage_gardner(pdt_ctx *ctx, const void *in_host, uint6
     if ((rc = ctx->symidx.ensure((size_t)sym_cap * sizeof(long long)))) return rc;
     if ((rc = ctx->scal.ensure(sizeof(DevScalars)))) return rc;
     if ((rc = ctx->seg_dev.ensure(sizeof(SegTail<T>) + 256))) return rc;
-    hipStream_t st = ctx->stream;
     T *d_in = (T *)ctx->agc.p, *d_nb = (T *)ctx->lock.p;
     DevScalars *d_sc = (DevScalars *)ctx->scal.p;
     SegTail<T> *d_tail = (SegTail<T> *)ctx->seg_dev.p;
     SamplerCarry<T> carry_in;
     carry_in.a = (T)state->next_sample; carry_in.b = (T)state->prev_bit; carry_in.c = (T)state->half_sample;
     carry_in.c_first = 1; carry_in.count0 = 0;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.memset_async(d_sc, 0, sizeof(DevScalars));
     PL.copy(OP_H2D, d_in, in_host, (size_t)C * sizeof(T));
     if (na) PL.copy(OP_H2D, d_in + C, in_host, (size_t)na * sizeof(T));
@@ -1964,17 +1957,11 @@ template <typename T> int stage_gardner(pdt_ctx *ctx, const void *in_host, uint6
         PL.copy(OP_H2D, d_nb, neighbour_host, (size_t)C * sizeof(T));
         if (na) PL.copy(OP_H2D, d_nb + C, neighbour_host, (size_t)na * sizeof(T));
     }
-    PDT_LAUNCH(256, (k_gardner<T, GardnerLds<T>::LEN, GardnerLds<T>::OUT>), dim3(1), dim3(256), 0, st, (const T *)d_in,
-               (const T *)(GP.argos_heap ? d_nb : nullptr), GP, (T *)ctx->sym.p, (long long *)ctx->symidx.p, &d_sc->nsym, sym_cap,
-               (const GardnerEntry<T> *)nullptr, carry_in, &d_tail->sampler, 0ll, 1, (const unsigned char *)nullptr);
-    DevScalars *back = ctx->pend_sc;                                  // pinned
-    PL.copy(OP_D2H, back, d_sc, sizeof(DevScalars));
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t nsym = back->nsym;
+    rec_gardner_walk<T>(PL, ctx->stream, d_in, GP.argos_heap ? d_nb : nullptr, GP, (T *)ctx->sym.p, (long long *)ctx->symidx.p, d_sc, sym_cap, carry_in,
+                        &d_tail->sampler);
+    DevScalars sc;
+    if ((rc = oneshot_run(ctx, d_sc, &sc))) return rc;
+    const uint64_t nsym = sc.nsym;
     if ((long long)nsym > sym_cap) return PDT_ERR_STATE;
     if (nsym && out_host) HIP_TRY(hipMemcpy(out_host, ctx->sym.p, (size_t)nsym * sizeof(T), hipMemcpyDeviceToHost));
     if (nsym && pick_out) {
@@ -1997,26 +1984,18 @@ template <typename T> int stage_static_gain(pdt_ctx *ctx, const void *iq_host, u
     if ((rc = ctx->pcm.ensure((size_t)n * fb + 16))) return rc;
     if ((rc = ctx->mag.ensure((size_t)(n + 1) * sizeof(T)))) return rc;
     if ((rc = ctx->scal.ensure(sizeof(DevScalars)))) return rc;
-    hipStream_t st = ctx->stream;
     DevScalars *d_sc = (DevScalars *)ctx->scal.p;
     IqSrc src;
     src.p = ctx->pcm.p;
     src.fmt = fmt == PDT_FMT_F32 ? 1 : 0;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.memset_async(d_sc, 0, sizeof(DevScalars));
     PL.copy(OP_H2D, ctx->pcm.p, iq_host, (size_t)n * fb);
-    PDT_LAUNCH(256, k_static_gain<T>, dim3(1), dim3(256), 0, st, src, (long long)n, (T *)ctx->mag.p, (T)level, 0.0, (T *)&d_sc->norm);
-    DevScalars *back = ctx->pend_sc;                                  // pinned
-    PL.copy(OP_D2H, back, d_sc, sizeof(DevScalars));
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    rec_static_gain<T>(PL, ctx->stream, src, (long long)n, (T *)ctx->mag.p, (T)level, 0.0, (T *)&d_sc->norm);
+    DevScalars sc;
+    if ((rc = oneshot_run(ctx, d_sc, &sc))) return rc;
     T g;
-    memcpy(&g, &back->norm, sizeof(T));
+    memcpy(&g, &sc.norm, sizeof(T));
     if (gain_out) *gain_out = (double)g;
     return PDT_OK;
 }
@@ -2028,48 +2007,29 @@ template <typename T> int stage_mm(pdt_ctx *ctx, const void *in_host, uint64_t n
     memset(&fresh, 0, sizeof fresh);
     if (!state) state = &fresh;
     if (nsym_out) *nsym_out = 0;
-    const bool argos = ctx->cfg.mode == PDT_MODE_ARGOS;
-    const T Fs = (T)ctx->cfg.sample_rate;
-    const T fsi = Fs * (T)(int)ctx->interp;
-    const T baud = ctx->lp.gardner_baud != 0 ? (T)ctx->lp.gardner_baud : argos ? (T)(400 * 2.0) : (T)(8320 * 2 + 0.3);
+    int rc;
     MmParams<T> MP;
-    const T rangeT = (T)(ctx->cfg.mm_step_range != 0 ? ctx->cfg.mm_step_range : 3.0);     // ARGOSdemod/main.c:277
-    MP.kp = (T)(ctx->cfg.mm_kp != 0 ? ctx->cfg.mm_kp : 0.15);
-    MP.step0 = (T)(int)fsi / baud;                                                        // MMClockRecovery.c:20
-    MP.step_max = (T)(int)fsi / (baud - rangeT);                                          // :9
-    MP.step_min = (T)(int)fsi / (baud + rangeT);                                          // :10
-    MP.n_total = (long long)n;
-    MP.chunk_out = (long long)n;                                                          // one call = one chunk
+    if ((rc = make_mm_params<T>(ctx, (long long)n, (long long)n, &MP))) return rc;         // one call = one chunk
     if (!state->started) { state->started = 1; state->next_sample = 0; state->step_size = (double)MP.step0; state->sample_last = 0; }
     if (n == 0) return PDT_OK;
     const long long sym_cap = (long long)((double)n / ((double)MP.step_min * 0.999)) + 64;
-    int rc;
     if ((rc = ctx->agc.ensure((size_t)(n + 1) * sizeof(T)))) return rc;
     if ((rc = ctx->sym.ensure((size_t)sym_cap * sizeof(T)))) return rc;
     if ((rc = ctx->symidx.ensure((size_t)sym_cap * sizeof(long long)))) return rc;
     if ((rc = ctx->scal.ensure(sizeof(DevScalars)))) return rc;
     if ((rc = ctx->seg_dev.ensure(sizeof(SegTail<T>) + 256))) return rc;
-    hipStream_t st = ctx->stream;
     DevScalars *d_sc = (DevScalars *)ctx->scal.p;
     SegTail<T> *d_tail = (SegTail<T> *)ctx->seg_dev.p;
     SamplerCarry<T> carry_in;
     carry_in.a = (T)state->next_sample; carry_in.b = (T)state->step_size; carry_in.c = (T)state->sample_last;
     carry_in.c_first = 0; carry_in.count0 = 0;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.memset_async(d_sc, 0, sizeof(DevScalars));
     PL.copy(OP_H2D, ctx->agc.p, in_host, (size_t)n * sizeof(T));
-    PDT_LAUNCH(PDT_GARDNER_THREADS, (k_mm<T, 8192, 1024>), dim3(1), dim3(PDT_GARDNER_THREADS), 0, st, (const T *)ctx->agc.p, MP,
-               (T *)ctx->sym.p, (long long *)ctx->symidx.p, &d_sc->nsym, sym_cap, carry_in, 1, &d_tail->sampler);
-    DevScalars *back = ctx->pend_sc;                                  // pinned
-    PL.copy(OP_D2H, back, d_sc, sizeof(DevScalars));
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t nsym = back->nsym;
+    rec_mm<T>(PL, ctx->stream, (const T *)ctx->agc.p, MP, (T *)ctx->sym.p, (long long *)ctx->symidx.p, d_sc, sym_cap, carry_in, 1, &d_tail->sampler);
+    DevScalars sc;
+    if ((rc = oneshot_run(ctx, d_sc, &sc))) return rc;
+    const uint64_t nsym = sc.nsym;
     if ((long long)nsym > sym_cap) return PDT_ERR_STATE;
     if (nsym && out_host) HIP_TRY(hipMemcpy(out_host, ctx->sym.p, (size_t)nsym * sizeof(T), hipMemcpyDeviceToHost));
     if (nsym && pick_out) HIP_TRY(hipMemcpy(pick_out, ctx->symidx.p, (size_t)nsym * sizeof(long long), hipMemcpyDeviceToHost));
@@ -2087,62 +2047,35 @@ template <typename T> int stage_agc(pdt_ctx *ctx, void *data_host, uint64_t n, d
     pdt_agc_state fresh;
     memset(&fresh, 0, sizeof fresh);
     if (!state) state = &fresh;
-    const bool argos = ctx->cfg.mode == PDT_MODE_ARGOS;
-    const int interp = (int)ctx->interp;
-    const T Fs = (T)ctx->cfg.sample_rate;
-    const T fsi = Fs * (T)interp;                                              // POESTIPdemod/main.c:429
-    AgcParams<T> AP;
-    AP.attack = attack != 0 ? (T)attack : ctx->lp.agc_attack != 0 ? (T)ctx->lp.agc_attack : (T)(79.5775 * (2.0 * M_PI / (double)fsi));
-    AP.decay = decay != 0 ? (T)decay : ctx->lp.agc_decay != 0 ? (T)ctx->lp.agc_decay : (T)(159.1549 * (2.0 * M_PI / (double)fsi));
-    AP.squelch = 0;
-    AP.squelch_thr = 0;
-    AP.raw_out = nullptr;
+    const AgcParams<T> AP = make_agc_params<T>(ctx, attack, decay);
     const T gain0 = state->started ? (T)state->gain : (T)initial;              // AGC.c:91-95: `initial` counts on the first call only
     state->started = 1;
     if (n == 0) { state->gain = (double)gain0; return PDT_OK; }
     // the whole-capture path's block geometry (any values give the same output)
-    const double fs_d = (double)ctx->cfg.sample_rate;
-    auto round4 = [](long long v) { return (v + 3) / 4 * 4; };
-    long long Ba = ctx->cfg.agc_block ? ctx->cfg.agc_block : (long long)((argos ? 0.125 : 0.0625) * fs_d * interp);
-    long long Wa = ctx->cfg.agc_warm ? ctx->cfg.agc_warm : (long long)((argos ? 2.0 : 1.0) * fs_d * interp);
-    Ba = std::max<long long>(64, round4(Ba));
-    Wa = round4(Wa);
-    const long long na = (long long)n, nb = (na + Ba - 1) / Ba, grid = (nb + 63) / 64;
+    long long Ba, Wa;
+    agc_block_warm(ctx, &Ba, &Wa);
+    const long long na = (long long)n, nb = (na + Ba - 1) / Ba;
     int rc;
     if ((rc = ctx->fir.ensure((size_t)(na + 1) * sizeof(T)))) return rc;
     if ((rc = ctx->agc.ensure((size_t)(na + 1) * sizeof(T)))) return rc;
     if ((rc = ctx->seams_agc.ensure((size_t)(nb + 1) * sizeof(AgcSeam<T>)))) return rc;
     if ((rc = ctx->agc_maps.ensure((size_t)(nb + 1) * (sizeof(AgcMap) + sizeof(double))))) return rc;
     if ((rc = ctx->scal.ensure(sizeof(DevScalars)))) return rc;
-    hipStream_t st = ctx->stream;
     const T *a_in = (const T *)ctx->fir.p;
-    T *a_out = (T *)ctx->agc.p;
+    T *a_out = (T *)ctx->agc.p, *ckpt;
     DevScalars *d_sc = (DevScalars *)ctx->scal.p;
-    T *d_norm = (T *)&d_sc->norm;
     AgcMap *d_maps = (AgcMap *)ctx->agc_maps.p;
-    double *d_guess = (double *)(d_maps + nb + 1);
     DevScalars sc;
     memset(&sc, 0, sizeof sc);
     memcpy(&sc.norm, &gain0, sizeof(T));
-    double agc_K = (sizeof(T) == 4) ? 11.0 : 34.0;
-    if (ctx->tune.agc_k > 0) agc_K = ctx->tune.agc_k;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.copy(OP_H2D, d_sc, &sc, sizeof sc);
     PL.copy(OP_H2D, ctx->fir.p, data_host, (size_t)na * sizeof(T));
-    PDT_LAUNCH(256, k_agc_affine<T>, dim3((unsigned)nb), dim3(256), 0, st, a_in, na, AP.decay, Ba, d_maps);
-    PDT_LAUNCH(1024, k_agc_guess<T>, dim3(1), dim3(1024), 0, st, (const AgcMap *)d_maps, nb, (const T *)d_norm, d_guess, 1, nb);
-    PDT_LAUNCH(64, k_agc_block<T>, dim3((unsigned)grid), dim3(64), 0, st, a_in, na, AP, d_norm, Ba, Wa, (const double *)d_guess,
-               (const T *)nullptr, a_out, (AgcSeam<T> *)ctx->seams_agc.p, agc_K, (T *)nullptr);
-    PDT_LAUNCH(1024, k_agc_scan<T>, dim3(1), dim3(1024), 0, st, na, Ba, (const AgcSeam<T> *)ctx->seams_agc.p, &d_sc->agc_first_bad);
-    PDT_LAUNCH(64, k_agc_fix<T>, dim3(1), dim3(64), 0, st, a_in, na, AP, Ba, (const T *)nullptr, a_out, (AgcSeam<T> *)ctx->seams_agc.p,
-               d_sc->counters, (const long long *)&d_sc->agc_first_bad, (T *)nullptr);
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = rec_agc_lanes<T>(ctx, PL, ctx->stream, a_in, na, AP, (T *)&d_sc->norm, Ba, Wa, true, d_maps, (double *)(d_maps + nb + 1), (const T *)nullptr, a_out,
+                               &ckpt)))
+        return rc;
+    rec_agc_fix<T>(ctx, PL, ctx->stream, a_in, na, AP, Ba, (const T *)nullptr, a_out, d_sc, ckpt);
+    if ((rc = oneshot_run(ctx))) return rc;
     HIP_TRY(hipMemcpy(data_host, a_out, (size_t)na * sizeof(T), hipMemcpyDeviceToHost));      // in place, as the reference
     AgcSeam<T> last;
     HIP_TRY(hipMemcpy(&last, (const AgcSeam<T> *)ctx->seams_agc.p + (nb - 1), sizeof last, hipMemcpyDeviceToHost));
@@ -2157,19 +2090,11 @@ template <typename T> int stage_squelch(pdt_ctx *ctx, void *data_host, const voi
     int rc;
     if ((rc = ctx->agc.ensure((size_t)(n + 4) * sizeof(T)))) return rc;
     if ((rc = ctx->lock.ensure((size_t)(n + 4) * sizeof(T)))) return rc;
-    hipStream_t st = ctx->stream;
-    Plan &PL = ctx->plan;
-    PL.clear();
-    PL.side_stream = ctx->stream2;
+    Plan &PL = oneshot_begin(ctx);
     PL.copy(OP_H2D, ctx->agc.p, data_host, (size_t)n * sizeof(T));
     PL.copy(OP_H2D, ctx->lock.p, lock_host, (size_t)n * sizeof(T));
-    PDT_LAUNCH(256, k_squelch<T>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, st, (T *)ctx->agc.p, (const T *)ctx->lock.p, (long long)n,
-               (T)thr);
-    {
-        pdt_ctx *self = ctx;
-        if ((rc = execute_plans(&self, 1))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    rec_squelch<T>(PL, ctx->stream, (T *)ctx->agc.p, (const T *)ctx->lock.p, (long long)n, (T)thr);
+    if ((rc = oneshot_run(ctx))) return rc;
     HIP_TRY(hipMemcpy(data_host, ctx->agc.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost));
     memset(ctx->stage_len, 0, sizeof ctx->stage_len);
     return PDT_OK;

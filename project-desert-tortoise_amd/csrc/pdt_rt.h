@@ -582,6 +582,24 @@ struct PlanGroups {
 // (pdt_api.hip)
 int execute_plans(pdt_ctx *const *ctxs, int M);
 
+// The plan of a call that runs a few launches on its own and waits for them (the stage entries, pdt_tip_check): begin, record,
+// run.  With d_sc the device scalars come back through the context's pinned copy, into *sc.
+inline Plan &oneshot_begin(pdt_ctx *ctx)
+{
+    ctx->plan.clear();
+    ctx->plan.side_stream = ctx->stream2;
+    return ctx->plan;
+}
+inline int oneshot_run(pdt_ctx *ctx, const DevScalars *d_sc = nullptr, DevScalars *sc = nullptr)
+{
+    if (d_sc) ctx->plan.copy(OP_D2H, ctx->pend_sc, d_sc, sizeof(DevScalars));
+    const int rc = execute_plans(&ctx, 1);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (d_sc) *sc = *ctx->pend_sc;
+    return PDT_OK;
+}
+
 template <typename T> PllParams<T> make_pll_params(const pdt_ctx *ctx)
 {
     // call-site constants: POESTIPdemod/main.c:32-46,413 / ARGOSdemod/main.c:33-44,265
@@ -662,6 +680,72 @@ inline SyncParams make_sync_params(bool argos, bool argos_twin = false)
         SP.len = 19; SP.allow_inverse = 1; SP.span = 813; SP.first_bits = 5; SP.nbytes = 102; SP.prefix = 2;
     }
     return SP;
+}
+
+// ---- the loop constants behind the PLL: the mains' call-site constants or the caller's (pdt_set_loop_params), derived here once
+// for the whole-capture chain and for the stage entries alike
+template <typename T> T output_rate(const pdt_ctx *ctx) { return (T)ctx->cfg.sample_rate * (T)(int)ctx->interp; }   // POESTIPdemod/main.c:429
+
+// symbol rate of both samplers: Manchester half-bits (main.c:90 / ARGOS main.c:64)
+template <typename T> T sampler_baud(const pdt_ctx *ctx)
+{
+    return ctx->lp.gardner_baud != 0 ? (T)ctx->lp.gardner_baud : ctx->cfg.mode == PDT_MODE_ARGOS ? (T)(400 * 2.0) : (T)(8320 * 2 + 0.3);
+}
+
+// NormalizingAGC's rates: an argument of the call (pdt_stage_agc), else the context's, else the mains'.  Squelch off: the chain
+// sets its own.
+template <typename T> AgcParams<T> make_agc_params(const pdt_ctx *ctx, double attack = 0, double decay = 0)
+{
+    const double w = 2.0 * M_PI / (double)output_rate<T>(ctx);
+    AgcParams<T> AP;
+    AP.attack = attack != 0 ? (T)attack : ctx->lp.agc_attack != 0 ? (T)ctx->lp.agc_attack : (T)(79.5775 * w);
+    AP.decay = decay != 0 ? (T)decay : ctx->lp.agc_decay != 0 ? (T)ctx->lp.agc_decay : (T)(159.1549 * w);
+    AP.squelch = 0;
+    AP.squelch_thr = 0;
+    AP.raw_out = nullptr;
+    return AP;
+}
+
+// GardenerClockRecovery over n_total samples in chunks of chunk_out (the Q16 heap fields stay 0: their callers fill them)
+template <typename T> GardnerParams<T> make_gardner_params(const pdt_ctx *ctx, long long n_total, long long chunk_out)
+{
+    const pdt_loop_params &lp = ctx->lp;
+    GardnerParams<T> GP;
+    GP.step = (T)(int)output_rate<T>(ctx) / sampler_baud<T>(ctx);              // GardenerClockRecovery.c:19
+    GP.kp = (lp.gardner_kp != 0 || (lp.zero_mask & PDT_LP_ZERO_GARDNER_KP)) ? (T)lp.gardner_kp : (T)3.0;
+    GP.lim = (lp.gardner_step_range != 0 || (lp.zero_mask & PDT_LP_ZERO_GARDNER_STEP_RANGE)) ? (T)lp.gardner_step_range : (T)0.1;
+    GP.n_total = n_total;
+    GP.chunk_out = chunk_out;
+    GP.argos_heap = 0;
+    GP.argos_field_bits = 0;
+    GP.argos_even = 0;
+    return GP;
+}
+
+inline double mm_step_range(const pdt_ctx *ctx) { return ctx->cfg.mm_step_range != 0 ? ctx->cfg.mm_step_range : 3.0; }   // ARGOSdemod/main.c:277
+
+// MMClockRecovery at the sampler's call site.  PDT_ERR_ARG for a range that leaves stepMax not positive and
+// finite; MP may be null (the check alone).
+template <typename T> int make_mm_params(const pdt_ctx *ctx, long long n_total, long long chunk_out, MmParams<T> *MP)
+{
+    const T baud = sampler_baud<T>(ctx), rate = (T)(int)output_rate<T>(ctx);
+    const double rg = mm_step_range(ctx);
+    if (!(rg >= 0) || rg >= (double)baud * 0.5) return PDT_ERR_ARG;
+    if (!MP) return PDT_OK;
+    MP->kp = (T)(ctx->cfg.mm_kp != 0 ? ctx->cfg.mm_kp : 0.15);
+    MP->step0 = rate / baud;                                                   // MMClockRecovery.c:20
+    MP->step_max = rate / (baud - (T)rg);                                      // :9
+    MP->step_min = rate / (baud + (T)rg);                                      // :10
+    MP->n_total = n_total;
+    MP->chunk_out = chunk_out;
+    return PDT_OK;
+}
+
+// ManchesterDecode's resynchronisation threshold (main.c:445 / ARGOS main.c:282 / the sound-card twin :65,393)
+template <typename T> T manchester_threshold(const pdt_ctx *ctx, bool argos, bool live)
+{
+    if (ctx->lp.manchester_threshold != 0 || (ctx->lp.zero_mask & PDT_LP_ZERO_MANCHESTER_THRESHOLD)) return (T)ctx->lp.manchester_threshold;
+    return argos ? (T)0.5 : live ? (T)0.75 : (T)1.0;
 }
 
 // (pdt_api.hip)

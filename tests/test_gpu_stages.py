@@ -1,6 +1,8 @@
 """Stage-level entry points: the oracle's per-chunk dumps replayed stage by stage -- each chunk handed to ONE stage's
 kernels with the reference function's statics as an explicit state record (pdt_manchester_state, pdt_fir_state), chunk after
 chunk; the outputs must be the oracle's stage streams, the carried records what the reference's statics hold."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -117,16 +119,37 @@ def test_agc_stage_replays_the_oracle_chunk_by_chunk(pdt, orc, fs, chunk):
         assert got.tobytes() == want[:n].tobytes()
 
 
-def test_agc_and_squelch_stages_argos(pdt, orc):
+@functools.lru_cache(maxsize=None)
+def argos_agc_streams(pdt, orc):
+    """the oracle's FIR, pre-Squelch AGC, AGC and lock streams of one synthetic ARGOS capture (computed once, read only)"""
     iq = pdt.synth_capture(1, 32000, 8.0, f0_hz=160.0, seed=46)
     o = orc.Oracle(orc.ARGOS, 32000, iq)
-    x, raw, want, lock = o.stage(orc.ST_FIR), o.stage(orc.ST_AGC_RAW), o.stage(orc.ST_AGC), o.stage(orc.ST_LOCK)
+    streams = [o.stage(st) for st in (orc.ST_FIR, orc.ST_AGC_RAW, orc.ST_AGC, orc.ST_LOCK)]
+    for a in streams:
+        a.setflags(write=False)
+    return o.norm_factor, streams
+
+
+def test_agc_and_squelch_stages_argos(pdt, orc):
+    norm_factor, (x, raw, want, lock) = argos_agc_streams(pdt, orc)
     with pdt.Demodulator(pdt.MODE_ARGOS, 32000) as d:
         st = pdt.AgcState()
-        got = np.concatenate([d.stage_agc(x[a:b], o.norm_factor, st) for a, b in chunks_of(len(x), 2400)])
+        got = np.concatenate([d.stage_agc(x[a:b], norm_factor, st) for a, b in chunks_of(len(x), 2400)])
         assert got.tobytes() == raw.tobytes()                                   # NormalizingAGC alone: what -r dumps
         sq = np.concatenate([d.stage_squelch(got[a:b], lock[a:b], 0.15) for a, b in chunks_of(len(x), 2400)])
         assert sq.tobytes() == want.tobytes()                                   # ... then Squelch (ARGOSdemod/main.c:276)
+
+
+@pytest.mark.parametrize("agc_block", [2048, 64])
+def test_agc_stage_argos_every_seam_repaired(pdt, orc, agc_block):
+    """The double build's AGC hook with a warm-up far too short, so that every seam is repaired: through the walkers' gain
+    checkpoints (blocks of 2 048 = two checkpoints, the smallest that have any) and without them (blocks of 64)."""
+    norm_factor, (x, raw, _, _) = argos_agc_streams(pdt, orc)
+    n = 20 * 2400
+    with pdt.Demodulator(pdt.MODE_ARGOS, 32000, agc_block=agc_block, agc_warm=64) as d:
+        st = pdt.AgcState()
+        got = np.concatenate([d.stage_agc(x[a:b], norm_factor, st) for a, b in chunks_of(n, 2400)])
+        assert got.dtype == raw.dtype and got.tobytes() == raw[:n].tobytes()
 
 
 def as_complex_float(iq):
@@ -303,3 +326,27 @@ def test_mm_stage_replays_the_oracle_chunk_by_chunk(pdt, orc, mode, fs, chunk):
         assert np.concatenate(syms).tobytes() == o.stage(orc.ST_SYM).tobytes()
         assert np.array_equal(np.concatenate(picks), o.stage(orc.ST_SYMIDX))
         assert st.started == 1 and st.sample_last == float(syms[-1][-1])
+
+
+def test_mm_step_range_refused_against_the_callers_baud(pdt):
+    """M&M's stepMax = Fs / (baud - range) must stay positive: range < baud / 2, with the baud rate the samplers really use.
+    POES at 50 ksps, pdt_set_loop_params(gardner_baud=10000) (accepted: 5 samples a symbol): a range of 6 000 is below half the
+    mains' 16 640.3 and above half of 10 000 -- the stage entry refuses what the whole-capture entry refuses."""
+    fs, chunk = 50000, 10000
+    iq = pdt.synth_capture(0, fs, 3.0, seed=52)
+    with pdt.Demodulator(pdt.MODE_POES, fs, chunk=chunk, sampler=1, mm_step_range=6000.0) as d:
+        d.set_loop_params(gardner_baud=10000.0)
+        with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+            d.stage_mm(np.zeros(chunk, dtype=np.float32), pdt.MmState())
+        with pytest.raises(pdt.PdtError, match=r"\(-1\)"):
+            d.demod(iq)
+    # ... and a range it allows: the hook's replay of the context's own AGC stream, chunk by chunk, is its symbol stream
+    with pdt.Demodulator(pdt.MODE_POES, fs, chunk=chunk, sampler=1, mm_step_range=3.0) as d:
+        d.set_loop_params(gardner_baud=10000.0)
+        d.demod(iq)
+        x, want = d.stage(pdt.ST_AGC), d.stage(pdt.ST_SYM)
+        assert len(want) > 20000
+        st = pdt.MmState()
+        got = np.concatenate([d.stage_mm(x[a:b], st)[0] for a, b in chunks_of(len(x), chunk * d.stats_interp())])
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+

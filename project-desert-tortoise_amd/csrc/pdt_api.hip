@@ -1,5 +1,6 @@
 // pdt_api.hip -- libpdt.so: context management, kernel orchestration and the C ABI of
-// include/pdt.h.  Compiled for gfx950 only, with -ffp-contract=off (see pdt_device_math.h).
+// include/pdt.h (the host -> HBM ingest the entries go through: pdt_ingest.hip).  Compiled for gfx950 only, with
+// -ffp-contract=off (see pdt_device_math.h).
 #include "pdt_rt.h"
 #include "pdt_analytic.h"
 #include "pdt_ddc.h"
@@ -7,11 +8,7 @@
 #include "pdt_bursts.h"
 #include "pdt_tone.h"
 
-#include <pthread.h>
-#include <sched.h>
-#include <sys/mman.h>
 #include <sys/stat.h>
-#include <sys/syscall.h>
 
 namespace pdtrt {
 PDT_CHAIN_INSTANCES(extern, float)
@@ -42,11 +39,6 @@ hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *t
                               long long tiles);
 hipError_t ddc_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, pdt::DdcWindow w);
 }  // namespace pdtrt
-
-static std::atomic<int> g_open_contexts{0};          // contexts alive in this process (pdt_open / pdt_close)
-// One ingest per GPU at a time.  Two contexts on one GPU (bin/demodMulti's two lanes) that read their captures at once would
-// share the PCIe link and both arrive late; taking turns, the second one's capture arrives while the first one's chain runs.
-static std::mutex g_link_mu[64];
 
 static std::mutex g_dev_mu;
 static std::map<std::string, std::string> g_dev;
@@ -280,454 +272,6 @@ void chunk_reports_range(const pdt_ctx *ctx, uint64_t c0, uint64_t c1, uint64_t 
 
 
 }  // namespace pdtrt
-
-namespace {
-
-// ---------------------------------------------------------------- host -> HBM ingest
-// The capture (a file the caller opened, or host memory) is cut into 2 MiB spans.  A few host threads bring the spans into
-// pinned slots -- pread from the page cache resp. memcpy, ~5 GB/s per thread -- and queue one asynchronous copy per span on a
-// copy stream; a slot is refilled when its previous copy has completed.  The demodulation stream then waits for the last
-// copy.  (One pageable hipMemcpy of the whole capture runs at a fraction of the link rate and cannot start before the file
-// has been read.)  Small captures take the plain copy.
-struct IngestSrc {
-    const unsigned char *mem = nullptr;   // host memory, or
-    int fd = -1;                          // an open file ...
-    uint64_t off = 0;                     // ... and the byte offset of the first sample
-};
-constexpr size_t PDT_INGEST_SPAN_DEFAULT = 2u << 20;
-constexpr int PDT_INGEST_SLOTS = 2;      // per thread
-
-// An ingest that goes on in the background: every span has a flag that says its copy has been queued; the caller makes its
-// stream wait for the spans of a prefix (ingest_wait_mark) and starts work on it while the rest still arrives, and joins the
-// threads at the end (ingest_join).
-struct IngestJob {
-    std::vector<std::thread> pool;
-    std::unique_ptr<std::atomic<int>[]> submitted;
-    std::unique_ptr<std::atomic<int>[]> slot_state;                  // 0 free, 1 filled (to be copied), 2 copy in flight
-    std::unique_ptr<size_t[]> slot_span;                             // the span a filled slot holds (written before state 1)
-    std::unique_ptr<size_t[]> slot_delta;                            // ... and where in the slot its first byte lies (O_DIRECT reads start on a 4 KiB boundary of the file)
-    int fd_direct = -1;                                              // the capture file once more, opened with O_DIRECT (or -1)
-    ~IngestJob() { if (fd_direct >= 0) close(fd_direct); }
-    std::atomic<int> failed{0};
-    size_t nspans = 0, span = 0, waited = 0;
-    hipStream_t cs[4] = { nullptr, nullptr, nullptr, nullptr };      // the copy streams the spans go round robin over
-    int ncs = 0;
-    // prefixes the caller will wait for (bytes, ascending; set before ingest_capture): when the last span of prefix m has been
-    // queued the submitter records one event per copy stream -- behind that prefix's copies and in front of everything later --
-    // and raises mark_ready[m]
-    std::vector<size_t> mark_bytes;
-    std::vector<size_t> mark_spans;
-    std::unique_ptr<std::atomic<int>[]> mark_ready;
-};
-
-// ---- where a capture file's bytes are, and where they should be read (round 6)
-// Every byte of a capture crosses host memory three times on its way -- out of the page cache, into a pinned slot, out again by
-// the DMA engine -- unless the file is read with O_DIRECT straight into the pinned slots: two.  At N = 8 GPUs the first is
-// ~1.3 TB/s of host traffic against the ~1.0 - 1.1 the two sockets deliver.  O_DIRECT is right for a file that is NOT
-// in the page cache (it then comes from the device either way; the copy through the cache is pure overhead) and wrong for one
-// that is (tmpfs does not offer it at all): a probe of the file's pages decides.  The same probe says on which NUMA node the
-// cached pages lie (move_pages); what to do with that is ingest_capture's decision (measured: see there).
-struct FilePlacement {
-    double resident = 1.0;      // fraction of the sampled pages that are in the page cache (1 = nothing to gain from O_DIRECT)
-    int node = -1;              // the NUMA node that holds most of the resident ones (-1 = unknown / mixed)
-};
-static FilePlacement probe_file(int fd, uint64_t off, size_t bytes)
-{
-    FilePlacement fp;
-    const long page = sysconf(_SC_PAGESIZE);
-    if (page <= 0 || bytes < (size_t)(64 * page)) return fp;
-    const uint64_t a0 = off / (uint64_t)page * (uint64_t)page;
-    const size_t len = (size_t)(off + bytes - a0);
-    void *m = mmap(nullptr, len, PROT_READ, MAP_SHARED, fd, (off_t)a0);
-    if (m == MAP_FAILED) return fp;
-    constexpr int NS = 64;
-    const size_t npages = (len + (size_t)page - 1) / (size_t)page;
-    unsigned char vec = 0;
-    void *where[NS];
-    int got = 0, res = 0;
-    for (int k = 0; k < NS; k++) {
-        const size_t pg = (size_t)((double)k + 0.5) * npages / NS;
-        void *addr = (unsigned char *)m + pg * (size_t)page;
-        if (mincore(addr, (size_t)page, &vec) != 0) continue;
-        got++;
-        if (vec & 1) where[res++] = addr;
-    }
-    if (got) fp.resident = (double)res / (double)got;
-    if (res >= NS / 2) {
-        // the node of every resident sample page: touch it (maps the page-cache page into this process), then ask
-        int status[NS];
-        volatile unsigned char sink = 0;
-        for (int k = 0; k < res; k++) { sink = sink + *(volatile unsigned char *)where[k]; status[k] = -1; }
-        if (syscall(SYS_move_pages, 0, (unsigned long)res, where, nullptr, status, 0) == 0) {
-            int count[64] = {0}, best = -1;
-            for (int k = 0; k < res; k++)
-                if (status[k] >= 0 && status[k] < 64) count[status[k]]++;
-            for (int nd = 0; nd < 64; nd++)
-                if (count[nd] * 5 >= res * 4) best = nd;             // four pages in five on one node
-            fp.node = best;
-        }
-    }
-    munmap(m, len);
-    return fp;
-}
-// the NUMA node a GPU hangs on, and that node's CPUs
-static int gpu_numa_node(int device)
-{
-    char bus[64] = {0}, path[160];
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof bus, device) != hipSuccess) { (void)hipGetLastError(); return -1; }
-    for (char *c = bus; *c; c++) *c = (char)tolower((unsigned char)*c);
-    snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/numa_node", bus);
-    FILE *f = fopen(path, "r");
-    int node = -1;
-    if (f) { if (fscanf(f, "%d", &node) != 1) node = -1; fclose(f); }
-    return node;
-}
-static bool node_cpus(int node, cpu_set_t *set)
-{
-    char path[96];
-    snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
-    FILE *f = fopen(path, "r");
-    if (!f) return false;
-    CPU_ZERO(set);
-    int a, b, any = 0;
-    char sep;
-    while (fscanf(f, "%d", &a) == 1) {
-        b = a;
-        if (fscanf(f, "%c", &sep) == 1 && sep == '-') {
-            if (fscanf(f, "%d", &b) != 1) break;
-            if (fscanf(f, "%c", &sep) != 1) sep = 0;
-        }
-        for (int c = a; c <= b && c < CPU_SETSIZE; c++) { CPU_SET(c, set); any = 1; }
-        if (sep != ',') break;
-    }
-    fclose(f);
-    return any != 0;
-}
-
-// Round 5: ONE thread talks to the HIP runtime.  The readers only fill pinned slots (pread / memcpy) and raise a flag; the
-// submitter -- the calling thread, or one more background thread when the ingest runs beside the chain -- queues the copies, one
-// event per slot, and hands a slot back to its reader when its copy has completed (hipEventQuery on the oldest copy in flight
-// of each copy stream).  With eight readers calling hipMemcpyAsync / hipEventRecord / hipEventSynchronize themselves the
-// runtime's locks were contended: beside a chain that is launching kernels the ingest fell from 52 to ~41 GB/s, and a burst of
-// fifty launches took up to 7 ms instead of 0.2 (round 4: "the readers contend with the launches in the runtime").
-int ingest_capture(pdt_ctx *ctx, const IngestSrc &src, size_t bytes, void *dst, IngestJob *job = nullptr)
-{
-    if (!bytes) return PDT_OK;
-    // (hour-long captures: 8 MiB spans -- fewer, larger copies: 3.6 GB in 75-95 ms against 110 with 2 MiB spans)
-    const size_t PDT_INGEST_SPAN = ctx->tune.ingest_span_mb > 0 ? ((size_t)ctx->tune.ingest_span_mb << 20)
-                                   : (bytes >= ((size_t)512 << 20) ? 4 * PDT_INGEST_SPAN_DEFAULT : PDT_INGEST_SPAN_DEFAULT);
-    const size_t nspans = (bytes + PDT_INGEST_SPAN - 1) / PDT_INGEST_SPAN;
-    if (src.mem && nspans <= 2 && !job) {
-        HIP_TRY(hipMemcpyAsync(dst, src.mem, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return PDT_OK;
-    }
-    unsigned hw = std::thread::hardware_concurrency();
-    // (round 4, 3.6 GB from tmpfs: 4 / 6 / 8 / 12 / 16 reader threads -> 100 / 92 / 88 / 90 / 89 ms for the whole call)
-    // Several contexts of one process (bin/demodMulti: two per GPU) share the host's cores: half of them, divided by the open
-    // contexts, never fewer than two readers (8 GPUs on a 256-thread host: 8 each; on a 32-thread host: 2 each).
-    const unsigned share = std::max(2u, (hw ? hw / 2u : 8u) / (unsigned)std::max(1, g_open_contexts.load()));
-    const unsigned t_max = ctx->tune.ingest_threads > 0 ? (unsigned)ctx->tune.ingest_threads : std::min(8u, share);
-    int T = (int)std::min<size_t>(std::min<unsigned>(hw ? hw / 2u + 1u : 4u, t_max), nspans);
-    if (T < 1) T = 1;
-    const int nslots = T * PDT_INGEST_SLOTS;
-    // ---- how the file is read (see probe_file): O_DIRECT straight into the pinned slots when its pages are not cached; readers
-    // and staging on the GPU's NUMA node when -- and only when -- its cached pages lie there
-    struct FdGuard { int fd = -1; ~FdGuard() { if (fd >= 0) close(fd); } } direct_guard;
-    int fd_direct = -1, bind_node = -1;
-    constexpr size_t DIO = 4096;                                   // alignment of O_DIRECT reads (offset, length, address)
-    if (!src.mem && bytes >= ((size_t)64 << 20)) {
-        FilePlacement fp;
-        if (ctx->tune.ingest_direct < 0 || ctx->tune.ingest_numa < 0) fp = probe_file(src.fd, src.off, bytes);
-        const bool want_direct = ctx->tune.ingest_direct > 0 || (ctx->tune.ingest_direct < 0 && fp.resident < 0.1);
-        if (want_direct) {
-            char link[64];
-            snprintf(link, sizeof link, "/proc/self/fd/%d", src.fd);
-            fd_direct = open(link, O_RDONLY | O_DIRECT | O_CLOEXEC);        // (EINVAL where the file system has no direct I/O: tmpfs)
-            direct_guard.fd = fd_direct;
-        }
-        const int gnode = gpu_numa_node(ctx->cfg.device);
-        // (Measured, round 6, one box -- GPU and the capture's pages both on node 1: readers and staging bound there 100 - 106 ms for
-        // the 3.6 GB file -> frame file path, not bound 94.6, profiles/r6/e2e_ab_numa.txt: eight readers crowd one socket's cores
-        // beside the box's other tenants, as in round 4.  So buffered reads are bound on request only (PDT_INGEST_NUMA); direct
-        // reads -- the device writes the staging memory, the GPU's DMA engine reads it -- keep staging and readers on the GPU's node.)
-        if (gnode >= 0 && (ctx->tune.ingest_numa > 0 || (ctx->tune.ingest_numa < 0 && fd_direct >= 0))) bind_node = gnode;
-        (void)fp.node;
-    }
-    ctx->ingest_was_direct = fd_direct >= 0 ? 1 : 0;
-    ctx->ingest_numa_node = bind_node;
-    cpu_set_t node_set;
-    const bool have_cpus = bind_node >= 0 && node_cpus(bind_node, &node_set);
-    const size_t slot_stride = PDT_INGEST_SPAN + (fd_direct >= 0 ? 2 * DIO : 0);
-    const size_t need = (size_t)nslots * slot_stride;
-    // The copy streams live at the LOWEST stream priority: streams of one priority share a few hardware queues, and a copy stream
-    // that lands on the queue of the demodulation stream waits behind that stream's kernels -- beside a running segment (a 5 ms PLL
-    // kernel) one of four copy streams stood still, and with it the ring of pinned slots: the overlapped ingest crawled at
-    // ~25 GB/s while kernels ran (round 5, tools/jobs/r5_e2e_ab.sh: four streams 95 ms, two -- no sharing -- 82 ms).  Another
-    // priority is another set of queues (the side stream uses the highest for the same reason).
-    auto make_copy_stream = [](hipStream_t *out) -> hipError_t {
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (least != greatest && hipStreamCreateWithPriority(out, hipStreamNonBlocking, least) == hipSuccess) return hipSuccess;
-        (void)hipGetLastError();
-        return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-    };
-    const auto t_setup0 = std::chrono::steady_clock::now();
-    // copy streams in use: hour-long captures spread their span copies over four (3.6 GB: 123 -> 107 ms for the whole call,
-    // ~51 GB/s from the page cache to HBM); ten-minute captures are no faster for it
-    const int NS = std::min(4, std::max(1, ctx->tune.ingest_streams > 0 ? ctx->tune.ingest_streams : (bytes >= ((size_t)512 << 20) ? 4 : 1)));
-    // (A context's first ingest sets these up, and a one-shot process -- bin/demodPOES -- pays for it in full: a stream is ~10 ms
-    // to create, its first copy ~6 ms more (the runtime starts its DMA queue then), the pinned staging 25 - 30 ms:
-    // tools/probes/cold_path_probe.hip.  Setting them up side by side, a thread each, was measured and made it WORSE -- the pinned
-    // allocation alone then took 0.1 - 0.7 s: the runtime serialises them, badly.  One after the other.)
-    if (need > ctx->ingest_pin_cap) {
-        if (ctx->ingest_pin) (void)hipHostFree(ctx->ingest_pin);
-        ctx->ingest_pin = nullptr;
-        ctx->ingest_pin_cap = 0;
-        // (the staging memory on the node the readers run on: MPOL_PREFERRED = 1 for this thread while the runtime allocates and
-        // pins it, MPOL_DEFAULT = 0 again afterwards)
-        unsigned long mask[16] = {0};
-        if (bind_node >= 0 && bind_node < 1024) {
-            mask[bind_node / (8 * sizeof(long))] = 1ul << (bind_node % (8 * sizeof(long)));
-            (void)syscall(SYS_set_mempolicy, 1, mask, (unsigned long)(8 * sizeof mask));
-        }
-        const hipError_t he = timed_host_malloc((void **)&ctx->ingest_pin, need);
-        if (bind_node >= 0) (void)syscall(SYS_set_mempolicy, 0, nullptr, 0ul);
-        if (he != hipSuccess) { (void)hipGetLastError(); return PDT_ERR_NOMEM; }
-        ctx->ingest_pin_cap = need;
-    }
-    if (!ctx->copy_stream) HIP_TRY(make_copy_stream(&ctx->copy_stream));
-    if (!ctx->ev_ingest) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_ingest, hipEventDisableTiming));
-    for (int q = 1; q < NS; q++) {
-        if (!ctx->copy_streams_more[q - 1]) HIP_TRY(make_copy_stream(&ctx->copy_streams_more[q - 1]));
-        if (!ctx->ev_ingest_more[q - 1]) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_ingest_more[q - 1], hipEventDisableTiming));
-    }
-    hipStream_t cs[4] = { ctx->copy_stream, nullptr, nullptr, nullptr };
-    for (int q = 1; q < NS; q++) cs[q] = ctx->copy_streams_more[q - 1];
-    while (ctx->ingest_ev.size() < (size_t)nslots) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->ingest_ev.push_back(e);
-    }
-    // the destination may still be read by work queued earlier on the demodulation stream
-    HIP_TRY(hipEventRecord(ctx->ev_ingest, ctx->stream));
-    for (int q = 0; q < NS; q++) HIP_TRY(hipStreamWaitEvent(cs[q], ctx->ev_ingest, 0));
-    if (ctx->tune.debug_overlap)
-        fprintf(stderr, "ingest_capture: streams / events / pinned staging ready after %.2f ms\n",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_setup0).count());
-    IngestJob local;
-    IngestJob *J = job ? job : &local;
-    for (int q = 0; q < NS; q++) J->cs[q] = cs[q];
-    J->ncs = NS;
-    J->submitted.reset(new std::atomic<int>[nspans]);
-    for (size_t k = 0; k < nspans; k++) J->submitted[k].store(0);
-    J->slot_state.reset(new std::atomic<int>[(size_t)nslots]);
-    for (int q = 0; q < nslots; q++) J->slot_state[(size_t)q].store(0);
-    J->slot_span.reset(new size_t[(size_t)nslots]);
-    J->slot_delta.reset(new size_t[(size_t)nslots]);
-    for (int q = 0; q < nslots; q++) J->slot_delta[(size_t)q] = 0;
-    if (J->fd_direct >= 0) close(J->fd_direct);
-    J->fd_direct = direct_guard.fd;
-    direct_guard.fd = -1;
-    J->nspans = nspans;
-    J->span = PDT_INGEST_SPAN;
-    J->waited = 0;
-    J->mark_spans.clear();
-    for (size_t b : J->mark_bytes) J->mark_spans.push_back(std::min(nspans, (b + PDT_INGEST_SPAN - 1) / PDT_INGEST_SPAN));
-    J->mark_ready.reset(new std::atomic<int>[J->mark_spans.size() + 1]);
-    for (size_t m = 0; m < J->mark_spans.size(); m++) J->mark_ready[m].store(0);
-    while (ctx->span_ev.size() < J->mark_spans.size() * (size_t)NS) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->span_ev.push_back(e);
-    }
-    std::atomic<int> &failed = J->failed;
-    // span k is read by thread k % T into its slot (k / T) % SLOTS: slot index (k % T) * SLOTS + (k / T) % SLOTS
-    // (the background form copies what the lambdas need: they outlive this call)
-    const IngestSrc src_c = src;
-    unsigned char *pin_base = (unsigned char *)ctx->ingest_pin;
-    auto reader = [J, src_c, bytes, nspans, T, PDT_INGEST_SPAN, pin_base, slot_stride, have_cpus, node_set](int t) {
-        std::atomic<int> &failed = J->failed;
-        const IngestSrc &src = src_c;
-        if (have_cpus) (void)pthread_setaffinity_np(pthread_self(), sizeof node_set, &node_set);      // the GPU's socket (see probe_file)
-        const int fd_direct = J->fd_direct;
-        int round = 0;
-        for (size_t k = (size_t)t; k < nspans && !failed; k += (size_t)T, round++) {
-            const int slot = t * PDT_INGEST_SLOTS + (round % PDT_INGEST_SLOTS);
-            std::atomic<int> &st = J->slot_state[(size_t)slot];
-            while (st.load(std::memory_order_acquire) != 0) {          // its previous copy is still on its way
-                if (failed) return;
-                std::this_thread::sleep_for(std::chrono::microseconds(10));
-            }
-            unsigned char *pin = pin_base + (size_t)slot * slot_stride;
-            const size_t at = k * PDT_INGEST_SPAN;
-            const size_t len = std::min(PDT_INGEST_SPAN, bytes - at);
-            size_t delta = 0;
-            if (src.mem) {
-                memcpy(pin, src.mem + at, len);
-            } else if (fd_direct >= 0) {
-                // from the device straight into the pinned slot: the read starts on the 4 KiB boundary below the span's first
-                // byte and ends on the one above its last (the slot has the room), the copy to the GPU starts `delta` bytes in
-                const uint64_t fo = src.off + at, a0 = fo & ~(uint64_t)4095;
-                delta = (size_t)(fo - a0);
-                const size_t want = (delta + len + 4095) & ~(size_t)4095;
-                size_t got = 0;
-                while (got < delta + len) {
-                    const ssize_t r = pread(fd_direct, pin + got, want - got, (off_t)(a0 + got));
-                    if (r < 0 && errno == EINTR) continue;
-                    if (r <= 0) { failed = r == 0 ? 2 : 3; return; }
-                    got += (size_t)r;
-                }
-            } else {
-                size_t got = 0;
-                while (got < len) {
-                    const ssize_t r = pread(src.fd, pin + got, len - got, (off_t)(src.off + at + got));
-                    if (r < 0 && errno == EINTR) continue;
-                    if (r <= 0) { failed = r == 0 ? 2 : 3; return; }      // 2: the file ends early; 3: read error
-                    got += (size_t)r;
-                }
-            }
-            J->slot_span[(size_t)slot] = k;
-            J->slot_delta[(size_t)slot] = delta;
-            st.store(1, std::memory_order_release);
-        }
-    };
-    const bool background = job != nullptr;
-    auto submitter = [ctx, J, bytes, dst, nspans, NS, nslots, PDT_INGEST_SPAN, pin_base, background, slot_stride]() {
-        std::atomic<int> &failed = J->failed;
-        std::lock_guard<std::mutex> link(g_link_mu[(unsigned)ctx->cfg.device % 64u]);      // (the readers fill their first slots meanwhile)
-        if (hipSetDevice(ctx->cfg.device) != hipSuccess) { failed = 1; return; }
-        // Spans are queued as their slots fill, in whatever order that is: a reader that is late (descheduled: the hosts are
-        // shared) holds up its own two slots only, not the ring (queued strictly in span order, one late reader stopped all
-        // copies).  `upto` = every span below it has been queued: what the prefixes' boundary events go by.  Per copy stream the
-        // slots in flight form a queue, oldest first.
-        std::vector<int> inflight[4];
-        size_t head[4] = { 0, 0, 0, 0 };
-        size_t upto = 0, queued = 0;
-        auto retire = [&](bool block) {
-            for (int q = 0; q < NS; q++)
-                while (head[q] < inflight[q].size()) {
-                    const int slot = inflight[q][head[q]];
-                    const hipError_t e = block ? hipEventSynchronize(ctx->ingest_ev[(size_t)slot]) : hipEventQuery(ctx->ingest_ev[(size_t)slot]);
-                    if (e == hipErrorNotReady) { (void)hipGetLastError(); break; }
-                    if (e != hipSuccess) { failed = 1; return; }
-                    J->slot_state[(size_t)slot].store(0, std::memory_order_release);
-                    head[q]++;
-                }
-        };
-        size_t mi = 0;
-        auto marks = [&]() {                                           // prefixes complete with the spans queued so far
-            while (upto < nspans && J->submitted[upto].load(std::memory_order_relaxed)) upto++;
-            while (mi < J->mark_spans.size() && J->mark_spans[mi] <= upto) {
-                for (int q = 0; q < NS; q++)
-                    if (hipEventRecord(ctx->span_ev[mi * (size_t)NS + (size_t)q], J->cs[q]) != hipSuccess) { failed = 1; return; }
-                J->mark_ready[mi].store(1, std::memory_order_release);
-                mi++;
-            }
-        };
-        int rr = 0;                                                    // copy streams round robin
-        // (developer aid, PDT_DEBUG_OVERLAP: how long the submitter had nothing to queue, and how many copies were in flight on
-        // average while it waited -- near the ring's half: the copies are the pace (a reader refills a slot as soon as its copy has
-        // completed); near zero: the readers are)
-        double idle_ms = 0, flying_sum = 0, api_ms = 0;
-        long long idle_n = 0;
-        const auto t_sub0 = std::chrono::steady_clock::now();
-        while (queued < nspans && !failed) {
-            bool any = false;
-            const auto t_it0 = std::chrono::steady_clock::now();
-            for (int slot = 0; slot < nslots && !failed; slot++) {
-                if (J->slot_state[(size_t)slot].load(std::memory_order_acquire) != 1) continue;
-                const size_t k = J->slot_span[(size_t)slot];
-                const size_t at = k * PDT_INGEST_SPAN;
-                const size_t len = std::min(PDT_INGEST_SPAN, bytes - at);
-                const int q = rr;
-                rr = (rr + 1 == NS) ? 0 : rr + 1;
-                if (hipMemcpyAsync((unsigned char *)dst + at, pin_base + (size_t)slot * slot_stride + J->slot_delta[(size_t)slot], len, hipMemcpyHostToDevice, J->cs[q]) != hipSuccess ||
-                    hipEventRecord(ctx->ingest_ev[(size_t)slot], J->cs[q]) != hipSuccess) {
-                    failed = 1;
-                    return;
-                }
-                J->slot_state[(size_t)slot].store(2, std::memory_order_release);
-                inflight[q].push_back(slot);
-                J->submitted[k].store(1, std::memory_order_release);
-                queued++;
-                any = true;
-                marks();
-            }
-            retire(false);
-            const auto t_it1 = std::chrono::steady_clock::now();
-            api_ms += std::chrono::duration<double, std::milli>(t_it1 - t_it0).count();
-            if (!any) {
-                int flying = 0;
-                for (int slot = 0; slot < nslots; slot++) flying += J->slot_state[(size_t)slot].load(std::memory_order_relaxed) == 2;
-                std::this_thread::sleep_for(std::chrono::microseconds(15));
-                idle_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_it1).count();
-                flying_sum += flying;
-                idle_n++;
-            }
-        }
-        marks();
-        if (ctx->tune.debug_overlap)
-            fprintf(stderr, "ingest submitter: %.2f ms in all: %.2f in the runtime (queueing, polling), %.2f with nothing to queue (%.1f of %d slots in flight on average)\n",
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_sub0).count(), api_ms, idle_ms,
-                    idle_n ? flying_sum / (double)idle_n : 0.0, nslots);
-        (void)nslots;
-        // the background form leaves the pinned slots free; the foreground form returns with its last copies still on their way
-        // (the caller's stream waits for them, and the call does not return before that stream is idle)
-        if (background) retire(true);
-    };
-    bool spawn_failed = false;
-    try {
-        for (int t = 0; t < T; t++) J->pool.emplace_back(reader, t);
-        if (job) J->pool.emplace_back(submitter);
-    } catch (const std::exception &) {
-        failed = 1;
-        spawn_failed = true;
-    }
-    // (background form: the readers are already running and may have set `failed` -- a short file, a read error: those codes
-    // come through ingest_wait_mark / ingest_join, always; only a thread that could not be started is reported here)
-    if (job) return spawn_failed ? PDT_ERR_NOMEM : PDT_OK;             // (the caller joins: ingest_join)
-    if (!failed) submitter();
-    for (auto &th : J->pool) th.join();
-    J->pool.clear();
-    if (failed == 2) return PDT_ERR_FORMAT;                // the file is shorter than announced
-    if (failed == 3) return PDT_ERR_IO;
-    if (failed) { (void)hipGetLastError(); return PDT_ERR_NOGPU; }
-    HIP_TRY(hipEventRecord(ctx->ev_ingest, ctx->copy_stream));
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_ingest, 0));
-    for (int q = 1; q < NS; q++) {
-        HIP_TRY(hipEventRecord(ctx->ev_ingest_more[q - 1], cs[q]));
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_ingest_more[q - 1], 0));
-    }
-    return PDT_OK;
-}
-
-// make `stream` wait for the copies of prefix `m` of the job (IngestJob::mark_bytes).  The host waits -- without touching the HIP
-// runtime: the submitter is in it all the time -- until the submitter has queued the prefix's last span and recorded one event
-// per copy stream behind it; the stream then waits for those events: for the prefix's copies and for nothing that was queued
-// later.  (Round 3 recorded an event per span and made the stream wait for each: ~300 calls, and the host's loop lagged 10 ms
-// behind the data.)
-int ingest_wait_mark(pdt_ctx *ctx, IngestJob &job, size_t m, hipStream_t stream)
-{
-    if (m >= job.mark_spans.size()) return PDT_ERR_STATE;
-    while (!job.mark_ready[m].load(std::memory_order_acquire)) {
-        if (job.failed) return job.failed == 2 ? PDT_ERR_FORMAT : job.failed == 3 ? PDT_ERR_IO : PDT_ERR_NOGPU;
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-    for (int q = 0; q < job.ncs; q++) HIP_TRY(hipStreamWaitEvent(stream, ctx->span_ev[m * (size_t)job.ncs + (size_t)q], 0));
-    return PDT_OK;
-}
-
-int ingest_join(IngestJob &job)
-{
-    for (auto &th : job.pool) th.join();
-    job.pool.clear();
-    if (job.failed == 2) return PDT_ERR_FORMAT;
-    if (job.failed == 3) return PDT_ERR_IO;
-    if (job.failed) { (void)hipGetLastError(); return PDT_ERR_NOGPU; }
-    return PDT_OK;
-}
-
-}  // namespace
 
 // ================================================================================= C ABI
 extern "C" {
@@ -991,7 +535,7 @@ int pdt_open(const pdt_config *cfg, pdt_ctx **out)
     if (argos_twin) ctx->axis_f.init(1 / (float)cfg->sample_rate);           // "Time += (1/Fs)", all float (ARGOSdemodPortAudio/main.c:285)
     ctx->axis_d.init(1.0 / (double)cfg->sample_rate);
     ctx->counted = true;
-    g_open_contexts.fetch_add(1);
+    ingest_open_contexts().fetch_add(1);
     *out = ctx;
     return PDT_OK;
 }
@@ -1012,15 +556,7 @@ void pdt_close(pdt_ctx *ctx)
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->qual_pin) (void)hipHostFree(ctx->qual_pin);
     if (ctx->packs_pin) (void)hipHostFree(ctx->packs_pin);
-    if (ctx->ingest_pin) (void)hipHostFree(ctx->ingest_pin);
-    for (hipEvent_t e : ctx->ingest_ev) (void)hipEventDestroy(e);
-    if (ctx->ev_ingest) (void)hipEventDestroy(ctx->ev_ingest);
-    if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    for (hipEvent_t e : ctx->span_ev) (void)hipEventDestroy(e);
-    for (int q = 0; q < 3; q++) {
-        if (ctx->ev_ingest_more[q]) (void)hipEventDestroy(ctx->ev_ingest_more[q]);
-        if (ctx->copy_streams_more[q]) (void)hipStreamDestroy(ctx->copy_streams_more[q]);
-    }
+    ctx->ingest.release();
     if (ctx->pend_sc) (void)hipHostFree(ctx->pend_sc);
     for (auto &t : ctx->timers) { if (!t.shared_a) (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1029,7 +565,7 @@ void pdt_close(pdt_ctx *ctx)
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    if (ctx->counted) g_open_contexts.fetch_sub(1);
+    if (ctx->counted) ingest_open_contexts().fetch_sub(1);
     delete ctx;
 }
 
@@ -1274,8 +810,8 @@ static int ingest_whole(pdt_ctx *ctx, const IngestSrc &src, size_t bytes)
 static void ingest_publish(pdt_ctx *ctx)
 {
     ctx->stats.ingest_ms = ctx->ingest_ms;
-    ctx->stats.ingest_direct = (uint32_t)ctx->ingest_was_direct;
-    ctx->stats.ingest_numa_node = ctx->ingest_numa_node;
+    ctx->stats.ingest_direct = (uint32_t)ctx->ingest.was_direct;
+    ctx->stats.ingest_numa_node = ctx->ingest.numa_node;
 }
 
 // One capture from host memory or a file, of any format the entry has let through: the bounded window when it does not fit

@@ -1,5 +1,6 @@
 // pdt_rt.h -- internals of libpdt.so shared by its translation units (round 6: the library is four of them, so that the device
-// code is compiled side by side -- pdt_api.hip: contexts, ingest, streaming, the C ABI; pdt_chain_f32.hip / pdt_chain_f64.hip: the
+// code is compiled side by side -- pdt_api.hip: contexts, streaming, the C ABI; pdt_ingest.hip: the host -> HBM ingest (its host side,
+// free of HIP: pdt_ingest.h); pdt_chain_f32.hip / pdt_chain_f64.hip: the
 // chain's launch recording (run_capture, finish_capture, the stage entries) instantiated for float resp. double, with every
 // kernel those launch; pdt_chain_wide_f32.hip / _f64.hip: the PLL kernels' slow-wrap variants).  Not installed, not part of the ABI.
 #ifndef PDT_RT_H
@@ -32,6 +33,7 @@
 #include "pdt_kernels_back.h"
 #include "pdt_kernels_front.h"
 #include "pdt_timeaxis.h"
+#include "pdt_ingest.h"
 
 using namespace pdt;
 
@@ -353,6 +355,18 @@ struct HaloCarry {
     uint64_t left = 0, pending = 0, in = 0, out = 0;
 };
 
+// What a context keeps for the host -> HBM ingest of a capture (pdt_ingest.hip): pinned slots filled by a few host threads, span
+// copies round robin over copy streams of their own.
+struct IngestRes {
+    void *pin = nullptr;                 // the pinned staging ...
+    size_t pin_cap = 0;                  // ... and its bytes
+    hipStream_t copy[4] = { nullptr, nullptr, nullptr, nullptr };
+    hipEvent_t all_queued[4] = { nullptr, nullptr, nullptr, nullptr };     // per copy stream: behind its last copy (foreground form)
+    std::vector<hipEvent_t> slot_ev, mark_ev;      // per pinned slot; per mark and copy stream (overlapped ingest)
+    int was_direct = 0, numa_node = -1;  // how the last ingest read its file (pdt_stats)
+    void release();
+};
+
 struct pdt_ctx {
     pdt_config cfg;
     pdt_loop_params lp = {};     // pdt_set_loop_params: 0 = the mains' constant
@@ -366,7 +380,7 @@ struct pdt_ctx {
     hipStream_t stream2 = nullptr;     // side stream: block-parallel PLL phase runs beside the sequential acquisition
 
     DevBuf pcm, pll, lock, fir, agc, sym, symidx, bits, bitsym, hits, frames, taps, mag, seams_pll, seams_agc, scal, lockinfo, term, seams_ema, gtable, gentries, gcand, gmfirst, stiles, gsegmap, gsegstart, gbands, gclist, gneed, gchain, gspan_keys, gspan_tails, gspan_rows, gspan_items, gspan_ctl, gspan_recs, gcentries, gflags, agc_maps, pll_head, taps_rot, pll_scratch, tip, sync_scr, agc_raw, agc_ckpt, pll_ckpt;
-    bool counted = false;        // this context is in g_open_contexts
+    bool counted = false;        // this context is in ingest_open_contexts()
     bool keep_agc_raw = false;   // pdt_keep_presquelch: also keep the AGC output before Squelch (stage PDT_ST_AGC_RAW)
     // pdt_keep_quality: the averagePhase stream (what CarrierTrackPLL returns, chunk by chunk) and the per-chunk counts
     bool keep_quality = false;
@@ -407,15 +421,9 @@ struct pdt_ctx {
     size_t packs_pin_cap = 0;
     pdt_ctx *leader = nullptr;          // context whose streams / events carried the last execution
     int batch_hint = 1;                 // captures demodulated together with this one (sizes the block-parallel geometry)
-    // host -> HBM ingest of a capture (file or memory): pinned slots filled by a few host threads, copies on a stream of their own
-    void *ingest_pin = nullptr;
-    size_t ingest_pin_cap = 0;
-    hipStream_t copy_stream = nullptr, copy_streams_more[3] = { nullptr, nullptr, nullptr };   // span copies go round robin over them
-    hipEvent_t ev_ingest = nullptr, ev_ingest_more[3] = { nullptr, nullptr, nullptr };
-    std::vector<hipEvent_t> ingest_ev, span_ev;      // per pinned slot; per span (overlapped ingest)
+    IngestRes ingest;
     double stream_gpu_ms = 0;
     double ingest_ms = 0;               // host wall time of the last ingest (issue of the last copy)
-    int ingest_was_direct = 0, ingest_numa_node = -1;   // how the last ingest read its file (pdt_stats)
     DevBuf stream_in, seg_dev, lt_theta, lt_phi;          // input window of the stream; small device block for the segment's carried-out state
     uint64_t stream_have = 0, stream_done = 0;   // samples in the window / of them already demodulated (local indices)
     uint64_t stream_total = 0;          // samples pushed since pdt_stream_begin
@@ -490,6 +498,16 @@ struct pdt_ctx {
 };
 
 namespace pdtrt {
+
+// ---------------------------------------------------------------- host -> HBM ingest (pdt_ingest.hip)
+// `bytes` of `src` to `dst` on the device, ordered behind what ctx->stream holds.  Without a job: ctx->stream waits for the
+// copies.  With one: the copies go on in the background; ingest_wait_mark makes a stream wait for prefix m of the job's
+// mark_bytes, ingest_join ends the job.
+int ingest_capture(pdt_ctx *ctx, const IngestSrc &src, size_t bytes, void *dst, IngestJob *job = nullptr);
+int ingest_wait_mark(pdt_ctx *ctx, IngestJob &job, size_t m, hipStream_t stream);
+int ingest_join(IngestJob &job);
+std::atomic<int> &ingest_open_contexts();        // contexts alive in this process (pdt_open / pdt_close)
+std::mutex &ingest_link(int device);             // one ingest per GPU at a time
 
 // ---------------------------------------------------------------- FIR taps (LowPassFilter.c:127-175)
 // Evaluated on the host with the operations the reference performs (sinf / sin of the sinc argument, cos in the Blackman

@@ -20,7 +20,7 @@
  *        end-to-end figure of BASELINE's metric)
  *
  * Host budget at N GPUs: 2 N worker threads + per ingesting context up to min(8, cores / 2 / contexts) reader
- * threads (csrc/pdt_api.hip: ingest_capture) and 2 x 8 MiB of pinned staging per reader; frame records 136 B each (4.9 MB per
+ * threads (csrc/pdt_ingest.h: ingest_layout) and 2 x 8 MiB of pinned staging per reader; frame records 136 B each (4.9 MB per
  * capture-hour) on the host until they are written.
  */
 #include <pthread.h>

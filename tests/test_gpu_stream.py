@@ -258,6 +258,28 @@ def _with_env(env, fn):
             os.environ.pop(k, None)
 
 
+def test_threaded_ingest_from_memory_equals_the_plain_copy(pdt):
+    """A capture from host memory in more than two spans goes through the reader threads, the pinned slots and the copy streams
+    in the foreground form.  1 MiB spans cut 6 MB into six, the last one short; one reader and three, one copy stream and four:
+    the bytes that land in HBM are those of the plain copy (one span), so the FIR stream and the text are equal, byte for byte."""
+    iq = pdt.synth_capture(0, 250000, 6.0, seed=83)                      # 1.5 M samples, 6 MB of PCM16
+
+    def run():
+        with pdt.Demodulator(pdt.MODE_POES, 250000) as d:
+            d.demod(iq)
+            st = d.stats()
+            assert st.ingest_direct == 0 and st.ingest_numa_node == -1
+            return d.text(), d.stage(pdt.ST_FIR).copy()
+
+    text, fir = _with_env({"PDT_INGEST_SPAN_MB": "256"}, run)
+    assert len(text) > 0 and fir.size > 0
+    for threads in ("1", "3"):
+        for streams in ("1", "4"):
+            t, f = _with_env({"PDT_INGEST_SPAN_MB": "1", "PDT_INGEST_THREADS": threads, "PDT_INGEST_STREAMS": streams}, run)
+            assert t == text, (threads, streams)
+            assert f.tobytes() == fir.tobytes(), (threads, streams)
+
+
 @pytest.mark.parametrize("fs,block,extra", [(250000, 1040000, {"PDT_GSPAN": "13"}), (250000, 260000, {})])
 def test_aligned_segments_take_the_whole_capture_kernels(pdt, orc, fs, block, extra):
     """Round 5: a segment whose first new sample lies on the grid of the whole-capture kernels' units (a multiple of the mix + FIR
@@ -470,24 +492,31 @@ def test_uncached_file_is_read_directly_into_the_pinned_staging(pdt, tmp_path):
         ref.demod(iq)
         want = ref.text()
 
-    def run(evict):
+    after = []                                                        # statistics of a small capture from memory on the same context
+
+    def run(evict, then_from_memory=False):
         fd = os.open(wav, os.O_RDONLY)
         try:
             if evict:
                 os.posix_fadvise(fd, 0, 0, os.POSIX_FADV_DONTNEED)
             with pdt.Demodulator(pdt.MODE_POES, fs).keep_pll(False) as d:
                 d.demod_file(fd, 44, len(iq))
-                return d.text(), d.stats()
+                text, st = d.text(), d.stats()
+                if then_from_memory:
+                    d.demod(iq[:100000])
+                    after.append(d.stats())
+                return text, st
         finally:
             os.close(fd)
 
     wfd = os.open(wav, os.O_RDWR)
     os.fsync(wfd)                                                     # (clean pages can be dropped)
     os.close(wfd)
-    text, st = _with_env({"PDT_INGEST_DIRECT": "1"}, lambda: run(False))          # forced: whatever the page cache holds
+    text, st = _with_env({"PDT_INGEST_DIRECT": "1"}, lambda: run(False, True))    # forced: whatever the page cache holds
     assert text == want
     if not st.ingest_direct:
         pytest.skip("no O_DIRECT on the file system under tmp_path")
+    assert after[0].ingest_direct == 0 and after[0].ingest_numa_node == -1      # the plain copy that followed says so: nothing stale
     text, st = run(True)                                              # evicted: the probe finds it cold
     assert text == want and st.ingest_direct == 1
     open(wav, "rb").read()                                            # cached again: buffered reads

@@ -23,6 +23,7 @@ pdt = importlib.import_module("project-desert-tortoise_amd")
 REF_POES = os.path.join(ROOT, "oracle/_ref/ref_demodPOES")
 REF_ARGOS = os.path.join(ROOT, "oracle/_ref/ref_demodARGOS")
 STAGES = ["iq", "time", "pll", "lock", "fir", "agc", "sym", "symt", "bits", "bitt", "taps"]
+REAL_STAGES = ["pll", "lock", "fir", "agc", "agcraw", "sym", "symt", "bits", "bitt", "avg"]
 
 POES_RATES = [18750, 32000, 50000, 100000, 250000]
 POES_SECONDS = 3.0
@@ -43,6 +44,39 @@ def run_ref(binary, wav, out, extra=(), dump=None):
     cmd += [wav, out]
     r = subprocess.run(cmd, capture_output=True, text=True, check=True)
     return r.stdout + r.stderr
+
+
+def real_argos(meta, tmp):
+    """Real ARGOS IQ (tests/real_captures.py): the reference's ARGOSdemod/packet.wav -- DATA, copied as it is --, the clip at
+    the wrong rate and bursts over the recording's noise, one run of the reference's objects per row of real_captures.TABLE."""
+    import shutil
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import real_captures as rc
+    ref_tree = os.environ.get("REF", "/root/reference")
+    with open(os.path.join(ref_tree, "ARGOSdemod", "packet.wav"), "rb") as f:
+        data = f.read()
+    if not os.path.exists(rc.PACKET_WAV) or open(rc.PACKET_WAV, "rb").read() != data:
+        with open(rc.PACKET_WAV, "wb") as g:
+            g.write(data)
+    meta["synth"][rc.PACKET_SHA256_KEY] = sha(rc.PACKET_WAV)
+    meta["synth"][rc.REALNOISE_SHA256_KEY] = hashlib.sha256(rc.capture("realnoise")[1].tobytes()).hexdigest()
+    for name, mode, chunk in rc.ROWS:
+        rate, iq = rc.capture(name)
+        key = rc.golden_name(name, mode, chunk)
+        wav = {"packet": rc.PACKET_WAV, "clip": rc.CLIP_WAV}.get(name) or os.path.join(tmp, name + ".wav")
+        if not os.path.exists(wav):
+            pdt.write_wav(wav, rate, iq)
+        out, dump = os.path.join(tmp, key + ".txt"), os.path.join(tmp, key)
+        log = run_ref(REF_ARGOS if mode == rc.ARGOS else REF_POES, wav, out, extra=["-c", str(chunk)], dump=dump)
+        meta["console"][key] = [l for l in log.splitlines() if "locked" in l or "Normalization" in l]
+        stages = REAL_STAGES if mode == rc.ARGOS else [s for s in REAL_STAGES if s not in ("lock", "agcraw")]   # (the POES file chain keeps neither)
+        meta["stages"][key] = {s: sha(f"{dump}.{s}") for s in stages}
+        nframes = rc.TABLE[(name, mode, chunk)][4]
+        assert os.path.exists(out) == (nframes > 0)                # the reference removes a file without packets
+        if nframes:
+            shutil.copyfile(out, os.path.join(HERE, key + ".txt"))
+        if name == "packet" and mode == rc.ARGOS and chunk in (2400, 1000):
+            shutil.copyfile(f"{dump}.avg", os.path.join(HERE, key + ".avg.f64"))
 
 
 def main():
@@ -83,6 +117,8 @@ def main():
         with open(f"{dump}.taps", "rb") as f, open(os.path.join(HERE, "taps_argos_32000.f64"), "wb") as g:
             g.write(f.read())
         run_ref(REF_ARGOS, wav, os.path.join(HERE, "argos_32000.c1000.txt"), extra=["-c", "1000"])
+
+        real_argos(meta, tmp)
 
     import zlib
     import numpy as np

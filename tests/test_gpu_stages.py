@@ -120,10 +120,15 @@ def test_agc_stage_replays_the_oracle_chunk_by_chunk(pdt, orc, fs, chunk):
 
 
 @functools.lru_cache(maxsize=None)
-def argos_agc_streams(pdt, orc):
-    """the oracle's FIR, pre-Squelch AGC, AGC and lock streams of one synthetic ARGOS capture (computed once, read only)"""
-    iq = pdt.synth_capture(1, 32000, 8.0, f0_hz=160.0, seed=46)
-    o = orc.Oracle(orc.ARGOS, 32000, iq)
+def argos_agc_streams(pdt, orc, capture=None, chunk=0):
+    """the oracle's FIR, pre-Squelch AGC, AGC and lock streams of one ARGOS capture (computed once, read only): a synthetic
+    one, or the one tests/real_captures.py has under the name `capture`"""
+    if capture is None:
+        iq = pdt.synth_capture(1, 32000, 8.0, f0_hz=160.0, seed=46)
+        o = orc.Oracle(orc.ARGOS, 32000, iq, chunk=chunk)
+    else:
+        import real_captures
+        o = real_captures.oracle(capture, orc.ARGOS, chunk)
     streams = [o.stage(st) for st in (orc.ST_FIR, orc.ST_AGC_RAW, orc.ST_AGC, orc.ST_LOCK)]
     for a in streams:
         a.setflags(write=False)

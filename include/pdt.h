@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 13): the carrier of a channel stream as a measurement -- pdt_tone_cfg, pdt_tone, pdt_tones,
+/* 4, additions without a bump (round 17): the ARGOS messages in the bits, either polarity, 1 .. 8 blocks, with the platform ID --
+ * pdt_argos_cfg, pdt_argos_msg, pdt_argos_messages, pdt_argos_messages_batch, pdt_stage_argos_messages, pdt_host_argos_messages,
+ * pdt_argos_msg_tile, pdt_format_argos_messages, pdt_write_argos_messages: a result beside the frames, which stay the reference's.
+ * 4, additions without a bump (round 13): the carrier of a channel stream as a measurement -- pdt_tone_cfg, pdt_tone, pdt_tones,
  * pdt_tones_batch, pdt_host_tones: frequency, level and C/N0 of every burst's carrier, or of a channel's carrier at a stride (the
  * Doppler curve).
  * 4, additions without a bump (round 12): every burst of a wideband capture in a window of its own -- pdt_window, pdt_burst_windows,
@@ -639,6 +642,63 @@ typedef struct pdt_tone {
 int  pdt_tones(pdt_ctx *ctx, const pdt_tone_cfg *cfg, pdt_tone *out, int cap, int *count);
 int  pdt_tones_batch(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, pdt_tone *out, int cap_each, int *counts);
 int  pdt_host_tones(uint32_t rate, double offset_hz, const float *iq, uint64_t n, const pdt_tone_cfg *cfg, pdt_tone *out, int cap, int *count);
+
+/* Who sent what: the ARGOS messages in the Manchester bits (ARGOS contexts).  The frames above are the reference's, byte for byte: one
+ * 13-bit word, upright only, so one-block messages of one polarity and 56 bits printed of the 52.  A platform sends 1 .. 8 blocks of 32
+ * bits behind a 20-bit ID, and a mirrored spectrum (I and Q swapped, a conjugated capture) complements every bit.  The messages are a
+ * result BESIDE the frames; the rule is fixed in csrc/pdt_argos_msg.h and pdt_host_argos_messages restates it on the host:
+ * with c[i] = bit i XOR the polarity, a head ends at bit e when c[e-12 .. e-4] = 000101111 (frame sync and initialisation bit), c[e-3 .. e]
+ * is a length code (N - 1 in three bits and an even-parity bit, N = 1 .. 8), the min_run raw bits in front of the sync are all equal --
+ * EITHER value: they are the bit-sync ones, whose Manchester pairing is arbitrary until the first data transition -- and e >= 12 + min_run;
+ * the body is the 20 + 32 N bits behind e.  Heads are taken in ascending e; one that begins inside the body of the message accepted
+ * before it is dropped.  28-bit IDs cannot be told from 20-bit ones without the platform registry: such a platform's first data byte is
+ * the rest of its ID.
+ * pdt_argos_cfg: NULL or a zero field = the default, min_run 6 (allowed 0 .. 15); min_run 0 with PDT_ARGOS_ZERO_MIN_RUN in zero_mask
+ * asks for no run at all (as pdt_loop_params.zero_mask does for a loop constant).
+ * pdt_argos_msg: bit_index = e; time_src and time = those of a pdt_frame whose sync word completes at bit e (an upright one-block
+ * message carries exactly its frame's); id, blocks = N, inverted = the polarity, run_value = the run's bits as that polarity reads them
+ * (1: the bit-sync ones came out as ones; 0 when min_run is 0); data = the 32 N data bits, MSB first, in 4 N bytes, the rest 0; complete = 1 when the stream holds the whole body, else
+ * data_bits (otherwise 32 N) says how many data bits are present, and the missing bits are 0.
+ *   pdt_argos_messages        the bits of the context's last whole-capture call (PDT_ST_BITS, in device memory; their count is read
+ *                             there): *count = the messages found, the first min(cap, *count) of them in out, in ascending bit_index.
+ *                             PDT_ERR_STATE when the last call left no resident bit stream (none yet, a stream open or ended, a capture
+ *                             taken in pieces, a stage-level call); PDT_ERR_ARG for a POES context, min_run outside 0 .. 15, cap < 0.
+ *                             Like pdt_tones it leaves frames, text, stages, statistics, survey and burst results exactly as they were
+ *                             (a profiled context's pdt_kernel_times gain the entries k_argos_msgs and k_argos_finish)
+ *   pdt_argos_messages_batch  the same for `count` contexts with ONE launch of each kernel (the windows of a round of
+ *                             pdt_demod_windows_*): context i's records at out + i cap_each, their number in counts[i].  The contexts
+ *                             must be distinct and live on one device (else PDT_ERR_ARG); every one is checked before anything runs
+ *   pdt_stage_argos_messages  stage-level entry: the kernels on a caller's string of '0'/'1' characters (any byte other than '0' is a
+ *                             one); the time stamp of bit k is k, as in pdt_stage_bytesync.  Nothing of the context's results changes
+ *   pdt_host_argos_messages   host only, no GPU: the same records for the same string
+ *   pdt_argos_msg_tile        the bits one workgroup tests (tests place heads at its seams)
+ * Text, host only: one line per COMPLETE message -- "%.5f" of time, "i" when inverted, " %d %05X" of blocks and id, " %02X" per data
+ * byte, "\n" -- through pdt_format_argos_messages (returns the bytes needed, writes at most cap) or pdt_write_argos_messages (to an
+ * open descriptor; PDT_ERR_IO when a write fails; *bytes_written may be NULL).                                                        */
+#define PDT_ARGOS_ZERO_MIN_RUN 1u
+typedef struct pdt_argos_cfg {
+    int32_t  min_run;
+    uint32_t zero_mask;
+    int32_t  reserved_[2];
+} pdt_argos_cfg;
+typedef struct pdt_argos_msg {
+    double   time;
+    int64_t  bit_index;
+    int64_t  time_src;
+    uint32_t id;
+    uint8_t  blocks, inverted, complete, run_value;
+    uint32_t data_bits;
+    uint32_t reserved_;
+    uint8_t  data[32];
+} pdt_argos_msg;
+int  pdt_argos_messages(pdt_ctx *ctx, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count);
+int  pdt_argos_messages_batch(pdt_ctx *const *ctxs, int count, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap_each, int *counts);
+int  pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap,
+                              int *count);
+int  pdt_host_argos_messages(const uint8_t *bits, uint64_t nbits, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count);
+int  pdt_argos_msg_tile(void);
+uint64_t pdt_format_argos_messages(const pdt_argos_msg *msgs, uint64_t n, char *buf, uint64_t cap);
+int  pdt_write_argos_messages(const pdt_argos_msg *msgs, uint64_t n, int fd, uint64_t *bytes_written);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

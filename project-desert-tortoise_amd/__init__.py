@@ -301,6 +301,76 @@ def tones_batch(ds, **cfg):
     return [out[i, :counts[i]].copy() for i in range(len(ds))]
 
 
+class ArgosCfg(C.Structure):
+    """pdt_argos_cfg: a zero means the default; min_run 0 with ARGOS_ZERO_MIN_RUN in zero_mask asks for no run"""
+    _fields_ = [("min_run", C.c_int32), ("zero_mask", C.c_uint32), ("reserved_", C.c_int32 * 2)]
+
+
+class ArgosMsg(C.Structure):
+    """pdt_argos_msg"""
+    _fields_ = [("time", C.c_double), ("bit_index", C.c_int64), ("time_src", C.c_int64), ("id", C.c_uint32), ("blocks", C.c_uint8),
+                ("inverted", C.c_uint8), ("complete", C.c_uint8), ("run_value", C.c_uint8), ("data_bits", C.c_uint32), ("reserved_", C.c_uint32),
+                ("data", C.c_uint8 * 32)]
+
+
+ARGOS_ZERO_MIN_RUN = 1
+# pdt_argos_msg as a numpy record
+ARGOS_MSG_DTYPE = np.dtype([("time", "<f8"), ("bit_index", "<i8"), ("time_src", "<i8"), ("id", "<u4"), ("blocks", "u1"), ("inverted", "u1"),
+                            ("complete", "u1"), ("run_value", "u1"), ("data_bits", "<u4"), ("reserved_", "<u4"), ("data", "u1", (32,))])
+assert ARGOS_MSG_DTYPE.itemsize == C.sizeof(ArgosMsg) == 72
+
+
+def _argos_cfg(min_run):
+    """min_run (None = the default, 6) -> pdt_argos_cfg or None; 0 travels with its flag bit"""
+    if min_run is None:
+        return None
+    return ArgosCfg(min_run=int(min_run), zero_mask=ARGOS_ZERO_MIN_RUN if int(min_run) == 0 else 0)
+
+
+def _bit_string(bits) -> np.ndarray:
+    """a string of '0'/'1' characters: bytes, or a uint8 array (any byte other than '0' is a one)"""
+    if isinstance(bits, (bytes, bytearray)):
+        return np.frombuffer(bytes(bits), dtype=np.uint8)
+    return np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+
+
+def argos_msg_tile() -> int:
+    """pdt_argos_msg_tile: the bits one workgroup of k_argos_msgs tests"""
+    return lib().pdt_argos_msg_tile()
+
+
+def host_argos_messages(bits, min_run=None, cap: int = 4096, with_count: bool = False):
+    """pdt_host_argos_messages: the ARGOS messages in a string of '0'/'1' characters, restated on the host (no GPU); the time stamp of
+    bit k is k.  Returns ARGOS_MSG_DTYPE[min(found, cap)]; with_count: (that, found)."""
+    a, c = _bit_string(bits), _argos_cfg(min_run)
+    out, count = np.zeros(max(cap, 1), dtype=ARGOS_MSG_DTYPE), C.c_int(0)
+    _check(lib().pdt_host_argos_messages(a.ctypes.data, a.size, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)),
+           "pdt_host_argos_messages")
+    got = out[:min(count.value, cap)]
+    return (got, count.value) if with_count else got
+
+
+def argos_messages_batch(ds, min_run=None, cap: int = 4096):
+    """pdt_argos_messages_batch: Demodulator.argos_messages() of several contexts of one device with ONE launch of each kernel: a list of
+    ARGOS_MSG_DTYPE arrays, one per context."""
+    c = _argos_cfg(min_run)
+    hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
+    out, counts = np.zeros((max(len(ds), 1), max(cap, 1)), dtype=ARGOS_MSG_DTYPE), (C.c_int * max(len(ds), 1))()
+    _check(lib().pdt_argos_messages_batch(hs, len(ds), C.byref(c) if c else None, out.ctypes.data, cap, counts),
+           "pdt_argos_messages_batch")
+    return [out[i, :min(counts[i], cap)].copy() for i in range(len(ds))]
+
+
+def format_argos_messages(msgs: np.ndarray) -> bytes:
+    """pdt_format_argos_messages: one line per complete message (host-only C, no GPU needed)"""
+    a = np.ascontiguousarray(msgs, dtype=ARGOS_MSG_DTYPE)
+    L = lib()
+    n = L.pdt_format_argos_messages(a.ctypes.data, len(a), None, 0)
+    buf = C.create_string_buffer(n + 1)
+    L.pdt_format_argos_messages(a.ctypes.data, len(a), buf, n)
+    return buf.raw[:n]
+
+
 def _carriers(rec, count: int):
     return [Carrier(rec[i].offset_hz, rec[i].peak_db, rec[i].floor_power) for i in range(count)]
 
@@ -322,6 +392,8 @@ ABI_SYMBOLS = [
     "pdt_device_math", "pdt_device_math_layout",
     "pdt_burst_windows", "pdt_demod_windows_device", "pdt_demod_windows", "pdt_demod_windows_held",
     "pdt_tones", "pdt_tones_batch", "pdt_host_tones",
+    "pdt_argos_messages", "pdt_argos_messages_batch", "pdt_stage_argos_messages", "pdt_host_argos_messages", "pdt_argos_msg_tile",
+    "pdt_format_argos_messages", "pdt_write_argos_messages",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_ddc"]        # include/pdt_dev.h (test-only)
 
@@ -473,6 +545,13 @@ def lib():
     L.pdt_tones.argtypes = [C.c_void_p, C.POINTER(ToneCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.pdt_tones_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(ToneCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.pdt_host_tones.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.POINTER(ToneCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_argos_messages.argtypes = [C.c_void_p, C.POINTER(ArgosCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_argos_messages_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(ArgosCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_stage_argos_messages.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ArgosCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_host_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ArgosCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_format_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
+    L.pdt_format_argos_messages.restype = C.c_uint64
+    L.pdt_write_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_device_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pdt_device_math_layout.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
@@ -851,6 +930,25 @@ class Demodulator:
         _check(self._L.pdt_tones(self._h, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)), "pdt_tones")
         return out[:count.value]
 
+    def argos_messages(self, min_run=None, cap: int = 4096, with_count: bool = False):
+        """pdt_argos_messages: the ARGOS messages in the bits of this context's last whole-capture call -- either polarity, 1 .. 8 blocks,
+        with the platform ID -- beside frames(), which stay the reference's.  min_run: the equal bits asked for in front of the sync
+        (None = 6).  Returns ARGOS_MSG_DTYPE[min(found, cap)]; with_count: (that, found)."""
+        c = _argos_cfg(min_run)
+        out, count = np.zeros(max(cap, 1), dtype=ARGOS_MSG_DTYPE), C.c_int(0)
+        _check(self._L.pdt_argos_messages(self._h, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)), "pdt_argos_messages")
+        got = out[:min(count.value, cap)]
+        return (got, count.value) if with_count else got
+
+    def stage_argos_messages(self, bits, min_run=None, cap: int = 4096, with_count: bool = False):
+        """pdt_stage_argos_messages: the message kernels on a string of '0'/'1' characters; the time stamp of bit k is k"""
+        a, c = _bit_string(bits), _argos_cfg(min_run)
+        out, count = np.zeros(max(cap, 1), dtype=ARGOS_MSG_DTYPE), C.c_int(0)
+        _check(self._L.pdt_stage_argos_messages(self._h, a.ctypes.data, a.size, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)),
+               "pdt_stage_argos_messages")
+        got = out[:min(count.value, cap)]
+        return (got, count.value) if with_count else got
+
     def device_math(self, fn: int, records: np.ndarray) -> np.ndarray:
         """pdt_device_math (test hook): the kernels' scalar primitive `fn` evaluated on this context's GPU, one record per lane.
         records: [n, nin] (or [n] where nin is 1) of the code's element type -- it is not converted; returns [n, nout]."""
@@ -1186,6 +1284,8 @@ def synth_lib():
         S.pdt_synth_poes_frame.restype = None
         S.pdt_synth_argos_payload.argtypes = [C.POINTER(SynthParams), C.c_uint64, C.c_void_p]
         S.pdt_synth_argos_payload.restype = None
+        S.pdt_synth_argos_message.argtypes = [C.POINTER(SynthParams), C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_void_p]
+        S.pdt_synth_argos_message.restype = None
         S.pdt_synth_sine_table.restype = C.POINTER(C.c_int16)
         S.pdt_synth_wav_header.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
         S.pdt_synth_wav_header.restype = None
@@ -1201,7 +1301,7 @@ def synth_params(kind: int, sample_rate: int, f0_hz: float = 1000.0, seed: int =
 
 def synth_capture(kind: int, sample_rate: int, seconds: float, f0_hz: float | None = None, seed: int = 1234,
                   start: int = 0) -> np.ndarray:
-    """int16[n,2] synthetic POES (kind 0) / ARGOS (kind 1) capture; bit-reproducible everywhere."""
+    """int16[n,2] synthetic POES (kind 0) / ARGOS (kind 1; kind 2: messages of 1 .. 8 blocks) capture; bit-reproducible everywhere."""
     if f0_hz is None:
         f0_hz = 1000.0 if kind == 0 else 120.0
     p = synth_params(kind, sample_rate, f0_hz, seed)
@@ -1221,6 +1321,13 @@ def synth_argos_payload(p: SynthParams, burst: int) -> np.ndarray:
     out = np.zeros(7, dtype=np.uint8)
     synth_lib().pdt_synth_argos_payload(C.byref(p), burst, out.ctypes.data)
     return out
+
+
+def synth_argos_message(p: SynthParams, burst: int) -> tuple[int, int, np.ndarray]:
+    """kind 2: (blocks, id, the 4 * blocks data bytes) of the message burst `burst` carries"""
+    blocks, ident, data = C.c_int(0), C.c_uint32(0), np.zeros(32, dtype=np.uint8)
+    synth_lib().pdt_synth_argos_message(C.byref(p), burst, C.byref(blocks), C.byref(ident), data.ctypes.data)
+    return blocks.value, ident.value, data[:4 * blocks.value]
 
 
 def write_wav(path: str, sample_rate: int, iq: np.ndarray):

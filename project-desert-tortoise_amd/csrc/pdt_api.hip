@@ -7,6 +7,7 @@
 #include "pdt_survey.h"
 #include "pdt_bursts.h"
 #include "pdt_tone.h"
+#include "pdt_argos_msg.h"
 
 #include <sys/stat.h>
 
@@ -33,6 +34,9 @@ hipError_t tones_launch(hipStream_t st, int nfft, const void *segs_dev, uint64_t
 int tone_plan(const pdt_tone_cfg *cfg, double fs, double range_hz, uint64_t len, int cap, pdt::TonePlan *p);
 void tone_sums(int nfft, double *sw, double *sw2);
 void tones_derive(const void *raw, const pdt::TonePlan &p, double fs, double offset_hz, double sw, double sw2, pdt_tone *out);
+// pdt_argos_msg.hip
+hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, hipEvent_t mid);
+int argos_min_run(const pdt_argos_cfg *cfg, int *K);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -550,7 +554,8 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
-                       &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out };
+                       &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
+                       &ctx->argos_work, &ctx->argos_bits };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1356,6 +1361,174 @@ int pdt_tones(pdt_ctx *ctx, const pdt_tone_cfg *cfg, pdt_tone *out, int cap, int
 {
     if (!ctx || !out || !count) return PDT_ERR_ARG;
     return tones_each(&ctx, 1, cfg, out, cap, count);
+}
+
+// ---------------------------------------------------------------- ARGOS messages (pdt_argos_msg.h)
+// One bit stream of a call: where it is, where its count is (both on the device), what its buffers hold, how many records are wanted
+struct ArgosJob {
+    const unsigned char *bits;
+    const unsigned long long *nbits_dev;
+    const unsigned *bitsym;
+    const long long *symidx;
+    long long bit_cap;
+    int cap;
+};
+
+// The streams of a call through one launch of each kernel over a table on the device, as the segments of pdt_tones are measured: the first
+// context supplies stream and work buffer -- the records and counts of all streams (read back in one copy), the table, every stream's
+// tile counts and candidate bitmap.  recs: stream i's records from at[i] on, found[i] of them counted, min(found[i], room) present.
+static int argos_run(pdt_ctx *c0, const std::vector<ArgosJob> &jobs, int K, std::vector<ArgosMsg> &recs, std::vector<size_t> &at,
+                     std::vector<unsigned> &found)
+{
+    const size_t n = jobs.size();
+    std::vector<ArgosCtx> table(n);
+    std::vector<long long> tiles(n);
+    at.assign(n + 1, 0);
+    long long ntiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        // accepted messages lie at least 65 bits apart (a head's first bit behind a body of 52 bits or more)
+        const long long room = std::min<long long>(jobs[i].cap, jobs[i].bit_cap / 65 + 1);
+        at[i + 1] = at[i] + (size_t)room;
+        tiles[i] = (jobs[i].bit_cap + ARGOS_MSG_TILE - 1) / ARGOS_MSG_TILE;
+        ntiles += tiles[i];
+    }
+    if (ntiles > 0x7fffffffll) return PDT_ERR_ARG;
+    const size_t o_cnt = at[n] * sizeof(ArgosMsg), o_tab = o_cnt + ((n * sizeof(unsigned) + 15) & ~(size_t)15), o_any = o_tab + n * sizeof(ArgosCtx),
+                 o_cand = o_any + (((size_t)ntiles * sizeof(unsigned) + 15) & ~(size_t)15), total = o_cand + (size_t)ntiles * ARGOS_MSG_WORDS * 8;
+    HIP_TRY(hipSetDevice(c0->cfg.device));
+    int rc;
+    if ((rc = c0->argos_work.ensure(total))) return rc;
+    unsigned char *w = (unsigned char *)c0->argos_work.p;
+    long long t0 = 0;
+    for (size_t i = 0; i < n; i++) {
+        ArgosCtx &r = table[i];
+        r.bits = jobs[i].bits;
+        r.nbits = jobs[i].nbits_dev;
+        r.bitsym = jobs[i].bitsym;
+        r.symidx = jobs[i].symidx;
+        r.cand = (unsigned long long *)(w + o_cand) + (size_t)t0 * ARGOS_MSG_WORDS;
+        r.tile_any = (unsigned *)(w + o_any) + t0;
+        r.out = (ArgosMsg *)w + at[i];
+        r.count = (unsigned *)(w + o_cnt) + i;
+        r.bit_cap = jobs[i].bit_cap;
+        r.cap = (int)(at[i + 1] - at[i]);
+        r.first_tile = (int)t0;
+        t0 += tiles[i];
+    }
+    // (the table of the previous call is no longer read: every call ends with a synchronize)
+    HIP_TRY(hipMemcpy(w + o_tab, table.data(), n * sizeof(ArgosCtx), hipMemcpyHostToDevice));
+    hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
+    if (c0->cfg.profile) {
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ev[0], c0->stream));
+    }
+    HIP_TRY(argos_msgs_launch(c0->stream, w + o_tab, (int)n, ntiles, K, ev[1]));
+    if (c0->cfg.profile) HIP_TRY(hipEventRecord(ev[2], c0->stream));
+    std::vector<unsigned char> back(o_tab);
+    HIP_TRY(hipMemcpyAsync(back.data(), w, o_tab, hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    if (c0->cfg.profile) {
+        const char *names[2] = { "k_argos_msgs", "k_argos_finish" };
+        for (int k = 0; k < 2; k++) {
+            pdt_kernel_time kt;
+            memset(&kt, 0, sizeof kt);
+            snprintf(kt.name, sizeof kt.name, "%s", names[k]);
+            kt.launches = 1;
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            kt.total_ms = ms;
+            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [&](const pdt_kernel_time &o) { return !strcmp(o.name, names[k]); }),
+                             c0->ktimes.end());
+            c0->ktimes.push_back(kt);
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    recs.resize(at[n]);
+    if (at[n]) memcpy(recs.data(), back.data(), at[n] * sizeof(ArgosMsg));
+    found.resize(n);
+    if (n) memcpy(found.data(), back.data() + o_cnt, n * sizeof(unsigned));
+    return PDT_OK;
+}
+
+// the whole capture's bits are on the device: a whole-capture call in one piece was the last to write them (stage-level calls and
+// pdt_stream_begin zero every stage length; a piece of a capture or of a stream clears bits_whole)
+static bool bits_resident(const pdt_ctx *c) { return c->bits_whole && !c->stream_open && c->stage_len[PDT_ST_FIR] != 0 && c->bit_time; }
+
+static int argos_each(pdt_ctx *const *ctxs, int count, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap_each, int *counts)
+{
+    int K;
+    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || argos_min_run(cfg, &K)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++) {
+        const pdt_ctx *c = ctxs[i];
+        if (!c || c->cfg.mode != PDT_MODE_ARGOS || c->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == c) return PDT_ERR_ARG;
+    }
+    for (int i = 0; i < count; i++)
+        if (!bits_resident(ctxs[i])) return PDT_ERR_STATE;
+    if (!count) return PDT_OK;
+    try {
+        std::vector<ArgosJob> jobs((size_t)count);
+        for (int i = 0; i < count; i++) {
+            const pdt_ctx *c = ctxs[i];
+            const uint64_t nb = c->stage_len[PDT_ST_BITS];              // (what the host read back; the kernels read the device's own count)
+            jobs[(size_t)i] = ArgosJob{ (const unsigned char *)c->bits.p, &((const DevScalars *)c->scal.p)->nbits, (const unsigned *)c->bitsym.p,
+                                        (const long long *)c->symidx.p, nb && c->bits.p && c->scal.p ? (long long)nb : 0, cap_each };
+        }
+        std::vector<ArgosMsg> recs;
+        std::vector<size_t> at;
+        std::vector<unsigned> found;
+        const int rc = argos_run(ctxs[0], jobs, K, recs, at, found);
+        if (rc) return rc;
+        for (int i = 0; i < count; i++) {
+            const size_t have = std::min<size_t>(found[(size_t)i], at[(size_t)i + 1] - at[(size_t)i]);
+            for (size_t k = 0; k < have; k++) {
+                ArgosMsg m = recs[at[(size_t)i] + k];
+                m.time = ctxs[i]->bit_time(m.time_src);
+                memcpy(&out[(size_t)i * (size_t)cap_each + k], &m, sizeof m);
+            }
+            counts[i] = (int)found[(size_t)i];
+        }
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    return PDT_OK;
+}
+
+int pdt_argos_messages_batch(pdt_ctx *const *ctxs, int count, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap_each, int *counts)
+{
+    return argos_each(ctxs, count, cfg, out, cap_each, counts);
+}
+
+int pdt_argos_messages(pdt_ctx *ctx, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count)
+{
+    if (!ctx || !count) return PDT_ERR_ARG;
+    return argos_each(&ctx, 1, cfg, out, cap, count);
+}
+
+int pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count)
+{
+    int K;
+    if (!ctx || (!bits_host && nbits) || nbits >= (1ull << 31) || cap < 0 || (!out && cap) || !count || argos_min_run(cfg, &K)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_ARGOS) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    // the string in a buffer of its own, its count in front of it: nothing the context's results live in is touched
+    int rc;
+    if ((rc = ctx->argos_bits.ensure(16 + (size_t)nbits))) return rc;
+    const unsigned long long nb = nbits;
+    HIP_TRY(hipMemcpy(ctx->argos_bits.p, &nb, sizeof nb, hipMemcpyHostToDevice));
+    if (nbits) HIP_TRY(hipMemcpy((unsigned char *)ctx->argos_bits.p + 16, bits_host, (size_t)nbits, hipMemcpyHostToDevice));
+    try {
+        const std::vector<ArgosJob> jobs(1, ArgosJob{ (const unsigned char *)ctx->argos_bits.p + 16, (const unsigned long long *)ctx->argos_bits.p, nullptr,
+                                                      nullptr, (long long)nbits, cap });
+        std::vector<ArgosMsg> recs;
+        std::vector<size_t> at;
+        std::vector<unsigned> found;
+        if ((rc = argos_run(ctx, jobs, K, recs, at, found))) return rc;
+        const size_t have = std::min<size_t>(found[0], at[1]);
+        if (have) memcpy(out, recs.data(), have * sizeof(ArgosMsg));
+        *count = (int)found[0];
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    return PDT_OK;
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

@@ -1,0 +1,241 @@
+// pdt_argos_msg.hip -- the ARGOS messages of a bit stream (pdt_argos_msg.h): the kernel that tests every bit for a head, the pass that
+// applies the overlap rule and extracts the bodies, their launch, the host restatement pdt_host_argos_messages and the text of the
+// records.  A unit of its own, beside pdt_tone.hip.
+#include <hip/hip_runtime.h>
+#include <errno.h>
+#include <stdio.h>
+#include <unistd.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/pdt.h"
+#include "pdt_argos_msg.h"
+
+static_assert(sizeof(pdt_argos_msg) == sizeof(pdt::ArgosMsg) && sizeof(pdt_argos_msg) == 72, "pdt_argos_msg");
+static_assert(sizeof(pdt::ArgosCtx) == 80, "the launch's table");
+
+namespace pdt {
+
+// the context workgroup `block` of the grid belongs to: the last whose first tile is not behind it (first_tile ascends, [0] = 0)
+__device__ __forceinline__ int argos_ctx_of(const ArgosCtx *__restrict__ table, int nctx, int block)
+{
+    int lo = 0, hi = nctx - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_tile <= block) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ long long argos_nbits(const ArgosCtx &c)
+{
+    if (c.bit_cap <= 0) return 0;
+    const unsigned long long n = *c.nbits;
+    return n < (unsigned long long)c.bit_cap ? (long long)n : c.bit_cap;
+}
+
+// One workgroup of 256 lanes per tile of ARGOS_MSG_TILE bits, all contexts of a call in one grid (a tile behind its context's device-side
+// bit count returns at once: the grid is sized by what the buffers hold).  The wavefronts pack the tile's bytes into 64-bit words with
+// __ballot -- bit l of a word = the bit at word * 64 + l -- and the 64 bits in front of the tile into a halo word (a head's test looks 27
+// bits back).  Four lanes share a word: each tests sixteen positions for both polarities on the window shifted out of (halo or previous
+// word, own word), the four 16-bit masks are joined by shuffles, and the word of the candidate bitmap goes to memory with the tile's
+// number of heads.  No atomics, no list that could overflow; nothing depends on the order in which anything runs.
+__global__ void __launch_bounds__(256) k_argos_msgs(const ArgosCtx *__restrict__ table, int nctx, int K)
+{
+    __shared__ unsigned long long words[1 + ARGOS_MSG_WORDS];
+    __shared__ unsigned wsum[4];
+    const ArgosCtx c = table[argos_ctx_of(table, nctx, (int)blockIdx.x)];
+    const long long tile = (long long)blockIdx.x - c.first_tile, base = tile * ARGOS_MSG_TILE, nbits = argos_nbits(c);
+    if (base >= nbits) return;
+    const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
+    for (int i = 0; i < ARGOS_MSG_WORDS / 4; i++) {
+        const int w = 4 * i + wave;
+        const long long idx = base + 64ll * w + lane;
+        const unsigned long long m = __ballot(idx < nbits && c.bits[idx] != '0');
+        if (lane == 0) words[1 + w] = m;
+    }
+    if (wave == 0) {
+        const long long idx = base - 64 + lane;                               // (base < nbits: every such bit exists, or lies in front of the stream)
+        const unsigned long long m = __ballot(idx >= 0 && c.bits[idx] != '0');
+        if (lane == 0) words[0] = m;
+    }
+    __syncthreads();
+    const int w = t >> 2, q = t & 3;
+    const unsigned long long prev = words[w], cur = words[1 + w];
+    unsigned long long mask = 0;
+#pragma unroll 4
+    for (int j = 0; j < 16; j++) {
+        const int pos = 16 * q + j, s = 64 - (ARGOS_MSG_WINDOW - 1) + pos;    // the window's first bit in (prev, cur): 37 .. 100
+        const long long e = base + 64ll * w + pos;
+        const unsigned long long v = s < 64 ? (prev >> s) | (cur << (64 - s)) : cur >> (s - 64);
+        if (e < nbits && argos_head((uint32_t)v & ((1u << ARGOS_MSG_WINDOW) - 1u), e, K)) mask |= 1ull << pos;
+    }
+    mask |= __shfl_xor(mask, 1);
+    mask |= __shfl_xor(mask, 2);
+    unsigned heads = 0;
+    if (q == 0) {
+        c.cand[tile * ARGOS_MSG_WORDS + w] = mask;
+        heads = (unsigned)__popcll(mask);
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) heads += __shfl_xor(heads, off);
+    if (lane == 0) wsum[wave] = heads;
+    __syncthreads();
+    if (t == 0) c.tile_any[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// One wavefront per context walks its candidates in ascending e: 64 tiles' counts at a time (a ballot finds the tiles with heads), a
+// tile's 64 bitmap words at a time, a word's bits one by one -- every step uniform over the wavefront.  A head behind the last accepted
+// body is accepted into a list in LDS; a full list, and the last one, is extracted a message per lane (body, flags, time source).
+__global__ void __launch_bounds__(64) k_argos_finish(const ArgosCtx *__restrict__ table, int K)
+{
+    constexpr int LIST = 256;
+    __shared__ long long acc_e[LIST];
+    __shared__ unsigned acc_h[LIST];
+    const ArgosCtx c = table[blockIdx.x];
+    const long long nbits = argos_nbits(c), ntiles = (nbits + ARGOS_MSG_TILE - 1) / ARGOS_MSG_TILE;
+    const int lane = (int)threadIdx.x;
+    long long last_end = -1;
+    unsigned found = 0;
+    int pend = 0;                                                             // messages in the list: records found - pend .. found - 1
+    auto extract = [&]() {
+        __syncthreads();
+        for (int k = lane; k < pend; k += 64) {
+            const unsigned idx = found - (unsigned)pend + (unsigned)k;
+            if (idx >= (unsigned)c.cap) continue;
+            const long long e = acc_e[k];
+            ArgosMsg *m = c.out + idx;
+            argos_fill(c.bits, nbits, e, acc_h[k], m);
+            const long long ts = c.bitsym ? c.symidx[c.bitsym[e]] : e;
+            m->time_src = ts;
+            m->time = (double)ts;
+        }
+        __syncthreads();
+        pend = 0;
+    };
+    for (long long t0 = 0; t0 < ntiles; t0 += 64) {
+        unsigned long long tiles = __ballot(t0 + lane < ntiles && c.tile_any[t0 + lane] != 0);
+        while (tiles) {
+            const long long tile = t0 + (__ffsll(tiles) - 1);
+            tiles &= tiles - 1;
+            const unsigned long long word = c.cand[tile * ARGOS_MSG_WORDS + lane];
+            unsigned long long nz = __ballot(word != 0);
+            while (nz) {
+                const int w = __ffsll(nz) - 1;
+                nz &= nz - 1;
+                unsigned long long hw = __shfl(word, w);
+                while (hw) {
+                    const long long e = tile * ARGOS_MSG_TILE + 64ll * w + (__ffsll(hw) - 1);
+                    hw &= hw - 1;
+                    if (e - 12 <= last_end) continue;
+                    const unsigned h = argos_head(argos_window(c.bits, e), e, K);
+                    if (!h) continue;
+                    last_end = argos_body_end(e, (int)(h & 15u));
+                    if (lane == 0) {
+                        acc_e[pend] = e;
+                        acc_h[pend] = h;
+                    }
+                    pend++;
+                    found++;
+                    if (pend == LIST) extract();
+                }
+            }
+        }
+    }
+    extract();
+    if (lane == 0) *c.count = found;
+}
+
+}  // namespace pdt
+
+using namespace pdt;
+
+namespace pdtrt {
+
+// the two kernels over the nctx records of a table that is on the device; tiles: the grid of the first (the sum of the contexts' tiles).
+// mid: recorded between the two when not NULL (a profiled context times them apart)
+hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, hipEvent_t mid)
+{
+    if (nctx < 1 || tiles < 0 || tiles > 0x7fffffffll || K < 0 || K > ARGOS_MSG_RUN_MAX) return hipErrorInvalidValue;
+    const ArgosCtx *table = (const ArgosCtx *)table_dev;
+    if (tiles) hipLaunchKernelGGL(k_argos_msgs, dim3((unsigned)tiles), dim3(256), 0, st, table, nctx, K);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (mid && (e = hipEventRecord(mid, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_argos_finish, dim3((unsigned)nctx), dim3(64), 0, st, table, K);
+    return hipGetLastError();
+}
+
+// cfg (NULL = the default) -> K; PDT_ERR_ARG outside 0 .. 15
+int argos_min_run(const pdt_argos_cfg *cfg, int *K)
+{
+    *K = ARGOS_MSG_RUN_DEFAULT;
+    if (!cfg) return PDT_OK;
+    if (cfg->min_run < 0 || cfg->min_run > ARGOS_MSG_RUN_MAX) return PDT_ERR_ARG;
+    if (cfg->min_run || (cfg->zero_mask & PDT_ARGOS_ZERO_MIN_RUN)) *K = cfg->min_run;
+    return PDT_OK;
+}
+
+}  // namespace pdtrt
+
+extern "C" {
+
+int pdt_argos_msg_tile(void) { return ARGOS_MSG_TILE; }
+
+int pdt_host_argos_messages(const uint8_t *bits, uint64_t nbits, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count)
+{
+    int K;
+    if ((!bits && nbits) || nbits >= (1ull << 31) || cap < 0 || (!out && cap) || !count || pdtrt::argos_min_run(cfg, &K)) return PDT_ERR_ARG;
+    *count = (int)argos_host_messages(bits, (long long)nbits, K, reinterpret_cast<ArgosMsg *>(out), cap);
+    return PDT_OK;
+}
+
+// one line per complete message: "%.5f", "i" when inverted, " %d %05X" (blocks, id), " %02X" per data byte, "\n"
+static void argos_text(const pdt_argos_msg *msgs, uint64_t n, std::string &s)
+{
+    char b[64];
+    for (uint64_t i = 0; i < n; i++) {
+        const pdt_argos_msg &m = msgs[i];
+        if (!m.complete || m.blocks < 1 || m.blocks > 8) continue;
+        snprintf(b, sizeof b, "%.5f%s %d %05X", m.time, m.inverted ? "i" : "", (int)m.blocks, (unsigned)m.id);
+        s += b;
+        for (int k = 0; k < 4 * m.blocks; k++) {
+            snprintf(b, sizeof b, " %02X", (unsigned)m.data[k]);
+            s += b;
+        }
+        s += '\n';
+    }
+}
+
+uint64_t pdt_format_argos_messages(const pdt_argos_msg *msgs, uint64_t n, char *buf, uint64_t cap)
+{
+    if (!msgs && n) return 0;
+    try {
+        std::string s;
+        argos_text(msgs, n, s);
+        if (buf && cap) memcpy(buf, s.data(), (size_t)std::min<uint64_t>(cap, s.size()));
+        return s.size();
+    } catch (const std::exception &) { return 0; }
+}
+
+int pdt_write_argos_messages(const pdt_argos_msg *msgs, uint64_t n, int fd, uint64_t *bytes_written)
+{
+    if (bytes_written) *bytes_written = 0;
+    if ((!msgs && n) || fd < 0) return PDT_ERR_ARG;
+    try {
+        std::string s;
+        argos_text(msgs, n, s);
+        size_t at = 0;
+        while (at < s.size()) {
+            const ssize_t r = write(fd, s.data() + at, s.size() - at);
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) return PDT_ERR_IO;
+            at += (size_t)r;
+        }
+        if (bytes_written) *bytes_written = s.size();
+        return PDT_OK;
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+}  // extern "C"

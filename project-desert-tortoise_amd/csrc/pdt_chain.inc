@@ -72,7 +72,8 @@ template <typename T> int finish_capture(pdt_ctx *ctx, uint64_t n, const FinishA
 
     // time stamp of the bit whose symbol was taken at global interpolated-sample index g, in a capture of n_all samples
     // (SURVEY Appendix B Q1/Q2/Q4)
-    auto frame_time = [&](long long g, long long n_all) -> double {
+    // (captured by value: pdt_argos_messages stamps bits with it after this call has returned)
+    auto frame_time = [ctx, argos, chunk, chunk_out, interp](long long g, long long n_all) -> double {
         if (argos && sizeof(T) == 4) return (double)ctx->axis_f.at((uint64_t)g + 1);     // the twin: float stamps (pdt_open)
         if (argos) return ctx->axis_d.at((uint64_t)g + 1);                   // waveDataTime[i] = (i+1)-th partial sum
         const long long c = g / chunk_out, rr = g % chunk_out;
@@ -110,6 +111,7 @@ template <typename T> int finish_capture(pdt_ctx *ctx, uint64_t n, const FinishA
     ctx->timers.clear();
     };
 
+    ctx->bits_whole = !seg;                   // (pdt_argos_messages: a piece's bits are not the capture's)
     if (seg) {
         // ---- stream segment: hand the new frames to the stream code, carry every stage's state to the next segment
         SegTail<T> tail;
@@ -291,6 +293,8 @@ template <typename T> int finish_capture(pdt_ctx *ctx, uint64_t n, const FinishA
         memcpy(o.bytes, r.bytes, 104);
         o.time = frame_time(r.time_src, N);
     }
+    // the same stamp for any bit of this capture, for as long as its bits stay resident (pdt_argos_messages)
+    ctx->bit_time = [frame_time, N](long long g) -> double { return frame_time(g, N); };
 
     collect_timers();
     if (ctx->progress_fn && !ctx->chunk_host.empty()) {          // pdt_set_progress: a whole capture reports once, at its end

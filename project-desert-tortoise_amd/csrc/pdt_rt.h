@@ -468,6 +468,11 @@ struct pdt_ctx {
     DevBuf tone_table, tone_out;
     int tone_sum_nfft = 0;              // the window's sums below are those of this many points (0 = none yet)
     double tone_sw = 0, tone_sw2 = 0;
+    // ARGOS messages (pdt_argos_msg.h): the launch's table, bitmaps and records on the device (first context of a call), the string of
+    // the stage entry; whether the last call left the whole capture's bits resident, and the time stamp of one of them as a frame's is formed
+    DevBuf argos_work, argos_bits;
+    bool bits_whole = false;
+    std::function<double(long long)> bit_time;
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
     int held_fmt = 0;

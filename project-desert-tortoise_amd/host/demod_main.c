@@ -64,6 +64,13 @@
  * line per segment at stride N along the channel, without the index: the Doppler curve (several channels: a file each, the index
  * appended as to the output's name).  Not from a pipe, not with -l, and not for a capture that left no channel stream in one piece: a
  * message, exit status 1.  Without -M nothing changes.
+ * -A <file> (an addition, demodARGOS): who sent what -- the ARGOS messages in the bits of whatever was demodulated (pdt_argos_messages,
+ * either polarity, 1 .. 8 blocks, the platform ID), one line per complete message, "%.5f" of its time, "i" when its bits
+ * arrived complemented, " %d %05X" of its blocks and ID, " %02X" per data byte.  One-shot runs, -x with -t <kHz>, -t auto and -t bursts
+ * (several channels: a file each, the index appended); -t each: every window's messages through one pdt_argos_messages_batch per round,
+ * beside the -M pass, their times counted from the capture's start as the packets' are.  The packets file is what it was.  Not for
+ * demodPOES, not from a pipe (-l -), and not for a capture that left no bit stream in one piece (one taken through the bounded
+ * window): a message, exit status 1.  Without -A nothing changes.
  */
 #include <ctype.h>
 #include <math.h>
@@ -80,14 +87,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -303,10 +310,39 @@ static int write_tones(pdt_ctx *ctx, const char *name)
     return 0;
 }
 
+/* -A: the messages in the bits of ctx's last capture, one line each (pdt_argos_messages at its defaults).  Returns 0 when
+ * the file is written. */
+static int write_messages(pdt_ctx *ctx, const char *name)
+{
+    const int cap = (int)(pdt_stage_len(ctx, PDT_ST_BITS) / 65 + 1);      /* (messages lie at least 65 bits apart) */
+    pdt_argos_msg *msgs = (pdt_argos_msg *)malloc((size_t)cap * sizeof *msgs);
+    int n = 0;
+    const int rc = msgs ? pdt_argos_messages(ctx, NULL, msgs, cap, &n) : PDT_ERR_NOMEM;
+    if (rc == PDT_ERR_STATE) printf("-A needs a capture taken in one piece: this one left no bit stream\n");
+    else if (rc != PDT_OK) printf("Message decoding failed: %s\n", pdt_strerror(rc));
+    FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !m) printf("Error opening %s\n", name);
+    if (!m) {
+        free(msgs);
+        return 1;
+    }
+    if (n > cap) n = cap;
+    fflush(m);
+    const int wrc = pdt_write_argos_messages(msgs, (uint64_t)n, fileno(m), NULL);
+    fclose(m);
+    free(msgs);
+    if (wrc != PDT_OK) {
+        printf("Error writing %s\n", name);
+        return 1;
+    }
+    printf("Messages: %d -> %s\n", n, name);
+    return 0;
+}
+
 /* -x with several -t: one wideband capture, one context per channel, the capture ingested once (pdt_demod_channels); every
  * channel's frames go to a file of its own, outFileName with ".<index>" appended */
 static int multi_channel(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim,
-                         const double *offsetsHz, int nch, const char *outFileName, const char *measureName)
+                         const double *offsetsHz, int nch, const char *outFileName, const char *measureName, const char *messageName)
 {
     pdt_ctx *ctxs[16];
     int rc = PDT_OK;
@@ -353,6 +389,10 @@ static int multi_channel(FILE *in, long data_offset, uint64_t nframes, size_t fr
         if (measureName) {
             snprintf(name, sizeof name, "%s.%d", measureName, i);
             if (write_tones(ctxs[i], name)) return 1;
+        }
+        if (messageName) {
+            snprintf(name, sizeof name, "%s.%d", messageName, i);
+            if (write_messages(ctxs[i], name)) return 1;
         }
         pdt_close(ctxs[i]);
     }
@@ -507,7 +547,7 @@ static int burst_channels(FILE *in, long data_offset, uint64_t nframes, size_t f
  * windows in rounds on a pool of contexts, from the copy of the capture the search left on the device (pdt_demod_windows_held).
  * Every window's records, their times counted from the capture's start, go to one file. */
 static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame_bytes, int fmt, const pdt_config *cfg, int decim, double max_s,
-                      int poolSize, const char *outFileName, const char *measureName)
+                      int poolSize, const char *outFileName, const char *measureName, const char *messageName)
 {
     enum { POOL = 64 };
     pdt_ctx *holder = NULL, *pool[POOL];
@@ -527,6 +567,8 @@ static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame
     }
     pdt_frame *all = NULL;
     uint64_t total = 0, room = 0;
+    pdt_argos_msg *msgs = NULL;                          /* -A: every window's messages, in window order */
+    uint64_t nmsgs = 0, msgRoom = 0;
     int locked = 0;
     FILE *measure = measureName && rc == PDT_OK ? fopen(measureName, "w") : NULL;
     if (measureName && rc == PDT_OK && !measure) {
@@ -554,6 +596,31 @@ static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame
                 if (counts[i])
                     fprintf(measure, "%d %.5f %.2f %.1f %.1f\n", index[i], (double)win[index[i]].first_frame / (double)in_rate + tones[i].time_s,
                             tones[i].freq_hz, tones[i].cn0_dbhz, 10.0 * log10(tones[i].power));
+        }
+        if (messageName && rc == PDT_OK) {
+            /* -A: the messages of every window of the round, all in one launch (pdt_argos_messages_batch); a window of a burst holds
+             * a handful at most */
+            enum { EACH = 16 };
+            static pdt_argos_msg got[POOL * EACH];
+            int counts[POOL];
+            rc = pdt_argos_messages_batch(pool, k, NULL, got, EACH, counts);
+            for (int i = 0; i < k && rc == PDT_OK; i++) {
+                const int n = counts[i] < EACH ? counts[i] : EACH;
+                if (nmsgs + (uint64_t)n > msgRoom) {
+                    msgRoom = 2 * (nmsgs + (uint64_t)n) + 64;
+                    pdt_argos_msg *grown = (pdt_argos_msg *)realloc(msgs, (size_t)msgRoom * sizeof *msgs);
+                    if (!grown) {
+                        rc = PDT_ERR_NOMEM;
+                        break;
+                    }
+                    msgs = grown;
+                }
+                const double shift = (double)win[r0 + i].first_frame / (double)in_rate;
+                for (int f = 0; f < n; f++) {
+                    msgs[nmsgs] = got[i * EACH + f];
+                    msgs[nmsgs++].time += shift;
+                }
+            }
         }
         for (int i = 0; i < k && rc == PDT_OK; i++) {
             const uint64_t n = pdt_num_frames(pool[i]);
@@ -591,6 +658,16 @@ static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame
         return 1;
     }
     printf("Bursts: %d, locked: %d, packets: %d\n", count, locked, (int)total);
+    if (messageName) {
+        FILE *m = fopen(messageName, "w");
+        if (!m || pdt_write_argos_messages(msgs, nmsgs, fileno(m), NULL) != PDT_OK) {
+            printf("Error writing %s\n", messageName);
+            return 1;
+        }
+        fclose(m);
+        printf("Messages: %d -> %s\n", (int)nmsgs, messageName);
+    }
+    free(msgs);
     FILE *o = fopen(outFileName, "w+");
     if (!o || pdt_write_records(all, total, fileno(o), NULL) != PDT_OK) {
         printf("Error writing output file\n");
@@ -623,6 +700,7 @@ int main(int argc, char **argv)
     int eachBurst = 0;                                                              /* -t each[:N]: every burst in a window of its own, N contexts */
     double offsetsHz[16];
     const char *outOverride = NULL, *measureName = NULL;                            /* -M: the carrier measurement's file */
+    const char *messageName = NULL;                                                 /* -A: the ARGOS messages' file */
     char outFileName[1100];
 
     printf(BANNER);
@@ -724,6 +802,9 @@ int main(int argc, char **argv)
         case 'M':                                       /* the carrier of every burst, or of the channel at a stride, to this file */
             measureName = optarg;
             break;
+        case 'A':                                       /* the ARGOS messages in the bits, to this file */
+            messageName = optarg;
+            break;
         case 'B':                                       /* -t bursts: the longest transmission that is a burst, seconds (0: no limit) */
             burstMaxS = atof(optarg);
             if (!(burstMaxS >= 0)) {
@@ -786,6 +867,10 @@ int main(int argc, char **argv)
     }
     if (measureName && (from_stdin || live || !decim)) {
         printf("-M needs a wideband capture file (-x) taken in one piece: not a pipe, not -l\n");
+        return 1;
+    }
+    if (messageName && (MODE != PDT_MODE_ARGOS || from_stdin)) {
+        printf("-A needs demodARGOS and a capture taken in one piece: not a pipe\n");
         return 1;
     }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
@@ -917,7 +1002,7 @@ int main(int argc, char **argv)
     cfg.device = device;
     cfg.sampler = sampler;
     cfg.chain = live ? PDT_CHAIN_LIVE : PDT_CHAIN_FILE;
-    if (eachBurst) return each_burst(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, burstMaxS, eachBurst, outFileName, measureName);
+    if (eachBurst) return each_burst(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, burstMaxS, eachBurst, outFileName, measureName, messageName);
     if (autoCarriers) {
         if (autoBursts ? burst_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, burstMaxS, offsetsHz, &nOffsets)
                        : auto_channels(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, autoCarriers, offsetsHz, &nOffsets))
@@ -928,7 +1013,7 @@ int main(int argc, char **argv)
             exit(1);
         }
     }
-    if (nOffsets > 1) return multi_channel(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, offsetsHz, nOffsets, outFileName, measureName);
+    if (nOffsets > 1) return multi_channel(in, data_offset, nframes, frame_bytes, sample_format, &cfg, decim, offsetsHz, nOffsets, outFileName, measureName, messageName);
     pdt_ctx *ctx = NULL;
     const double t_open0 = now_ms();
     int rc = pdt_open(&cfg, &ctx);
@@ -1008,6 +1093,11 @@ int main(int argc, char **argv)
     }
 #endif
     if (measureName && write_tones(ctx, measureName)) {
+        fclose(out);
+        remove(outFileName);
+        exit(1);
+    }
+    if (messageName && write_messages(ctx, messageName)) {
         fclose(out);
         remove(outFileName);
         exit(1);

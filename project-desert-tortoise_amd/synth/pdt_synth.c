@@ -96,18 +96,27 @@ void pdt_synth_argos_payload(const pdt_synth_params *p, uint64_t burst, uint8_t 
         out[b] = (uint8_t)pdt_synth_argos_payload_byte(p->seed, burst, b);
 }
 
+void pdt_synth_argos_message(const pdt_synth_params *p, uint64_t burst, int *blocks, uint32_t *id, uint8_t data[32])
+{
+    const uint32_t n = pdt_synth_argos_blocks(p->seed, burst);
+    *blocks = (int)n;
+    *id = pdt_synth_argos_id(p->seed, burst);
+    for (uint32_t b = 0; b < 32; b++)
+        data[b] = b < 4 * n ? (uint8_t)pdt_synth_argos_data_byte(p->seed, burst, b) : 0;
+}
+
 #ifdef PDT_SYNTH_MAIN
-/* synth_wav poes|argos <sample_rate> <seconds> <f0_hz> <seed> out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]
+/* synth_wav poes|argos|argosn <sample_rate> <seconds> <f0_hz> <seed> out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]
  * with the optional arguments: a pass -- lead_s / tail_s seconds of noise only at the ends, the carrier ramping from f0_hz to
  * f_end_hz in between, the amplitude envelope's floor (0 = flat), the noise amplitude multiplied by noise_x */
 #include <stdio.h>
 int main(int argc, char **argv)
 {
     if (argc < 7) {
-        fprintf(stderr, "usage: %s poes|argos sample_rate seconds f0_hz seed out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]\n", argv[0]);
+        fprintf(stderr, "usage: %s poes|argos|argosn sample_rate seconds f0_hz seed out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]\n", argv[0]);
         return 2;
     }
-    int kind = strcmp(argv[1], "argos") == 0;
+    int kind = strcmp(argv[1], "argosn") == 0 ? 2 : strcmp(argv[1], "argos") == 0;      /* argosn: messages of 1 .. 8 blocks (kind 2) */
     uint32_t fs = (uint32_t)strtoul(argv[2], NULL, 10);
     double secs = atof(argv[3]);
     pdt_synth_params p;

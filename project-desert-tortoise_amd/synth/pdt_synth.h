@@ -17,6 +17,10 @@
  *             carrier, then 400 bit/s Manchester PM (m = 1.1 rad) of
  *             15 x '1', 0001 0111, 1, 0000, 56 payload bits, 1010
  *             (sync "0001011110000": ARGOSdemod/main.c:284), noise 25 dB down.
+ *  ARGOS as specified (kind 2): the same bursts with messages of every length: 15 x '1',
+ *             0001 0111, 1, the length code of N (N - 1 in three bits and an even-parity
+ *             bit), a 20-bit ID, 32 N data bits, then carrier off; N = 1 + (burst + seed)
+ *             mod 8, so eight consecutive bursts cover every length (360 .. 920 ms).
  *
  * A pass as a receiver sees it (round 6; every field 0 = off, the captures above unchanged): noise only before
  * `signal_start` (the receiver is on before the satellite rises) and from `signal_end` on (it stays on after it has set);
@@ -41,7 +45,7 @@
 #define PDT_SYNTH_TABLE_SIZE (1u << PDT_SYNTH_TABLE_BITS)
 
 typedef struct pdt_synth_params {
-    uint32_t kind;          /* 0 = POES, 1 = ARGOS                                        */
+    uint32_t kind;          /* 0 = POES, 1 = ARGOS, 2 = ARGOS with messages of 1 .. 8 blocks */
     uint32_t sample_rate;   /* Hz                                                         */
     uint32_t carrier_step;  /* round(f0 / Fs * 2^32)                                      */
     uint32_t phase0;        /* phi0 in turns * 2^32                                       */
@@ -98,6 +102,33 @@ PDT_SYNTH_FN uint32_t pdt_synth_argos_bit(uint64_t seed, uint64_t burst, uint32_
     return (j & 1u) ? 0u : 1u;                            /* 84..87 = 1010 */
 }
 
+/* kind 2: the blocks N = 1 .. 8 of burst `burst`, its 20-bit ID, byte `b` (0 .. 4 N - 1) of its data */
+PDT_SYNTH_FN uint32_t pdt_synth_argos_blocks(uint64_t seed, uint64_t burst) { return 1u + (uint32_t)((burst + seed) & 7u); }
+PDT_SYNTH_FN uint32_t pdt_synth_argos_id(uint64_t seed, uint64_t burst)
+{
+    return (uint32_t)(pdt_synth_mix(seed ^ (burst * 64u + 33u) * 0xA24BAED4963EE407ull) >> 24) & 0xFFFFFu;
+}
+PDT_SYNTH_FN uint32_t pdt_synth_argos_data_byte(uint64_t seed, uint64_t burst, uint32_t b)
+{
+    return (uint32_t)(pdt_synth_mix(seed ^ (burst * 64u + b + 34u) * 0x9FB21C651E98DF25ull) >> 24) & 0xFFu;
+}
+
+/* kind 2: bit `j` (0 .. 47 + 32 N) of a burst's message */
+PDT_SYNTH_FN uint32_t pdt_synth_argos_msg_bit(uint64_t seed, uint64_t burst, uint32_t j)
+{
+    if (j < 15) return 1;
+    if (j < 23) return (0x17u >> (22 - j)) & 1u;         /* 0001 0111 */
+    if (j == 23) return 1;
+    if (j < 28) {
+        const uint32_t n1 = pdt_synth_argos_blocks(seed, burst) - 1u;
+        const uint32_t code = (n1 << 1) | (((n1 >> 2) ^ (n1 >> 1) ^ n1) & 1u);
+        return (code >> (27 - j)) & 1u;
+    }
+    if (j < 48) return (pdt_synth_argos_id(seed, burst) >> (47 - j)) & 1u;
+    const uint32_t k = j - 48;
+    return (pdt_synth_argos_data_byte(seed, burst, k >> 3) >> (7 - (k & 7))) & 1u;
+}
+
 PDT_SYNTH_FN int32_t pdt_synth_noise(uint64_t h, int32_t gain_q16)
 {   /* Irwin-Hall(4) of 16-bit uniforms, zero mean, scaled by gain/65536 */
     int32_t s = (int32_t)(h & 0xFFFF) + (int32_t)((h >> 16) & 0xFFFF) + (int32_t)((h >> 32) & 0xFFFF) +
@@ -151,8 +182,10 @@ PDT_SYNTH_FN void pdt_synth_sample(const pdt_synth_params *p, const int16_t *sin
             /* unmodulated carrier */
         } else {
             uint64_t k = ((off - lead) * 800ull) / p->sample_rate;     /* symbol index */
-            if (k < 176) {
-                uint32_t v = pdt_synth_argos_bit(p->seed, burst, (uint32_t)(k >> 1));
+            const uint64_t nsym = p->kind == 2 ? 2u * (48u + 32u * pdt_synth_argos_blocks(p->seed, burst)) : 176u;
+            if (k < nsym) {
+                uint32_t v = p->kind == 2 ? pdt_synth_argos_msg_bit(p->seed, burst, (uint32_t)(k >> 1))
+                                          : pdt_synth_argos_bit(p->seed, burst, (uint32_t)(k >> 1));
                 int up = (v != 0) ^ (int)(k & 1);
                 theta += up ? p->mod_index : (uint32_t)(0u - p->mod_index);
             } else {
@@ -187,6 +220,8 @@ void pdt_synth_wav_header(uint8_t hdr[44], uint32_t sample_rate, uint64_t nframe
 /* frames / payloads the generator transmitted (for round-trip checks) */
 void pdt_synth_poes_frame(const pdt_synth_params *p, uint64_t fr, uint8_t out[104]);
 void pdt_synth_argos_payload(const pdt_synth_params *p, uint64_t burst, uint8_t out[7]);
+/* kind 2: the message burst `burst` carries -- its blocks, its ID, its 4 N data bytes (the rest of data: 0) */
+void pdt_synth_argos_message(const pdt_synth_params *p, uint64_t burst, int *blocks, uint32_t *id, uint8_t data[32]);
 #ifdef __cplusplus
 }
 #endif

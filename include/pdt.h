@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 17): the ARGOS messages in the bits, either polarity, 1 .. 8 blocks, with the platform ID --
+/* 4, additions without a bump (round 18): a second, opt-in rule for the ARGOS messages' heads -- pdt_argos_cfg.rule (the first of the two
+ * reserved words: a zeroed cfg is the rule there was), PDT_ARGOS_RULE_FIRST, PDT_ARGOS_RULE_BEST, PDT_ARGOS_MSG_RUN_LEN,
+ * PDT_ARGOS_MSG_SLIP; no new symbol.
+ * 4, additions without a bump (round 17): the ARGOS messages in the bits, either polarity, 1 .. 8 blocks, with the platform ID --
  * pdt_argos_cfg, pdt_argos_msg, pdt_argos_messages, pdt_argos_messages_batch, pdt_stage_argos_messages, pdt_host_argos_messages,
  * pdt_argos_msg_tile, pdt_format_argos_messages, pdt_write_argos_messages: a result beside the frames, which stay the reference's.
  * 4, additions without a bump (round 13): the carrier of a channel stream as a measurement -- pdt_tone_cfg, pdt_tone, pdt_tones,
@@ -655,6 +658,18 @@ int  pdt_host_tones(uint32_t rate, double offset_hz, const float *iq, uint64_t n
  * the rest of its ID.
  * pdt_argos_cfg: NULL or a zero field = the default, min_run 6 (allowed 0 .. 15); min_run 0 with PDT_ARGOS_ZERO_MIN_RUN in zero_mask
  * asks for no run at all (as pdt_loop_params.zero_mask does for a loop constant).
+ * pdt_argos_cfg.rule: PDT_ARGOS_RULE_FIRST (0, the default) is the rule above.  PDT_ARGOS_RULE_BEST (1) tolerates one stray bit and picks
+ * among overlapping heads by the length of their run: with run_len(s), s in {0, 1}, = the number of equal raw bits that end at bit
+ * e-13-s (counted backwards to at most 15, not past bit 0; 0 when that bit does not exist), a head at e -- sync and length code as
+ * above -- takes s = 0 if run_len(0) >= min_run, otherwise s = 1 if run_len(1) >= min_run, otherwise it is none (min_run 0: s = 0); the
+ * bit e-13 of an s = 1 head is a stray bit of either value.  Its score is 2 run_len(s) + (1 - s), its span [e-12, e+20+32 N].  A head
+ * is accepted if and only if no accepted head of higher priority -- the higher score, at equal score the smaller e -- has a span that
+ * overlaps its own; rejected heads leave no trace and the records come in ascending e.  Selection runs per cluster: in ascending e a
+ * head joins the current cluster if its span begins at or before the largest span end seen in it and the cluster holds fewer than 256
+ * heads, else it opens a new one; the heads accepted in the preceding cluster count as accepted (this matters only where the cap of 256
+ * closed it).  Under rule 1 run_value = the bit e-13-s as the polarity reads it (0 when run_len is 0) and reserved_ carries run_len and
+ * s (PDT_ARGOS_MSG_RUN_LEN, PDT_ARGOS_MSG_SLIP); under rule 0 reserved_ is 0.  Any other rule is PDT_ERR_ARG at every entry.  A profiled
+ * context's kernel times name rule 1's kernels k_argos_heads and k_argos_pick.
  * pdt_argos_msg: bit_index = e; time_src and time = those of a pdt_frame whose sync word completes at bit e (an upright one-block
  * message carries exactly its frame's); id, blocks = N, inverted = the polarity, run_value = the run's bits as that polarity reads them
  * (1: the bit-sync ones came out as ones; 0 when min_run is 0); data = the 32 N data bits, MSB first, in 4 N bytes, the rest 0; complete = 1 when the stream holds the whole body, else
@@ -676,10 +691,15 @@ int  pdt_host_tones(uint32_t rate, double offset_hz, const float *iq, uint64_t n
  * byte, "\n" -- through pdt_format_argos_messages (returns the bytes needed, writes at most cap) or pdt_write_argos_messages (to an
  * open descriptor; PDT_ERR_IO when a write fails; *bytes_written may be NULL).                                                        */
 #define PDT_ARGOS_ZERO_MIN_RUN 1u
+#define PDT_ARGOS_RULE_FIRST 0
+#define PDT_ARGOS_RULE_BEST  1
+#define PDT_ARGOS_MSG_RUN_LEN(m) ((int)((m)->reserved_ & 0xffu))        /* rule 1: run_len(s) of the record *m */
+#define PDT_ARGOS_MSG_SLIP(m)    ((int)(((m)->reserved_ >> 8) & 1u))    /* rule 1: s, 1 = a stray bit between run and sync */
 typedef struct pdt_argos_cfg {
     int32_t  min_run;
     uint32_t zero_mask;
-    int32_t  reserved_[2];
+    int32_t  rule;
+    int32_t  reserved_;
 } pdt_argos_cfg;
 typedef struct pdt_argos_msg {
     double   time;

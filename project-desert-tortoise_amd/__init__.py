@@ -302,8 +302,8 @@ def tones_batch(ds, **cfg):
 
 
 class ArgosCfg(C.Structure):
-    """pdt_argos_cfg: a zero means the default; min_run 0 with ARGOS_ZERO_MIN_RUN in zero_mask asks for no run"""
-    _fields_ = [("min_run", C.c_int32), ("zero_mask", C.c_uint32), ("reserved_", C.c_int32 * 2)]
+    """pdt_argos_cfg: a zero means the default; min_run 0 with ARGOS_ZERO_MIN_RUN in zero_mask asks for no run; rule = ARGOS_RULE_*"""
+    _fields_ = [("min_run", C.c_int32), ("zero_mask", C.c_uint32), ("rule", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class ArgosMsg(C.Structure):
@@ -314,17 +314,31 @@ class ArgosMsg(C.Structure):
 
 
 ARGOS_ZERO_MIN_RUN = 1
+ARGOS_RULE_FIRST, ARGOS_RULE_BEST = 0, 1         # PDT_ARGOS_RULE_*: the first head in ascending e (the default); the best head of a cluster
 # pdt_argos_msg as a numpy record
 ARGOS_MSG_DTYPE = np.dtype([("time", "<f8"), ("bit_index", "<i8"), ("time_src", "<i8"), ("id", "<u4"), ("blocks", "u1"), ("inverted", "u1"),
                             ("complete", "u1"), ("run_value", "u1"), ("data_bits", "<u4"), ("reserved_", "<u4"), ("data", "u1", (32,))])
 assert ARGOS_MSG_DTYPE.itemsize == C.sizeof(ArgosMsg) == 72
 
 
-def _argos_cfg(min_run):
-    """min_run (None = the default, 6) -> pdt_argos_cfg or None; 0 travels with its flag bit"""
-    if min_run is None:
+def _argos_cfg(min_run, rule=None):
+    """min_run (None = the default, 6) and rule (None = ARGOS_RULE_FIRST) -> pdt_argos_cfg or None; min_run 0 travels with its flag bit"""
+    if min_run is None and rule is None:
         return None
-    return ArgosCfg(min_run=int(min_run), zero_mask=ARGOS_ZERO_MIN_RUN if int(min_run) == 0 else 0)
+    c = ArgosCfg(rule=int(rule or 0))
+    if min_run is not None:
+        c.min_run, c.zero_mask = int(min_run), ARGOS_ZERO_MIN_RUN if int(min_run) == 0 else 0
+    return c
+
+
+def argos_run_len(msgs):
+    """PDT_ARGOS_MSG_RUN_LEN of records of rule ARGOS_RULE_BEST: the length of the run each head was taken with"""
+    return np.asarray(msgs["reserved_"]) & 0xFF
+
+
+def argos_slip(msgs):
+    """PDT_ARGOS_MSG_SLIP of records of rule ARGOS_RULE_BEST: 1 where a stray bit stands between run and sync"""
+    return (np.asarray(msgs["reserved_"]) >> 8) & 1
 
 
 def _bit_string(bits) -> np.ndarray:
@@ -339,10 +353,10 @@ def argos_msg_tile() -> int:
     return lib().pdt_argos_msg_tile()
 
 
-def host_argos_messages(bits, min_run=None, cap: int = 4096, with_count: bool = False):
+def host_argos_messages(bits, min_run=None, cap: int = 4096, with_count: bool = False, rule=None):
     """pdt_host_argos_messages: the ARGOS messages in a string of '0'/'1' characters, restated on the host (no GPU); the time stamp of
-    bit k is k.  Returns ARGOS_MSG_DTYPE[min(found, cap)]; with_count: (that, found)."""
-    a, c = _bit_string(bits), _argos_cfg(min_run)
+    bit k is k.  rule: ARGOS_RULE_FIRST (None) or ARGOS_RULE_BEST.  Returns ARGOS_MSG_DTYPE[min(found, cap)]; with_count: (that, found)."""
+    a, c = _bit_string(bits), _argos_cfg(min_run, rule)
     out, count = np.zeros(max(cap, 1), dtype=ARGOS_MSG_DTYPE), C.c_int(0)
     _check(lib().pdt_host_argos_messages(a.ctypes.data, a.size, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)),
            "pdt_host_argos_messages")
@@ -350,10 +364,10 @@ def host_argos_messages(bits, min_run=None, cap: int = 4096, with_count: bool = 
     return (got, count.value) if with_count else got
 
 
-def argos_messages_batch(ds, min_run=None, cap: int = 4096):
+def argos_messages_batch(ds, min_run=None, cap: int = 4096, rule=None):
     """pdt_argos_messages_batch: Demodulator.argos_messages() of several contexts of one device with ONE launch of each kernel: a list of
     ARGOS_MSG_DTYPE arrays, one per context."""
-    c = _argos_cfg(min_run)
+    c = _argos_cfg(min_run, rule)
     hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
     out, counts = np.zeros((max(len(ds), 1), max(cap, 1)), dtype=ARGOS_MSG_DTYPE), (C.c_int * max(len(ds), 1))()
     _check(lib().pdt_argos_messages_batch(hs, len(ds), C.byref(c) if c else None, out.ctypes.data, cap, counts),
@@ -930,19 +944,19 @@ class Demodulator:
         _check(self._L.pdt_tones(self._h, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)), "pdt_tones")
         return out[:count.value]
 
-    def argos_messages(self, min_run=None, cap: int = 4096, with_count: bool = False):
+    def argos_messages(self, min_run=None, cap: int = 4096, with_count: bool = False, rule=None):
         """pdt_argos_messages: the ARGOS messages in the bits of this context's last whole-capture call -- either polarity, 1 .. 8 blocks,
         with the platform ID -- beside frames(), which stay the reference's.  min_run: the equal bits asked for in front of the sync
         (None = 6).  Returns ARGOS_MSG_DTYPE[min(found, cap)]; with_count: (that, found)."""
-        c = _argos_cfg(min_run)
+        c = _argos_cfg(min_run, rule)
         out, count = np.zeros(max(cap, 1), dtype=ARGOS_MSG_DTYPE), C.c_int(0)
         _check(self._L.pdt_argos_messages(self._h, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)), "pdt_argos_messages")
         got = out[:min(count.value, cap)]
         return (got, count.value) if with_count else got
 
-    def stage_argos_messages(self, bits, min_run=None, cap: int = 4096, with_count: bool = False):
+    def stage_argos_messages(self, bits, min_run=None, cap: int = 4096, with_count: bool = False, rule=None):
         """pdt_stage_argos_messages: the message kernels on a string of '0'/'1' characters; the time stamp of bit k is k"""
-        a, c = _bit_string(bits), _argos_cfg(min_run)
+        a, c = _bit_string(bits), _argos_cfg(min_run, rule)
         out, count = np.zeros(max(cap, 1), dtype=ARGOS_MSG_DTYPE), C.c_int(0)
         _check(self._L.pdt_stage_argos_messages(self._h, a.ctypes.data, a.size, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)),
                "pdt_stage_argos_messages")

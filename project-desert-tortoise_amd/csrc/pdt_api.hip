@@ -35,8 +35,8 @@ int tone_plan(const pdt_tone_cfg *cfg, double fs, double range_hz, uint64_t len,
 void tone_sums(int nfft, double *sw, double *sw2);
 void tones_derive(const void *raw, const pdt::TonePlan &p, double fs, double offset_hz, double sw, double sw2, pdt_tone *out);
 // pdt_argos_msg.hip
-hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, hipEvent_t mid);
-int argos_min_run(const pdt_argos_cfg *cfg, int *K);
+hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, int rule, hipEvent_t mid);
+int argos_min_run(const pdt_argos_cfg *cfg, int *K, int *rule);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -1377,7 +1377,7 @@ struct ArgosJob {
 // The streams of a call through one launch of each kernel over a table on the device, as the segments of pdt_tones are measured: the first
 // context supplies stream and work buffer -- the records and counts of all streams (read back in one copy), the table, every stream's
 // tile counts and candidate bitmap.  recs: stream i's records from at[i] on, found[i] of them counted, min(found[i], room) present.
-static int argos_run(pdt_ctx *c0, const std::vector<ArgosJob> &jobs, int K, std::vector<ArgosMsg> &recs, std::vector<size_t> &at,
+static int argos_run(pdt_ctx *c0, const std::vector<ArgosJob> &jobs, int K, int rule, std::vector<ArgosMsg> &recs, std::vector<size_t> &at,
                      std::vector<unsigned> &found)
 {
     const size_t n = jobs.size();
@@ -1386,7 +1386,7 @@ static int argos_run(pdt_ctx *c0, const std::vector<ArgosJob> &jobs, int K, std:
     at.assign(n + 1, 0);
     long long ntiles = 0;
     for (size_t i = 0; i < n; i++) {
-        // accepted messages lie at least 65 bits apart (a head's first bit behind a body of 52 bits or more)
+        // accepted messages lie at least 65 bits apart (a head's first bit behind a body of 52 bits or more; rule 1: spans do not overlap)
         const long long room = std::min<long long>(jobs[i].cap, jobs[i].bit_cap / 65 + 1);
         at[i + 1] = at[i] + (size_t)room;
         tiles[i] = (jobs[i].bit_cap + ARGOS_MSG_TILE - 1) / ARGOS_MSG_TILE;
@@ -1422,13 +1422,13 @@ static int argos_run(pdt_ctx *c0, const std::vector<ArgosJob> &jobs, int K, std:
         for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
         HIP_TRY(hipEventRecord(ev[0], c0->stream));
     }
-    HIP_TRY(argos_msgs_launch(c0->stream, w + o_tab, (int)n, ntiles, K, ev[1]));
+    HIP_TRY(argos_msgs_launch(c0->stream, w + o_tab, (int)n, ntiles, K, rule, ev[1]));
     if (c0->cfg.profile) HIP_TRY(hipEventRecord(ev[2], c0->stream));
     std::vector<unsigned char> back(o_tab);
     HIP_TRY(hipMemcpyAsync(back.data(), w, o_tab, hipMemcpyDeviceToHost, c0->stream));
     HIP_TRY(hipStreamSynchronize(c0->stream));
     if (c0->cfg.profile) {
-        const char *names[2] = { "k_argos_msgs", "k_argos_finish" };
+        const char *names[2] = { rule == ARGOS_RULE_BEST ? "k_argos_heads" : "k_argos_msgs", rule == ARGOS_RULE_BEST ? "k_argos_pick" : "k_argos_finish" };
         for (int k = 0; k < 2; k++) {
             pdt_kernel_time kt;
             memset(&kt, 0, sizeof kt);
@@ -1456,8 +1456,8 @@ static bool bits_resident(const pdt_ctx *c) { return c->bits_whole && !c->stream
 
 static int argos_each(pdt_ctx *const *ctxs, int count, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap_each, int *counts)
 {
-    int K;
-    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || argos_min_run(cfg, &K)) return PDT_ERR_ARG;
+    int K, rule;
+    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || argos_min_run(cfg, &K, &rule)) return PDT_ERR_ARG;
     for (int i = 0; i < count; i++) {
         const pdt_ctx *c = ctxs[i];
         if (!c || c->cfg.mode != PDT_MODE_ARGOS || c->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
@@ -1478,7 +1478,7 @@ static int argos_each(pdt_ctx *const *ctxs, int count, const pdt_argos_cfg *cfg,
         std::vector<ArgosMsg> recs;
         std::vector<size_t> at;
         std::vector<unsigned> found;
-        const int rc = argos_run(ctxs[0], jobs, K, recs, at, found);
+        const int rc = argos_run(ctxs[0], jobs, K, rule, recs, at, found);
         if (rc) return rc;
         for (int i = 0; i < count; i++) {
             const size_t have = std::min<size_t>(found[(size_t)i], at[(size_t)i + 1] - at[(size_t)i]);
@@ -1506,8 +1506,8 @@ int pdt_argos_messages(pdt_ctx *ctx, const pdt_argos_cfg *cfg, pdt_argos_msg *ou
 
 int pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count)
 {
-    int K;
-    if (!ctx || (!bits_host && nbits) || nbits >= (1ull << 31) || cap < 0 || (!out && cap) || !count || argos_min_run(cfg, &K)) return PDT_ERR_ARG;
+    int K, rule;
+    if (!ctx || (!bits_host && nbits) || nbits >= (1ull << 31) || cap < 0 || (!out && cap) || !count || argos_min_run(cfg, &K, &rule)) return PDT_ERR_ARG;
     if (ctx->cfg.mode != PDT_MODE_ARGOS) return PDT_ERR_ARG;
     if (ctx->stream_open) return PDT_ERR_STATE;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
@@ -1523,7 +1523,7 @@ int pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nb
         std::vector<ArgosMsg> recs;
         std::vector<size_t> at;
         std::vector<unsigned> found;
-        if ((rc = argos_run(ctx, jobs, K, recs, at, found))) return rc;
+        if ((rc = argos_run(ctx, jobs, K, rule, recs, at, found))) return rc;
         const size_t have = std::min<size_t>(found[0], at[1]);
         if (have) memcpy(out, recs.data(), have * sizeof(ArgosMsg));
         *count = (int)found[0];

@@ -22,6 +22,26 @@
 //   bit_index = e; time_src and time are those of a pdt_frame whose sync word completes at bit e (symidx[bitsym[e]])
 // 28-bit IDs cannot be told from 20-bit ones without the platform registry: out of scope, the first 8 data bits of such a platform's
 // message are the rest of its ID.
+//
+// The text above is rule 0, PDT_ARGOS_RULE_FIRST, the default.  Rule 1, PDT_ARGOS_RULE_BEST, keeps b, p, sync, length code, body, complete
+// and the time source and differs in this:
+//   run_len(s)   for s in {0, 1}: the number of equal RAW bits that end at b[e-13-s], counted backwards to at most 15 and not past bit 0;
+//                0 when bit e-13-s does not exist
+//   a HEAD at e  needs the sync and a valid code at e; it takes s = 0 if run_len(0) >= K, otherwise s = 1 if run_len(1) >= K, otherwise it
+//                is no head (K = 0: s = 0 always).  The bit b[e-13] of an s = 1 head is a STRAY bit of either value: when the bit-sync ones
+//                come out as zeros, the decoder's resync at the first data transition can leave one between the run and the sync.  The
+//                test looks at 29 bits; at most one polarity matches at an e
+//   score        2 run_len(s) + (1 - s), 0 .. 31;  span = [e - 12, e + 20 + 32 N], the run and the stray bit are not part of it
+//   selection    priority: the higher score first, at equal score the smaller e.  A head is accepted if and only if no accepted head of
+//                higher priority has a span that overlaps its own (greedy selection in priority order): a false head in the stretch where
+//                the loop pulls in has a short run and loses to the true head inside its body.  Records in ascending e; rejected heads
+//                leave no trace
+//   clusters     heads in ascending e; a head joins the current cluster if its span begins at or before the largest span end seen in that
+//                cluster and the cluster holds fewer than ARGOS_CLUSTER_MAX = 256 heads, otherwise it opens a new one.  Selection runs
+//                per cluster, the accepted heads of the preceding cluster counting as accepted already (which matters only when the cap
+//                closed that cluster: clusters the cap did not cut do not overlap, so apart from the cap this is the global greedy
+//                selection).  The cap is part of the rule: it bounds kernel and host alike
+//   record       run_value = c[e-13-s], 0 when run_len is 0; reserved_ = run_len | s << 8 (rule 0: 0)
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -32,6 +52,9 @@ constexpr int ARGOS_MSG_TILE = 4096;                       // bits a workgroup o
 constexpr int ARGOS_MSG_WORDS = ARGOS_MSG_TILE / 64;
 constexpr int ARGOS_MSG_RUN_MAX = 15, ARGOS_MSG_RUN_DEFAULT = 6;
 constexpr int ARGOS_MSG_WINDOW = 13 + ARGOS_MSG_RUN_MAX;   // bits a head's test looks at: 28, the window below
+constexpr int ARGOS_BEST_WINDOW = ARGOS_MSG_WINDOW + 1;    // ... under rule 1: 29, the stray bit
+constexpr int ARGOS_CLUSTER_MAX = 256;                     // heads of a cluster of rule 1
+constexpr int ARGOS_RULE_FIRST = 0, ARGOS_RULE_BEST = 1;   // (= PDT_ARGOS_RULE_* of include/pdt.h)
 
 struct ArgosMsg {                   // (= pdt_argos_msg of include/pdt.h)
     double time;
@@ -75,6 +98,41 @@ __host__ __device__ __forceinline__ unsigned argos_head(uint32_t V, long long e,
     return (n1 + 1u) | (p << 4) | ((K && (run != 0) != (p != 0)) ? 32u : 0u);
 }
 
+// Rule 1: a head's test on the window V of the 29 raw bits up to e: bit j of V = b[e - 28 + j] (bit 28 = b[e]; bits in front of the stream:
+// any value).  Returns 0: no head; else N | polarity << 4 | run_value << 5 | run_len << 8 | s << 12 (the low six bits as rule 0's).
+__host__ __device__ __forceinline__ unsigned argos_head_best(uint32_t V, long long e, int K)
+{
+    if (e < 12) return 0;
+    const uint32_t sync = (V >> 16) & 0x1ffu;               // bit 0 = b[e-12] .. bit 8 = b[e-4]
+    unsigned p;
+    if (sync == 0x1e8u) p = 0;
+    else if (sync == 0x017u) p = 1;
+    else return 0;
+    const uint32_t q = ((V >> 25) & 15u) ^ (p ? 15u : 0u);   // bit 0 = c[e-3] (the MSB of N - 1) .. bit 3 = c[e] (the parity)
+    const unsigned n1 = ((q & 1u) << 2) | (q & 2u) | ((q >> 2) & 1u), par = (q >> 3) & 1u;
+    if ((((n1 >> 2) ^ (n1 >> 1) ^ n1) & 1u) != par) return 0;
+    unsigned len[2], val[2];
+    for (int s = 0; s < 2; s++) {
+        uint32_t r = (V >> (1 - s)) & 0x7fffu;              // bit 14 = b[e-13-s] .. bit 0 = b[e-27-s]
+        val[s] = r >> 14;
+        if (val[s]) r ^= 0x7fffu;                           // the run as zeros from bit 14 down: its length = 14 - the highest one
+        const long long exist = e - 12 - s;                 // bits b[0 .. e-13-s]
+        const unsigned n = r ? (unsigned)__builtin_clz(r) - 17u : 15u;
+        len[s] = exist <= 0 ? 0u : n < (unsigned long long)exist ? n : (unsigned)exist;
+    }
+    unsigned s;
+    if (K == 0 || len[0] >= (unsigned)K) s = 0;
+    else if (len[1] >= (unsigned)K) s = 1;
+    else return 0;
+    const unsigned rv = len[s] ? val[s] ^ p : 0u;
+    return (n1 + 1u) | (p << 4) | (rv << 5) | (len[s] << 8) | (s << 12);
+}
+__host__ __device__ __forceinline__ unsigned argos_best_run_len(unsigned h) { return (h >> 8) & 15u; }
+__host__ __device__ __forceinline__ unsigned argos_best_slip(unsigned h) { return (h >> 12) & 1u; }
+__host__ __device__ __forceinline__ unsigned argos_best_score(unsigned h) { return 2u * argos_best_run_len(h) + 1u - argos_best_slip(h); }
+// what reserved_ carries under rule 1
+__host__ __device__ __forceinline__ uint32_t argos_best_reserved(unsigned h) { return argos_best_run_len(h) | (argos_best_slip(h) << 8); }
+
 // up to 32 bits c[pos .. pos + count), MSB first; bits behind the stream are 0
 __host__ __device__ __forceinline__ uint32_t argos_take(const unsigned char *bits, long long nbits, long long pos, int count, unsigned p)
 {
@@ -93,6 +151,18 @@ __host__ __device__ __forceinline__ uint32_t argos_window(const unsigned char *b
     uint32_t V = 0;
     for (int j = 0; j < ARGOS_MSG_WINDOW; j++) {
         const long long i = e - (ARGOS_MSG_WINDOW - 1) + j;
+        const unsigned char byte = bits[i >= 0 ? i : 0];
+        V |= (uint32_t)(i >= 0 && byte != '0') << j;
+    }
+    return V;
+}
+
+// ... and of argos_head_best: 29 bits
+__host__ __device__ __forceinline__ uint32_t argos_window_best(const unsigned char *bits, long long e)
+{
+    uint32_t V = 0;
+    for (int j = 0; j < ARGOS_BEST_WINDOW; j++) {
+        const long long i = e - (ARGOS_BEST_WINDOW - 1) + j;
         const unsigned char byte = bits[i >= 0 ? i : 0];
         V |= (uint32_t)(i >= 0 && byte != '0') << j;
     }
@@ -143,6 +213,62 @@ inline long long argos_host_messages(const unsigned char *bits, long long nbits,
         }
         found++;
     }
+    return found;
+}
+
+// Rule 1 on the host, in one pass, as argos_host_messages delivers rule 0: a cluster is gathered, resolved by taking the live head of the
+// highest priority and striking what overlaps it until none is live, and its winners are appended in ascending e
+inline long long argos_host_messages_best(const unsigned char *bits, long long nbits, int K, ArgosMsg *out, long long cap)
+{
+    long long found = 0, prev_end = -1, cl_end = -1, e_of[ARGOS_CLUSTER_MAX];
+    unsigned h_of[ARGOS_CLUSTER_MAX];
+    int cl_n = 0;
+    auto resolve = [&]() {
+        bool live[ARGOS_CLUSTER_MAX], taken[ARGOS_CLUSTER_MAX];
+        for (int i = 0; i < cl_n; i++) {
+            live[i] = e_of[i] - 12 > prev_end;              // the preceding cluster's accepted heads all lie in front
+            taken[i] = false;
+        }
+        long long ends = -1;
+        for (;;) {
+            int w = -1;
+            for (int i = 0; i < cl_n; i++)
+                if (live[i] && (w < 0 || argos_best_score(h_of[i]) > argos_best_score(h_of[w]))) w = i;
+            if (w < 0) break;
+            const long long wb = e_of[w] - 12, we = argos_body_end(e_of[w], (int)(h_of[w] & 15u));
+            for (int i = 0; i < cl_n; i++)
+                if (live[i] && e_of[i] - 12 <= we && wb <= argos_body_end(e_of[i], (int)(h_of[i] & 15u))) live[i] = false;
+            taken[w] = true;
+            if (we > ends) ends = we;
+        }
+        for (int i = 0; i < cl_n; i++) {
+            if (!taken[i]) continue;
+            if (found < cap) {
+                ArgosMsg *m = &out[found];
+                argos_fill(bits, nbits, e_of[i], h_of[i], m);
+                m->reserved_ = argos_best_reserved(h_of[i]);
+                m->time_src = e_of[i];
+                m->time = (double)e_of[i];
+            }
+            found++;
+        }
+        prev_end = ends;
+        cl_n = 0;
+        cl_end = -1;
+    };
+    uint32_t V = 0;
+    for (long long e = 0; e < nbits; e++) {
+        V = (V >> 1) | ((uint32_t)(bits[e] != '0') << (ARGOS_BEST_WINDOW - 1));
+        const unsigned h = argos_head_best(V, e, K);
+        if (!h) continue;
+        if (cl_n && (e - 12 > cl_end || cl_n == ARGOS_CLUSTER_MAX)) resolve();
+        e_of[cl_n] = e;
+        h_of[cl_n] = h;
+        cl_n++;
+        const long long end = argos_body_end(e, (int)(h & 15u));
+        if (end > cl_end) cl_end = end;
+    }
+    if (cl_n) resolve();
     return found;
 }
 

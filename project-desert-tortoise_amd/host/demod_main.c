@@ -71,6 +71,9 @@
  * beside the -M pass, their times counted from the capture's start as the packets' are.  The packets file is what it was.  Not for
  * demodPOES, not from a pipe (-l -), and not for a capture that left no bit stream in one piece (one taken through the bounded
  * window): a message, exit status 1.  Without -A nothing changes.
+ * -R first|best (an addition, demodARGOS, with -A): the rule that picks the messages' heads.  first, or no -R: PDT_ARGOS_RULE_FIRST, what
+ * -A did before there was a choice.  best: PDT_ARGOS_RULE_BEST -- one stray bit between run and sync is tolerated and, of heads whose
+ * spans overlap, the one with the longest run wins; on every route -A has.
  */
 #include <ctype.h>
 #include <math.h>
@@ -87,7 +90,7 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
@@ -310,14 +313,18 @@ static int write_tones(pdt_ctx *ctx, const char *name)
     return 0;
 }
 
-/* -A: the messages in the bits of ctx's last capture, one line each (pdt_argos_messages at its defaults).  Returns 0 when
- * the file is written. */
+/* -R: the rule -A decodes by; NULL = the library's defaults */
+static pdt_argos_cfg messageCfgBest;
+static const pdt_argos_cfg *messageCfg = NULL;
+
+/* -A: the messages in the bits of ctx's last capture, one line each (pdt_argos_messages at its defaults or by -R's rule).
+ * Returns 0 when the file is written. */
 static int write_messages(pdt_ctx *ctx, const char *name)
 {
     const int cap = (int)(pdt_stage_len(ctx, PDT_ST_BITS) / 65 + 1);      /* (messages lie at least 65 bits apart) */
     pdt_argos_msg *msgs = (pdt_argos_msg *)malloc((size_t)cap * sizeof *msgs);
     int n = 0;
-    const int rc = msgs ? pdt_argos_messages(ctx, NULL, msgs, cap, &n) : PDT_ERR_NOMEM;
+    const int rc = msgs ? pdt_argos_messages(ctx, messageCfg, msgs, cap, &n) : PDT_ERR_NOMEM;
     if (rc == PDT_ERR_STATE) printf("-A needs a capture taken in one piece: this one left no bit stream\n");
     else if (rc != PDT_OK) printf("Message decoding failed: %s\n", pdt_strerror(rc));
     FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
@@ -603,7 +610,7 @@ static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame
             enum { EACH = 16 };
             static pdt_argos_msg got[POOL * EACH];
             int counts[POOL];
-            rc = pdt_argos_messages_batch(pool, k, NULL, got, EACH, counts);
+            rc = pdt_argos_messages_batch(pool, k, messageCfg, got, EACH, counts);
             for (int i = 0; i < k && rc == PDT_OK; i++) {
                 const int n = counts[i] < EACH ? counts[i] : EACH;
                 if (nmsgs + (uint64_t)n > msgRoom) {
@@ -805,6 +812,19 @@ int main(int argc, char **argv)
         case 'A':                                       /* the ARGOS messages in the bits, to this file */
             messageName = optarg;
             break;
+#ifdef PDT_ARGOS
+        case 'R':                                       /* the rule that picks the messages' heads */
+            if (strcmp(optarg, "best") == 0) {
+                memset(&messageCfgBest, 0, sizeof messageCfgBest);
+                messageCfgBest.rule = PDT_ARGOS_RULE_BEST;
+                messageCfg = &messageCfgBest;
+            } else if (strcmp(optarg, "first") == 0) messageCfg = NULL;
+            else {
+                printf("-R first or -R best\n");
+                return 1;
+            }
+            break;
+#endif
         case 'B':                                       /* -t bursts: the longest transmission that is a burst, seconds (0: no limit) */
             burstMaxS = atof(optarg);
             if (!(burstMaxS >= 0)) {

@@ -720,6 +720,76 @@ int  pdt_argos_msg_tile(void);
 uint64_t pdt_format_argos_messages(const pdt_argos_msg *msgs, uint64_t n, char *buf, uint64_t cap);
 int  pdt_write_argos_messages(const pdt_argos_msg *msgs, uint64_t n, int fd, uint64_t *bytes_written);
 
+/* ARGOS bits without a loop: feed-forward bit decisions per burst window (ARGOS contexts).  The bits above come out of the reference's
+ * chain -- a PLL that must pull in, a squelch, a Gardner loop, a Manchester decoder that guesses the symbol pairing -- and a window whose
+ * carrier lies at the edge of the loop's range, or whose pairing is never found, holds no message under either rule.  A burst needs no
+ * loop: pdt_tones measures its carrier in the 160 ms it opens with, and the modulation is +-1.1 rad Manchester at 400 bit/s, so with
+ * half-bit sums h0, h1 the sign of Im(h0 conj h1) is the bit, whatever the residual carrier.  These entries are a second, opt-in source
+ * of bits BESIDE everything else; the rule is fixed in csrc/pdt_ff.h and pdt_host_ff_bits restates it on the host.  Of a
+ * float32 I,Q stream at Fs -- 800 must divide Fs, H = Fs / 800 in 4 .. 128 -- the first L = min(n, 2 Fs) samples are used.  The carrier is
+ * taken out with the down-converter's mixer at step = round(residual_hz 2^32 / Fs).  Hypothesis (r, tau), r = -R .. R, tau = 0 .. 2 H - 1:
+ * half-bit k covers the samples [tau + b_k, tau + b_{k+1}), b_k = (k P_r + 32768) >> 16, P_r = llrint(H 65536 (1 + r ppm 1e-6)); it holds
+ * K / 2 bits, K the largest even number with tau + b_K <= L.  s_k = the float sum over half-bit k (I and Q each, in ascending index),
+ * d_m = Im(s_2m conj s_2m+1), the metric M(r, tau) = the uint64 sum of |d_m| 2^32 truncated (0 for a d_m that is not finite, 2^52 from
+ * |d_m| = 2^20 on).  The winner is the largest M -- ties: the smaller |r|, then the smaller r, then the smaller tau -- and bit m is '1'
+ * when d_m > 0, its soft value d_m, its sample index tau + b_{2m+2}.  tau spans both pairings and the message rule reads either polarity.
+ * pdt_ff_cfg: NULL or a zero field = the default -- rate_steps R = 20 (allowed 0 .. 32; 0 with PDT_FF_ZERO_RATE_STEPS in zero_mask asks for
+ * the nominal rate alone), rate_step_ppm 625 (R ppm 1e-6 may not exceed 0.1), and the residual MEASURED: the residual_hz of the first
+ * segment of pdt_tones at that call's defaults (a context: its mode's search range; pdt_stage_ff_bits and pdt_host_ff_bits: pdt_host_tones'
+ * defaults); a stream shorter than the segment, a rate without an allowed segment length or a record with valid = 0 gives residual 0 and
+ * tone_valid 0.  PDT_FF_RESIDUAL_GIVEN in flags: residual_hz is the caller's (finite, |residual_hz| < Fs / 2) and tone_valid is 1.
+ * pdt_ff_sync: residual_hz, tone_valid and step as used, the winner's tau, rate = r, period = P_r and metric = M, nbits = K / 2.
+ *   pdt_ff_bits          the context's channel stream (PDT_ST_CHANNEL of its last whole-capture call): *sync = the record; the bits stay
+ *                        on the device, in buffers of the context's own (not PDT_ST_BITS), for pdt_ff_read.  PDT_ERR_STATE as for
+ *                        pdt_tones; PDT_ERR_ARG for a POES context, a sample rate or a cfg that is not allowed.  Like pdt_tones it leaves
+ *                        frames, text, stages, statistics, survey, burst, tone and message results exactly as they were (a profiled
+ *                        context's pdt_kernel_times gain the entries k_ff_mix, k_ff_search and k_ff_pick).  The tone record is the
+ *                        call's one round trip to the host: its frequency is derived there, in double
+ *   pdt_ff_bits_batch    the same for `count` contexts with ONE launch of each kernel (the windows of a round of pdt_demod_windows_*):
+ *                        context i's record in syncs[i].  The contexts must be distinct, live on one device and have one sample rate
+ *                        (else PDT_ERR_ARG); every one is checked before anything runs
+ *   pdt_ff_read          the bits of the context's last pdt_ff_* or pdt_stage_ff_bits call: *count = their number, the first
+ *                        min(cap, *count) characters, soft values and sample indices in bits, soft and index (each may be NULL), the
+ *                        record in *sync (may be NULL).  PDT_ERR_STATE before such a call
+ *   pdt_ff_messages      pdt_ff_bits, then the messages of pdt_argos_cfg's rule in those bits (pdt_argos_messages' kernels, unchanged, on
+ *                        the device's own bit count): records as pdt_argos_messages gives them with time_src = the sample index of bit
+ *                        bit_index and time = time_src / Fs, seconds of the channel stream.  sync may be NULL
+ *   pdt_ff_messages_batch  the same for `count` contexts, ONE launch of each kernel: context i's records at out + i cap_each, their
+ *                        number in counts[i], its record in syncs[i] (syncs may be NULL)
+ *   pdt_stage_ff_bits    stage-level entry: the kernels on a caller's float32 I,Q stream of n samples at `rate` (the way in for a plain
+ *                        recording of one burst); results through *sync and pdt_ff_read.  Nothing of the context's results changes
+ *   pdt_host_ff_bits     host only, no GPU: the same record, bits, soft values and sample indices for the same stream
+ *   pdt_host_ff_mix      host only: the stream v the rule sums, out = n pairs (every sample, not only the first L)                    */
+#define PDT_FF_ZERO_RATE_STEPS 1u
+#define PDT_FF_RESIDUAL_GIVEN  1u
+typedef struct pdt_ff_cfg {
+    int32_t  rate_steps;
+    uint32_t zero_mask;
+    double   rate_step_ppm;
+    double   residual_hz;
+    uint32_t flags;
+    uint32_t reserved_;
+} pdt_ff_cfg;
+typedef struct pdt_ff_sync {
+    double   residual_hz;
+    int32_t  tone_valid;
+    uint32_t step;
+    int32_t  tau, rate;
+    int64_t  period;
+    uint64_t metric;
+    uint64_t nbits;
+} pdt_ff_sync;
+int  pdt_ff_bits(pdt_ctx *ctx, const pdt_ff_cfg *cfg, pdt_ff_sync *sync);
+int  pdt_ff_bits_batch(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, pdt_ff_sync *syncs);
+int  pdt_ff_read(pdt_ctx *ctx, pdt_ff_sync *sync, uint8_t *bits, float *soft, int64_t *index, uint64_t cap, uint64_t *count);
+int  pdt_ff_messages(pdt_ctx *ctx, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule, pdt_ff_sync *sync, pdt_argos_msg *out, int cap, int *count);
+int  pdt_ff_messages_batch(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule, pdt_ff_sync *syncs,
+                           pdt_argos_msg *out, int cap_each, int *counts);
+int  pdt_stage_ff_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ff_cfg *cfg, pdt_ff_sync *sync);
+int  pdt_host_ff_bits(uint32_t rate, const float *iq, uint64_t n, const pdt_ff_cfg *cfg, pdt_ff_sync *sync, uint8_t *bits, float *soft,
+                      int64_t *index, uint64_t cap, uint64_t *count);
+int  pdt_host_ff_mix(uint32_t rate, double residual_hz, const float *iq, uint64_t n, float *out);
+
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);
 uint64_t pdt_frames(const pdt_ctx *ctx, pdt_frame *out, uint64_t max_frames);

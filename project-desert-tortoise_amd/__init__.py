@@ -375,6 +375,93 @@ def argos_messages_batch(ds, min_run=None, cap: int = 4096, rule=None):
     return [out[i, :min(counts[i], cap)].copy() for i in range(len(ds))]
 
 
+class FfCfg(C.Structure):
+    """pdt_ff_cfg: a zero means the default; rate_steps 0 with FF_ZERO_RATE_STEPS in zero_mask asks for the nominal rate alone;
+    FF_RESIDUAL_GIVEN in flags: residual_hz is the caller's, otherwise the carrier is measured"""
+    _fields_ = [("rate_steps", C.c_int32), ("zero_mask", C.c_uint32), ("rate_step_ppm", C.c_double), ("residual_hz", C.c_double),
+                ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class FfSync(C.Structure):
+    """pdt_ff_sync"""
+    _fields_ = [("residual_hz", C.c_double), ("tone_valid", C.c_int32), ("step", C.c_uint32), ("tau", C.c_int32), ("rate", C.c_int32),
+                ("period", C.c_int64), ("metric", C.c_uint64), ("nbits", C.c_uint64)]
+
+
+FF_ZERO_RATE_STEPS, FF_RESIDUAL_GIVEN = 1, 1
+# pdt_ff_sync as a numpy record
+FF_SYNC_DTYPE = np.dtype([("residual_hz", "<f8"), ("tone_valid", "<i4"), ("step", "<u4"), ("tau", "<i4"), ("rate", "<i4"), ("period", "<i8"),
+                          ("metric", "<u8"), ("nbits", "<u8")])
+assert FF_SYNC_DTYPE.itemsize == C.sizeof(FfSync) == 48 and C.sizeof(FfCfg) == 32
+FfBits = collections.namedtuple("FfBits", "sync bits soft index")        # FF_SYNC_DTYPE record, '0'/'1' uint8[n], float32[n], int64[n]
+
+
+def _ff_cfg(rate_steps=None, rate_step_ppm=None, residual_hz=None):
+    """rate_steps (None = 20), rate_step_ppm (None = 625) and residual_hz (None = measure the carrier) -> pdt_ff_cfg or None"""
+    if rate_steps is None and rate_step_ppm is None and residual_hz is None:
+        return None
+    c = FfCfg()
+    if rate_steps is not None:
+        c.rate_steps, c.zero_mask = int(rate_steps), FF_ZERO_RATE_STEPS if int(rate_steps) == 0 else 0
+    if rate_step_ppm is not None:
+        c.rate_step_ppm = float(rate_step_ppm)
+    if residual_hz is not None:
+        c.residual_hz, c.flags = float(residual_hz), FF_RESIDUAL_GIVEN
+    return c
+
+
+def ff_max_bits(rate: int, n: int) -> int:
+    """room for the bits of any hypothesis of a stream of n samples at `rate` (the shortest allowed period is 0.9 H)"""
+    return min(n, 2 * rate) * 800 // (rate * 18 // 10) + 2 if rate >= 800 else 2
+
+
+def host_ff_mix(rate: int, residual_hz: float, iq: np.ndarray) -> np.ndarray:
+    """pdt_host_ff_mix: the stream the feed-forward rule sums -- iq with the carrier at residual_hz taken out by the down-converter's
+    mixer -- on the host (no GPU): float32[n, 2]"""
+    a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+    out = np.zeros(max(a.size, 2), dtype="<f4")
+    _check(lib().pdt_host_ff_mix(rate, float(residual_hz), a.ctypes.data, a.size // 2, out.ctypes.data), "pdt_host_ff_mix")
+    return out[:a.size // 2 * 2].reshape(-1, 2)
+
+
+def host_ff_bits(rate: int, iq: np.ndarray, rate_steps=None, rate_step_ppm=None, residual_hz=None) -> FfBits:
+    """pdt_host_ff_bits: the feed-forward bits of a float32 I,Q stream at `rate` restated on the host (no GPU), bit for bit what the
+    kernels compute: FfBits(sync, bits, soft, index).  residual_hz None: the carrier is measured (pdt_host_tones' first segment)."""
+    a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+    c, n = _ff_cfg(rate_steps, rate_step_ppm, residual_hz), a.size // 2
+    cap = ff_max_bits(rate, n)
+    sync, count = np.zeros(1, dtype=FF_SYNC_DTYPE), C.c_uint64(0)
+    bits, soft, index = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype="<f4"), np.zeros(cap, dtype="<i8")
+    _check(lib().pdt_host_ff_bits(rate, a.ctypes.data, n, C.byref(c) if c else None, sync.ctypes.data, bits.ctypes.data, soft.ctypes.data,
+                                  index.ctypes.data, cap, C.byref(count)), "pdt_host_ff_bits")
+    k = min(count.value, cap)
+    return FfBits(sync[0], bits[:k], soft[:k], index[:k])
+
+
+def ff_bits_batch(ds, rate_steps=None, rate_step_ppm=None, residual_hz=None) -> np.ndarray:
+    """pdt_ff_bits_batch: Demodulator.ff_bits() of several contexts of one device and rate with ONE launch of each kernel (the windows of
+    a round of demod_windows_held): FF_SYNC_DTYPE[len(ds)]; each context's bits through its ff_read()."""
+    c = _ff_cfg(rate_steps, rate_step_ppm, residual_hz)
+    hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
+    syncs = np.zeros(max(len(ds), 1), dtype=FF_SYNC_DTYPE)
+    _check(lib().pdt_ff_bits_batch(hs, len(ds), C.byref(c) if c else None, syncs.ctypes.data), "pdt_ff_bits_batch")
+    return syncs[:len(ds)]
+
+
+def ff_messages_batch(ds, min_run=None, cap: int = 64, rule=None, rate_steps=None, rate_step_ppm=None, residual_hz=None, with_sync: bool = False):
+    """pdt_ff_messages_batch: feed-forward bits, then the ARGOS messages in them, for several contexts with ONE launch of each kernel: a
+    list of ARGOS_MSG_DTYPE arrays, one per context (time = time_src / Fs, time_src = the sample index in the channel stream);
+    with_sync: (that, FF_SYNC_DTYPE[len(ds)])."""
+    c, a = _ff_cfg(rate_steps, rate_step_ppm, residual_hz), _argos_cfg(min_run, rule)
+    hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
+    syncs = np.zeros(max(len(ds), 1), dtype=FF_SYNC_DTYPE)
+    out, counts = np.zeros((max(len(ds), 1), max(cap, 1)), dtype=ARGOS_MSG_DTYPE), (C.c_int * max(len(ds), 1))()
+    _check(lib().pdt_ff_messages_batch(hs, len(ds), C.byref(c) if c else None, C.byref(a) if a else None, syncs.ctypes.data, out.ctypes.data, cap,
+                                       counts), "pdt_ff_messages_batch")
+    got = [out[i, :min(counts[i], cap)].copy() for i in range(len(ds))]
+    return (got, syncs[:len(ds)]) if with_sync else got
+
+
 def format_argos_messages(msgs: np.ndarray) -> bytes:
     """pdt_format_argos_messages: one line per complete message (host-only C, no GPU needed)"""
     a = np.ascontiguousarray(msgs, dtype=ARGOS_MSG_DTYPE)
@@ -408,6 +495,8 @@ ABI_SYMBOLS = [
     "pdt_tones", "pdt_tones_batch", "pdt_host_tones",
     "pdt_argos_messages", "pdt_argos_messages_batch", "pdt_stage_argos_messages", "pdt_host_argos_messages", "pdt_argos_msg_tile",
     "pdt_format_argos_messages", "pdt_write_argos_messages",
+    "pdt_ff_bits", "pdt_ff_bits_batch", "pdt_ff_read", "pdt_ff_messages", "pdt_ff_messages_batch", "pdt_stage_ff_bits", "pdt_host_ff_bits",
+    "pdt_host_ff_mix",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_ddc"]        # include/pdt_dev.h (test-only)
 
@@ -566,6 +655,16 @@ def lib():
     L.pdt_format_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.pdt_format_argos_messages.restype = C.c_uint64
     L.pdt_write_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    L.pdt_ff_bits.argtypes = [C.c_void_p, C.POINTER(FfCfg), C.c_void_p]
+    L.pdt_ff_bits_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(FfCfg), C.c_void_p]
+    L.pdt_ff_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.pdt_ff_messages.argtypes = [C.c_void_p, C.POINTER(FfCfg), C.POINTER(ArgosCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_ff_messages_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(FfCfg), C.POINTER(ArgosCfg), C.c_void_p, C.c_void_p, C.c_int,
+                                        C.POINTER(C.c_int)]
+    L.pdt_stage_ff_bits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(FfCfg), C.c_void_p]
+    L.pdt_host_ff_bits.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(FfCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                   C.POINTER(C.c_uint64)]
+    L.pdt_host_ff_mix.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pdt_device_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pdt_device_math_layout.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
@@ -953,6 +1052,46 @@ class Demodulator:
         _check(self._L.pdt_argos_messages(self._h, C.byref(c) if c else None, out.ctypes.data, cap, C.byref(count)), "pdt_argos_messages")
         got = out[:min(count.value, cap)]
         return (got, count.value) if with_count else got
+
+    def ff_bits(self, rate_steps=None, rate_step_ppm=None, residual_hz=None):
+        """pdt_ff_bits: feed-forward bit decisions on this context's channel stream (one burst's window): the FF_SYNC_DTYPE record; the
+        bits stay on the device for ff_read().  residual_hz None: the carrier is measured as tones() measures its first segment."""
+        c = _ff_cfg(rate_steps, rate_step_ppm, residual_hz)
+        sync = np.zeros(1, dtype=FF_SYNC_DTYPE)
+        _check(self._L.pdt_ff_bits(self._h, C.byref(c) if c else None, sync.ctypes.data), "pdt_ff_bits")
+        return sync[0]
+
+    def stage_ff_bits(self, rate: int, iq: np.ndarray, rate_steps=None, rate_step_ppm=None, residual_hz=None) -> FfBits:
+        """pdt_stage_ff_bits + pdt_ff_read: the feed-forward kernels on a float32 I,Q stream at `rate` (a plain recording of one burst):
+        FfBits(sync, bits, soft, index).  Nothing of this context's results changes."""
+        a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+        c = _ff_cfg(rate_steps, rate_step_ppm, residual_hz)
+        sync = np.zeros(1, dtype=FF_SYNC_DTYPE)
+        _check(self._L.pdt_stage_ff_bits(self._h, rate, a.ctypes.data, a.size // 2, C.byref(c) if c else None, sync.ctypes.data), "pdt_stage_ff_bits")
+        got = self.ff_read()
+        return FfBits(sync[0], got.bits, got.soft, got.index)
+
+    def ff_read(self) -> FfBits:
+        """pdt_ff_read: the bits of this context's last ff_bits / ff_messages / stage_ff_bits call (or a batch it was part of):
+        FfBits(sync, bits, soft, index)"""
+        sync, count = np.zeros(1, dtype=FF_SYNC_DTYPE), C.c_uint64(0)
+        _check(self._L.pdt_ff_read(self._h, sync.ctypes.data, None, None, None, 0, C.byref(count)), "pdt_ff_read")
+        cap = max(count.value, 1)
+        bits, soft, index = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype="<f4"), np.zeros(cap, dtype="<i8")
+        _check(self._L.pdt_ff_read(self._h, sync.ctypes.data, bits.ctypes.data, soft.ctypes.data, index.ctypes.data, cap, C.byref(count)), "pdt_ff_read")
+        k = min(count.value, cap)
+        return FfBits(sync[0], bits[:k], soft[:k], index[:k])
+
+    def ff_messages(self, min_run=None, cap: int = 64, rule=None, rate_steps=None, rate_step_ppm=None, residual_hz=None, with_sync: bool = False):
+        """pdt_ff_messages: ff_bits(), then the ARGOS messages in those bits by argos_messages()' rule, in one call: ARGOS_MSG_DTYPE[found]
+        with time_src = the sample index in the channel stream and time = that / Fs; with_sync: (that, the FF_SYNC_DTYPE record)."""
+        c, a = _ff_cfg(rate_steps, rate_step_ppm, residual_hz), _argos_cfg(min_run, rule)
+        sync = np.zeros(1, dtype=FF_SYNC_DTYPE)
+        out, count = np.zeros(max(cap, 1), dtype=ARGOS_MSG_DTYPE), C.c_int(0)
+        _check(self._L.pdt_ff_messages(self._h, C.byref(c) if c else None, C.byref(a) if a else None, sync.ctypes.data, out.ctypes.data, cap,
+                                       C.byref(count)), "pdt_ff_messages")
+        got = out[:min(count.value, cap)]
+        return (got, sync[0]) if with_sync else got
 
     def stage_argos_messages(self, bits, min_run=None, cap: int = 4096, with_count: bool = False, rule=None):
         """pdt_stage_argos_messages: the message kernels on a string of '0'/'1' characters; the time stamp of bit k is k"""

@@ -8,6 +8,7 @@
 #include "pdt_bursts.h"
 #include "pdt_tone.h"
 #include "pdt_argos_msg.h"
+#include "pdt_ff.h"
 
 #include <sys/stat.h>
 
@@ -37,6 +38,10 @@ void tones_derive(const void *raw, const pdt::TonePlan &p, double fs, double off
 // pdt_argos_msg.hip
 hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, int rule, hipEvent_t mid);
 int argos_min_run(const pdt_argos_cfg *cfg, int *K, int *rule);
+// pdt_ff.hip
+hipError_t ff_launch(hipStream_t st, const void *table_dev, int nwin, long long mix_tiles, long long groups, const long long *periods_dev, int R,
+                     int H, long long pmax, const float *tab_dev, void *metric_dev, size_t metric_bytes, void *syncs_dev, hipEvent_t *ev);
+int ff_plan(const pdt_ff_cfg *cfg, uint32_t rate, int *H, int *R, double *ppm, int *given, double *residual);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -555,7 +560,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
-                       &ctx->argos_work, &ctx->argos_bits };
+                       &ctx->argos_work, &ctx->argos_bits, &ctx->ff_work, &ctx->ff_in, &ctx->ff_out };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1529,6 +1534,305 @@ int pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nb
         *count = (int)found[0];
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
     return PDT_OK;
+}
+
+// ---------------------------------------------------------------- feed-forward bits (pdt_ff.h)
+// One stream of a call: the context whose result buffers take its bits, where it is (device), its samples, the search range of its tone
+struct FfJob {
+    pdt_ctx *owner;
+    const float *y;
+    uint64_t n;
+    double range_hz;
+};
+
+// a context's result buffer: the count, the record, then the time source, soft values, bit -> symbol map and characters of `cap` bits
+struct FfOut {
+    size_t o_idx, o_soft, o_sym, o_bits, total;
+    explicit FfOut(uint64_t cap)
+    {
+        const size_t c = ((size_t)cap + 15) & ~(size_t)15;
+        o_idx = 64;
+        o_soft = o_idx + 8 * c;
+        o_sym = o_soft + 4 * c;
+        o_bits = o_sym + 4 * c;
+        total = o_bits + c;
+    }
+};
+
+// The carrier of every stream: the first segment of pdt_tones at its defaults, all streams in one launch of k_tones through the first
+// context's tables and buffers; the frequency is derived here, on the host, in double.  A stream without a whole segment, a rate without
+// an allowed segment length and a record that is not valid leave residual 0 and valid 0.
+static int ff_tones(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, std::vector<double> &residual, std::vector<int> &valid)
+{
+    const size_t n = jobs.size();
+    std::vector<ToneSeg> table;
+    std::vector<int> rec(n, -1);
+    TonePlan plan;
+    memset(&plan, 0, sizeof plan);
+    for (size_t i = 0; i < n; i++) {
+        TonePlan p;
+        if (tone_plan(nullptr, (double)rate, jobs[i].range_hz, jobs[i].n, 1, &p) != PDT_OK || !p.nseg) continue;
+        rec[i] = (int)table.size();
+        table.push_back(ToneSeg{ jobs[i].y, (long long)p.first, rec[i], p.kmax });
+        plan = p;
+    }
+    if (table.empty()) return PDT_OK;
+    int rc = survey_tables(c0, plan.nfft);
+    if (!rc) rc = c0->tone_table.ensure(table.size() * sizeof(ToneSeg));
+    if (!rc) rc = c0->tone_out.ensure(table.size() * sizeof(ToneRaw));
+    if (rc) return rc;
+    std::vector<ToneRaw> raw(table.size());
+    HIP_TRY(hipMemcpy(c0->tone_table.p, table.data(), table.size() * sizeof(ToneSeg), hipMemcpyHostToDevice));
+    HIP_TRY(tones_launch(c0->stream, plan.nfft, c0->tone_table.p, table.size(), plan.noise_lo, plan.noise_hi, (const float *)c0->survey_win.p,
+                         (const float *)c0->survey_tw.p, c0->tone_out.p));
+    HIP_TRY(hipMemcpyAsync(raw.data(), c0->tone_out.p, raw.size() * sizeof(ToneRaw), hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    if (c0->tone_sum_nfft != plan.nfft) {
+        tone_sums(plan.nfft, &c0->tone_sw, &c0->tone_sw2);
+        c0->tone_sum_nfft = plan.nfft;
+    }
+    plan.nseg = 1;
+    for (size_t i = 0; i < n; i++) {
+        if (rec[i] < 0) continue;
+        pdt_tone t;
+        tones_derive(&raw[(size_t)rec[i]], plan, (double)rate, 0.0, c0->tone_sw, c0->tone_sw2, &t);
+        if (t.valid) {
+            residual[i] = t.residual_hz;
+            valid[i] = 1;
+        }
+    }
+    return PDT_OK;
+}
+
+// The streams of a call through one launch of each kernel over a table on the device: the first context supplies stream, rotation table
+// and the work buffer (table, periods, the mixed streams, the metrics); every stream's bits, count and record go to its owner's buffer
+// and stay there.  syncs (may be NULL): the records, which k_ff_pick also leaves side by side in the work buffer, read back in one copy
+// before the one synchronize that ends the call.
+static int ff_run(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, const pdt_ff_cfg *cfg, pdt_ff_sync *syncs)
+{
+    int H, R, given;
+    double ppm, res0;
+    int rc = ff_plan(cfg, rate, &H, &R, &ppm, &given, &res0);
+    if (rc) return rc;
+    const size_t n = jobs.size();
+    if (!n) return PDT_OK;
+    HIP_TRY(hipSetDevice(c0->cfg.device));
+    if ((rc = real_table(c0))) return rc;
+    std::vector<double> residual(n, res0);
+    std::vector<int> valid(n, given);
+    if (!given && (rc = ff_tones(c0, jobs, rate, residual, valid))) return rc;
+    const int nr = 2 * R + 1;
+    std::vector<long long> periods((size_t)nr);
+    for (int r = -R; r <= R; r++) periods[(size_t)(r + R)] = ff_period(H, r, ppm);
+    const long long pmin = periods.front(), pmax = periods.back();
+    const size_t o_per = n * sizeof(FfWin), o_v = o_per + (((size_t)nr * 8 + 15) & ~(size_t)15), metric_each = (size_t)nr * (size_t)(2 * H) * 8;
+    std::vector<unsigned char> head(o_v);
+    FfWin *table = (FfWin *)head.data();
+    memcpy(head.data() + o_per, periods.data(), (size_t)nr * 8);
+    std::vector<size_t> at_v(n);
+    size_t at = o_v;
+    long long tiles = 0, groups = 0;
+    for (size_t i = 0; i < n; i++) {
+        const long long L = (long long)std::min<uint64_t>(jobs[i].n, 2ull * rate);
+        const uint64_t cap = (uint64_t)(ff_halves(L, 0, pmin) >> 1);
+        const FfOut o(cap);
+        pdt_ctx *own = jobs[i].owner;
+        own->ff_rate = 0;
+        if ((rc = own->ff_out.ensure(o.total))) return rc;
+        own->ff_cap = cap;
+        at_v[i] = at;
+        at += ((size_t)L * 8 + 15) & ~(size_t)15;
+        FfWin &w = table[i];
+        unsigned char *p = (unsigned char *)own->ff_out.p;
+        w.y = jobs[i].y;
+        w.bits = p + o.o_bits;
+        w.soft = (float *)(p + o.o_soft);
+        w.symidx = (long long *)(p + o.o_idx);
+        w.bitsym = (unsigned *)(p + o.o_sym);
+        w.nbits = (unsigned long long *)p;
+        w.sync = (FfSync *)(p + 16);
+        w.L = L;
+        w.residual_hz = residual[i];
+        w.step = ddc_step((double)rate, residual[i]);
+        w.tone_valid = valid[i];
+        w.tile0 = (int32_t)tiles;
+        w.group0 = (int32_t)groups;
+        w.segs = (int32_t)((cap + FF_SEARCH_BITS - 1) / FF_SEARCH_BITS);
+        w.reserved_ = 0;
+        tiles += (L + FF_MIX_TILE - 1) / FF_MIX_TILE;
+        groups += (long long)nr * w.segs;
+        if (tiles > 0x7fffffffll || groups > 0x7fffffffll) return PDT_ERR_ARG;
+    }
+    const size_t o_metric = at, o_syncs = o_metric + n * metric_each, total = o_syncs + n * sizeof(FfSync);
+    if ((rc = c0->ff_work.ensure(total))) return rc;
+    unsigned char *wk = (unsigned char *)c0->ff_work.p;
+    for (size_t i = 0; i < n; i++) {
+        table[i].v = (float *)(wk + at_v[i]);
+        table[i].metric = (unsigned long long *)(wk + o_metric + i * metric_each);
+    }
+    // (the table of the previous call is no longer read: every call ends with a synchronize)
+    HIP_TRY(hipMemcpy(wk, head.data(), o_v, hipMemcpyHostToDevice));
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    if (c0->cfg.profile) {
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ev[0], c0->stream));
+    }
+    HIP_TRY(ff_launch(c0->stream, wk, (int)n, tiles, groups, (const long long *)(wk + o_per), R, H, pmax, (const float *)c0->an_tab.p, wk + o_metric,
+                      n * metric_each, wk + o_syncs, c0->cfg.profile ? ev + 1 : nullptr));
+    if (c0->cfg.profile) HIP_TRY(hipEventRecord(ev[3], c0->stream));
+    std::vector<FfSync> back(n);
+    HIP_TRY(hipMemcpyAsync(back.data(), wk + o_syncs, n * sizeof(FfSync), hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    if (c0->cfg.profile) {
+        const char *names[3] = { "k_ff_mix", "k_ff_search", "k_ff_pick" };
+        for (int k = 0; k < 3; k++) {
+            pdt_kernel_time kt;
+            memset(&kt, 0, sizeof kt);
+            snprintf(kt.name, sizeof kt.name, "%s", names[k]);
+            kt.launches = 1;
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            kt.total_ms = ms;
+            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [&](const pdt_kernel_time &o) { return !strcmp(o.name, names[k]); }),
+                             c0->ktimes.end());
+            c0->ktimes.push_back(kt);
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    for (size_t i = 0; i < n; i++) {
+        jobs[i].owner->ff_rate = rate;
+        if (syncs) memcpy(&syncs[i], &back[i], sizeof(pdt_ff_sync));
+    }
+    return PDT_OK;
+}
+
+// the contexts of a call, checked as pdt_tones checks its own, and ARGOS ones
+static int ff_check(pdt_ctx *const *ctxs, int count)
+{
+    if (count < 0 || (count && !ctxs)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++) {
+        const pdt_ctx *c = ctxs[i];
+        if (!c || c->cfg.mode != PDT_MODE_ARGOS) return PDT_ERR_ARG;
+        if (c->cfg.device != ctxs[0]->cfg.device || c->cfg.sample_rate != ctxs[0]->cfg.sample_rate) return PDT_ERR_ARG;
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == c) return PDT_ERR_ARG;
+    }
+    int H, R, given;
+    double ppm, res;
+    if (count && ff_plan(nullptr, ctxs[0]->cfg.sample_rate, &H, &R, &ppm, &given, &res)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++)
+        if (ctxs[i]->stream_open || !ctxs[i]->stage_len[PDT_ST_CHANNEL] || !ctxs[i]->channel.p) return PDT_ERR_STATE;
+    return PDT_OK;
+}
+
+static int ff_each(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, pdt_ff_sync *syncs)
+{
+    const int rc = ff_check(ctxs, count);
+    if (rc || !count) return rc;
+    try {
+        std::vector<FfJob> jobs((size_t)count);
+        for (int i = 0; i < count; i++)
+            jobs[(size_t)i] = FfJob{ ctxs[i], (const float *)ctxs[i]->channel.p, ctxs[i]->stage_len[PDT_ST_CHANNEL], search_range_hz(ctxs[i]) };
+        return ff_run(ctxs[0], jobs, ctxs[0]->cfg.sample_rate, cfg, syncs);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+int pdt_ff_bits_batch(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, pdt_ff_sync *syncs)
+{
+    if (count > 0 && !syncs) return PDT_ERR_ARG;
+    return ff_each(ctxs, count, cfg, syncs);
+}
+
+int pdt_ff_bits(pdt_ctx *ctx, const pdt_ff_cfg *cfg, pdt_ff_sync *sync)
+{
+    if (!ctx || !sync) return PDT_ERR_ARG;
+    return ff_each(&ctx, 1, cfg, sync);
+}
+
+int pdt_stage_ff_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ff_cfg *cfg, pdt_ff_sync *sync)
+{
+    int H, R, given;
+    double ppm, res;
+    if (!ctx || !sync || (!iq_host && n) || ctx->cfg.mode != PDT_MODE_ARGOS || ff_plan(cfg, rate, &H, &R, &ppm, &given, &res)) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    // the stream in a buffer of its own (the first 2 Fs samples are all that is read, the tone's segment lies inside them): nothing
+    // the context's results live in is touched
+    const uint64_t keep = std::min<uint64_t>(n, 2ull * rate);
+    int rc;
+    if ((rc = ctx->ff_in.ensure((size_t)keep * 8 + 16))) return rc;
+    if (keep) HIP_TRY(hipMemcpy(ctx->ff_in.p, iq_host, (size_t)keep * 8, hipMemcpyHostToDevice));
+    try {
+        const std::vector<FfJob> jobs(1, FfJob{ ctx, (const float *)ctx->ff_in.p, keep, -1.0 });
+        return ff_run(ctx, jobs, rate, cfg, sync);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+int pdt_ff_read(pdt_ctx *ctx, pdt_ff_sync *sync, uint8_t *bits, float *soft, int64_t *index, uint64_t cap, uint64_t *count)
+{
+    if (!ctx || !count) return PDT_ERR_ARG;
+    if (!ctx->ff_rate || !ctx->ff_out.p) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    unsigned char head[64];
+    HIP_TRY(hipMemcpy(head, ctx->ff_out.p, sizeof head, hipMemcpyDeviceToHost));
+    unsigned long long nb;
+    memcpy(&nb, head, sizeof nb);
+    nb = std::min<unsigned long long>(nb, ctx->ff_cap);
+    if (sync) memcpy(sync, head + 16, sizeof *sync);
+    const FfOut o(ctx->ff_cap);
+    const unsigned char *p = (const unsigned char *)ctx->ff_out.p;
+    const size_t k = (size_t)std::min<uint64_t>(cap, nb);
+    if (bits && k) HIP_TRY(hipMemcpy(bits, p + o.o_bits, k, hipMemcpyDeviceToHost));
+    if (soft && k) HIP_TRY(hipMemcpy(soft, p + o.o_soft, k * 4, hipMemcpyDeviceToHost));
+    if (index && k) HIP_TRY(hipMemcpy(index, p + o.o_idx, k * 8, hipMemcpyDeviceToHost));
+    *count = nb;
+    return PDT_OK;
+}
+
+static int ff_messages_each(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule_cfg, pdt_ff_sync *syncs, pdt_argos_msg *out,
+                            int cap_each, int *counts)
+{
+    int K, rule;
+    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || argos_min_run(rule_cfg, &K, &rule)) return PDT_ERR_ARG;
+    int rc = ff_each(ctxs, count, cfg, syncs);
+    if (rc || !count) return rc;
+    try {
+        std::vector<ArgosJob> jobs((size_t)count);
+        for (int i = 0; i < count; i++) {
+            const pdt_ctx *c = ctxs[i];
+            const FfOut o(c->ff_cap);
+            const unsigned char *p = (const unsigned char *)c->ff_out.p;
+            jobs[(size_t)i] = ArgosJob{ p + o.o_bits, (const unsigned long long *)p, (const unsigned *)(p + o.o_sym), (const long long *)(p + o.o_idx),
+                                        (long long)c->ff_cap, cap_each };
+        }
+        std::vector<ArgosMsg> recs;
+        std::vector<size_t> at;
+        std::vector<unsigned> found;
+        if ((rc = argos_run(ctxs[0], jobs, K, rule, recs, at, found))) return rc;
+        const double fs = (double)ctxs[0]->cfg.sample_rate;
+        for (int i = 0; i < count; i++) {
+            const size_t have = std::min<size_t>(found[(size_t)i], at[(size_t)i + 1] - at[(size_t)i]);
+            for (size_t k = 0; k < have; k++) {
+                ArgosMsg m = recs[at[(size_t)i] + k];
+                m.time = (double)m.time_src / fs;
+                memcpy(&out[(size_t)i * (size_t)cap_each + k], &m, sizeof m);
+            }
+            counts[i] = (int)found[(size_t)i];
+        }
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    return PDT_OK;
+}
+
+int pdt_ff_messages_batch(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule, pdt_ff_sync *syncs, pdt_argos_msg *out,
+                          int cap_each, int *counts)
+{
+    return ff_messages_each(ctxs, count, cfg, rule, syncs, out, cap_each, counts);
+}
+
+int pdt_ff_messages(pdt_ctx *ctx, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule, pdt_ff_sync *sync, pdt_argos_msg *out, int cap, int *count)
+{
+    if (!ctx || !count) return PDT_ERR_ARG;
+    return ff_messages_each(&ctx, 1, cfg, rule, sync, out, cap, count);
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

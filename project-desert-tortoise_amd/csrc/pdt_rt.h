@@ -473,6 +473,11 @@ struct pdt_ctx {
     DevBuf argos_work, argos_bits;
     bool bits_whole = false;
     std::function<double(long long)> bit_time;
+    // feed-forward bits (pdt_ff.h): the launch's table, periods, mixed streams and metrics on the device (first context of a call), the
+    // stream of the stage entry, and this context's own results -- count, record, time source, soft values, characters -- of ff_cap bits
+    DevBuf ff_work, ff_in, ff_out;
+    uint64_t ff_cap = 0;
+    uint32_t ff_rate = 0;               // 0 = no feed-forward call yet
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
     int held_fmt = 0;

@@ -74,6 +74,11 @@
  * -R first|best (an addition, demodARGOS, with -A): the rule that picks the messages' heads.  first, or no -R: PDT_ARGOS_RULE_FIRST, what
  * -A did before there was a choice.  best: PDT_ARGOS_RULE_BEST -- one stray bit between run and sync is tolerated and, of heads whose
  * spans overlap, the one with the longest run wins; on every route -A has.
+ * -b (an addition, demodARGOS, with -A): the messages are read out of feed-forward bits instead of the loop's.  With -t each
+ * every window's carrier is measured, its bit timing searched and its messages decoded by one pdt_ff_messages_batch per round, times from
+ * the capture's start as -A has them.  With a plain I,Q file -- one recording of one burst, no -x, no -f, no -l -- the first two seconds
+ * of the file go through pdt_stage_ff_bits and the message kernels; a message's time is its sample index / Fs.  The packets file is what
+ * it was: the chain runs as always.  On any other route, without -A, and for demodPOES: a message, exit status 1.
  */
 #include <ctype.h>
 #include <math.h>
@@ -90,14 +95,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:b" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:b"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -316,6 +321,54 @@ static int write_tones(pdt_ctx *ctx, const char *name)
 /* -R: the rule -A decodes by; NULL = the library's defaults */
 static pdt_argos_cfg messageCfgBest;
 static const pdt_argos_cfg *messageCfg = NULL;
+
+/* -b: -A's messages come from feed-forward bits (pdt_ff_messages_batch, pdt_stage_ff_bits) */
+static int feedForward = 0;
+
+/* -A -b on a plain I,Q file: the file's first two seconds, as float32 (a 16-bit sample / 32768), through the feed-forward kernels and the
+ * message kernels; a message's time is the sample index of its bit / Fs.  Returns 0 when the file is written. */
+static int write_messages_ff(pdt_ctx *ctx, const int16_t *iq16, uint64_t n, uint32_t rate, const char *name)
+{
+    float *iq = (float *)malloc((size_t)(n ? n : 1) * 2 * sizeof *iq);
+    pdt_ff_sync sync;
+    uint64_t nbits = 0;
+    int rc = iq ? PDT_OK : PDT_ERR_NOMEM;
+    for (uint64_t i = 0; rc == PDT_OK && i < 2 * n; i++) iq[i] = (float)iq16[i] / 32768.0f;
+    if (rc == PDT_OK) rc = pdt_stage_ff_bits(ctx, rate, iq, n, NULL, &sync);
+    free(iq);
+    if (rc == PDT_OK) rc = pdt_ff_read(ctx, NULL, NULL, NULL, NULL, 0, &nbits);
+    uint8_t *bits = (uint8_t *)malloc((size_t)nbits + 1);
+    int64_t *index = (int64_t *)malloc(((size_t)nbits + 1) * sizeof *index);
+    const int cap = (int)(nbits / 65 + 1);
+    pdt_argos_msg *msgs = (pdt_argos_msg *)malloc((size_t)cap * sizeof *msgs);
+    int found = 0;
+    if (rc == PDT_OK && (!bits || !index || !msgs)) rc = PDT_ERR_NOMEM;
+    if (rc == PDT_OK) rc = pdt_ff_read(ctx, NULL, bits, NULL, index, nbits, &nbits);
+    if (rc == PDT_OK) rc = pdt_stage_argos_messages(ctx, bits, nbits, messageCfg, msgs, cap, &found);
+    if (rc == PDT_ERR_ARG) printf("-b needs a sample rate that 800 divides, from 3.2 to 102.4 kHz\n");
+    else if (rc != PDT_OK) printf("Message decoding failed: %s\n", pdt_strerror(rc));
+    FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !m) printf("Error opening %s\n", name);
+    int bad = !m;
+    if (m) {
+        if (found > cap) found = cap;
+        for (int i = 0; i < found; i++) {
+            msgs[i].time_src = index[msgs[i].bit_index];
+            msgs[i].time = (double)msgs[i].time_src / (double)rate;
+        }
+        printf("Feed-forward bits: %llu, carrier %.2f Hz, offset %d, rate step %d\n", (unsigned long long)nbits, sync.residual_hz, (int)sync.tau,
+               (int)sync.rate);
+        fflush(m);
+        bad = pdt_write_argos_messages(msgs, (uint64_t)found, fileno(m), NULL) != PDT_OK;
+        fclose(m);
+        if (bad) printf("Error writing %s\n", name);
+        else printf("Messages: %d -> %s\n", found, name);
+    }
+    free(bits);
+    free(index);
+    free(msgs);
+    return bad;
+}
 
 /* -A: the messages in the bits of ctx's last capture, one line each (pdt_argos_messages at its defaults or by -R's rule).
  * Returns 0 when the file is written. */
@@ -610,7 +663,25 @@ static int each_burst(FILE *in, long data_offset, uint64_t nframes, size_t frame
             enum { EACH = 16 };
             static pdt_argos_msg got[POOL * EACH];
             int counts[POOL];
-            rc = pdt_argos_messages_batch(pool, k, messageCfg, got, EACH, counts);
+            if (feedForward) {
+                /* -b: feed-forward bits of every window that left a channel stream, then the same message kernels, one launch each */
+                pdt_ctx *with[POOL];
+                static pdt_argos_msg some[POOL * EACH];
+                int index[POOL], part[POOL], m = 0;
+                for (int i = 0; i < k; i++) {
+                    counts[i] = 0;
+                    if (pdt_stage_len(pool[i], PDT_ST_CHANNEL)) {
+                        with[m] = pool[i];
+                        index[m++] = i;
+                    }
+                }
+                rc = pdt_ff_messages_batch(with, m, NULL, messageCfg, NULL, some, EACH, part);
+                for (int i = 0; i < m && rc == PDT_OK; i++) {
+                    counts[index[i]] = part[i];
+                    memcpy(got + index[i] * EACH, some + i * EACH, EACH * sizeof *got);
+                }
+            } else
+                rc = pdt_argos_messages_batch(pool, k, messageCfg, got, EACH, counts);
             for (int i = 0; i < k && rc == PDT_OK; i++) {
                 const int n = counts[i] < EACH ? counts[i] : EACH;
                 if (nmsgs + (uint64_t)n > msgRoom) {
@@ -825,6 +896,9 @@ int main(int argc, char **argv)
             }
             break;
 #endif
+        case 'b':                                       /* -A's messages out of feed-forward bits */
+            feedForward = 1;
+            break;
         case 'B':                                       /* -t bursts: the longest transmission that is a burst, seconds (0: no limit) */
             burstMaxS = atof(optarg);
             if (!(burstMaxS >= 0)) {
@@ -887,6 +961,10 @@ int main(int argc, char **argv)
     }
     if (measureName && (from_stdin || live || !decim)) {
         printf("-M needs a wideband capture file (-x) taken in one piece: not a pipe, not -l\n");
+        return 1;
+    }
+    if (feedForward && (MODE != PDT_MODE_ARGOS || !messageName || from_stdin || live || real || (decim && !eachBurst))) {
+        printf("-b needs demodARGOS with -A, and -t each or a plain I,Q file: not -l, -f or another -t\n");
         return 1;
     }
     if (messageName && (MODE != PDT_MODE_ARGOS || from_stdin)) {
@@ -1084,6 +1162,16 @@ int main(int argc, char **argv)
     rc = pdt_demod_fd(ctx, fileno(in), (uint64_t)data_offset, in_frames, sample_format);
 #endif
     const double t_demod1 = now_ms();
+    int16_t *ffIq = NULL;                                            /* -b: the recording's first two seconds */
+    uint64_t ffFrames = 0;
+    if (feedForward && rc == PDT_OK) {
+        ffFrames = in_frames < 2ull * rate ? in_frames : 2ull * rate;
+        ffIq = (int16_t *)malloc((size_t)(ffFrames ? ffFrames : 1) * 4);
+        if (!ffIq || fseek(in, data_offset, SEEK_SET) || fread(ffIq, 4, (size_t)ffFrames, in) != (size_t)ffFrames) {
+            printf("Error reading %s\n", inFileName);
+            rc = PDT_ERR_IO;
+        }
+    }
     fclose(in);
     if (rc != PDT_OK) {
         printf("Demodulation failed: %s\n", pdt_strerror(rc));
@@ -1117,11 +1205,12 @@ int main(int argc, char **argv)
         remove(outFileName);
         exit(1);
     }
-    if (messageName && write_messages(ctx, messageName)) {
+    if (messageName && (feedForward ? write_messages_ff(ctx, ffIq, ffFrames, rate, messageName) : write_messages(ctx, messageName))) {
         fclose(out);
         remove(outFileName);
         exit(1);
     }
+    free(ffIq);
     pdt_stats st;
     pdt_get_stats(ctx, &st);
     print_norm_and_lock(&prog, &st);                                 /* (what the progress function has not printed) */

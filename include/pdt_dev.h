@@ -19,6 +19,12 @@ int pdt_dev_set(const char *name, const char *value);
  * left untabulated).  0 when the last run had no such rows.  What tools/span_hist.py turns into profiles/r6/gardner_row_exits_*.  */
 struct pdt_ctx;
 unsigned long long pdt_dev_span_rows(const struct pdt_ctx *ctx, unsigned *n_exits_out, unsigned long long max);
+/* (measurement aid, round 20) The same rows through the staged span walk: the number of rows, and for the first `max`
+ * of them three numbers in out[3 k ...]: the distinct exits of the row's first chunk (as above), the distinct sampler states left
+ * at the re-key point, and the stage-2 work items they were cut into.  The last two are 0 for a row that was not staged: the
+ * last run had no re-key point (PDT_GSPAN_REKEY=0, a short row), or the row was left untabulated or had too many exits to
+ * deduplicate and went through all its chunks in stage 1. */
+unsigned long long pdt_dev_span_rekey(const struct pdt_ctx *ctx, unsigned *out, unsigned long long max);
 /* The down-converter's kernel on ONE record, as a piece of a stream hands it over (csrc/pdt_ddc.h): x_dev is the address of input
  * sample 0 in device memory, the samples lo <= i < hi are present and zeros lie elsewhere, g0 is the global index of input 0
  * (the phase of input i is (g0 + i) step), and outputs 0 <= m < n_out, each centred on input m decim, go to out_dev as float32

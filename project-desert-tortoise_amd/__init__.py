@@ -498,7 +498,7 @@ ABI_SYMBOLS = [
     "pdt_ff_bits", "pdt_ff_bits_batch", "pdt_ff_read", "pdt_ff_messages", "pdt_ff_messages_batch", "pdt_stage_ff_bits", "pdt_host_ff_bits",
     "pdt_host_ff_mix",
 ]
-DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_ddc"]        # include/pdt_dev.h (test-only)
+DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
 
 _lib = None
 

@@ -77,6 +77,10 @@ void Tuning::load()
     if (const char *e = get("PDT_FIX_PASSES")) fix_passes = atoi(e);
     if (const char *e = get("PDT_GSEG")) gseg = std::min(64, std::max(2, atoi(e)));
     if (const char *e = get("PDT_GSPAN")) gspan = std::min(256, std::max(1, atoi(e)));
+    if (const char *e = get("PDT_GSPAN_REKEY")) gspan_rekey = std::min(255, std::max(0, atoi(e)));      // chunks walked before the re-key; 0: single stage
+    if (const char *e = get("PDT_GSPAN_SUB")) gspan_sub = atoi(e);                                     // lanes per row in stage 2: 8, 16 or 32
+    if (const char *e = get("PDT_GSPAN_WIN2")) gspan_win2 = atoi(e);                                   // stage 2's LDS window per row: 512, 1024 or 2048 floats
+    if (const char *e = get("PDT_GSPAN_FIT")) gspan_fit = std::min(64, std::max(2, atoi(e)));            // the span the rule would want (the search for a short last group still runs)
     if (const char *e = get("PDT_GSPAN_CAP")) gspan_cap = std::max(64, atoi(e));          // (tests: rows that do not fit the key list)
     fir_generic = get("PDT_FIR_GENERIC") != nullptr;
     mix_unfused = get("PDT_MIX_UNFUSED") != nullptr;
@@ -319,6 +323,29 @@ unsigned long long pdt_dev_span_rows(const pdt_ctx *ctx, unsigned *n_exits_out, 
     return n;
 }
 
+unsigned long long pdt_dev_span_rekey(const pdt_ctx *ctx, unsigned *out, unsigned long long max)
+{
+    if (!ctx || ctx->gspan_nrows <= 0 || !ctx->gspan_rows.p) return 0;
+    const unsigned long long n = (unsigned long long)ctx->gspan_nrows, m = std::min(n, max);
+    if (out && m) {
+        const bool staged = ctx->gspan_rekey > 0 && ctx->gspan_info.p;
+        std::vector<GardnerSpanRow> rows((size_t)m);
+        std::vector<GardnerSpanRowInfo> info((size_t)m);
+        if (hipSetDevice(ctx->cfg.device) != hipSuccess ||
+            hipMemcpy(rows.data(), ctx->gspan_rows.p, (size_t)m * sizeof(GardnerSpanRow), hipMemcpyDeviceToHost) != hipSuccess ||
+            (staged && hipMemcpy(info.data(), ctx->gspan_info.p, (size_t)m * sizeof(GardnerSpanRowInfo), hipMemcpyDeviceToHost) != hipSuccess)) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        for (size_t k = 0; k < (size_t)m; k++) {
+            out[3 * k] = rows[k].n;
+            out[3 * k + 1] = staged ? info[k].states : 0u;
+            out[3 * k + 2] = staged ? info[k].items : 0u;
+        }
+    }
+    return n;
+}
+
 // test-only (include/pdt_dev.h): the down-converter on exactly this record, one launch by value; no context
 int pdt_dev_ddc(int device, uint32_t in_rate, int decim, double offset_hz, int sample_format, const void *x_dev, long long lo, long long hi,
                 uint64_t n_out, uint64_t g0, void *out_dev)
@@ -556,7 +583,7 @@ void pdt_close(pdt_ctx *ctx)
     DevBuf *bufs[] = { &ctx->pcm, &ctx->pll, &ctx->lock, &ctx->fir, &ctx->agc, &ctx->sym, &ctx->symidx, &ctx->bits, &ctx->bitsym,
                        &ctx->hits, &ctx->frames, &ctx->taps, &ctx->mag, &ctx->seams_pll, &ctx->seams_agc, &ctx->scal, &ctx->lockinfo,
                        &ctx->term, &ctx->seams_ema, &ctx->gtable, &ctx->gentries, &ctx->gcand,
-                       &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
+                       &ctx->gmfirst, &ctx->stiles, &ctx->gsegmap, &ctx->gsegstart, &ctx->gbands, &ctx->gclist, &ctx->gspan_keys, &ctx->gspan_tails, &ctx->gspan_rows, &ctx->gspan_items, &ctx->gspan_ctl, &ctx->gspan_recs, &ctx->gspan_rep, &ctx->gspan_list2, &ctx->gspan_items2, &ctx->gspan_info, &ctx->gcentries, &ctx->gflags, &ctx->agc_maps, &ctx->pll_head, &ctx->taps_rot, &ctx->pll_scratch, &ctx->tip, &ctx->stream_in, &ctx->sync_scr, &ctx->agc_raw, &ctx->agc_ckpt, &ctx->pll_ckpt, &ctx->packs_dev, &ctx->seg_dev, &ctx->lt_theta, &ctx->lt_phi,
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,

@@ -559,6 +559,7 @@ template <typename T> struct Chain {
     bool use_mm = false;
     bool use_table = false;
     GardnerDomain GD{};
+    int span_rekey = 0, span_sub = 16, span_win2 = 1024;     // the staged span walk: chunks before the re-key (0: one stage), stage 2's lanes and window per row
     SamplerCarry<T> carry_in{};
     SegTail<T> *d_tail = nullptr;
     SamplerCarry<T> *d_carry_out = nullptr;
@@ -1311,6 +1312,7 @@ template <typename T> struct Chain {
         use_mm = ctx->cfg.sampler == PDT_SAMPLER_MM;
         use_table = false;
         GD.q_min = 0; GD.u = 0; GD.n_q = 0; GD.n_cand = 0; GD.pad_q = 0; GD.idx_bits = 20; GD.span = 1;
+        span_rekey = 0;
         if constexpr (std::is_same<T, float>::value) {
             const int table_len = 1 << 22;     // the table kernel walks the chunk in LDS windows: no size limit of its own
             const float nT = (float)chunk_out, stepf = (float)GP.step;
@@ -1348,7 +1350,17 @@ template <typename T> struct Chain {
                     // the symbols of a chunk: 16 chunks suit an hour at 250 ksps (666 symbols a chunk) and cost an hour at 18.75 ksps
                     // (8 876 a chunk: 7.7 of its 16 ms) or at 50 ksps (3 328: 3.4 of 13 ms) most of their sampler's time.  The minimum
                     // of the sum: span = sqrt(138 000 / symbols per chunk) -- 14, 6 and 4.)
-                    const int span_fit = (int)std::min(16.0, std::max(2.0, std::round(std::sqrt(138000.0 / ((double)chunk_out / (double)stepf)))));
+                    // (Round 20: chunks of few symbols -- 666 at an hour of 250 ksps -- take the staged walk, whose stage 2 carries four
+                    // rows per wavefront, so rows are walked in one round of wavefronts however many there are; measured there with the
+                    // wanted span at 14, 18, 22 / 26 and 32 -- rows of 13, 17, 23 and 31 chunks after the search below -- tables + chain
+                    // + emission 4.05, 3.69, 3.57 and 3.86 ms: sqrt(322 000 / symbols per chunk), at most 24.  Chunks of more symbols
+                    // keep the rule above and its single stage.)
+                    const double chunk_syms = (double)chunk_out / (double)stepf;
+                    const int rekey_rule = (int)std::min(3.0, std::round(1332.0 / chunk_syms));       // chunks in front of the re-key point
+                    const int rekey_want = ctx->tune.gspan_rekey >= 0 ? ctx->tune.gspan_rekey : rekey_rule;
+                    int span_fit = rekey_want > 0 ? (int)std::min(24.0, std::max(2.0, std::round(std::sqrt(322000.0 / chunk_syms))))
+                                                  : (int)std::min(16.0, std::max(2.0, std::round(std::sqrt(138000.0 / chunk_syms))));
+                    if (ctx->tune.gspan_fit > 0) span_fit = ctx->tune.gspan_fit;
                     int span = ctx->tune.gspan > 0 ? ctx->tune.gspan : ((n_chunks - seg_c_first >= 4096 && (!seg || seg_fast)) ? span_fit : 1);
                     if (2 * n_q > 32 * PDT_GSPAN_BITMAP_WORDS || 8 * (long long)stepf + 256 >= PDT_GSUB_WIN) span = 1;
                     while (span > 1 && ((double)span * max_count >= (double)((1u << (32 - idx_bits)) - 2u) || (n_chunks - 1) / span - seg_c_first / span < 4))
@@ -1367,6 +1379,25 @@ template <typename T> struct Chain {
                     }
                     if (!row_aligned(span)) span = 1;
                     GD.span = span;
+                    // The staged span walk (k_gardner_span_rekey).  The exits of a row's first chunk go on merging behind it, by symbols
+                    // walked: 28 -> 17 -> 12 states after 666 and 1 332 more symbols, ~8 after 3 300 (DESIGN 4.7).  The re-key point lies
+                    // where about 1 300 symbols are through -- two chunks at an hour of 250 ksps; with chunks of 3 328 or 8 876 symbols a
+                    // row starts with ~7 keys and is short: one stage, as before.  Behind the re-key point a row takes 16 lanes (a second
+                    // item where it has more states) and 1 024 floats of LDS (measured: 8 lanes and 512 floats, 16 and 512 or 2 048,
+                    // 32 and 2 048 all lose 0.1 - 0.3 ms to it; 8 lanes and 1 024 floats are 32 KiB and 256 registers a wavefront).
+                    span_rekey = 0;
+                    span_sub = (ctx->tune.gspan_sub == 8 || ctx->tune.gspan_sub == 32) ? ctx->tune.gspan_sub : 16;
+                    span_win2 = (ctx->tune.gspan_win2 == 512 || ctx->tune.gspan_win2 == 1024 || ctx->tune.gspan_win2 == 2048)
+                                    ? ctx->tune.gspan_win2 : 1024;
+                    if (span_sub == 32) span_win2 = 2048;                  // (two rows: the window stage 1 has)
+                    if (span_sub == 8 && span_win2 > 1024) span_win2 = 1024;      // (eight rows: 32 KiB)
+                    if (span >= 3) {
+                        int a = rekey_want;
+                        if (ctx->tune.gspan_rekey < 0 && span - 1 - a < 4) a = 0;      // too little left behind it for three more launches
+                        if (a >= span - 1) a = 0;                          // (nothing left for stage 2: stage 1 walks the rows through)
+                        if (8 * (long long)stepf + 256 >= span_win2) a = 0;
+                        span_rekey = a;
+                    }
                 }
             }
         }
@@ -1379,6 +1410,7 @@ template <typename T> struct Chain {
         int rc = PDT_OK;
         (void)rc;
         ctx->gardner_mode = use_table ? 1 : 0;
+        ctx->gspan_rekey = (use_table && GD.span > 1) ? span_rekey : 0;
         ctx->gspan_nrows = (use_table && GD.span > 1 && chunk_out > 0) ? (n_out + chunk_out - 1) / chunk_out > 0 ? ((n_out + chunk_out - 1) / chunk_out - 1) / GD.span : 0 : 0;
         // stream segment: the sequential samplers go on from the carried state at chunk first / chunk; the symbol buffer starts
         // with the two symbols the Manchester stage looks back on, placed so that local and global symbol parities agree
@@ -1490,10 +1522,43 @@ template <typename T> struct Chain {
                                        (GardnerBand *)ctx->gbands.p, (const unsigned *)ctx->gclist.p, (const unsigned *)ctx->gtable.p,
                                        (unsigned *)ctx->gspan_keys.p, cap_keys, (GardnerSpanRow *)ctx->gspan_rows.p,
                                        (GardnerSpanItem *)ctx->gspan_items.p, (GardnerSpanCtl *)ctx->gspan_ctl.p);
+                    if (span_rekey > 0) {
+                        // stage 2's lists: a representative per distinct state (at most the keys), their items, a note per row
+                        if ((rc = ctx->gspan_rep.ensure((size_t)cap_keys * sizeof(unsigned)))) return rc;
+                        if ((rc = ctx->gspan_list2.ensure((size_t)cap_keys * sizeof(unsigned)))) return rc;
+                        if ((rc = ctx->gspan_items2.ensure(((size_t)cap_keys / (size_t)span_sub + (size_t)n_tab + 1) * sizeof(GardnerSpanItem)))) return rc;
+                        if ((rc = ctx->gspan_info.ensure((size_t)n_tab * sizeof(GardnerSpanRowInfo)))) return rc;
+                    }
                     const unsigned walkers = (unsigned)std::min<long long>(n_tab / PDT_GSUB + 64, 256ll * 16);     // persistent wavefronts (8 KiB of LDS each)
-                    PDT_LAUNCH(64, (k_gardner_span_walk<PDT_GSUB_WIN>), dim3(walkers), dim3(64), 0, st, (const float *)d_agc, GP, GD,
+                    PDT_LAUNCH(64, (k_gardner_span_walk<PDT_GSUB_WIN, PDT_GSUB, false>), dim3(walkers), dim3(64), 0, st, (const float *)d_agc, GP, GD,
                                        (const unsigned *)ctx->gspan_keys.p, (const GardnerSpanItem *)ctx->gspan_items.p,
-                                       (GardnerSpanCtl *)ctx->gspan_ctl.p, (unsigned *)ctx->gspan_tails.p, (GardnerSpanRec *)ctx->gspan_recs.p);
+                                       (GardnerSpanCtl *)ctx->gspan_ctl.p, (unsigned *)ctx->gspan_tails.p, (GardnerSpanRec *)ctx->gspan_recs.p,
+                                       (const GardnerSpanRow *)ctx->gspan_rows.p, (const unsigned *)nullptr, span_rekey);
+                    if (span_rekey > 0) {
+                        PDT_LAUNCH(64 * PDT_GSPAN_REKEY_ROWS, k_gardner_span_rekey, dim3((unsigned)((n_tab + PDT_GSPAN_REKEY_ROWS - 1) / PDT_GSPAN_REKEY_ROWS)), dim3(64 * PDT_GSPAN_REKEY_ROWS), 0, st, GD, n_tab, (const GardnerSpanRow *)ctx->gspan_rows.p,
+                                           (const GardnerSpanRec *)ctx->gspan_recs.p, span_rekey, (unsigned)span_sub, (unsigned *)ctx->gspan_rep.p,
+                                           (unsigned *)ctx->gspan_list2.p, (GardnerSpanItem *)ctx->gspan_items2.p, (GardnerSpanCtl *)ctx->gspan_ctl.p,
+                                           (GardnerSpanRowInfo *)ctx->gspan_info.p);
+                        // persistent wavefronts again: as many as two items a row would fill, within what the LDS lets be resident
+                        const int nsub = 64 / span_sub;
+                        const long long resident = 256ll * std::max(1, (140 * 1024) / (nsub * span_win2 * 4));
+                        const unsigned walkers2 = (unsigned)std::min<long long>(2 * n_tab / nsub + 64, resident);
+#define PDT_SPAN_STAGE2(NSUB, WIN2)                                                                                                          \
+    PDT_LAUNCH(64, (k_gardner_span_walk<WIN2, NSUB, true>), dim3(walkers2), dim3(64), 0, st, (const float *)d_agc, GP, GD,                   \
+               (const unsigned *)ctx->gspan_keys.p, (const GardnerSpanItem *)ctx->gspan_items2.p, (GardnerSpanCtl *)ctx->gspan_ctl.p,        \
+               (unsigned *)ctx->gspan_tails.p, (GardnerSpanRec *)ctx->gspan_recs.p, (const GardnerSpanRow *)ctx->gspan_rows.p,               \
+               (const unsigned *)ctx->gspan_list2.p, span_rekey)
+                        if (span_sub == 8 && span_win2 == 512) PDT_SPAN_STAGE2(8, 512);
+                        else if (span_sub == 8) PDT_SPAN_STAGE2(8, 1024);
+                        else if (span_sub == 16 && span_win2 == 512) PDT_SPAN_STAGE2(4, 512);
+                        else if (span_sub == 16 && span_win2 == 1024) PDT_SPAN_STAGE2(4, 1024);
+                        else if (span_sub == 16) PDT_SPAN_STAGE2(4, 2048);
+                        else PDT_SPAN_STAGE2(2, 2048);
+#undef PDT_SPAN_STAGE2
+                        PDT_LAUNCH(64, k_gardner_span_spread, dim3((unsigned)n_tab), dim3(64), 0, st, GD, n_tab, (const GardnerSpanRow *)ctx->gspan_rows.p,
+                                           (const GardnerSpanRowInfo *)ctx->gspan_info.p, (const unsigned *)ctx->gspan_rep.p, span_rekey,
+                                           (unsigned *)ctx->gspan_tails.p, (GardnerSpanRec *)ctx->gspan_recs.p);
+                    }
                     PDT_LAUNCH(128, k_gardner_span_join, dim3((unsigned)n_tab), dim3(128), 0, st, GD, n_tab, (const unsigned *)ctx->gcand.p,
                                        (const GardnerBand *)ctx->gbands.p, (const unsigned *)ctx->gclist.p, (unsigned *)ctx->gtable.p,
                                        (const unsigned *)ctx->gspan_keys.p, (const unsigned *)ctx->gspan_tails.p,

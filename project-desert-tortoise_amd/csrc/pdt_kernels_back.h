@@ -1436,13 +1436,26 @@ __device__ __forceinline__ void k_gardner_table_merge(const float *__restrict__ 
 // (Measured at an hour of 250 ksps, 5 625 rows of ~20 distinct exits: one row per wavefront 2.7 ms; four rows per wavefront,
 // 16 keys each, 3.6 ms -- the walk of a lone wavefront is bound by the latency of its symbol step, ~600 clocks, not by issue slots,
 // so what counts is the number of resident wavefronts.  The same packing for the emission: 2.65 against 2.4 ms.)
-#define PDT_GSUB 1                                   // rows per wavefront
+// (Round 20: the staged walk.  Trajectories that pick the same samples merge exactly, and the ~28 exits of a row's
+// first chunk go on merging behind it: ~17 distinct states two chunks of 666 symbols on, ~12 after three, 4 at the end of a row of
+// 13.  So stage 1 -- the walk above, one row per wavefront -- stops after `rekey` chunks; k_gardner_span_rekey deduplicates the
+// states it left (bit patterns of ns, prev, half) and cuts the distinct ones into items of 64 / NSUB; stage 2 -- the same walker,
+// NSUB rows per wavefront -- takes those through the rest of the row; k_gardner_span_spread copies what a representative recorded
+// to the keys that merged into it.  Packing alone, without the merge, lost: the note above.)
+#define PDT_GSUB 1                                   // rows per wavefront (stage 1)
 #define PDT_GSUB_WIN 2048                            // LDS window (floats)
 #define PDT_GSUB_KEYS (64 / PDT_GSUB)                // keys per work item
+#define PDT_GSPAN_REKEY_MAX 256                      // a row with more first-chunk exits is not deduplicated: stage 1 walks it through
 struct GardnerSpanRow { unsigned off, n; };     // the row's keys: [off, off + n) of the key list; n = ~0u: not tabulated
 struct GardnerSpanItem { unsigned row, first, cnt; };
 struct GardnerSpanRec { float ns, prev, half; unsigned count; };   // sampler state in front of a chunk, symbols since the row's second chunk
-struct GardnerSpanCtl { unsigned long long keys; unsigned items, cursor, overflow, pad_; };     // keys: a 64-bit cursor (never wraps)
+struct GardnerSpanCtl {
+    unsigned long long keys;                          // a 64-bit cursor (never wraps)
+    unsigned items, cursor, overflow, pad_;
+    unsigned long long both2;                         // stage 2: distinct states at the re-key point (low word) and their items (high word)
+    unsigned cursor2, pad2_;                          // ... and the stage-2 walkers' cursor
+};
+struct GardnerSpanRowInfo { unsigned states, items; };    // per row: distinct states at the re-key point, stage-2 items (0, 0: not staged)
 
 __device__ __forceinline__ void k_gardner_span_keys(GardnerDomain D, long long n_rows, const unsigned *__restrict__ cand_k,
                                                     GardnerBand *__restrict__ bands, const unsigned *__restrict__ clist,
@@ -1592,36 +1605,73 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
             nout = 0;
         }
     };
+    // The span walkers (no emission) run a wavefront or two per SIMD, so nothing hides the latency of staging a window: they
+    // fetch the next window's samples into registers before they walk the current one (round 20).  The emission has wavefronts
+    // enough and keeps its registers.
+    constexpr bool PREFETCH = !EMIT;
+    struct __attribute__((packed, aligned(4))) Q { float v[4]; };
+    Q pre[PREFETCH ? NSUB : 1][PREFETCH ? WIN / 256 : 1];
+    bool have_pre = false;
 #pragma unroll 1
     for (;;) {
         __syncthreads();
         if (wbase + WIN <= n_cur) {
             // a window inside the chunk: 16-byte loads (the chunk's samples are 4-byte aligned only), no test
-            struct __attribute__((packed, aligned(4))) Q { float v[4]; };
+            if (PREFETCH) {
+                if (!have_pre) {
+#pragma unroll
+                    for (int u = 0; u < NSUB; u++)
+#pragma unroll
+                        for (int v = 0; v < WIN / 256; v++)
+                            pre[PREFETCH ? u : 0][PREFETCH ? v : 0] = *reinterpret_cast<const Q *>(in + c_sub[u] * C + wbase + (v * 64 + lane) * 4);
+                }
+                __builtin_amdgcn_sched_barrier(0);             // (all loads in flight before the first store waits for one)
+#pragma unroll
+                for (int u = 0; u < NSUB; u++)
+#pragma unroll
+                    for (int v = 0; v < WIN / 256; v++) {
+                        const Q r = pre[PREFETCH ? u : 0][PREFETCH ? v : 0];
+                        *reinterpret_cast<float4 *>(win + u * WIN + (v * 64 + lane) * 4) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+                    }
+            } else {
+#pragma unroll
+                for (int u = 0; u < NSUB; u++) {
+                    const float *src = in + c_sub[u] * C + wbase;
+                    float *wu = win + u * WIN;
+#pragma unroll
+                    for (int v = 0; v < WIN / 256; v++) {
+                        const int t = (v * 64 + lane) * 4;
+                        const Q r = *reinterpret_cast<const Q *>(src + t);
+                        *reinterpret_cast<float4 *>(wu + t) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+                    }
+                }
+            }
+        } else {
+            // the chunk's last window: the samples up to the chunk's end (zeros behind them), then the few values the sampler can ask
+            // for past the end (Q3).  (Round 20: the loads of a row in flight together.  One element per trip of a rolled loop waited
+            // for every load in turn -- NSUB x WIN / 64 memory latencies per chunk, a third of the chunk's time at 2 048 floats.)
 #pragma unroll
             for (int u = 0; u < NSUB; u++) {
                 const float *src = in + c_sub[u] * C + wbase;
                 float *wu = win + u * WIN;
+                float r[WIN / 64];
 #pragma unroll
-                for (int v = 0; v < WIN / 256; v++) {
-                    const int t = (v * 64 + lane) * 4;
-                    const Q r = *reinterpret_cast<const Q *>(src + t);
-                    *reinterpret_cast<float4 *>(wu + t) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+                for (int v = 0; v < WIN / 64; v++) {
+                    const int t = v * 64 + lane;
+                    r[v] = (wbase + t < n_cur) ? src[t] : 0.0f;
                 }
+#pragma unroll
+                for (int v = 0; v < WIN / 64; v++) wu[v * 64 + lane] = r[v];
             }
-        } else {
-            // the chunk's last window: the samples, then the few values the sampler can ask for past the end (Q3)
+            __syncthreads();
 #pragma unroll 1
-            for (int t = lane; t < NSUB * WIN; t += 64) {
-                const int u = t / WIN, tt = t - u * WIN;
+            for (int t = lane; t < NSUB * margin; t += 64) {
+                const int u = t / margin;
+                const int idx = n_cur + (t - u * margin), at = idx - wbase;
                 long long cu = c_sub[0];
 #pragma unroll
                 for (int q = 1; q < NSUB; q++) cu = (u == q) ? c_sub[q] : cu;
-                const int idx = wbase + tt;
-                float r = 0.0f;
-                if (idx < n_cur) r = in[cu * C + idx];
-                else if (idx < n_cur + margin) r = gardner_beyond(in, (const float *)nullptr, P, cu, (long long)n_cur, (long long)idx);
-                win[t] = r;
+                if (at < WIN) win[u * WIN + at] = gardner_beyond(in, (const float *)nullptr, P, cu, (long long)n_cur, (long long)idx);
             }
         }
         __syncthreads();
@@ -1629,6 +1679,18 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
         const bool last_window = (wend - margin >= n_cur);
         const float stop = last_window ? nT : (float)(wend - margin);    // lanes leave the window at rint(ns) >= stop
         const float *wrel = win + mysub * WIN - wbase;                    // indexed with chunk-relative indices
+        if (PREFETCH) {
+            // the next window, where it lies inside the chunk: its loads are under way while this one is walked
+            const int nb = wend - margin - back;
+            have_pre = !last_window && nb + WIN <= n_cur;
+            if (have_pre) {
+#pragma unroll
+                for (int u = 0; u < NSUB; u++)
+#pragma unroll
+                    for (int v = 0; v < WIN / 256; v++)
+                        pre[PREFETCH ? u : 0][PREFETCH ? v : 0] = *reinterpret_cast<const Q *>(in + c_sub[u] * C + nb + (v * 64 + lane) * 4);
+            }
+        }
         if (wbase == 0) {
             // first symbol: the mid-point index is the stale one of the previous chunk (Q3)
             const float rn = __builtin_rintf(L.ns);
@@ -1691,30 +1753,39 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
 }
 
 
-template <int WIN>
+// STAGE2 = false: the items of k_gardner_span_keys, a state per key (gardner_entry_from_candidate), from the row's second chunk on --
+// through the row when rekey = 0 or the row has more than PDT_GSPAN_REKEY_MAX keys, else through `rekey` chunks, leaving the
+// state in front of the next one in recs[key][rekey].  STAGE2 = true: the items of k_gardner_span_rekey, whose list2 names the
+// representative key of every distinct state; from recs[key][rekey] (its symbol count too) through the rest of the row.
+// Either way a lane records the state in front of every chunk it walks under its key and, at the row's end, the key's tail.
+template <int WIN, int NSUB, bool STAGE2>
 __device__ __forceinline__ void k_gardner_span_walk(const float *__restrict__ in, GardnerParams<float> P, GardnerDomain D,
                                                     const unsigned *__restrict__ keys, const GardnerSpanItem *__restrict__ items,
                                                     GardnerSpanCtl *__restrict__ ctl, unsigned *__restrict__ tails,
-                                                    GardnerSpanRec *__restrict__ recs /* per key: the state in front of each of those chunks */)
+                                                    GardnerSpanRec *__restrict__ recs /* per key: the state in front of each of those chunks */,
+                                                    const GardnerSpanRow *__restrict__ rows, const unsigned *__restrict__ list2, int rekey)
 {
-    __shared__ __attribute__((aligned(16))) float win[PDT_GSUB * WIN];
+    static_assert(STAGE2 || NSUB == 1, "stage 1 ends row by row: one row per wavefront");
+    constexpr int SUBW = 64 / NSUB;
+    __shared__ __attribute__((aligned(16))) float win[NSUB * WIN];
     __shared__ float s_ref[3];
     __shared__ unsigned s_next;
     const int lane = threadIdx.x;
-    const int mysub = lane / PDT_GSUB_KEYS, sublane = lane % PDT_GSUB_KEYS;
+    const int mysub = lane / SUBW, sublane = lane % SUBW;
     const float nT = (float)P.chunk_out;
-    const unsigned n_items = ctl->items;                                 // (final: the key kernel has finished)
+    const unsigned n_items = STAGE2 ? (unsigned)(ctl->both2 >> 32) : ctl->items;         // (final: the kernel that cut them has finished)
+    unsigned *cursor = STAGE2 ? &ctl->cursor2 : &ctl->cursor;
     for (;;) {
         __syncthreads();
-        if (lane == 0) s_next = atomicAdd(&ctl->cursor, (unsigned)PDT_GSUB);
+        if (lane == 0) s_next = atomicAdd(cursor, (unsigned)NSUB);
         __syncthreads();
         const unsigned q0 = s_next;
         if (q0 >= n_items) break;
         // sub-group u takes item q0 + u; the ones past the end shadow item q0
-        long long c_sub[PDT_GSUB];
+        long long c_sub[NSUB];
         GardnerSpanItem mine = items[q0];
 #pragma unroll
-        for (int u = 0; u < PDT_GSUB; u++) {
+        for (int u = 0; u < NSUB; u++) {
             const GardnerSpanItem it = (q0 + (unsigned)u < n_items) ? items[q0 + u] : items[q0];
             c_sub[u] = (long long)it.row * D.span + 1;
             if (mysub == u) {
@@ -1728,26 +1799,162 @@ __device__ __forceinline__ void k_gardner_span_walk(const float *__restrict__ in
         L.ns = L.prev = L.half = 0;
         long long my_c = 0;
 #pragma unroll
-        for (int u = 0; u < PDT_GSUB; u++) my_c = (mysub == u) ? c_sub[u] : my_c;
-        if (L.active) gardner_entry_from_candidate(in, P, D, my_c, (int)keys[mine.first + sublane], L.ns, L.prev, L.half);
+        for (int u = 0; u < NSUB; u++) my_c = (mysub == u) ? c_sub[u] : my_c;
+        // the chunks this item walks: g_lo <= g < g_hi of the row (the same for every sub-group)
+        int g_lo = 1, g_hi = D.span;
+        unsigned my_key = 0;                                             // where this lane records: an index into keys / tails / recs
+        if (STAGE2) {
+            g_lo = rekey + 1;
+            if (L.active) {
+                my_key = list2[mine.first + sublane];
+                const GardnerSpanRec rc = recs[(size_t)my_key * (size_t)(D.span - 1) + (size_t)rekey];
+                L.ns = rc.ns; L.prev = rc.prev; L.half = rc.half; L.count = rc.count;
+            }
+        } else {
+            if (rekey > 0 && rows[mine.row].n <= (unsigned)PDT_GSPAN_REKEY_MAX) g_hi = rekey + 1;
+            my_key = mine.first + sublane;
+            if (L.active) gardner_entry_from_candidate(in, P, D, my_c, (int)keys[my_key], L.ns, L.prev, L.half);
+        }
         if (lane == 0) { s_ref[0] = L.ns; s_ref[1] = L.prev; s_ref[2] = L.half; }       // (item q0's first key: always there)
         __syncthreads();
         // idle lanes start from that state, over their own sub-group's samples: whatever the samples, a symbol step advances by
         // step +- 0.1, so they stay inside the staged windows like everybody else
         if (!L.active) { L.ns = s_ref[0]; L.prev = s_ref[1]; L.half = s_ref[2]; }
-        for (int g = 1; g < D.span; g++) {
-            long long cc[PDT_GSUB];
+        GardnerSpanRec *my_recs = recs + (size_t)my_key * (size_t)(D.span - 1);
+        for (int g = g_lo; g < g_hi; g++) {
+            long long cc[NSUB];
 #pragma unroll
-            for (int u = 0; u < PDT_GSUB; u++) cc[u] = c_sub[u] + (g - 1);
+            for (int u = 0; u < NSUB; u++) cc[u] = c_sub[u] + (g - 1);
             if (L.active) {
                 GardnerSpanRec rc;
                 rc.ns = L.ns; rc.prev = L.prev; rc.half = L.half; rc.count = L.count;
-                recs[(size_t)(mine.first + sublane) * (size_t)(D.span - 1) + (size_t)(g - 1)] = rc;
+                my_recs[g - 1] = rc;
             }
-            gardner_sub_chunk<WIN, PDT_GSUB, false>(win, in, P, cc, L, nullptr, nullptr, 0, 0);
+            gardner_sub_chunk<WIN, NSUB, false>(win, in, P, cc, L, nullptr, nullptr, 0, 0);
             if (g + 1 < D.span) L.ns = L.ns - nT;                         // roll over; `half` is deliberately not (Q3)
         }
-        if (L.active) tails[mine.first + sublane] = gardner_encode_exit(D, L.q_last, L.i_last, L.count);
+        if (L.active) {
+            if (g_hi < D.span) {
+                GardnerSpanRec rc;                                       // stage 1 ends here: the state in front of chunk g_hi
+                rc.ns = L.ns; rc.prev = L.prev; rc.half = L.half; rc.count = L.count;
+                my_recs[g_hi - 1] = rc;
+            } else
+                tails[my_key] = gardner_encode_exit(D, L.q_last, L.i_last, L.count);
+        }
+    }
+}
+
+// One wavefront per row between the two stages, four rows to a workgroup: the row's keys whose states in front of chunk rekey + 1
+// are equal bit for bit (all three of ns, prev, half: two histories can round to the same ns) share one representative, the first
+// of them.  rep[key] = the representative's index in the key list (its own for a representative); list2 = the representatives,
+// row after row; items2 = the row's representatives cut into items of at most `subw`.  A row that stage 1 walked through (not
+// tabulated, or more than PDT_GSPAN_REKEY_MAX keys) gets no items and info (0, 0).  The distinct states of all rows are at most
+// the keys, so list2 -- as long as the key list -- cannot overflow.  Space in both lists is taken by ONE fetch-and-add per
+// workgroup (states in the low word, items in the high one): a pair per row queued 14 000 of them on one line, 0.16 ms.
+#define PDT_GSPAN_REKEY_ROWS 4
+__device__ __forceinline__ void k_gardner_span_rekey(GardnerDomain D, long long n_rows, const GardnerSpanRow *__restrict__ rows,
+                                                     const GardnerSpanRec *__restrict__ recs, int rekey, unsigned subw,
+                                                     unsigned *__restrict__ rep, unsigned *__restrict__ list2,
+                                                     GardnerSpanItem *__restrict__ items2, GardnerSpanCtl *__restrict__ ctl,
+                                                     GardnerSpanRowInfo *__restrict__ info)
+{
+    __shared__ unsigned s_state[PDT_GSPAN_REKEY_ROWS][3][PDT_GSPAN_REKEY_MAX];
+    __shared__ unsigned s_jj[PDT_GSPAN_REKEY_ROWS][PDT_GSPAN_REKEY_MAX], s_rk[PDT_GSPAN_REKEY_ROWS][PDT_GSPAN_REKEY_MAX];
+    __shared__ unsigned s_cnt[PDT_GSPAN_REKEY_ROWS][2];
+    __shared__ unsigned long long s_got;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long r = (long long)blockIdx.x * PDT_GSPAN_REKEY_ROWS + w;
+    GardnerSpanRow rw;
+    rw.off = 0; rw.n = 0;
+    if (r < n_rows) rw = rows[r];
+    const bool staged = rw.n != ~0u && rw.n != 0u && rw.n <= (unsigned)PDT_GSPAN_REKEY_MAX;
+    const int n = staged ? (int)rw.n : 0;
+    unsigned *s_ns = s_state[w][0], *s_prev = s_state[w][1], *s_half = s_state[w][2], *s_j = s_jj[w], *s_rank = s_rk[w];
+    for (int i = lane; i < n; i += 64) {
+        const GardnerSpanRec rc = recs[(size_t)(rw.off + (unsigned)i) * (size_t)(D.span - 1) + (size_t)rekey];
+        s_ns[i] = __float_as_uint(rc.ns); s_prev[i] = __float_as_uint(rc.prev); s_half[i] = __float_as_uint(rc.half);
+    }
+    __syncthreads();
+    unsigned total = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool valid = i < n;
+        const int ii = valid ? i : 0;
+        const unsigned a = s_ns[ii], b = s_prev[ii], c = s_half[ii];
+        int j = ii;
+        const int j_end = (i0 + 64 < n) ? i0 + 64 : n;
+        for (int jj = 0; jj < j_end; jj++)                               // (every lane reads the same word: a broadcast)
+            if (jj < j && s_ns[jj] == a && s_prev[jj] == b && s_half[jj] == c) j = jj;
+        const bool is_rep = valid && j == i;
+        const unsigned long long m = __ballot(is_rep);
+        if (valid) {
+            s_j[i] = (unsigned)j;
+            s_rank[i] = total + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+        }
+        total += (unsigned)__popcll(m);
+    }
+    const unsigned n_it = (total + subw - 1u) / subw;
+    if (lane == 0) {
+        s_cnt[w][0] = total; s_cnt[w][1] = n_it;
+        if (r < n_rows) {
+            GardnerSpanRowInfo ri;
+            ri.states = total; ri.items = n_it;
+            info[r] = ri;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned st = 0, it = 0;
+        for (int q = 0; q < PDT_GSPAN_REKEY_ROWS; q++) { st += s_cnt[q][0]; it += s_cnt[q][1]; }
+        s_got = (st | it) ? atomicAdd(&ctl->both2, (unsigned long long)st | ((unsigned long long)it << 32)) : 0ull;
+    }
+    __syncthreads();
+    unsigned base = (unsigned)s_got, ibase = (unsigned)(s_got >> 32);
+    for (int q = 0; q < w; q++) { base += s_cnt[q][0]; ibase += s_cnt[q][1]; }
+    for (int i = lane; i < n; i += 64) {
+        const unsigned j = s_j[i];
+        rep[rw.off + (unsigned)i] = rw.off + j;
+        if (j == (unsigned)i) list2[base + s_rank[i]] = rw.off + (unsigned)i;
+    }
+    for (unsigned q = lane; q < n_it; q += 64u) {
+        GardnerSpanItem it;
+        it.row = (unsigned)r;
+        it.first = base + subw * q;
+        it.cnt = (total - subw * q < subw) ? total - subw * q : subw;
+        items2[ibase + q] = it;
+    }
+}
+
+// One wavefront per row behind stage 2: a key that merged into a representative gets the representative's records behind the
+// re-key point and its tail, the symbol counts shifted by what the two had counted up to there (equal states can have been
+// reached with different counts).  The tail's count keeps the limit gardner_encode_exit applies.
+__device__ __forceinline__ void k_gardner_span_spread(GardnerDomain D, long long n_rows, const GardnerSpanRow *__restrict__ rows,
+                                                      const GardnerSpanRowInfo *__restrict__ info, const unsigned *__restrict__ rep,
+                                                      int rekey, unsigned *__restrict__ tails, GardnerSpanRec *__restrict__ recs)
+{
+    const long long r = blockIdx.x;
+    if (r >= n_rows) return;
+    if (info[r].states == 0u) return;                                    // (stage 1 walked this row through)
+    const GardnerSpanRow rw = rows[r];
+    const size_t per = (size_t)(D.span - 1);
+    for (unsigned i = threadIdx.x; i < rw.n; i += blockDim.x) {
+        const unsigned k = rw.off + i, rp = rep[k];
+        if (rp == k) continue;
+        GardnerSpanRec *mine = recs + (size_t)k * per;
+        const GardnerSpanRec *from = recs + (size_t)rp * per;
+        const unsigned diff = mine[rekey].count - from[rekey].count;     // (modulo 2^32: the sums below come out right either way)
+        for (int g = rekey + 1; g < D.span - 1; g++) {
+            GardnerSpanRec rc = from[g];
+            rc.count += diff;
+            mine[g] = rc;
+        }
+        const unsigned tail = tails[rp];
+        unsigned out = PDT_GTAB_MISS;
+        if (tail != PDT_GTAB_MISS) {
+            const unsigned cnt = (tail >> D.idx_bits) + diff;
+            if (cnt > 0u && cnt < (1u << (32 - D.idx_bits)) - 1u) out = (tail & ((1u << D.idx_bits) - 1u)) | (cnt << D.idx_bits);
+        }
+        tails[k] = out;
     }
 }
 

@@ -277,7 +277,7 @@ struct Tuning {
     double overlap_split[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     long long hbm_limit_mb = 0, window_piece = 0, burst_slab_rows = 0;
     int ingest_direct = -1, ingest_numa = -1;        // -1 = decide by probing the file (ingest_capture), 0 = never, 1 = always try
-    int scout_syms = 0, gspan = 0, gspan_cap = 0, ingest_threads = 0, ingest_span_mb = 0, ingest_streams = 0, overlap_segments = 0, overlap_min_mb = 0, fir_wg_per_cu = 0, agc_tpb = 0, gseg = 0, pll_block = 0, fix_passes = 2;
+    int scout_syms = 0, gspan = 0, gspan_cap = 0, gspan_rekey = -1 /* -1: the rule in sampler_domain */, gspan_sub = 0, gspan_win2 = 0, gspan_fit = 0, ingest_threads = 0, ingest_span_mb = 0, ingest_streams = 0, overlap_segments = 0, overlap_min_mb = 0, fir_wg_per_cu = 0, agc_tpb = 0, gseg = 0, pll_block = 0, fix_passes = 2;
     bool fir_generic = false, mix_unfused = false, quality_inline = false, gemit_groups = false, agc_unfused = false, no_excl = false, gardner_onebuf = false, gardner_noring = false, gardner_sequential = false, seg_sequential = false, agc_lanes = false, overlap = true, debug_overlap = false, chain_one_range = false, ema_noguess = false, debug_sync = false, pll_noshort = false, pll_nockpt = false, pll_noconsensus = false, pll_notail = false, seg_plain = false, sync_block = false, gardner_nostride = false, manch_3pass = false, sync_serial = false;
     void load();                 // (pdt_api.hip: from the registry pdt_dev_set fills)
 };
@@ -379,7 +379,7 @@ struct pdt_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
     hipStream_t stream2 = nullptr;     // side stream: block-parallel PLL phase runs beside the sequential acquisition
 
-    DevBuf pcm, pll, lock, fir, agc, sym, symidx, bits, bitsym, hits, frames, taps, mag, seams_pll, seams_agc, scal, lockinfo, term, seams_ema, gtable, gentries, gcand, gmfirst, stiles, gsegmap, gsegstart, gbands, gclist, gneed, gchain, gspan_keys, gspan_tails, gspan_rows, gspan_items, gspan_ctl, gspan_recs, gcentries, gflags, agc_maps, pll_head, taps_rot, pll_scratch, tip, sync_scr, agc_raw, agc_ckpt, pll_ckpt;
+    DevBuf pcm, pll, lock, fir, agc, sym, symidx, bits, bitsym, hits, frames, taps, mag, seams_pll, seams_agc, scal, lockinfo, term, seams_ema, gtable, gentries, gcand, gmfirst, stiles, gsegmap, gsegstart, gbands, gclist, gneed, gchain, gspan_keys, gspan_tails, gspan_rows, gspan_items, gspan_ctl, gspan_recs, gspan_rep, gspan_list2, gspan_items2, gspan_info, gcentries, gflags, agc_maps, pll_head, taps_rot, pll_scratch, tip, sync_scr, agc_raw, agc_ckpt, pll_ckpt;
     bool counted = false;        // this context is in ingest_open_contexts()
     bool keep_agc_raw = false;   // pdt_keep_presquelch: also keep the AGC output before Squelch (stage PDT_ST_AGC_RAW)
     // pdt_keep_quality: the averagePhase stream (what CarrierTrackPLL returns, chunk by chunk) and the per-chunk counts
@@ -404,6 +404,7 @@ struct pdt_ctx {
     long long gcand_key = -1;          // (chunk_out, step) the candidate list on the device was built for
     int gardner_mode = 0;              // 0 sequential, 1 state table (last run)
     long long gspan_nrows = 0;         // table rows of several chunks in the last run (0: none) -- pdt_dev_span_rows
+    int gspan_rekey = 0;               // chunks its span walk went before the re-key (0: single stage) -- pdt_dev_span_rekey
     const void *pcm_dev = nullptr;     // input actually used (own copy or caller's buffer)
     int pcm_fmt = 0;                   // 0 = int16 pairs, 1 = float32 pairs (InFmt::pcm_fmt)
 

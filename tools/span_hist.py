@@ -24,6 +24,10 @@ with pdt.Demodulator(pdt.MODE_POES, fs).keep_pll(False) as d:
     rows = int(L.pdt_dev_span_rows(d._h, None, 0))
     out = np.zeros(max(rows, 1), dtype=np.uint32)
     L.pdt_dev_span_rows(d._h, out.ctypes.data, rows)
+    L.pdt_dev_span_rekey.restype = C.c_uint64
+    L.pdt_dev_span_rekey.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    staged = np.zeros((max(rows, 1), 3), dtype=np.uint32)
+    L.pdt_dev_span_rekey(d._h, staged.ctypes.data, rows)
     st = d.stats()
 ex = out[:rows]
 ok = ex[ex != 0xFFFFFFFF]
@@ -35,3 +39,13 @@ if len(ok):
         k = int(((ok >= lo) & (ok < hi)).sum())
         print(f"  {lo:>4d} .. {hi - 1 if hi < (1 << 30) else 'more':>4}: {k:>7d} rows ({100.0 * k / len(ok):5.1f} %)")
     print(f"rows with at most 4 distinct exits: {100.0 * float((ok <= 4).mean()):.2f} %")
+# the staged span walk (pdt_dev_span_rekey): what is left of those exits at the re-key point, and the stage-2 items they make
+sg = staged[:rows]
+sg = sg[sg[:, 1] > 0]
+if len(sg):
+    k, s2, it = sg[:, 0], sg[:, 1], sg[:, 2]
+    print(f"staged rows: {len(sg)}; distinct states at the re-key point: min {s2.min()}, median {int(np.median(s2))}, mean {s2.mean():.1f}, "
+          f"95 % {int(np.percentile(s2, 95))}, max {s2.max()} (their first-chunk exits: median {int(np.median(k))}, mean {k.mean():.1f})")
+    print(f"stage-2 items per row: mean {it.mean():.2f}, max {it.max()}; rows with more than one: {100.0 * float((it > 1).mean()):.1f} %")
+else:
+    print("no row went through the staged walk")

@@ -720,6 +720,61 @@ int  pdt_argos_msg_tile(void);
 uint64_t pdt_format_argos_messages(const pdt_argos_msg *msgs, uint64_t n, char *buf, uint64_t cap);
 int  pdt_write_argos_messages(const pdt_argos_msg *msgs, uint64_t n, int fd, uint64_t *bytes_written);
 
+/* POES frames from a flywheel synchroniser (POES contexts).  The frames above are the reference's: a minor frame is taken
+ * only if all 19 bits of its sync word (or of the complement) are right, sync words are ignored while a frame is open, and the first
+ * match wins.  One wrong bit among the 19 loses 832 good ones, and one false match swallows the true sync word behind it.  Minor frames
+ * come every F = 832 bits, so these entries believe a sync word because its neighbours are where they should be: a second, opt-in
+ * source of pdt_frame records BESIDE the frames; the rule is fixed in csrc/pdt_tip_sync.h and pdt_host_tip_sync restates it on the host.
+ * With S = 1110110111100010000 and a position p = the index of the bit that would complete a sync word (pdt_frame.bit_index),
+ * 18 <= p < n: dist+(p) = the Hamming distance of bits p-18 .. p to S and dist-(p) = 19 - dist+(p); p is a CANDIDATE of polarity s when
+ * dist_s(p) <= max_errors; its SUPPORT u_s(p) is the number of k in {-window .. -1, 1 .. window} for which p + k F is a candidate of s
+ * (exact multiples of F only; a position outside [18, n) is none).  p is a HEAD of s when p + 813 < n -- the whole frame is present,
+ * incomplete frames are not emitted -- and either it is a candidate with u_s >= 1, or u_s >= fly: the flywheel, whose own sync word
+ * may be arbitrarily damaged.  A head's key is (u_s, candidate, -dist_s), compared lexicographically; where both polarities are heads
+ * at one p the larger key stands, the upright one at equal keys.  A head h is emitted if and only if no other head g with
+ * |g - h| <= F - 4 has a larger key, or an equal one and g < h -- judged against all heads, emitted or not, so the result depends on no
+ * order, and frames that overlap by up to three bits (a slipped bit) are both emitted.  A record is filled as the reference prints a
+ * frame: bytes 0xED 0xE2, the five bits behind p under three zero bits, then 101 bytes MSB first, every data bit complemented for an
+ * inverted head; nbytes 104, complete 1; time and time_src those of a pdt_frame whose sync word completes at bit p.  Records come in
+ * ascending bit_index; pdt_write_records / pdt_format_records print them, pdt_tip_check_records validates them.
+ * pdt_tip_sync_cfg: NULL or a zero field = the default -- max_errors 2 (allowed 0 .. 3; a real 0 with PDT_TIP_SYNC_ZERO_MAX_ERRORS in
+ * zero_mask), window 2 (1 .. 8), fly 3 (2 .. 2 window).  pdt_tip_sync_info (optional, parallel to the records): the distance, support
+ * and candidate bit of the polarity that stands.
+ *   pdt_tip_sync         the bits of the context's last whole-capture call (PDT_ST_BITS, in device memory; their count is read there):
+ *                        *count = the frames found, the first min(cap, *count) of them in out (and info, when not NULL).
+ *                        PDT_ERR_STATE when the last call left no resident bit stream (none yet, a stream open or ended, a capture
+ *                        taken in pieces, a stage-level call); PDT_ERR_ARG for an ARGOS context, a cfg out of range, cap < 0.  It leaves
+ *                        frames, text, stages, statistics and every other result exactly as they were (a profiled context's
+ *                        pdt_kernel_times gain the entries k_tip_cand, k_tip_heads, k_tip_pick, k_tip_scan and k_tip_pack)
+ *   pdt_tip_sync_batch   the same for `count` contexts with ONE launch of each kernel (the slots of pdt_demod_batch_device): context
+ *                        i's records at out + i cap_each (info + i cap_each), their number in counts[i].  The contexts must be
+ *                        distinct and live on one device (else PDT_ERR_ARG); every one is checked before anything runs
+ *   pdt_stage_tip_sync   stage-level entry: the kernels on a caller's string of '0'/'1' characters (any byte other than '0' is a one);
+ *                        the time stamp of bit k is k.  Nothing of the context's results changes
+ *   pdt_host_tip_sync    host only, no GPU: the same records for the same string
+ *   pdt_tip_sync_tile    the bits one workgroup tests (tests place sync words at its seams)                                          */
+#define PDT_TIP_SYNC_ZERO_MAX_ERRORS 1u
+typedef struct pdt_tip_sync_cfg {
+    int32_t  max_errors;
+    int32_t  window;
+    int32_t  fly;
+    uint32_t zero_mask;
+} pdt_tip_sync_cfg;
+typedef struct pdt_tip_sync_info {
+    uint8_t  sync_errors;  /* dist_s(p) of the polarity that stands: wrong bits among the 19                                 */
+    uint8_t  support;      /* u_s(p): neighbouring slots with a candidate                                                    */
+    uint8_t  candidate;    /* 1 = the head's own sync word is within max_errors; 0 = a flywheel head                          */
+    uint8_t  reserved;
+} pdt_tip_sync_info;
+int  pdt_tip_sync(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count);
+int  pdt_tip_sync_batch(pdt_ctx *const *ctxs, int count, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap_each,
+                        int *counts);
+int  pdt_stage_tip_sync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, const pdt_tip_sync_cfg *cfg, pdt_frame *out,
+                        pdt_tip_sync_info *info, int cap, int *count);
+int  pdt_host_tip_sync(const uint8_t *bits, uint64_t nbits, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap,
+                       int *count);
+int  pdt_tip_sync_tile(void);
+
 /* ARGOS bits without a loop: feed-forward bit decisions per burst window (ARGOS contexts).  The bits above come out of the reference's
  * chain -- a PLL that must pull in, a squelch, a Gardner loop, a Manchester decoder that guesses the symbol pairing -- and a window whose
  * carrier lies at the edge of the loop's range, or whose pairing is never found, holds no message under either rule.  A burst needs no
@@ -947,6 +1002,10 @@ typedef struct pdt_tip_summary {
 int      pdt_tip_check(pdt_ctx *ctx, pdt_tip_summary *out);
 /* Per-frame records of the last pdt_tip_check, in frame order; returns the number copied. */
 uint64_t pdt_tip_frames(const pdt_ctx *ctx, pdt_tip_frame *out, uint64_t max_frames);
+/* The same validation kernel on a caller's array of frame records (those of pdt_tip_sync, say): the summary in *out, the per-frame
+ * records in per_frame[0 .. n) when not NULL.  POES contexts only; the context supplies device and stream, and nothing of its results
+ * -- pdt_tip_frames included -- changes.  PDT_ERR_ARG for a null pointer with n > 0 or n >= 2^31; PDT_ERR_STATE while a stream is open. */
+int      pdt_tip_check_records(pdt_ctx *ctx, const pdt_frame *frames, uint64_t n, pdt_tip_summary *out, pdt_tip_frame *per_frame);
 
 /* Per-kernel device times of the last call (cfg.profile = 1). Returns the entry count. */
 int      pdt_kernel_times(const pdt_ctx *ctx, pdt_kernel_time *out, int max_entries);

@@ -375,6 +375,61 @@ def argos_messages_batch(ds, min_run=None, cap: int = 4096, rule=None):
     return [out[i, :min(counts[i], cap)].copy() for i in range(len(ds))]
 
 
+class TipSyncCfg(C.Structure):
+    """pdt_tip_sync_cfg: a zero means the default; max_errors 0 with TIP_SYNC_ZERO_MAX_ERRORS in zero_mask asks for exact sync words"""
+    _fields_ = [("max_errors", C.c_int32), ("window", C.c_int32), ("fly", C.c_int32), ("zero_mask", C.c_uint32)]
+
+
+TIP_SYNC_ZERO_MAX_ERRORS = 1
+# pdt_tip_sync_info as a numpy record: the distance, support and candidate bit of the polarity that stands
+TIP_SYNC_INFO_DTYPE = np.dtype([("sync_errors", "u1"), ("support", "u1"), ("candidate", "u1"), ("reserved", "u1")])
+assert TIP_SYNC_INFO_DTYPE.itemsize == 4
+
+
+def _tip_sync_cfg(max_errors=None, window=None, fly=None):
+    """the three constants of the flywheel's rule (None = the default: 2, 2, 3) -> pdt_tip_sync_cfg or None; max_errors 0 travels with
+    its flag bit"""
+    if max_errors is None and window is None and fly is None:
+        return None
+    c = TipSyncCfg(window=int(window or 0), fly=int(fly or 0))
+    if max_errors is not None:
+        c.max_errors, c.zero_mask = int(max_errors), TIP_SYNC_ZERO_MAX_ERRORS if int(max_errors) == 0 else 0
+    return c
+
+
+def _tip_sync_result(out, info, found: int, cap: int, with_info: bool, with_count: bool):
+    n = min(found, cap)
+    got = (out[:n].copy(), info[:n].copy()) if with_info else out[:n].copy()
+    return (got, found) if with_count else got
+
+
+def tip_sync_tile() -> int:
+    """pdt_tip_sync_tile: the bits one workgroup of k_tip_cand tests"""
+    return lib().pdt_tip_sync_tile()
+
+
+def host_tip_sync(bits, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False, with_count: bool = False):
+    """pdt_host_tip_sync: the POES minor frames a flywheel synchroniser finds in a string of '0'/'1' characters, restated on the host
+    (no GPU); the time stamp of bit k is k.  Returns FRAME_DTYPE[min(found, cap)]; with_info: (that, TIP_SYNC_INFO_DTYPE[..]);
+    with_count: (that, found)."""
+    a, c = _bit_string(bits), _tip_sync_cfg(max_errors, window, fly)
+    out, info, count = np.zeros(max(cap, 1), dtype=FRAME_DTYPE), np.zeros(max(cap, 1), dtype=TIP_SYNC_INFO_DTYPE), C.c_int(0)
+    _check(lib().pdt_host_tip_sync(a.ctypes.data, a.size, C.byref(c) if c else None, out.ctypes.data, info.ctypes.data, cap, C.byref(count)),
+           "pdt_host_tip_sync")
+    return _tip_sync_result(out, info, count.value, cap, with_info, with_count)
+
+
+def tip_sync_batch(ds, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False):
+    """pdt_tip_sync_batch: Demodulator.tip_sync() of several contexts of one device with ONE launch of each kernel: a list of FRAME_DTYPE
+    arrays (with_info: of (frames, info) pairs), one per context."""
+    c = _tip_sync_cfg(max_errors, window, fly)
+    hs = (C.c_void_p * max(len(ds), 1))(*[d._h for d in ds])
+    out, info = np.zeros((max(len(ds), 1), max(cap, 1)), dtype=FRAME_DTYPE), np.zeros((max(len(ds), 1), max(cap, 1)), dtype=TIP_SYNC_INFO_DTYPE)
+    counts = (C.c_int * max(len(ds), 1))()
+    _check(lib().pdt_tip_sync_batch(hs, len(ds), C.byref(c) if c else None, out.ctypes.data, info.ctypes.data, cap, counts), "pdt_tip_sync_batch")
+    return [_tip_sync_result(out[i], info[i], counts[i], cap, with_info, False) for i in range(len(ds))]
+
+
 class FfCfg(C.Structure):
     """pdt_ff_cfg: a zero means the default; rate_steps 0 with FF_ZERO_RATE_STEPS in zero_mask asks for the nominal rate alone;
     FF_RESIDUAL_GIVEN in flags: residual_hz is the caller's, otherwise the carrier is measured"""
@@ -497,6 +552,7 @@ ABI_SYMBOLS = [
     "pdt_format_argos_messages", "pdt_write_argos_messages",
     "pdt_ff_bits", "pdt_ff_bits_batch", "pdt_ff_read", "pdt_ff_messages", "pdt_ff_messages_batch", "pdt_stage_ff_bits", "pdt_host_ff_bits",
     "pdt_host_ff_mix",
+    "pdt_tip_sync", "pdt_tip_sync_batch", "pdt_stage_tip_sync", "pdt_host_tip_sync", "pdt_tip_sync_tile", "pdt_tip_check_records",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
 
@@ -652,6 +708,11 @@ def lib():
     L.pdt_argos_messages_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(ArgosCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.pdt_stage_argos_messages.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ArgosCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.pdt_host_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ArgosCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_tip_sync.argtypes = [C.c_void_p, C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_tip_sync_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_stage_tip_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_host_tip_sync.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_tip_check_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TipSummary), C.c_void_p]
     L.pdt_format_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.pdt_format_argos_messages.restype = C.c_uint64
     L.pdt_write_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
@@ -1331,6 +1392,32 @@ class Demodulator:
         if n:
             self._L.pdt_tip_frames(self._h, rec.ctypes.data, n)
         return {k: int(getattr(sm, k)) for k, _ in TipSummary._fields_}, rec
+
+    def tip_check_records(self, frames):
+        """pdt_tip_check_records: tip_check()'s validation on a caller's FRAME_DTYPE array (the frames of tip_sync(), say): (summary dict,
+        per-frame structured array).  The context's own results stay as they were."""
+        a = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+        sm, rec = TipSummary(), np.zeros(max(len(a), 1), dtype=TIP_DTYPE)
+        _check(self._L.pdt_tip_check_records(self._h, a.ctypes.data, len(a), C.byref(sm), rec.ctypes.data), "pdt_tip_check_records")
+        return {k: int(getattr(sm, k)) for k, _ in TipSummary._fields_}, rec[:len(a)]
+
+    def tip_sync(self, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False, with_count: bool = False):
+        """pdt_tip_sync: the POES minor frames a flywheel synchroniser finds in the bits of this context's last whole-capture call -- a
+        sync word with up to max_errors wrong bits (None = 2) counts when a neighbouring slot within `window` frames (None = 2) has one
+        too, and a slot with `fly` such neighbours (None = 3) is a frame whatever its own sync word.  Returns FRAME_DTYPE[min(found,
+        cap)]; with_info: (that, TIP_SYNC_INFO_DTYPE[..]); with_count: (that, found).  Frames, text and stages stay as they were."""
+        c = _tip_sync_cfg(max_errors, window, fly)
+        out, info, count = np.zeros(max(cap, 1), dtype=FRAME_DTYPE), np.zeros(max(cap, 1), dtype=TIP_SYNC_INFO_DTYPE), C.c_int(0)
+        _check(self._L.pdt_tip_sync(self._h, C.byref(c) if c else None, out.ctypes.data, info.ctypes.data, cap, C.byref(count)), "pdt_tip_sync")
+        return _tip_sync_result(out, info, count.value, cap, with_info, with_count)
+
+    def stage_tip_sync(self, bits, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False, with_count: bool = False):
+        """pdt_stage_tip_sync: the flywheel's kernels on a string of '0'/'1' characters; the time stamp of bit k is k"""
+        a, c = _bit_string(bits), _tip_sync_cfg(max_errors, window, fly)
+        out, info, count = np.zeros(max(cap, 1), dtype=FRAME_DTYPE), np.zeros(max(cap, 1), dtype=TIP_SYNC_INFO_DTYPE), C.c_int(0)
+        _check(self._L.pdt_stage_tip_sync(self._h, a.ctypes.data, a.size, C.byref(c) if c else None, out.ctypes.data, info.ctypes.data, cap,
+                                          C.byref(count)), "pdt_stage_tip_sync")
+        return _tip_sync_result(out, info, count.value, cap, with_info, with_count)
 
     def kernel_times(self) -> dict[str, tuple[int, float]]:
         n = self._L.pdt_kernel_times(self._h, None, 0)

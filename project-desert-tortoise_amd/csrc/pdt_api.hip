@@ -8,6 +8,7 @@
 #include "pdt_bursts.h"
 #include "pdt_tone.h"
 #include "pdt_argos_msg.h"
+#include "pdt_tip_sync.h"
 #include "pdt_ff.h"
 
 #include <sys/stat.h>
@@ -38,6 +39,10 @@ void tones_derive(const void *raw, const pdt::TonePlan &p, double fs, double off
 // pdt_argos_msg.hip
 hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, int rule, hipEvent_t mid);
 int argos_min_run(const pdt_argos_cfg *cfg, int *K, int *rule);
+// pdt_tip_sync.hip
+extern const char *const tip_sync_kernel_names[5];
+hipError_t tip_sync_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, pdt::TipSyncRule R, hipEvent_t *ev);
+int tip_sync_rule(const pdt_tip_sync_cfg *cfg, pdt::TipSyncRule *R);
 // pdt_ff.hip
 hipError_t ff_launch(hipStream_t st, const void *table_dev, int nwin, long long mix_tiles, long long groups, const long long *periods_dev, int R,
                      int H, long long pmax, const float *tab_dev, void *metric_dev, size_t metric_bytes, void *syncs_dev, hipEvent_t *ev);
@@ -587,7 +592,8 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
-                       &ctx->argos_work, &ctx->argos_bits, &ctx->ff_work, &ctx->ff_in, &ctx->ff_out };
+                       &ctx->argos_work, &ctx->argos_bits, &ctx->ff_work, &ctx->ff_in, &ctx->ff_out,
+                       &ctx->tip_sync_work, &ctx->tip_sync_bits, &ctx->tip_recs };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1558,6 +1564,186 @@ int pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nb
         if ((rc = argos_run(ctx, jobs, K, rule, recs, at, found))) return rc;
         const size_t have = std::min<size_t>(found[0], at[1]);
         if (have) memcpy(out, recs.data(), have * sizeof(ArgosMsg));
+        *count = (int)found[0];
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    return PDT_OK;
+}
+
+// ---------------------------------------------------------------- flywheel frame synchroniser (pdt_tip_sync.h)
+// One bit stream of a call, as an ArgosJob describes one
+struct TipSyncJob {
+    const unsigned char *bits;
+    const unsigned long long *nbits_dev;
+    const unsigned *bitsym;
+    const long long *symidx;
+    long long bit_cap;
+    int cap;
+};
+
+// The streams of a call through one launch of each kernel over a table on the device, as argos_run does it: the first context supplies
+// stream and work buffer -- the records, info records and counts of all streams (read back in one copy), the table, every stream's tile
+// counts, offsets and six bitmaps.  recs / infos: stream i's records from at[i] on, found[i] of them counted, min(found[i], room) present.
+static int tip_sync_run(pdt_ctx *c0, const std::vector<TipSyncJob> &jobs, TipSyncRule R, std::vector<TipSyncRec> &recs, std::vector<TipSyncInfo> &infos,
+                        std::vector<size_t> &at, std::vector<unsigned> &found)
+{
+    const size_t n = jobs.size();
+    std::vector<TipSyncCtx> table(n);
+    std::vector<long long> tiles(n);
+    at.assign(n + 1, 0);
+    long long ntiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        // emitted heads lie at least 829 bits apart
+        const long long room = std::min<long long>(jobs[i].cap, jobs[i].bit_cap / TIP_SYNC_MIN_GAP + 1);
+        at[i + 1] = at[i] + (size_t)room;
+        tiles[i] = (jobs[i].bit_cap + TIP_SYNC_TILE - 1) / TIP_SYNC_TILE;
+        ntiles += tiles[i];
+    }
+    if (ntiles > 0x7fffffffll) return PDT_ERR_ARG;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_info = up16(at[n] * sizeof(TipSyncRec)), o_cnt = o_info + up16(at[n] * sizeof(TipSyncInfo)), o_tab = o_cnt + up16(n * sizeof(unsigned)),
+                 o_tcnt = o_tab + up16(n * sizeof(TipSyncCtx)), o_toff = o_tcnt + up16((size_t)ntiles * sizeof(unsigned)),
+                 o_maps = o_toff + up16((size_t)ntiles * sizeof(unsigned)), map_bytes = (size_t)ntiles * TIP_SYNC_WORDS * 8, total = o_maps + 6 * map_bytes;
+    HIP_TRY(hipSetDevice(c0->cfg.device));
+    int rc;
+    if ((rc = c0->tip_sync_work.ensure(total))) return rc;
+    unsigned char *w = (unsigned char *)c0->tip_sync_work.p;
+    long long t0 = 0;
+    for (size_t i = 0; i < n; i++) {
+        TipSyncCtx &r = table[i];
+        auto map = [&](int k) { return (unsigned long long *)(w + o_maps + (size_t)k * map_bytes) + (size_t)t0 * TIP_SYNC_WORDS; };
+        r.bits = jobs[i].bits;
+        r.nbits = jobs[i].nbits_dev;
+        r.bitsym = jobs[i].bitsym;
+        r.symidx = jobs[i].symidx;
+        r.packed = map(0);
+        r.cand[0] = map(1);
+        r.cand[1] = map(2);
+        r.head[0] = map(3);
+        r.head[1] = map(4);
+        r.emit = map(5);
+        r.tile_cnt = (unsigned *)(w + o_tcnt) + t0;
+        r.tile_off = (unsigned *)(w + o_toff) + t0;
+        r.out = (TipSyncRec *)w + at[i];
+        r.info = (TipSyncInfo *)(w + o_info) + at[i];
+        r.count = (unsigned *)(w + o_cnt) + i;
+        r.bit_cap = jobs[i].bit_cap;
+        r.cap = (int)(at[i + 1] - at[i]);
+        r.first_tile = (int)t0;
+        t0 += tiles[i];
+    }
+    // (the table of the previous call is no longer read: every call ends with a synchronize)
+    HIP_TRY(hipMemcpy(w + o_tab, table.data(), n * sizeof(TipSyncCtx), hipMemcpyHostToDevice));
+    hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (c0->cfg.profile)
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(tip_sync_launch(c0->stream, w + o_tab, (int)n, ntiles, R, c0->cfg.profile ? ev : nullptr));
+    std::vector<unsigned char> back(o_tab);
+    HIP_TRY(hipMemcpyAsync(back.data(), w, o_tab, hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipStreamSynchronize(c0->stream));
+    if (c0->cfg.profile) {
+        for (int k = 0; k < 5; k++) {
+            const char *name = tip_sync_kernel_names[k];
+            pdt_kernel_time kt;
+            memset(&kt, 0, sizeof kt);
+            snprintf(kt.name, sizeof kt.name, "%s", name);
+            kt.launches = 1;
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            kt.total_ms = ms;
+            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [&](const pdt_kernel_time &o) { return !strcmp(o.name, name); }),
+                             c0->ktimes.end());
+            c0->ktimes.push_back(kt);
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    recs.resize(at[n]);
+    infos.resize(at[n]);
+    if (at[n]) {
+        memcpy(recs.data(), back.data(), at[n] * sizeof(TipSyncRec));
+        memcpy(infos.data(), back.data() + o_info, at[n] * sizeof(TipSyncInfo));
+    }
+    found.resize(n);
+    if (n) memcpy(found.data(), back.data() + o_cnt, n * sizeof(unsigned));
+    return PDT_OK;
+}
+
+static int tip_sync_each(pdt_ctx *const *ctxs, int count, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap_each, int *counts)
+{
+    TipSyncRule R;
+    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || tip_sync_rule(cfg, &R)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++) {
+        const pdt_ctx *c = ctxs[i];
+        if (!c || c->cfg.mode != PDT_MODE_POES || c->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
+        for (int j = 0; j < i; j++)
+            if (ctxs[j] == c) return PDT_ERR_ARG;
+    }
+    for (int i = 0; i < count; i++)
+        if (!bits_resident(ctxs[i])) return PDT_ERR_STATE;
+    if (!count) return PDT_OK;
+    try {
+        std::vector<TipSyncJob> jobs((size_t)count);
+        for (int i = 0; i < count; i++) {
+            const pdt_ctx *c = ctxs[i];
+            const uint64_t nb = c->stage_len[PDT_ST_BITS];              // (what the host read back; the kernels read the device's own count)
+            jobs[(size_t)i] = TipSyncJob{ (const unsigned char *)c->bits.p, &((const DevScalars *)c->scal.p)->nbits, (const unsigned *)c->bitsym.p,
+                                          (const long long *)c->symidx.p, nb && c->bits.p && c->scal.p ? (long long)nb : 0, cap_each };
+        }
+        std::vector<TipSyncRec> recs;
+        std::vector<TipSyncInfo> infos;
+        std::vector<size_t> at;
+        std::vector<unsigned> found;
+        const int rc = tip_sync_run(ctxs[0], jobs, R, recs, infos, at, found);
+        if (rc) return rc;
+        for (int i = 0; i < count; i++) {
+            const size_t have = std::min<size_t>(found[(size_t)i], at[(size_t)i + 1] - at[(size_t)i]);
+            for (size_t k = 0; k < have; k++) {
+                TipSyncRec m = recs[at[(size_t)i] + k];
+                m.time = ctxs[i]->bit_time(m.time_src);
+                memcpy(&out[(size_t)i * (size_t)cap_each + k], &m, sizeof m);
+                if (info) memcpy(&info[(size_t)i * (size_t)cap_each + k], &infos[at[(size_t)i] + k], sizeof(TipSyncInfo));
+            }
+            counts[i] = (int)found[(size_t)i];
+        }
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    return PDT_OK;
+}
+
+int pdt_tip_sync_batch(pdt_ctx *const *ctxs, int count, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap_each, int *counts)
+{
+    return tip_sync_each(ctxs, count, cfg, out, info, cap_each, counts);
+}
+
+int pdt_tip_sync(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count)
+{
+    if (!ctx || !count) return PDT_ERR_ARG;
+    return tip_sync_each(&ctx, 1, cfg, out, info, cap, count);
+}
+
+int pdt_stage_tip_sync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info,
+                       int cap, int *count)
+{
+    TipSyncRule R;
+    if (!ctx || (!bits_host && nbits) || nbits >= (1ull << 31) || cap < 0 || (!out && cap) || !count || tip_sync_rule(cfg, &R)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    // the string in a buffer of its own, its count in front of it: nothing the context's results live in is touched
+    int rc;
+    if ((rc = ctx->tip_sync_bits.ensure(16 + (size_t)nbits))) return rc;
+    const unsigned long long nb = nbits;
+    HIP_TRY(hipMemcpy(ctx->tip_sync_bits.p, &nb, sizeof nb, hipMemcpyHostToDevice));
+    if (nbits) HIP_TRY(hipMemcpy((unsigned char *)ctx->tip_sync_bits.p + 16, bits_host, (size_t)nbits, hipMemcpyHostToDevice));
+    try {
+        const std::vector<TipSyncJob> jobs(1, TipSyncJob{ (const unsigned char *)ctx->tip_sync_bits.p + 16, (const unsigned long long *)ctx->tip_sync_bits.p,
+                                                          nullptr, nullptr, (long long)nbits, cap });
+        std::vector<TipSyncRec> recs;
+        std::vector<TipSyncInfo> infos;
+        std::vector<size_t> at;
+        std::vector<unsigned> found;
+        if ((rc = tip_sync_run(ctx, jobs, R, recs, infos, at, found))) return rc;
+        const size_t have = std::min<size_t>(found[0], at[1]);
+        if (have) memcpy(out, recs.data(), have * sizeof(TipSyncRec));
+        if (have && info) memcpy(info, infos.data(), have * sizeof(TipSyncInfo));
         *count = (int)found[0];
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
     return PDT_OK;
@@ -2668,6 +2854,40 @@ uint64_t pdt_stream_frames(const pdt_ctx *ctx, pdt_frame *out, uint64_t max_fram
 // ---------------------------------------------------------------- frame validation
 static_assert(sizeof(pdt_tip_frame) == sizeof(pdt::TipFrame) && sizeof(pdt_tip_frame) == 12, "pdt_tip_frame layout");
 
+// the summary of a validation run: the kernel's counters, and the modes MATLAB forms over the per-frame records
+static void tip_reduce(const TipCounters &cnt, const pdt_tip_frame *recs, const pdt_frame *frames, unsigned nf, pdt_tip_summary *out)
+{
+    out->frames_checked = cnt.frames_checked;
+    out->good_frames = cnt.good_frames;
+    out->bad_chunks = cnt.bad_chunks;
+    out->good_chunks = 5 * cnt.frames_checked - cnt.bad_chunks;
+    out->time_frames = cnt.time_frames;
+    // MATLAB mode(): most frequent value, the smallest one on ties
+    unsigned best = 0;
+    for (int v = 0; v < 256; v++) if (cnt.hist_sc[v] > best) { best = cnt.hist_sc[v]; out->spacecraft = v; }
+    best = 0;
+    for (int v = 0; v < 512; v++) if (cnt.hist_day[v] > best) { best = cnt.hist_day[v]; out->day = v; }
+    // T0 = spacecraft ms of day minus the local frame time (daytimeDecode.m:26,34); frameTime is what the text
+    // file holds ("%.5f"); the time stamps live on the host (pdt_timeaxis.h), so this small reduction does too
+    std::vector<double> t0;
+    for (unsigned f = 0; f < nf; f++) {
+        const pdt_tip_frame &r = recs[f];
+        if (r.has_time && r.day_ms >= 0) {
+            const double t = round(frames[f].time * 1e5) / 1e5;
+            const double v = (double)r.day_ms - t * 1000.0;
+            if (v > 0) t0.push_back(round(v));
+        }
+    }
+    std::sort(t0.begin(), t0.end());
+    size_t best_n = 0;
+    for (size_t i = 0; i < t0.size();) {
+        size_t j = i;
+        while (j < t0.size() && t0[j] == t0[i]) j++;
+        if (j - i > best_n) { best_n = j - i; out->t0_ms = (int64_t)t0[i]; }
+        i = j;
+    }
+}
+
 int pdt_tip_check(pdt_ctx *ctx, pdt_tip_summary *out)
 {
     if (!ctx || !out) return PDT_ERR_ARG;
@@ -2693,35 +2913,7 @@ int pdt_tip_check(pdt_ctx *ctx, pdt_tip_summary *out)
     PL.copy(OP_D2H, &cnt, d_cnt, sizeof cnt);
     PL.copy(OP_D2H, ctx->tip_host.data(), d_rec, (size_t)nf * sizeof(TipFrame));
     if ((rc = oneshot_run(ctx))) return rc;
-    out->frames_checked = cnt.frames_checked;
-    out->good_frames = cnt.good_frames;
-    out->bad_chunks = cnt.bad_chunks;
-    out->good_chunks = 5 * cnt.frames_checked - cnt.bad_chunks;
-    out->time_frames = cnt.time_frames;
-    // MATLAB mode(): most frequent value, the smallest one on ties
-    unsigned best = 0;
-    for (int v = 0; v < 256; v++) if (cnt.hist_sc[v] > best) { best = cnt.hist_sc[v]; out->spacecraft = v; }
-    best = 0;
-    for (int v = 0; v < 512; v++) if (cnt.hist_day[v] > best) { best = cnt.hist_day[v]; out->day = v; }
-    // T0 = spacecraft ms of day minus the local frame time (daytimeDecode.m:26,34); frameTime is what the text
-    // file holds ("%.5f"); the time stamps live on the host (pdt_timeaxis.h), so this small reduction does too
-    std::vector<double> t0;
-    for (unsigned f = 0; f < nf; f++) {
-        const pdt_tip_frame &r = ctx->tip_host[f];
-        if (r.has_time && r.day_ms >= 0) {
-            const double t = round(ctx->frames_host[f].time * 1e5) / 1e5;
-            const double v = (double)r.day_ms - t * 1000.0;
-            if (v > 0) t0.push_back(round(v));
-        }
-    }
-    std::sort(t0.begin(), t0.end());
-    size_t best_n = 0;
-    for (size_t i = 0; i < t0.size();) {
-        size_t j = i;
-        while (j < t0.size() && t0[j] == t0[i]) j++;
-        if (j - i > best_n) { best_n = j - i; out->t0_ms = (int64_t)t0[i]; }
-        i = j;
-    }
+    tip_reduce(cnt, ctx->tip_host.data(), ctx->frames_host.data(), nf, out);
     return PDT_OK;
 }
 
@@ -2731,6 +2923,55 @@ uint64_t pdt_tip_frames(const pdt_ctx *ctx, pdt_tip_frame *out, uint64_t max_fra
     const uint64_t n = std::min<uint64_t>(max_frames, ctx->tip_host.size());
     if (out && n) memcpy(out, ctx->tip_host.data(), (size_t)n * sizeof(pdt_tip_frame));
     return n;
+}
+
+// k_tip_check on a caller's records: they go to the device as the FrameRec the kernel reads, in a buffer of their own -- ctx->tip and
+// tip_host (pdt_tip_frames) keep what the last pdt_tip_check left
+int pdt_tip_check_records(pdt_ctx *ctx, const pdt_frame *frames, uint64_t n, pdt_tip_summary *out, pdt_tip_frame *per_frame)
+{
+    if (!ctx || !out || (!frames && n) || n >= (1ull << 31)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;             // TIP minor frames only
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;
+    memset(out, 0, sizeof *out);
+    out->spacecraft = -1;
+    out->day = -1;
+    out->t0_ms = -1;
+    if (n == 0) return PDT_OK;
+    const unsigned nf = (unsigned)n;
+    try {
+        std::vector<FrameRec> in(nf);
+        for (unsigned f = 0; f < nf; f++) {
+            FrameRec &r = in[f];
+            memset(&r, 0, sizeof r);
+            r.bit_index = frames[f].bit_index;
+            r.time_src = frames[f].time_src;
+            r.inverted = frames[f].inverted;
+            r.nbytes = frames[f].nbytes;
+            r.complete = frames[f].complete;
+            memcpy(r.bytes, frames[f].bytes, sizeof r.bytes);
+        }
+        std::vector<pdt_tip_frame> recs(nf);
+        const size_t o_rec = (sizeof(TipCounters) + 15) & ~(size_t)15, o_in = (o_rec + (size_t)nf * sizeof(TipFrame) + 15) & ~(size_t)15;
+        int rc;
+        if ((rc = ctx->tip_recs.ensure(o_in + (size_t)nf * sizeof(FrameRec)))) return rc;
+        unsigned char *w = (unsigned char *)ctx->tip_recs.p;
+        TipCounters *d_cnt = (TipCounters *)w;
+        TipFrame *d_rec = (TipFrame *)(w + o_rec);
+        FrameRec *d_in = (FrameRec *)(w + o_in);
+        hipStream_t st = ctx->stream;
+        Plan &PL = oneshot_begin(ctx);
+        PL.memset_async(d_cnt, 0, sizeof(TipCounters));
+        PL.copy(OP_H2D, d_in, in.data(), (size_t)nf * sizeof(FrameRec));
+        PDT_LAUNCH(256, k_tip_check, dim3((nf + 255) / 256), dim3(256), 0, st, (const FrameRec *)d_in, nf, d_rec, d_cnt);
+        TipCounters cnt;
+        PL.copy(OP_D2H, &cnt, d_cnt, sizeof cnt);
+        PL.copy(OP_D2H, recs.data(), d_rec, (size_t)nf * sizeof(TipFrame));
+        if ((rc = oneshot_run(ctx))) return rc;
+        tip_reduce(cnt, recs.data(), frames, nf, out);
+        if (per_frame) memcpy(per_frame, recs.data(), (size_t)nf * sizeof(pdt_tip_frame));
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    return PDT_OK;
 }
 
 uint64_t pdt_num_frames(const pdt_ctx *ctx) { return ctx ? ctx->frames_host.size() : 0; }

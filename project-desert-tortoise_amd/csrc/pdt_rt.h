@@ -474,6 +474,9 @@ struct pdt_ctx {
     DevBuf argos_work, argos_bits;
     bool bits_whole = false;
     std::function<double(long long)> bit_time;
+    // flywheel frame synchroniser (pdt_tip_sync.h): the launch's table, bitmaps and records on the device (first context of a call), the
+    // string of the stage entry; the records, counters and results of pdt_tip_check_records
+    DevBuf tip_sync_work, tip_sync_bits, tip_recs;
     // feed-forward bits (pdt_ff.h): the launch's table, periods, mixed streams and metrics on the device (first context of a call), the
     // stream of the stage entry, and this context's own results -- count, record, time source, soft values, characters -- of ff_cap bits
     DevBuf ff_work, ff_in, ff_out;

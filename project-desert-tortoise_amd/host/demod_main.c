@@ -79,6 +79,10 @@
  * the capture's start as -A has them.  With a plain I,Q file -- one recording of one burst, no -x, no -f, no -l -- the first two seconds
  * of the file go through pdt_stage_ff_bits and the message kernels; a message's time is its sample index / Fs.  The packets file is what
  * it was: the chain runs as always.  On any other route, without -A, and for demodPOES: a message, exit status 1.
+ * -W <file> (an addition, demodPOES): the minor frames a flywheel synchroniser finds in the bits of the capture (pdt_tip_sync, DESIGN
+ * 4.18), in the minor-frame text format, beside the unchanged minorFrames file.  -w E,W,G sets its three constants (max_errors, window,
+ * fly; default 2,2,3); with -q a second validation line, for these frames, follows the reference's.  One channel of a capture taken
+ * in one piece: demodARGOS, a pipe and several -t refuse both switches, and a file demodulated in pieces ends with a message that says so.
  */
 #include <ctype.h>
 #include <math.h>
@@ -95,14 +99,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:b" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:bW:w:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:b"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:bW:w:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -368,6 +372,38 @@ static int write_messages_ff(pdt_ctx *ctx, const int16_t *iq16, uint64_t n, uint
     free(index);
     free(msgs);
     return bad;
+}
+
+/* -W: the minor frames the flywheel synchroniser finds in the bits of ctx's last capture, in the minor-frame text format (pdt_tip_sync at
+ * its defaults or with -w's constants).  Returns 0 when the file is written; the records stay in *frames for -q. */
+static int write_flywheel(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const char *name, pdt_frame **frames, int *count)
+{
+    const int cap = (int)(pdt_stage_len(ctx, PDT_ST_BITS) / 829 + 1);     /* (emitted frames lie at least 829 bits apart) */
+    pdt_frame *fr = (pdt_frame *)malloc((size_t)cap * sizeof *fr);
+    int n = 0;
+    const int rc = fr ? pdt_tip_sync(ctx, cfg, fr, NULL, cap, &n) : PDT_ERR_NOMEM;
+    if (rc == PDT_ERR_STATE) printf("-W needs a capture taken in one piece: this one was demodulated in pieces and left no whole bit stream\n");
+    else if (rc == PDT_ERR_ARG) printf("-w E,W,G: E from 0 to 3, W from 1 to 8, G from 2 to 2 W\n");
+    else if (rc != PDT_OK) printf("Flywheel synchroniser failed: %s\n", pdt_strerror(rc));
+    FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !m) printf("Error opening %s\n", name);
+    if (!m) {
+        free(fr);
+        return 1;
+    }
+    if (n > cap) n = cap;
+    fflush(m);
+    const int wrc = pdt_write_records(fr, (uint64_t)n, fileno(m), NULL);
+    fclose(m);
+    if (wrc != PDT_OK) {
+        printf("Error writing %s\n", name);
+        free(fr);
+        return 1;
+    }
+    printf("Flywheel frames: %d -> %s\n", n, name);
+    *frames = fr;
+    *count = n;
+    return 0;
 }
 
 /* -A: the messages in the bits of ctx's last capture, one line each (pdt_argos_messages at its defaults or by -R's rule).
@@ -779,6 +815,9 @@ int main(int argc, char **argv)
     double offsetsHz[16];
     const char *outOverride = NULL, *measureName = NULL;                            /* -M: the carrier measurement's file */
     const char *messageName = NULL;                                                 /* -A: the ARGOS messages' file */
+    const char *flywheelName = NULL;                                                /* -W: the flywheel synchroniser's frames' file */
+    pdt_tip_sync_cfg flywheelCfg;                                                   /* -w E,W,G: its constants */
+    int flywheelCfgGiven = 0;
     char outFileName[1100];
 
     printf(BANNER);
@@ -896,6 +935,24 @@ int main(int argc, char **argv)
             }
             break;
 #endif
+        case 'W':                                       /* the flywheel synchroniser's minor frames, to this file */
+            flywheelName = optarg;
+            break;
+        case 'w': {                                     /* max_errors, window, fly of the flywheel's rule */
+            int e = 0, w = 0, g = 0;
+            char tail = 0;
+            if (sscanf(optarg, "%d,%d,%d%c", &e, &w, &g, &tail) != 3 || e < 0 || w < 1 || g < 2) {
+                printf("-w E,W,G: E from 0 to 3, W from 1 to 8, G from 2 to 2 W\n");
+                return 1;
+            }
+            memset(&flywheelCfg, 0, sizeof flywheelCfg);
+            flywheelCfg.max_errors = e;
+            flywheelCfg.window = w;
+            flywheelCfg.fly = g;
+            flywheelCfg.zero_mask = e == 0 ? PDT_TIP_SYNC_ZERO_MAX_ERRORS : 0;
+            flywheelCfgGiven = 1;
+            break;
+        }
         case 'b':                                       /* -A's messages out of feed-forward bits */
             feedForward = 1;
             break;
@@ -969,6 +1026,14 @@ int main(int argc, char **argv)
     }
     if (messageName && (MODE != PDT_MODE_ARGOS || from_stdin)) {
         printf("-A needs demodARGOS and a capture taken in one piece: not a pipe\n");
+        return 1;
+    }
+    if ((flywheelName || flywheelCfgGiven) && (MODE != PDT_MODE_POES || from_stdin || nOffsets > 1 || autoCarriers)) {
+        printf("-W and -w need demodPOES, one channel and a capture taken in one piece: not a pipe, not several -t\n");
+        return 1;
+    }
+    if (flywheelCfgGiven && !flywheelName) {
+        printf("-w sets the constants of -W <file>\n");
         return 1;
     }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
@@ -1211,6 +1276,13 @@ int main(int argc, char **argv)
         exit(1);
     }
     free(ffIq);
+    pdt_frame *flyFrames = NULL;
+    int flyCount = 0;
+    if (flywheelName && write_flywheel(ctx, flywheelCfgGiven ? &flywheelCfg : NULL, flywheelName, &flyFrames, &flyCount)) {
+        fclose(out);
+        remove(outFileName);
+        exit(1);
+    }
     pdt_stats st;
     pdt_get_stats(ctx, &st);
     print_norm_and_lock(&prog, &st);                                 /* (what the progress function has not printed) */
@@ -1249,10 +1321,14 @@ int main(int argc, char **argv)
             printf("Spacecraft: %d=>%s\n", q.spacecraft, name);
             if (q.day >= 0) printf("Julean Day: %d \n", q.day);
         }
+        if (flywheelName && pdt_tip_check_records(ctx, flyFrames, (uint64_t)flyCount, &q, NULL) == PDT_OK)
+            printf("\nFlywheel: %llu out of %llu Error Free Frames, %llu Good Chunks and %llu Bad Chunks\n", (unsigned long long)q.good_frames,
+                   (unsigned long long)q.frames_checked, (unsigned long long)q.good_chunks, (unsigned long long)q.bad_chunks);
     }
 #else
     (void)quality;
 #endif
+    free(flyFrames);
     time_t t2 = time(NULL);
     struct tm tm2 = *localtime(&t2);
     printf("\nThat took %d seconds!\n", (tm2.tm_min * 60 + tm2.tm_sec) - (tm.tm_min * 60 + tm.tm_sec));

@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 18): a second, opt-in rule for the ARGOS messages' heads -- pdt_argos_cfg.rule (the first of the two
+/* 4, additions without a bump (round 22): POES bits without a loop -- pdt_ffp_cfg, pdt_ffp_sync, pdt_ffp_block, pdt_ffp_bits, pdt_ffp_read,
+ * pdt_ffp_blocks, pdt_ffp_frames, pdt_stage_ffp_bits, pdt_stage_ffp_frames, pdt_host_ffp_bits, pdt_host_ffp_mix: a second, opt-in source
+ * of POES bits and, through the flywheel, of minor frames, beside everything else.
+ * 4, additions without a bump (round 18): a second, opt-in rule for the ARGOS messages' heads -- pdt_argos_cfg.rule (the first of the two
  * reserved words: a zeroed cfg is the rule there was), PDT_ARGOS_RULE_FIRST, PDT_ARGOS_RULE_BEST, PDT_ARGOS_MSG_RUN_LEN,
  * PDT_ARGOS_MSG_SLIP; no new symbol.
  * 4, additions without a bump (round 17): the ARGOS messages in the bits, either polarity, 1 .. 8 blocks, with the platform ID --
@@ -844,6 +847,118 @@ int  pdt_stage_ff_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64
 int  pdt_host_ff_bits(uint32_t rate, const float *iq, uint64_t n, const pdt_ff_cfg *cfg, pdt_ff_sync *sync, uint8_t *bits, float *soft,
                       int64_t *index, uint64_t cap, uint64_t *count);
 int  pdt_host_ff_mix(uint32_t rate, double residual_hz, const float *iq, uint64_t n, float *out);
+
+/* POES bits without a loop: feed-forward carrier, clock and bit decisions on a whole stream (POES contexts).  The bits above
+ * come out of the reference's chain -- a PLL that must pull in, an AGC, a Gardner loop, a Manchester decoder -- whose acquisition is a
+ * serial walk, and weak passes lose frames before the flywheel (pdt_tip_sync) ever sees their bits.  A TIP signal needs no loop: it
+ * carries a residual carrier all the time, the modulation is +-1.06 rad Manchester at 8320 bit/s, so the full-bit sum h0 + h1 of any
+ * bit is a piece of bare carrier, the sum of these pieces over neighbouring bits is a phase reference, Im((h0 - h1) conj ref) is the
+ * bit's soft value, and the bit clock is found block by block by exhaustive search.  These entries are a second, opt-in source of bits --
+ * and, through the flywheel's unchanged kernels, of minor frames -- BESIDE everything else; the rule is fixed in csrc/pdt_ffp.h and
+ * pdt_host_ffp_bits restates it on the host:
+ *   input     a float32 I,Q stream y of n samples at Fs, n < 2^36; the half-bit lasts P = Fs / 16640 samples, 3 <= P <= 64: 49920 <= Fs <=
+ *             1064960.  cfg: B bits per block (208; 64 .. 832), T clock hypotheses (32; 8 .. 64), W bits of reference either side (16;
+ *             0 .. 64), J blocks of smoothing either side (4; 0 .. 16)
+ *   time grid every point of the time axis is an integer in Q16, 1 / 65536 sample, int64.  The nominal start of half-bit k is
+ *             t_k = (k Fs 65536) / 16640, rounded down (= (k Fs 256) / 65); the offset of clock phase f (any integer, in steps of 1 / T bit)
+ *             is o(f) = (f 2 Fs 65536) / (16640 T), rounded down (towards minus infinity for a negative f).  Under f, bit m >= 0 covers
+ *             [t_2m + o, t_2m+2 + o), its half-bits meet at t_2m+1 + o.  A bit EXISTS under f when t_2m + o >= 0 and t_2m+2 + o <= n 65536
+ *   carrier   measured (the default): pdt_tones' arithmetic (k_tones, tone_derive, unchanged) over the segments of nfft samples at stride
+ *             nfft from sample 0, nfft and the search set that call's defaults; residual_j = the record's residual_hz, derived on the
+ *             host in double (the call's one round trip).  step_j = ddc_step(Fs, residual_j); a segment with valid = 0 takes the step of
+ *             the nearest earlier valid one, or 0 when there is none; the tail behind the last whole segment takes the last segment's
+ *             step; a stream without a whole segment, or a rate without an allowed nfft, has step 0 throughout.  Given
+ *             (PDT_FFP_RESIDUAL_GIVEN): one step = ddc_step(Fs, residual_hz) for the whole stream.  The mixer's phase is continuous:
+ *             the start phase of segment j is the uint32 wrap-around sum of step_i nfft over the earlier segments, sample i of segment
+ *             j (the tail counts to the last segment) has phase(i) = start_j + (i - j nfft) step_j mod 2^32
+ *   v[i]      = ddc_mix(y[i], phase(i)) with the down-converter's table; v = 0 outside [0, n)
+ *   sums      the sum over a Q16 interval [a, b), a < b, is the fma chain s = fmaf(v[i], w_i, s) from +0 in ascending i, I and Q each,
+ *             over the samples i = a >> 16 .. (b - 1) >> 16, w_i = the part of [i, i + 1) inside [a, b) as a float, frac / 65536
+ *             (exact; a sample wholly inside has w = 1)
+ *   bit       h0, h1 = the sums of its two half-bits; c = h0 + h1 and e = h0 - h1, component by component
+ *   ref_m     under f: the float addition chain from +0 of c over the bits m - W .. m + W that exist under f, in ascending order
+ *   d_m       = fmaf(e.im, ref.re, -(e.re ref.im)), the product rounded first: Im(e conj ref)
+ *   q(d)      pdt_ff_bits': 0 when d is not finite, 2^52 when |d| >= 2^20, else (uint64)(|d| 2^32), truncated
+ *   blocks    L = (2 B Fs + 8320) / 16640 samples, B nominal bits rounded to the nearest sample; block b covers the samples [b L, (b + 1) L),
+ *             nb = ceil(n / L) of them.  M(b, tau), tau = 0 .. T - 1: the uint64 sum of q(d_m) over the bits that exist under tau and
+ *             start inside block b
+ *   smoothing Ms(b, tau) = the sum of M(b + j, tau) over |j| <= J, blocks outside the stream left out; tau_b = the arg-max of Ms(b, .),
+ *             ties to the smaller tau
+ *   unwrap    phi_0 = tau_0; phi_b = phi_{b-1} + delta_b, delta_b = (tau_b - tau_{b-1}) mod T folded into (-T / 2, T / 2] (2 delta > T:
+ *             delta - T).  A drifting recorder clock lets phi run on; the bit index m stays the index of one physical bit
+ *   ownership m_lo(b) = the smallest m >= 0 whose start under phi_b is >= b L 65536; m_end(b) = the largest m that exists under phi_b (-1
+ *             when none).  Block b decides the bits m_lo(b) <= m < m_hi(b), all of them under phi_b: m_hi(b) = min(m_lo(b + 1), m_end(b)
+ *             + 1) (the last block: m_end(b) + 1); its count is max(0, m_hi - m_lo).  Output positions are the exclusive scan of the counts
+ *   decision  bit '1' when d_m > 0, else '0'; the soft value is d_m (every NaN as the quiet NaN 0x7fc00000); the time source is the
+ *             sample index at which the bit ends, (t_2m+2 + o + 65535) >> 16
+ * The carrier reference is absolute, so there is no pairing or polarity guess; a mirrored spectrum complements the bits and the
+ * flywheel reads either polarity.  A jump of phi in a stretch of noise costs a bit slip there; slips are the flywheel's business.
+ * pdt_ffp_cfg: NULL or a zero field = the default; ref_bits 0 with PDT_FFP_ZERO_REF_BITS and smooth_blocks 0 with PDT_FFP_ZERO_SMOOTH in
+ * zero_mask are real zeros.  PDT_FFP_RESIDUAL_GIVEN in flags: residual_hz is the caller's (finite, |residual_hz| < Fs / 2).
+ * pdt_ffp_sync: residual_hz and step = the caller's, or those of the first valid segment (0 when there is none); nfft = the segments' length
+ * (0 when the residual was given), segs and segs_valid = the tone segments measured and how many were valid; nblocks, nbits, block_len = L,
+ * and B, T, W, J as used.  pdt_ffp_block: block b's tau_b, phi_b, first_bit = m_lo(b), count and metric = Ms(b, tau_b).
+ *   pdt_ffp_bits         the context's channel stream (PDT_ST_CHANNEL of its last whole-capture call): *sync = the record; the bits stay
+ *                        on the device, in buffers of the context's own (not PDT_ST_BITS), for pdt_ffp_read.  PDT_ERR_STATE as for
+ *                        pdt_tones; PDT_ERR_ARG for an ARGOS context, a sample rate or a cfg that is not allowed.  Like pdt_tones it leaves
+ *                        frames, text, stages, statistics, survey, burst, tone and flywheel results exactly as they were (a profiled
+ *                        context's pdt_kernel_times gain the entries k_ffp_mix, k_ffp_search, k_ffp_track and k_ffp_bits).  The tone
+ *                        records are the call's one round trip to the host: the frequencies are derived there, in double
+ *   pdt_ffp_read         the bits of the context's last pdt_ffp_* or pdt_stage_ffp_* call: *count = their number, the first
+ *                        min(cap, *count) characters, soft values and sample indices in bits, soft and index (each may be NULL), the
+ *                        record in *sync (may be NULL).  PDT_ERR_STATE before such a call
+ *   pdt_ffp_blocks       the per-block table of that call: *count = the number of blocks, the first min(cap, *count) records in out
+ *   pdt_ffp_frames       pdt_ffp_bits, then the minor frames of pdt_tip_sync_cfg's rule in those bits (pdt_tip_sync's kernels, unchanged,
+ *                        on the device's own bit count): records as pdt_tip_sync gives them with time_src = the sample index at which
+ *                        bit bit_index ends and time = time_src / Fs -- seconds of the stream, NOT the reference's running sum of
+ *                        symbol periods.  sync and info may be NULL.  max_errors 0, window 1 and fly 2 is as strict as the rule gets
+ *   pdt_stage_ffp_bits   stage-level entry: the kernels on a caller's float32 I,Q stream of n samples at `rate` (the way in for a plain
+ *                        recording); results through *sync, pdt_ffp_read and pdt_ffp_blocks.  The whole stream is resident on the
+ *                        device (PDT_ERR_NOMEM otherwise).  Nothing of the context's results changes
+ *   pdt_stage_ffp_frames the same, then the frames as pdt_ffp_frames gives them
+ *   pdt_host_ffp_bits    host only, no GPU: the same record, bits, soft values, sample indices and per-block table for the same stream,
+ *                        written from the rule's text (blocks may be NULL)
+ *   pdt_host_ffp_mix     host only: the stream v the rule sums, out = n pairs                                                          */
+#define PDT_FFP_ZERO_REF_BITS  1u
+#define PDT_FFP_ZERO_SMOOTH    2u
+#define PDT_FFP_RESIDUAL_GIVEN 1u
+typedef struct pdt_ffp_cfg {
+    int32_t  block_bits;      /* B */
+    int32_t  clock_steps;     /* T */
+    int32_t  ref_bits;        /* W */
+    int32_t  smooth_blocks;   /* J */
+    uint32_t zero_mask;
+    uint32_t flags;
+    double   residual_hz;
+} pdt_ffp_cfg;
+typedef struct pdt_ffp_sync {
+    double   residual_hz;
+    uint32_t step;
+    int32_t  nfft;
+    uint64_t segs, segs_valid;
+    uint64_t nblocks, nbits;
+    int64_t  block_len;
+    int32_t  block_bits, clock_steps, ref_bits, smooth_blocks;
+} pdt_ffp_sync;
+typedef struct pdt_ffp_block {
+    int64_t  phi;
+    int64_t  first_bit;
+    uint64_t count;
+    uint64_t metric;
+    int32_t  tau;
+    int32_t  reserved_;
+} pdt_ffp_block;
+int  pdt_ffp_bits(pdt_ctx *ctx, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync);
+int  pdt_ffp_read(pdt_ctx *ctx, pdt_ffp_sync *sync, uint8_t *bits, float *soft, int64_t *index, uint64_t cap, uint64_t *count);
+int  pdt_ffp_blocks(pdt_ctx *ctx, pdt_ffp_block *out, uint64_t cap, uint64_t *count);
+int  pdt_ffp_frames(pdt_ctx *ctx, const pdt_ffp_cfg *cfg, const pdt_tip_sync_cfg *tip_cfg, pdt_ffp_sync *sync, pdt_frame *out,
+                    pdt_tip_sync_info *info, int cap, int *count);
+int  pdt_stage_ffp_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync);
+int  pdt_stage_ffp_frames(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ffp_cfg *cfg, const pdt_tip_sync_cfg *tip_cfg,
+                          pdt_ffp_sync *sync, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count);
+int  pdt_host_ffp_bits(uint32_t rate, const float *iq, uint64_t n, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync, uint8_t *bits, float *soft,
+                       int64_t *index, uint64_t cap, uint64_t *count, pdt_ffp_block *blocks, uint64_t block_cap);
+int  pdt_host_ffp_mix(uint32_t rate, const float *iq, uint64_t n, const pdt_ffp_cfg *cfg, float *out);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

@@ -517,6 +517,73 @@ def ff_messages_batch(ds, min_run=None, cap: int = 64, rule=None, rate_steps=Non
     return (got, syncs[:len(ds)]) if with_sync else got
 
 
+class FfpCfg(C.Structure):
+    """pdt_ffp_cfg: a zero means the default; ref_bits 0 with FFP_ZERO_REF_BITS and smooth_blocks 0 with FFP_ZERO_SMOOTH in zero_mask are
+    real zeros; FFP_RESIDUAL_GIVEN in flags: residual_hz is the caller's, otherwise the carrier is measured segment by segment"""
+    _fields_ = [("block_bits", C.c_int32), ("clock_steps", C.c_int32), ("ref_bits", C.c_int32), ("smooth_blocks", C.c_int32),
+                ("zero_mask", C.c_uint32), ("flags", C.c_uint32), ("residual_hz", C.c_double)]
+
+
+FFP_ZERO_REF_BITS, FFP_ZERO_SMOOTH, FFP_RESIDUAL_GIVEN = 1, 2, 1
+# pdt_ffp_sync and pdt_ffp_block as numpy records
+FFP_SYNC_DTYPE = np.dtype([("residual_hz", "<f8"), ("step", "<u4"), ("nfft", "<i4"), ("segs", "<u8"), ("segs_valid", "<u8"), ("nblocks", "<u8"),
+                           ("nbits", "<u8"), ("block_len", "<i8"), ("block_bits", "<i4"), ("clock_steps", "<i4"), ("ref_bits", "<i4"),
+                           ("smooth_blocks", "<i4")])
+FFP_BLOCK_DTYPE = np.dtype([("phi", "<i8"), ("first_bit", "<i8"), ("count", "<u8"), ("metric", "<u8"), ("tau", "<i4"), ("reserved_", "<i4")])
+assert FFP_SYNC_DTYPE.itemsize == 72 and FFP_BLOCK_DTYPE.itemsize == 40 and C.sizeof(FfpCfg) == 32
+# FFP_SYNC_DTYPE record, '0'/'1' uint8[n], float32[n], int64[n], FFP_BLOCK_DTYPE[nblocks]
+FfpBits = collections.namedtuple("FfpBits", "sync bits soft index blocks")
+
+
+def _ffp_cfg(block_bits=None, clock_steps=None, ref_bits=None, smooth_blocks=None, residual_hz=None):
+    """B (None = 208), T (32), W (16), J (4) and residual_hz (None = measure the carrier) -> pdt_ffp_cfg or None"""
+    if block_bits is None and clock_steps is None and ref_bits is None and smooth_blocks is None and residual_hz is None:
+        return None
+    c = FfpCfg(block_bits=int(block_bits or 0), clock_steps=int(clock_steps or 0))
+    if ref_bits is not None:
+        c.ref_bits = int(ref_bits)
+        c.zero_mask |= FFP_ZERO_REF_BITS if int(ref_bits) == 0 else 0
+    if smooth_blocks is not None:
+        c.smooth_blocks = int(smooth_blocks)
+        c.zero_mask |= FFP_ZERO_SMOOTH if int(smooth_blocks) == 0 else 0
+    if residual_hz is not None:
+        c.residual_hz, c.flags = float(residual_hz), FFP_RESIDUAL_GIVEN
+    return c
+
+
+def ffp_max_bits(rate: int, n: int, block_bits=None) -> int:
+    """room for the bits of a stream of n samples at `rate`: every block of B bits decides at most B + 3"""
+    B = int(block_bits or 208)
+    L = (2 * B * rate + 8320) // 16640
+    return ((n + L - 1) // L) * (B + 3) + 1 if rate > 0 else 1
+
+
+def host_ffp_mix(rate: int, iq: np.ndarray, **cfg) -> np.ndarray:
+    """pdt_host_ffp_mix: the stream the feed-forward POES rule sums -- iq with the carrier taken out segment by segment, the phase
+    continuous -- on the host (no GPU): float32[n, 2]"""
+    a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+    c = _ffp_cfg(**cfg)
+    out = np.zeros(max(a.size, 2), dtype="<f4")
+    _check(lib().pdt_host_ffp_mix(rate, a.ctypes.data, a.size // 2, C.byref(c) if c else None, out.ctypes.data), "pdt_host_ffp_mix")
+    return out[:a.size // 2 * 2].reshape(-1, 2)
+
+
+def host_ffp_bits(rate: int, iq: np.ndarray, **cfg) -> FfpBits:
+    """pdt_host_ffp_bits: the feed-forward bits of a float32 I,Q POES stream at `rate` restated on the host (no GPU), bit for bit what
+    the kernels compute: FfpBits(sync, bits, soft, index, blocks).  cfg: block_bits, clock_steps, ref_bits, smooth_blocks, residual_hz
+    (None = the carrier is measured)."""
+    a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+    c, n = _ffp_cfg(**cfg), a.size // 2
+    cap = ffp_max_bits(rate, n, cfg.get("block_bits"))
+    sync, count = np.zeros(1, dtype=FFP_SYNC_DTYPE), C.c_uint64(0)
+    bits, soft, index = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype="<f4"), np.zeros(cap, dtype="<i8")
+    blocks = np.zeros(cap, dtype=FFP_BLOCK_DTYPE)
+    _check(lib().pdt_host_ffp_bits(rate, a.ctypes.data, n, C.byref(c) if c else None, sync.ctypes.data, bits.ctypes.data, soft.ctypes.data,
+                                   index.ctypes.data, cap, C.byref(count), blocks.ctypes.data, cap), "pdt_host_ffp_bits")
+    k = min(count.value, cap)
+    return FfpBits(sync[0], bits[:k], soft[:k], index[:k], blocks[:int(sync[0]["nblocks"])])
+
+
 def format_argos_messages(msgs: np.ndarray) -> bytes:
     """pdt_format_argos_messages: one line per complete message (host-only C, no GPU needed)"""
     a = np.ascontiguousarray(msgs, dtype=ARGOS_MSG_DTYPE)
@@ -552,6 +619,8 @@ ABI_SYMBOLS = [
     "pdt_format_argos_messages", "pdt_write_argos_messages",
     "pdt_ff_bits", "pdt_ff_bits_batch", "pdt_ff_read", "pdt_ff_messages", "pdt_ff_messages_batch", "pdt_stage_ff_bits", "pdt_host_ff_bits",
     "pdt_host_ff_mix",
+    "pdt_ffp_bits", "pdt_ffp_read", "pdt_ffp_blocks", "pdt_ffp_frames", "pdt_stage_ffp_bits", "pdt_stage_ffp_frames", "pdt_host_ffp_bits",
+    "pdt_host_ffp_mix",
     "pdt_tip_sync", "pdt_tip_sync_batch", "pdt_stage_tip_sync", "pdt_host_tip_sync", "pdt_tip_sync_tile", "pdt_tip_check_records",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
@@ -726,6 +795,16 @@ def lib():
     L.pdt_host_ff_bits.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(FfCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                    C.POINTER(C.c_uint64)]
     L.pdt_host_ff_mix.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.pdt_ffp_bits.argtypes = [C.c_void_p, C.POINTER(FfpCfg), C.c_void_p]
+    L.pdt_ffp_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.pdt_ffp_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.pdt_ffp_frames.argtypes = [C.c_void_p, C.POINTER(FfpCfg), C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_stage_ffp_bits.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(FfpCfg), C.c_void_p]
+    L.pdt_stage_ffp_frames.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(FfpCfg), C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.pdt_host_ffp_bits.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(FfpCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                    C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64]
+    L.pdt_host_ffp_mix.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(FfpCfg), C.c_void_p]
     L.pdt_device_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.pdt_device_math_layout.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if L.pdt_abi_version() != 4:
@@ -1153,6 +1232,58 @@ class Demodulator:
                                        C.byref(count)), "pdt_ff_messages")
         got = out[:min(count.value, cap)]
         return (got, sync[0]) if with_sync else got
+
+    def ffp_bits(self, **cfg):
+        """pdt_ffp_bits: feed-forward carrier, clock and bit decisions on this POES context's channel stream: the FFP_SYNC_DTYPE record;
+        the bits stay on the device for ffp_read().  cfg: block_bits, clock_steps, ref_bits, smooth_blocks, residual_hz (None = measured)."""
+        c = _ffp_cfg(**cfg)
+        sync = np.zeros(1, dtype=FFP_SYNC_DTYPE)
+        _check(self._L.pdt_ffp_bits(self._h, C.byref(c) if c else None, sync.ctypes.data), "pdt_ffp_bits")
+        return sync[0]
+
+    def ffp_read(self) -> FfpBits:
+        """pdt_ffp_read + pdt_ffp_blocks: the bits and the per-block table of this context's last ffp_* / stage_ffp_* call:
+        FfpBits(sync, bits, soft, index, blocks)"""
+        sync, count = np.zeros(1, dtype=FFP_SYNC_DTYPE), C.c_uint64(0)
+        _check(self._L.pdt_ffp_read(self._h, sync.ctypes.data, None, None, None, 0, C.byref(count)), "pdt_ffp_read")
+        cap = max(count.value, 1)
+        bits, soft, index = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype="<f4"), np.zeros(cap, dtype="<i8")
+        _check(self._L.pdt_ffp_read(self._h, sync.ctypes.data, bits.ctypes.data, soft.ctypes.data, index.ctypes.data, cap, C.byref(count)), "pdt_ffp_read")
+        k = min(count.value, cap)
+        nb = C.c_uint64(0)
+        _check(self._L.pdt_ffp_blocks(self._h, None, 0, C.byref(nb)), "pdt_ffp_blocks")
+        blocks = np.zeros(max(nb.value, 1), dtype=FFP_BLOCK_DTYPE)
+        _check(self._L.pdt_ffp_blocks(self._h, blocks.ctypes.data, nb.value, C.byref(nb)), "pdt_ffp_blocks")
+        return FfpBits(sync[0], bits[:k], soft[:k], index[:k], blocks[:nb.value])
+
+    def stage_ffp_bits(self, rate: int, iq: np.ndarray, **cfg) -> FfpBits:
+        """pdt_stage_ffp_bits + ffp_read(): the feed-forward POES kernels on a float32 I,Q stream at `rate` (a plain recording).  Nothing
+        of this context's results changes."""
+        a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+        c = _ffp_cfg(**cfg)
+        sync = np.zeros(1, dtype=FFP_SYNC_DTYPE)
+        _check(self._L.pdt_stage_ffp_bits(self._h, rate, a.ctypes.data, a.size // 2, C.byref(c) if c else None, sync.ctypes.data), "pdt_stage_ffp_bits")
+        got = self.ffp_read()
+        return FfpBits(sync[0], got.bits, got.soft, got.index, got.blocks)
+
+    def ffp_frames(self, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False, with_count: bool = False, **cfg):
+        """pdt_ffp_frames: ffp_bits(), then the minor frames the flywheel finds in those bits, in one call: FRAME_DTYPE[found] with
+        time_src = the sample index at which the bit ends and time = that / Fs, seconds of the stream"""
+        c, t = _ffp_cfg(**cfg), _tip_sync_cfg(max_errors, window, fly)
+        out, info, count = np.zeros(max(cap, 1), dtype=FRAME_DTYPE), np.zeros(max(cap, 1), dtype=TIP_SYNC_INFO_DTYPE), C.c_int(0)
+        _check(self._L.pdt_ffp_frames(self._h, C.byref(c) if c else None, C.byref(t) if t else None, None, out.ctypes.data, info.ctypes.data, cap,
+                                      C.byref(count)), "pdt_ffp_frames")
+        return _tip_sync_result(out, info, count.value, cap, with_info, with_count)
+
+    def stage_ffp_frames(self, rate: int, iq: np.ndarray, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False,
+                         with_count: bool = False, **cfg):
+        """pdt_stage_ffp_frames: the same on a float32 I,Q stream at `rate`; the bits through ffp_read()"""
+        a = np.ascontiguousarray(iq, dtype="<f4").reshape(-1)
+        c, t = _ffp_cfg(**cfg), _tip_sync_cfg(max_errors, window, fly)
+        out, info, count = np.zeros(max(cap, 1), dtype=FRAME_DTYPE), np.zeros(max(cap, 1), dtype=TIP_SYNC_INFO_DTYPE), C.c_int(0)
+        _check(self._L.pdt_stage_ffp_frames(self._h, rate, a.ctypes.data, a.size // 2, C.byref(c) if c else None, C.byref(t) if t else None, None,
+                                            out.ctypes.data, info.ctypes.data, cap, C.byref(count)), "pdt_stage_ffp_frames")
+        return _tip_sync_result(out, info, count.value, cap, with_info, with_count)
 
     def stage_argos_messages(self, bits, min_run=None, cap: int = 4096, with_count: bool = False, rule=None):
         """pdt_stage_argos_messages: the message kernels on a string of '0'/'1' characters; the time stamp of bit k is k"""

@@ -10,6 +10,7 @@
 #include "pdt_argos_msg.h"
 #include "pdt_tip_sync.h"
 #include "pdt_ff.h"
+#include "pdt_ffp.h"
 
 #include <sys/stat.h>
 
@@ -47,6 +48,14 @@ int tip_sync_rule(const pdt_tip_sync_cfg *cfg, pdt::TipSyncRule *R);
 hipError_t ff_launch(hipStream_t st, const void *table_dev, int nwin, long long mix_tiles, long long groups, const long long *periods_dev, int R,
                      int H, long long pmax, const float *tab_dev, void *metric_dev, size_t metric_bytes, void *syncs_dev, hipEvent_t *ev);
 int ff_plan(const pdt_ff_cfg *cfg, uint32_t rate, int *H, int *R, double *ppm, int *given, double *residual);
+// pdt_ffp.hip
+int ffp_plan(const pdt_ffp_cfg *cfg, uint32_t rate, uint64_t n, pdt::FfpRule *r, int *given, double *residual);
+int ffp_run_device(hipStream_t st, const float *y, const pdt::FfpRule &r, const pdt::FfpSync &head, const std::vector<uint32_t> &steps,
+                   const std::vector<uint32_t> &starts, const float *tab_dev, void *work, const pdt::FfpOutPtrs &out, uint64_t bit_cap, hipEvent_t *ev);
+uint64_t ffp_bit_cap(const pdt::FfpRule &r);
+size_t ffp_work_bytes(const pdt::FfpRule &r, size_t nent);
+void ffp_steps(const pdt_tone *tones, uint64_t nseg, int nfft, const pdt::FfpRule &r, int given, double residual, std::vector<uint32_t> &steps,
+               std::vector<uint32_t> &starts, pdt::FfpSync *head);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -592,7 +601,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
-                       &ctx->argos_work, &ctx->argos_bits, &ctx->ff_work, &ctx->ff_in, &ctx->ff_out,
+                       &ctx->argos_work, &ctx->argos_bits, &ctx->ff_work, &ctx->ff_in, &ctx->ff_out, &ctx->ffp_work, &ctx->ffp_in, &ctx->ffp_out,
                        &ctx->tip_sync_work, &ctx->tip_sync_bits, &ctx->tip_recs };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -2046,6 +2055,248 @@ int pdt_ff_messages(pdt_ctx *ctx, const pdt_ff_cfg *cfg, const pdt_argos_cfg *ru
 {
     if (!ctx || !count) return PDT_ERR_ARG;
     return ff_messages_each(&ctx, 1, cfg, rule, sync, out, cap, count);
+}
+
+// ---------------------------------------------------------------- feed-forward POES bits (pdt_ffp.h)
+// a context's result buffer: the count, the record, then the per-block table, the positions, and the time source, soft values, bit ->
+// symbol map and characters of `cap` bits
+struct FfpOut {
+    size_t o_blocks, o_pos, o_idx, o_soft, o_sym, o_bits, total;
+    FfpOut(uint64_t nb, uint64_t cap)
+    {
+        const size_t c = ((size_t)cap + 15) & ~(size_t)15;
+        o_blocks = 128;
+        o_pos = o_blocks + (((size_t)nb * sizeof(FfpBlock) + 15) & ~(size_t)15);
+        o_idx = o_pos + ((((size_t)nb + 1) * 8 + 15) & ~(size_t)15);
+        o_soft = o_idx + 8 * c;
+        o_sym = o_soft + 4 * c;
+        o_bits = o_sym + 4 * c;
+        total = o_bits + c + 16;
+    }
+};
+
+// The carrier of the stream y (device, n samples): every segment of pdt_tones at its defaults and stride nfft, in one launch of k_tones
+// through the context's tables and buffers; the frequencies are derived here, on the host, in double.  tones: one record per segment.
+static int ffp_tones(pdt_ctx *c, const float *y, uint64_t n, uint32_t rate, double range_hz, std::vector<pdt_tone> &tones, int *nfft)
+{
+    tones.clear();
+    *nfft = tone_default_nfft((double)rate);
+    TonePlan plan;
+    if (!*nfft || n < (uint64_t)*nfft) return PDT_OK;
+    const uint64_t want = n / (uint64_t)*nfft;
+    if (want > 0x7fffffffull) return PDT_ERR_ARG;
+    if (tone_plan(nullptr, (double)rate, range_hz, n, (int)want, &plan) != PDT_OK || !plan.nseg) return PDT_OK;
+    std::vector<ToneSeg> table((size_t)plan.nseg);
+    for (uint64_t j = 0; j < plan.nseg; j++) table[(size_t)j] = ToneSeg{ y, (long long)(plan.first + j * plan.stride), (int32_t)j, plan.kmax };
+    int rc = survey_tables(c, plan.nfft);
+    if (!rc) rc = c->tone_table.ensure(table.size() * sizeof(ToneSeg));
+    if (!rc) rc = c->tone_out.ensure(table.size() * sizeof(ToneRaw));
+    if (rc) return rc;
+    std::vector<ToneRaw> raw(table.size());
+    HIP_TRY(hipMemcpy(c->tone_table.p, table.data(), table.size() * sizeof(ToneSeg), hipMemcpyHostToDevice));
+    HIP_TRY(tones_launch(c->stream, plan.nfft, c->tone_table.p, table.size(), plan.noise_lo, plan.noise_hi, (const float *)c->survey_win.p,
+                         (const float *)c->survey_tw.p, c->tone_out.p));
+    HIP_TRY(hipMemcpyAsync(raw.data(), c->tone_out.p, raw.size() * sizeof(ToneRaw), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->tone_sum_nfft != plan.nfft) {
+        tone_sums(plan.nfft, &c->tone_sw, &c->tone_sw2);
+        c->tone_sum_nfft = plan.nfft;
+    }
+    tones.resize(table.size());
+    tones_derive(raw.data(), plan, (double)rate, 0.0, c->tone_sw, c->tone_sw2, tones.data());
+    return PDT_OK;
+}
+
+// The stream y (device, n samples at `rate`) through the four kernels: the context supplies stream, rotation table, work buffer and the
+// result buffer the bits stay in.  One synchronize ends the call; the record comes back with it.
+static int ffp_run(pdt_ctx *c, const float *y, uint64_t n, uint32_t rate, double range_hz, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync)
+{
+    FfpRule r;
+    int given;
+    double residual;
+    int rc = ffp_plan(cfg, rate, n, &r, &given, &residual);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = real_table(c))) return rc;
+    std::vector<pdt_tone> tones;
+    int nfft = 0;
+    if (!given && (rc = ffp_tones(c, y, n, rate, range_hz, tones, &nfft))) return rc;
+    std::vector<uint32_t> steps, starts;
+    FfpSync head;
+    ffp_steps(tones.data(), tones.size(), nfft, r, given, residual, steps, starts, &head);
+    const uint64_t cap = ffp_bit_cap(r);
+    if (cap >= (1ull << 31)) return PDT_ERR_ARG;
+    const FfpOut o((uint64_t)r.nb, cap);
+    c->ffp_rate = 0;
+    if ((rc = c->ffp_out.ensure(o.total))) return rc;
+    if ((rc = c->ffp_work.ensure(ffp_work_bytes(r, steps.size())))) return rc;
+    c->ffp_cap = cap;
+    c->ffp_blocks = (uint64_t)r.nb;
+    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (c->cfg.profile) {
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ev[0], c->stream));
+    }
+    unsigned char *p = (unsigned char *)c->ffp_out.p;
+    const FfpOutPtrs ptrs{ (unsigned long long *)p, (FfpSync *)(p + 16), (FfpBlock *)(p + o.o_blocks), (unsigned long long *)(p + o.o_pos),
+                           (long long *)(p + o.o_idx), (float *)(p + o.o_soft), (unsigned *)(p + o.o_sym), p + o.o_bits };
+    if ((rc = ffp_run_device(c->stream, y, r, head, steps, starts, (const float *)c->an_tab.p, c->ffp_work.p, ptrs, cap,
+                             c->cfg.profile ? ev + 1 : nullptr)))
+        return rc;
+    if (c->cfg.profile) HIP_TRY(hipEventRecord(ev[4], c->stream));
+    FfpSync back;
+    HIP_TRY(hipMemcpyAsync(&back, (unsigned char *)c->ffp_out.p + 16, sizeof back, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->cfg.profile) {
+        const char *names[4] = { "k_ffp_mix", "k_ffp_search", "k_ffp_track", "k_ffp_bits" };
+        for (int k = 0; k < 4; k++) {
+            pdt_kernel_time kt;
+            memset(&kt, 0, sizeof kt);
+            snprintf(kt.name, sizeof kt.name, "%s", names[k]);
+            kt.launches = k == 2 ? 2 : 1;
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            kt.total_ms = ms;
+            c->ktimes.erase(std::remove_if(c->ktimes.begin(), c->ktimes.end(), [&](const pdt_kernel_time &x) { return !strcmp(x.name, names[k]); }),
+                            c->ktimes.end());
+            c->ktimes.push_back(kt);
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    c->ffp_rate = rate;
+    if (sync) memcpy(sync, &back, sizeof back);
+    return PDT_OK;
+}
+
+// the context of a call, checked as pdt_tones checks its own, and a POES one
+static int ffp_check(const pdt_ctx *c, const pdt_ffp_cfg *cfg)
+{
+    if (!c || c->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;
+    FfpRule r;
+    int given;
+    double res;
+    if (ffp_plan(cfg, c->cfg.sample_rate, 0, &r, &given, &res)) return PDT_ERR_ARG;
+    if (c->stream_open || !c->stage_len[PDT_ST_CHANNEL] || !c->channel.p) return PDT_ERR_STATE;
+    return PDT_OK;
+}
+
+int pdt_ffp_bits(pdt_ctx *ctx, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync)
+{
+    if (!ctx || !sync) return PDT_ERR_ARG;
+    const int rc = ffp_check(ctx, cfg);
+    if (rc) return rc;
+    try {
+        return ffp_run(ctx, (const float *)ctx->channel.p, ctx->stage_len[PDT_ST_CHANNEL], ctx->cfg.sample_rate, search_range_hz(ctx), cfg, sync);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+// the caller's stream in a buffer of the context's own: nothing its results live in is touched
+static int ffp_stage_in(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ffp_cfg *cfg)
+{
+    FfpRule r;
+    int given;
+    double res;
+    if (!ctx || (!iq_host && n) || ctx->cfg.mode != PDT_MODE_POES || ffp_plan(cfg, rate, n, &r, &given, &res)) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    int rc;
+    if ((rc = ctx->ffp_in.ensure((size_t)n * 8 + 16))) return rc;
+    if (n) HIP_TRY(hipMemcpy(ctx->ffp_in.p, iq_host, (size_t)n * 8, hipMemcpyHostToDevice));
+    return PDT_OK;
+}
+
+int pdt_stage_ffp_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync)
+{
+    if (!sync) return PDT_ERR_ARG;
+    const int rc = ffp_stage_in(ctx, rate, iq_host, n, cfg);
+    if (rc) return rc;
+    try {
+        return ffp_run(ctx, (const float *)ctx->ffp_in.p, n, rate, -1.0, cfg, sync);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+int pdt_ffp_read(pdt_ctx *ctx, pdt_ffp_sync *sync, uint8_t *bits, float *soft, int64_t *index, uint64_t cap, uint64_t *count)
+{
+    if (!ctx || !count) return PDT_ERR_ARG;
+    if (!ctx->ffp_rate || !ctx->ffp_out.p) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    unsigned char head[128];
+    HIP_TRY(hipMemcpy(head, ctx->ffp_out.p, sizeof head, hipMemcpyDeviceToHost));
+    unsigned long long nb;
+    memcpy(&nb, head, sizeof nb);
+    nb = std::min<unsigned long long>(nb, ctx->ffp_cap);
+    if (sync) memcpy(sync, head + 16, sizeof *sync);
+    const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
+    const unsigned char *p = (const unsigned char *)ctx->ffp_out.p;
+    const size_t k = (size_t)std::min<uint64_t>(cap, nb);
+    if (bits && k) HIP_TRY(hipMemcpy(bits, p + o.o_bits, k, hipMemcpyDeviceToHost));
+    if (soft && k) HIP_TRY(hipMemcpy(soft, p + o.o_soft, k * 4, hipMemcpyDeviceToHost));
+    if (index && k) HIP_TRY(hipMemcpy(index, p + o.o_idx, k * 8, hipMemcpyDeviceToHost));
+    *count = nb;
+    return PDT_OK;
+}
+
+int pdt_ffp_blocks(pdt_ctx *ctx, pdt_ffp_block *out, uint64_t cap, uint64_t *count)
+{
+    if (!ctx || !count || (!out && cap)) return PDT_ERR_ARG;
+    if (!ctx->ffp_rate || !ctx->ffp_out.p) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
+    const size_t k = (size_t)std::min<uint64_t>(cap, ctx->ffp_blocks);
+    if (k) HIP_TRY(hipMemcpy(out, (const unsigned char *)ctx->ffp_out.p + o.o_blocks, k * sizeof(pdt_ffp_block), hipMemcpyDeviceToHost));
+    *count = ctx->ffp_blocks;
+    return PDT_OK;
+}
+
+// the flywheel's kernels on the bits the last ffp_run left in the context's buffer, on the device's own count
+static int ffp_frames_of(pdt_ctx *ctx, TipSyncRule R, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count)
+{
+    try {
+        const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
+        const unsigned char *p = (const unsigned char *)ctx->ffp_out.p;
+        const std::vector<TipSyncJob> jobs(1, TipSyncJob{ p + o.o_bits, (const unsigned long long *)p, (const unsigned *)(p + o.o_sym),
+                                                          (const long long *)(p + o.o_idx), (long long)ctx->ffp_cap, cap });
+        std::vector<TipSyncRec> recs;
+        std::vector<TipSyncInfo> infos;
+        std::vector<size_t> at;
+        std::vector<unsigned> found;
+        const int rc = tip_sync_run(ctx, jobs, R, recs, infos, at, found);
+        if (rc) return rc;
+        const size_t have = std::min<size_t>(found[0], at[1]);
+        const double fs = (double)ctx->ffp_rate;
+        for (size_t k = 0; k < have; k++) {
+            TipSyncRec m = recs[k];
+            m.time = (double)m.time_src / fs;
+            memcpy(&out[k], &m, sizeof m);
+            if (info) memcpy(&info[k], &infos[k], sizeof(TipSyncInfo));
+        }
+        *count = (int)found[0];
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    return PDT_OK;
+}
+
+int pdt_ffp_frames(pdt_ctx *ctx, const pdt_ffp_cfg *cfg, const pdt_tip_sync_cfg *tip_cfg, pdt_ffp_sync *sync, pdt_frame *out, pdt_tip_sync_info *info,
+                   int cap, int *count)
+{
+    TipSyncRule R;
+    if (!ctx || !count || cap < 0 || (!out && cap) || tip_sync_rule(tip_cfg, &R)) return PDT_ERR_ARG;
+    pdt_ffp_sync s;
+    int rc = pdt_ffp_bits(ctx, cfg, &s);
+    if (rc) return rc;
+    if (sync) *sync = s;
+    return ffp_frames_of(ctx, R, out, info, cap, count);
+}
+
+int pdt_stage_ffp_frames(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ffp_cfg *cfg, const pdt_tip_sync_cfg *tip_cfg,
+                         pdt_ffp_sync *sync, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count)
+{
+    TipSyncRule R;
+    if (!ctx || !count || cap < 0 || (!out && cap) || tip_sync_rule(tip_cfg, &R)) return PDT_ERR_ARG;
+    pdt_ffp_sync s;
+    int rc = pdt_stage_ffp_bits(ctx, rate, iq_host, n, cfg, &s);
+    if (rc) return rc;
+    if (sync) *sync = s;
+    return ffp_frames_of(ctx, R, out, info, cap, count);
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

@@ -482,6 +482,11 @@ struct pdt_ctx {
     DevBuf ff_work, ff_in, ff_out;
     uint64_t ff_cap = 0;
     uint32_t ff_rate = 0;               // 0 = no feed-forward call yet
+    // feed-forward POES bits (pdt_ffp.h): the call's work buffer -- the mixer's table, the mixed stream, the metrics --, the stream of the
+    // stage entries, and this context's own results -- count, record, per-block table, positions, time source, soft values, characters
+    DevBuf ffp_work, ffp_in, ffp_out;
+    uint64_t ffp_cap = 0, ffp_blocks = 0;
+    uint32_t ffp_rate = 0;              // 0 = no such call yet
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
     int held_fmt = 0;

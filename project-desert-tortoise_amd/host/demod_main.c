@@ -78,7 +78,11 @@
  * every window's carrier is measured, its bit timing searched and its messages decoded by one pdt_ff_messages_batch per round, times from
  * the capture's start as -A has them.  With a plain I,Q file -- one recording of one burst, no -x, no -f, no -l -- the first two seconds
  * of the file go through pdt_stage_ff_bits and the message kernels; a message's time is its sample index / Fs.  The packets file is what
- * it was: the chain runs as always.  On any other route, without -A, and for demodPOES: a message, exit status 1.
+ * it was: the chain runs as always.  On any other route and without -A: a message, exit status 1.
+ * -b -W <file> (demodPOES): -W's file holds the flywheel's frames out of feed-forward POES bits instead of the loop's: with -x
+ * and one -t the channel stream goes through pdt_ffp_frames, a plain 16-bit I,Q file's samples / 32768 through pdt_stage_ffp_frames; a
+ * frame's time is its sample index / Fs.  -w and -q work as before; the minorFrames file is what it was.  -b without -W, with -l, -f, a
+ * pipe or several -t: a message, exit status 1.
  * -W <file> (an addition, demodPOES): the minor frames a flywheel synchroniser finds in the bits of the capture (pdt_tip_sync, DESIGN
  * 4.18), in the minor-frame text format, beside the unchanged minorFrames file.  -w E,W,G sets its three constants (max_errors, window,
  * fly; default 2,2,3); with -q a second validation line, for these frames, follows the reference's.  One channel of a capture taken
@@ -403,6 +407,46 @@ static int write_flywheel(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const char 
     printf("Flywheel frames: %d -> %s\n", n, name);
     *frames = fr;
     *count = n;
+    return 0;
+}
+
+/* -b -W (demodPOES): the flywheel's frames out of feed-forward bits (pdt_ffp_frames on the channel stream of a -x capture,
+ * pdt_stage_ffp_frames on a plain I,Q file's samples); a frame's time is the sample index of its bit / Fs, seconds of the
+ * stream.  Returns 0 when the file is written; the records stay in *frames for -q. */
+static int write_flywheel_ffp(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const char *name, const float *iq, uint64_t n, uint32_t rate, int channel,
+                              pdt_frame **frames, int *count)
+{
+    const uint64_t ns = channel ? pdt_stage_len(ctx, PDT_ST_CHANNEL) : n;
+    const int cap = (int)(ns / (829 * 6) + 2);                            /* (a bit lasts at least 6 samples, frames lie 829 bits apart) */
+    pdt_frame *fr = (pdt_frame *)malloc((size_t)cap * sizeof *fr);
+    pdt_ffp_sync sync;
+    int found = 0;
+    memset(&sync, 0, sizeof sync);
+    const int rc = !fr ? PDT_ERR_NOMEM : channel ? pdt_ffp_frames(ctx, NULL, cfg, &sync, fr, NULL, cap, &found)
+                                                 : pdt_stage_ffp_frames(ctx, rate, iq, n, NULL, cfg, &sync, fr, NULL, cap, &found);
+    if (rc == PDT_ERR_STATE) printf("-b -W needs a capture taken in one piece: this one left no whole channel stream\n");
+    else if (rc == PDT_ERR_ARG) printf("-b needs a sample rate from 49.92 to 1064.96 kHz; -w E,W,G: E from 0 to 3, W from 1 to 8, G from 2 to 2 W\n");
+    else if (rc != PDT_OK) printf("Feed-forward bits failed: %s\n", pdt_strerror(rc));
+    FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !m) printf("Error opening %s\n", name);
+    if (!m) {
+        free(fr);
+        return 1;
+    }
+    if (found > cap) found = cap;
+    printf("Feed-forward bits: %llu in %llu blocks, carrier %.2f Hz, %llu of %llu tone segments valid\n", (unsigned long long)sync.nbits,
+           (unsigned long long)sync.nblocks, sync.residual_hz, (unsigned long long)sync.segs_valid, (unsigned long long)sync.segs);
+    fflush(m);
+    const int wrc = pdt_write_records(fr, (uint64_t)found, fileno(m), NULL);
+    fclose(m);
+    if (wrc != PDT_OK) {
+        printf("Error writing %s\n", name);
+        free(fr);
+        return 1;
+    }
+    printf("Flywheel frames: %d -> %s\n", found, name);
+    *frames = fr;
+    *count = found;
     return 0;
 }
 
@@ -1020,7 +1064,11 @@ int main(int argc, char **argv)
         printf("-M needs a wideband capture file (-x) taken in one piece: not a pipe, not -l\n");
         return 1;
     }
-    if (feedForward && (MODE != PDT_MODE_ARGOS || !messageName || from_stdin || live || real || (decim && !eachBurst))) {
+    if (feedForward && MODE == PDT_MODE_POES && (!flywheelName || messageName || from_stdin || live || real || nOffsets > 1 || autoCarriers)) {
+        printf("-b needs demodARGOS with -A, or demodPOES with -W <file> and a plain I,Q file or one -x channel: not -l, -f, a pipe or several -t\n");
+        return 1;
+    }
+    if (feedForward && MODE == PDT_MODE_ARGOS && (!messageName || from_stdin || live || real || (decim && !eachBurst))) {
         printf("-b needs demodARGOS with -A, and -t each or a plain I,Q file: not -l, -f or another -t\n");
         return 1;
     }
@@ -1227,10 +1275,14 @@ int main(int argc, char **argv)
     rc = pdt_demod_fd(ctx, fileno(in), (uint64_t)data_offset, in_frames, sample_format);
 #endif
     const double t_demod1 = now_ms();
-    int16_t *ffIq = NULL;                                            /* -b: the recording's first two seconds */
+    int16_t *ffIq = NULL;                                            /* -b: the recording's first two seconds (demodPOES: all of it) */
     uint64_t ffFrames = 0;
-    if (feedForward && rc == PDT_OK) {
-        ffFrames = in_frames < 2ull * rate ? in_frames : 2ull * rate;
+    if (feedForward && rc == PDT_OK && MODE == PDT_MODE_POES && !decim && sample_format != PDT_FMT_PCM16) {
+        printf("-b -W on a plain file needs 16-bit I,Q samples\n");
+        rc = PDT_ERR_FORMAT;
+    }
+    if (feedForward && rc == PDT_OK && !(MODE == PDT_MODE_POES && decim)) {
+        ffFrames = in_frames < 2ull * rate || MODE == PDT_MODE_POES ? in_frames : 2ull * rate;
         ffIq = (int16_t *)malloc((size_t)(ffFrames ? ffFrames : 1) * 4);
         if (!ffIq || fseek(in, data_offset, SEEK_SET) || fread(ffIq, 4, (size_t)ffFrames, in) != (size_t)ffFrames) {
             printf("Error reading %s\n", inFileName);
@@ -1275,10 +1327,25 @@ int main(int argc, char **argv)
         remove(outFileName);
         exit(1);
     }
-    free(ffIq);
     pdt_frame *flyFrames = NULL;
     int flyCount = 0;
-    if (flywheelName && write_flywheel(ctx, flywheelCfgGiven ? &flywheelCfg : NULL, flywheelName, &flyFrames, &flyCount)) {
+    float *ffpIq = NULL;                                             /* -b -W on a plain file: its samples / 32768 */
+    if (flywheelName && feedForward && !decim) {
+        ffpIq = (float *)malloc((size_t)(ffFrames ? ffFrames : 1) * 2 * sizeof *ffpIq);
+        if (!ffpIq) {
+            printf("Out of memory\n");
+            exit(1);
+        }
+        for (uint64_t i = 0; i < 2 * ffFrames; i++) ffpIq[i] = (float)ffIq[i] / 32768.0f;
+        free(ffIq);
+        ffIq = NULL;
+    }
+    const int flyBad = !flywheelName ? 0
+                       : feedForward ? write_flywheel_ffp(ctx, flywheelCfgGiven ? &flywheelCfg : NULL, flywheelName, ffpIq, ffFrames, rate, decim != 0, &flyFrames, &flyCount)
+                                     : write_flywheel(ctx, flywheelCfgGiven ? &flywheelCfg : NULL, flywheelName, &flyFrames, &flyCount);
+    free(ffpIq);
+    free(ffIq);
+    if (flyBad) {
         fclose(out);
         remove(outFileName);
         exit(1);

@@ -60,7 +60,9 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 22): POES bits without a loop -- pdt_ffp_cfg, pdt_ffp_sync, pdt_ffp_block, pdt_ffp_bits, pdt_ffp_read,
+/* 4, additions without a bump (round 23): POES frames' failed parity groups repaired from the soft bit values -- pdt_tip_repair_info,
+ * pdt_tip_repair_summary, pdt_tip_repair, pdt_stage_tip_repair, pdt_host_tip_repair: opt-in, beside everything else.
+ * 4, additions without a bump (round 22): POES bits without a loop -- pdt_ffp_cfg, pdt_ffp_sync, pdt_ffp_block, pdt_ffp_bits, pdt_ffp_read,
  * pdt_ffp_blocks, pdt_ffp_frames, pdt_stage_ffp_bits, pdt_stage_ffp_frames, pdt_host_ffp_bits, pdt_host_ffp_mix: a second, opt-in source
  * of POES bits and, through the flywheel, of minor frames, beside everything else.
  * 4, additions without a bump (round 18): a second, opt-in rule for the ARGOS messages' heads -- pdt_argos_cfg.rule (the first of the two
@@ -959,6 +961,64 @@ int  pdt_stage_ffp_frames(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uin
 int  pdt_host_ffp_bits(uint32_t rate, const float *iq, uint64_t n, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync, uint8_t *bits, float *soft,
                        int64_t *index, uint64_t cap, uint64_t *count, pdt_ffp_block *blocks, uint64_t block_cap);
 int  pdt_host_ffp_mix(uint32_t rate, const float *iq, uint64_t n, const pdt_ffp_cfg *cfg, float *out);
+
+/* POES frames: repair of failed parity groups from the soft bit values (POES contexts).  The flywheel places the minor frames
+ * of a weak pass; what it hands out are hard decisions, and pdt_tip_check only REPORTS the five even-parity groups of a frame.  Where a
+ * group's parity is odd, complementing its least reliable bit (Wagner's rule for a single-parity code) is the most likely correction.
+ * These entries are opt-in and stand BESIDE everything else; the rule is fixed in csrc/pdt_tip_repair.h and pdt_host_tip_repair restates
+ * it on the host:
+ *   input     pdt_frame records as pdt_tip_sync / pdt_ffp_frames give them, and a stream of n float32 soft values: value k belongs to
+ *             bit k of the stream the records were found in (pdt_ffp_read's soft)
+ *   CHECKED   a record is checked <=> complete == 1 and nbytes == 104 and 18 <= bit_index and bit_index + 813 < n.  Any other record is
+ *             left as it is and marked skipped
+ *   BITS      frame bit j, 0 <= j < 832, is bit 7 - (j & 7) of bytes[j >> 3]; its soft value is soft[bit_index - 18 + j]
+ *   GROUPS    pdt_tip_check's, unchanged: group g = 0 .. 4 covers frame bits 16 + 136 g .. 151 + 136 g (bytes 2 + 17 g .. 18 + 17 g) and
+ *             its parity bit, frame bit 826 + g (bit 5 - g of bytes[103]).  The group FAILS when the number of ones among these 137 bits
+ *             OF THE RECORD is odd; the record of an inverted head is already complemented back, so polarity plays no part
+ *   CANDIDATE the group's bits that came from the stream.  In group 0 frame bits 16, 17 and 18 are the sync word's last three bits, which
+ *             the flywheel writes as zeros: they count toward the parity but are never candidates -- 134 candidates in group 0, 137 in
+ *             the others
+ *   r(k)      the uint32 bit pattern of |soft[k]|: a NaN counts as 0, -0 as 0, Inf sorts above every finite value
+ *   KEY       of the candidate at frame bit j: (uint64) r << 16 | j
+ *   REPAIR    in a failing group the candidate with the smallest key is complemented in the record: ties go to the earlier bit, a data
+ *             bit goes before the parity bit.  Nothing else changes -- not time, bit_index, time_src, inverted or bytes 0 - 1
+ *   INFO      per record: status (1 checked, 0 skipped); failed, bit g set where group g failed BEFORE the repair; pos[g] = the frame bit
+ *             complemented in group g, or 0xFFFF; least[g] and next[g] = the floats whose bit patterns are the r of the smallest and the
+ *             second smallest key of group g, filled whether or not the group failed (a repair is judged by its margin).  A skipped
+ *             record: failed 0, pos 0xFFFF, least and next 0
+ *   SUMMARY   records checked, records skipped, records with a failing group, groups repaired
+ * After the repair every group of a checked record passes BY CONSTRUCTION: -q and pdt_tip_check_records on repaired records say nothing,
+ * and `failed` is the parity record to keep.  A group with two wrong bits passes as it is, one with three is made worse: the rule helps
+ * while single errors dominate -- at 9 x the noise of the weak capture it turns most damaged frames right, at 12 x it does not help
+ * (DESIGN 4.20's table).  The 131 bits of bytes 87 - 103 that no group covers are never touched.
+ *   pdt_tip_repair        the caller's records (uploaded to a buffer of their own, as pdt_tip_check_records uploads its) against the soft
+ *                         values of the context's last pdt_ffp_* / pdt_stage_ffp_* call, which are still in device memory, on the
+ *                         device's own bit count: frames[0 .. n) repaired in place, info[0 .. n) (may be NULL) and *summary filled.
+ *                         PDT_ERR_STATE when no such call left bits, or a stream is open; PDT_ERR_ARG for an ARGOS context, a null
+ *                         pointer with n > 0, a null summary, or n >= 2^31.  No other result of the context changes (a profiled context's
+ *                         pdt_kernel_times gain the entry k_tip_repair)
+ *   pdt_stage_tip_repair  stage-level entry: the kernel on a caller's nbits soft values from any source (nbits < 2^31, else PDT_ERR_ARG).
+ *                         Nothing of the context's results changes, the feed-forward bits included
+ *   pdt_host_tip_repair   host only, no GPU: the same bytes in frames, info and summary                                                */
+#define PDT_TIP_REPAIR_NONE 0xFFFFu
+typedef struct pdt_tip_repair_info {
+    uint8_t  status;       /* 1 = checked, 0 = skipped                                                                       */
+    uint8_t  failed;       /* bit g set = group g failed before the repair: the parity record to keep                        */
+    uint16_t pos[5];       /* the frame bit complemented in group g, PDT_TIP_REPAIR_NONE when the group passed                */
+    float    least[5];     /* the smallest |soft| among group g's candidates ...                                             */
+    float    next[5];      /* ... and the second smallest: the margin of a repair                                            */
+} pdt_tip_repair_info;
+typedef struct pdt_tip_repair_summary {
+    uint64_t checked;      /* records checked                                                                                */
+    uint64_t skipped;      /* records left as they were                                                                      */
+    uint64_t failing;      /* checked records with at least one failing group                                                */
+    uint64_t repaired;     /* groups repaired = bits complemented                                                            */
+} pdt_tip_repair_summary;
+int  pdt_tip_repair(pdt_ctx *ctx, pdt_frame *frames, uint64_t n, pdt_tip_repair_info *info, pdt_tip_repair_summary *summary);
+int  pdt_stage_tip_repair(pdt_ctx *ctx, const float *soft_host, uint64_t nbits, pdt_frame *frames, uint64_t n, pdt_tip_repair_info *info,
+                          pdt_tip_repair_summary *summary);
+int  pdt_host_tip_repair(const float *soft, uint64_t nbits, pdt_frame *frames, uint64_t n, pdt_tip_repair_info *info,
+                         pdt_tip_repair_summary *summary);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

@@ -430,6 +430,31 @@ def tip_sync_batch(ds, max_errors=None, window=None, fly=None, cap: int = 65536,
     return [_tip_sync_result(out[i], info[i], counts[i], cap, with_info, False) for i in range(len(ds))]
 
 
+# pdt_tip_repair_info as a numpy record, and pdt_tip_repair_summary
+TIP_REPAIR_INFO_DTYPE = np.dtype([("status", "u1"), ("failed", "u1"), ("pos", "<u2", (5,)), ("least", "<f4", (5,)), ("next", "<f4", (5,))])
+assert TIP_REPAIR_INFO_DTYPE.itemsize == 52
+TIP_REPAIR_NONE = 0xFFFF
+
+
+class TipRepairSummary(C.Structure):
+    _fields_ = [("checked", C.c_uint64), ("skipped", C.c_uint64), ("failing", C.c_uint64), ("repaired", C.c_uint64)]
+
+
+def _tip_repair_result(a, info, sm):
+    return a, info[:len(a)], {k: int(getattr(sm, k)) for k, _ in TipRepairSummary._fields_}
+
+
+def host_tip_repair(soft, frames):
+    """pdt_host_tip_repair: the failed parity groups of POES minor frames repaired from the soft bit values, restated on the host (no
+    GPU).  soft: float32[n], value k belongs to bit k of the stream the FRAME_DTYPE records were found in.  Returns (the repaired copy of
+    the records, TIP_REPAIR_INFO_DTYPE[len], summary dict); `failed` is the parity record to keep -- repaired records pass every check."""
+    s = np.ascontiguousarray(soft, dtype="<f4").reshape(-1)
+    a = np.array(frames, dtype=FRAME_DTYPE, copy=True).reshape(-1)
+    info, sm = np.zeros(max(len(a), 1), dtype=TIP_REPAIR_INFO_DTYPE), TipRepairSummary()
+    _check(lib().pdt_host_tip_repair(s.ctypes.data, s.size, a.ctypes.data, len(a), info.ctypes.data, C.byref(sm)), "pdt_host_tip_repair")
+    return _tip_repair_result(a, info, sm)
+
+
 class FfCfg(C.Structure):
     """pdt_ff_cfg: a zero means the default; rate_steps 0 with FF_ZERO_RATE_STEPS in zero_mask asks for the nominal rate alone;
     FF_RESIDUAL_GIVEN in flags: residual_hz is the caller's, otherwise the carrier is measured"""
@@ -622,6 +647,7 @@ ABI_SYMBOLS = [
     "pdt_ffp_bits", "pdt_ffp_read", "pdt_ffp_blocks", "pdt_ffp_frames", "pdt_stage_ffp_bits", "pdt_stage_ffp_frames", "pdt_host_ffp_bits",
     "pdt_host_ffp_mix",
     "pdt_tip_sync", "pdt_tip_sync_batch", "pdt_stage_tip_sync", "pdt_host_tip_sync", "pdt_tip_sync_tile", "pdt_tip_check_records",
+    "pdt_tip_repair", "pdt_stage_tip_repair", "pdt_host_tip_repair",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
 
@@ -782,6 +808,9 @@ def lib():
     L.pdt_stage_tip_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.pdt_host_tip_sync.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(TipSyncCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.pdt_tip_check_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(TipSummary), C.c_void_p]
+    L.pdt_tip_repair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TipRepairSummary)]
+    L.pdt_stage_tip_repair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TipRepairSummary)]
+    L.pdt_host_tip_repair.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TipRepairSummary)]
     L.pdt_format_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.pdt_format_argos_messages.restype = C.c_uint64
     L.pdt_write_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
@@ -1532,6 +1561,24 @@ class Demodulator:
         _check(self._L.pdt_tip_check_records(self._h, a.ctypes.data, len(a), C.byref(sm), rec.ctypes.data), "pdt_tip_check_records")
         return {k: int(getattr(sm, k)) for k, _ in TipSummary._fields_}, rec[:len(a)]
 
+    def tip_repair(self, frames):
+        """pdt_tip_repair: the failed parity groups of FRAME_DTYPE records (those of ffp_frames(), say) repaired from the soft values this
+        context's last ffp_* / stage_ffp_* call left on the device: (repaired copy, TIP_REPAIR_INFO_DTYPE[len], summary dict).  The
+        context's own results stay as they were."""
+        a = np.array(frames, dtype=FRAME_DTYPE, copy=True).reshape(-1)
+        info, sm = np.zeros(max(len(a), 1), dtype=TIP_REPAIR_INFO_DTYPE), TipRepairSummary()
+        _check(self._L.pdt_tip_repair(self._h, a.ctypes.data, len(a), info.ctypes.data, C.byref(sm)), "pdt_tip_repair")
+        return _tip_repair_result(a, info, sm)
+
+    def stage_tip_repair(self, soft, frames):
+        """pdt_stage_tip_repair: the same kernel on a caller's float32 soft values from any source"""
+        s = np.ascontiguousarray(soft, dtype="<f4").reshape(-1)
+        a = np.array(frames, dtype=FRAME_DTYPE, copy=True).reshape(-1)
+        info, sm = np.zeros(max(len(a), 1), dtype=TIP_REPAIR_INFO_DTYPE), TipRepairSummary()
+        _check(self._L.pdt_stage_tip_repair(self._h, s.ctypes.data, s.size, a.ctypes.data, len(a), info.ctypes.data, C.byref(sm)),
+               "pdt_stage_tip_repair")
+        return _tip_repair_result(a, info, sm)
+
     def tip_sync(self, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False, with_count: bool = False):
         """pdt_tip_sync: the POES minor frames a flywheel synchroniser finds in the bits of this context's last whole-capture call -- a
         sync word with up to max_errors wrong bits (None = 2) counts when a neighbouring slot within `window` frames (None = 2) has one
@@ -1674,7 +1721,7 @@ def synth_capture(kind: int, sample_rate: int, seconds: float, f0_hz: float | No
                   start: int = 0) -> np.ndarray:
     """int16[n,2] synthetic POES (kind 0) / ARGOS (kind 1; kind 2: messages of 1 .. 8 blocks) capture; bit-reproducible everywhere."""
     if f0_hz is None:
-        f0_hz = 1000.0 if kind == 0 else 120.0
+        f0_hz = 1000.0 if kind in (0, 3) else 120.0            # (kind 3: POES frames that carry their parity)
     p = synth_params(kind, sample_rate, f0_hz, seed)
     n = int(round(seconds * sample_rate))
     out = np.zeros((n, 2), dtype="<i2")

@@ -56,6 +56,9 @@ uint64_t ffp_bit_cap(const pdt::FfpRule &r);
 size_t ffp_work_bytes(const pdt::FfpRule &r, size_t nent);
 void ffp_steps(const pdt_tone *tones, uint64_t nseg, int nfft, const pdt::FfpRule &r, int given, double residual, std::vector<uint32_t> &steps,
                std::vector<uint32_t> &starts, pdt::FfpSync *head);
+// pdt_tip_repair.hip
+hipError_t tip_repair_launch(hipStream_t st, void *recs_dev, unsigned nrec, const float *soft_dev, const unsigned long long *nbits_dev, long long bit_cap,
+                             void *info_dev, void *sum_dev);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -602,7 +605,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
                        &ctx->argos_work, &ctx->argos_bits, &ctx->ff_work, &ctx->ff_in, &ctx->ff_out, &ctx->ffp_work, &ctx->ffp_in, &ctx->ffp_out,
-                       &ctx->tip_sync_work, &ctx->tip_sync_bits, &ctx->tip_recs };
+                       &ctx->tip_sync_work, &ctx->tip_sync_bits, &ctx->tip_recs, &ctx->tip_repair_work, &ctx->tip_repair_soft };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -2297,6 +2300,80 @@ int pdt_stage_ffp_frames(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint
     if (rc) return rc;
     if (sync) *sync = s;
     return ffp_frames_of(ctx, R, out, info, cap, count);
+}
+
+// ---------------------------------------------------------------- parity repair from the soft values (pdt_tip_repair.h)
+// k_tip_repair on the caller's records against soft values that are on the device (their count too: read as min(*nbits_dev, bit_cap)).
+// The records go up as they are, into a buffer of their own beside their info records and the counters; one synchronize ends the call.
+static int tip_repair_run(pdt_ctx *c, const float *soft_dev, const unsigned long long *nbits_dev, long long bit_cap, pdt_frame *frames, uint64_t n,
+                          pdt_tip_repair_info *info, pdt_tip_repair_summary *summary)
+{
+    memset(summary, 0, sizeof *summary);
+    if (n == 0) return PDT_OK;
+    const size_t o_rec = 64, o_info = o_rec + (((size_t)n * sizeof(pdt_frame) + 15) & ~(size_t)15);
+    int rc;
+    if ((rc = c->tip_repair_work.ensure(o_info + (size_t)n * sizeof(pdt_tip_repair_info)))) return rc;
+    unsigned char *w = (unsigned char *)c->tip_repair_work.p;
+    hipStream_t st = c->stream;
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    HIP_TRY(hipMemsetAsync(w, 0, o_rec, st));
+    HIP_TRY(hipMemcpyAsync(w + o_rec, frames, (size_t)n * sizeof(pdt_frame), hipMemcpyHostToDevice, st));
+    if (c->cfg.profile) {
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ev[0], st));
+    }
+    HIP_TRY(tip_repair_launch(st, w + o_rec, (unsigned)n, soft_dev, nbits_dev, bit_cap, w + o_info, w));
+    if (c->cfg.profile) HIP_TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(hipMemcpyAsync(frames, w + o_rec, (size_t)n * sizeof(pdt_frame), hipMemcpyDeviceToHost, st));
+    if (info) HIP_TRY(hipMemcpyAsync(info, w + o_info, (size_t)n * sizeof(pdt_tip_repair_info), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(summary, w, sizeof *summary, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->cfg.profile) {
+        pdt_kernel_time kt;
+        memset(&kt, 0, sizeof kt);
+        snprintf(kt.name, sizeof kt.name, "%s", "k_tip_repair");
+        kt.launches = 1;
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+        kt.total_ms = ms;
+        c->ktimes.erase(std::remove_if(c->ktimes.begin(), c->ktimes.end(), [&](const pdt_kernel_time &x) { return !strcmp(x.name, kt.name); }),
+                        c->ktimes.end());
+        c->ktimes.push_back(kt);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    return PDT_OK;
+}
+
+int pdt_tip_repair(pdt_ctx *ctx, pdt_frame *frames, uint64_t n, pdt_tip_repair_info *info, pdt_tip_repair_summary *summary)
+{
+    if (!ctx || !summary || (!frames && n) || n >= (1ull << 31)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;             // TIP minor frames only
+    if (ctx->stream_open || !ctx->ffp_rate || !ctx->ffp_out.p) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    try {
+        const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
+        const unsigned char *p = (const unsigned char *)ctx->ffp_out.p;
+        return tip_repair_run(ctx, (const float *)(p + o.o_soft), (const unsigned long long *)p, (long long)ctx->ffp_cap, frames, n, info, summary);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+int pdt_stage_tip_repair(pdt_ctx *ctx, const float *soft_host, uint64_t nbits, pdt_frame *frames, uint64_t n, pdt_tip_repair_info *info,
+                         pdt_tip_repair_summary *summary)
+{
+    if (!ctx || !summary || (!frames && n) || n >= (1ull << 31) || (!soft_host && nbits) || nbits >= (1ull << 31)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    try {
+        int rc;
+        if ((rc = ctx->tip_repair_soft.ensure(16 + (size_t)nbits * 4))) return rc;      // the count, then the values
+        unsigned char *p = (unsigned char *)ctx->tip_repair_soft.p;
+        const unsigned long long count = nbits;
+        HIP_TRY(hipMemcpyAsync(p, &count, sizeof count, hipMemcpyHostToDevice, ctx->stream));
+        if (nbits) HIP_TRY(hipMemcpyAsync(p + 16, soft_host, (size_t)nbits * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                                     // (`count` leaves scope)
+        return tip_repair_run(ctx, (const float *)(p + 16), (const unsigned long long *)p, (long long)nbits, frames, n, info, summary);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

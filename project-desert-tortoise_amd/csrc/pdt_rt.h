@@ -487,6 +487,8 @@ struct pdt_ctx {
     DevBuf ffp_work, ffp_in, ffp_out;
     uint64_t ffp_cap = 0, ffp_blocks = 0;
     uint32_t ffp_rate = 0;              // 0 = no such call yet
+    // parity repair (pdt_tip_repair.h): the caller's records, their info records and the counters; the soft values of the stage entry
+    DevBuf tip_repair_work, tip_repair_soft;
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
     int held_fmt = 0;

@@ -83,6 +83,11 @@
  * and one -t the channel stream goes through pdt_ffp_frames, a plain 16-bit I,Q file's samples / 32768 through pdt_stage_ffp_frames; a
  * frame's time is its sample index / Fs.  -w and -q work as before; the minorFrames file is what it was.  -b without -W, with -l, -f, a
  * pipe or several -t: a message, exit status 1.
+ * -b -W <file> -Q <report> (demodPOES): the -W frames' failed parity groups are repaired from the feed-forward bits' soft values before they
+ * are written (pdt_tip_repair); <report> gets one line per record that had a failing group -- its time, then group, frame bit,
+ * least and next for each failing group --, and a summary line precedes the -W count.  After the repair every group
+ * passes by construction: -q's flywheel line on these frames says nothing, the report is the parity record to keep.  -Q without -b (the
+ * loop's bits carry no soft values) or for demodARGOS: a message, exit status 1.
  * -W <file> (an addition, demodPOES): the minor frames a flywheel synchroniser finds in the bits of the capture (pdt_tip_sync, DESIGN
  * 4.18), in the minor-frame text format, beside the unchanged minorFrames file.  -w E,W,G sets its three constants (max_errors, window,
  * fly; default 2,2,3); with -q a second validation line, for these frames, follows the reference's.  One channel of a capture taken
@@ -103,14 +108,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:bW:w:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:bW:w:Q:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:bW:w:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:bW:w:Q:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -413,8 +418,10 @@ static int write_flywheel(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const char 
 /* -b -W (demodPOES): the flywheel's frames out of feed-forward bits (pdt_ffp_frames on the channel stream of a -x capture,
  * pdt_stage_ffp_frames on a plain I,Q file's samples); a frame's time is the sample index of its bit / Fs, seconds of the
  * stream.  Returns 0 when the file is written; the records stay in *frames for -q. */
+static int write_repair_report(pdt_ctx *ctx, pdt_frame *fr, int found, const char *name);
+
 static int write_flywheel_ffp(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const char *name, const float *iq, uint64_t n, uint32_t rate, int channel,
-                              pdt_frame **frames, int *count)
+                              const char *repairName, pdt_frame **frames, int *count)
 {
     const uint64_t ns = channel ? pdt_stage_len(ctx, PDT_ST_CHANNEL) : n;
     const int cap = (int)(ns / (829 * 6) + 2);                            /* (a bit lasts at least 6 samples, frames lie 829 bits apart) */
@@ -436,6 +443,12 @@ static int write_flywheel_ffp(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const c
     if (found > cap) found = cap;
     printf("Feed-forward bits: %llu in %llu blocks, carrier %.2f Hz, %llu of %llu tone segments valid\n", (unsigned long long)sync.nbits,
            (unsigned long long)sync.nblocks, sync.residual_hz, (unsigned long long)sync.segs_valid, (unsigned long long)sync.segs);
+    if (repairName && write_repair_report(ctx, fr, found, repairName)) {
+        fclose(m);
+        remove(name);
+        free(fr);
+        return 1;
+    }
     fflush(m);
     const int wrc = pdt_write_records(fr, (uint64_t)found, fileno(m), NULL);
     fclose(m);
@@ -447,6 +460,38 @@ static int write_flywheel_ffp(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const c
     printf("Flywheel frames: %d -> %s\n", found, name);
     *frames = fr;
     *count = found;
+    return 0;
+}
+
+/* -Q: the failed parity groups of the -b -W frames repaired in place from the soft values the feed-forward call left on the device
+ * (pdt_tip_repair), and the report: one line per record that had a failing group -- "%.5f" of its time, then " g bit least
+ * next" ("%d %d %.9g %.9g") for each failing group in ascending g.  Returns 0 when the report is written. */
+static int write_repair_report(pdt_ctx *ctx, pdt_frame *fr, int found, const char *name)
+{
+    pdt_tip_repair_info *info = (pdt_tip_repair_info *)malloc((size_t)(found ? found : 1) * sizeof *info);
+    pdt_tip_repair_summary sum;
+    const int rc = !info ? PDT_ERR_NOMEM : pdt_tip_repair(ctx, fr, (uint64_t)found, info, &sum);
+    if (rc != PDT_OK) printf("Parity repair failed: %s\n", pdt_strerror(rc));
+    FILE *q = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !q) printf("Error opening %s\n", name);
+    if (!q) {
+        free(info);
+        return 1;
+    }
+    for (int f = 0; f < found; f++) {
+        if (!info[f].failed) continue;
+        fprintf(q, "%.5f", fr[f].time);
+        for (int g = 0; g < 5; g++)
+            if (info[f].failed >> g & 1) fprintf(q, " %d %d %.9g %.9g", g, (int)info[f].pos[g], (double)info[f].least[g], (double)info[f].next[g]);
+        fprintf(q, "\n");
+    }
+    free(info);
+    if (fclose(q)) {
+        printf("Error writing %s\n", name);
+        return 1;
+    }
+    printf("Parity repair: %llu records checked, %llu skipped, %llu with a failing group, %llu groups repaired -> %s\n",
+           (unsigned long long)sum.checked, (unsigned long long)sum.skipped, (unsigned long long)sum.failing, (unsigned long long)sum.repaired, name);
     return 0;
 }
 
@@ -860,6 +905,7 @@ int main(int argc, char **argv)
     const char *outOverride = NULL, *measureName = NULL;                            /* -M: the carrier measurement's file */
     const char *messageName = NULL;                                                 /* -A: the ARGOS messages' file */
     const char *flywheelName = NULL;                                                /* -W: the flywheel synchroniser's frames' file */
+    const char *repairName = NULL;                                                  /* -Q: the parity repair's report */
     pdt_tip_sync_cfg flywheelCfg;                                                   /* -w E,W,G: its constants */
     int flywheelCfgGiven = 0;
     char outFileName[1100];
@@ -982,6 +1028,9 @@ int main(int argc, char **argv)
         case 'W':                                       /* the flywheel synchroniser's minor frames, to this file */
             flywheelName = optarg;
             break;
+        case 'Q':                                       /* -b -W: repair the frames' failed parity groups, the report to this file */
+            repairName = optarg;
+            break;
         case 'w': {                                     /* max_errors, window, fly of the flywheel's rule */
             int e = 0, w = 0, g = 0;
             char tail = 0;
@@ -1078,6 +1127,10 @@ int main(int argc, char **argv)
     }
     if ((flywheelName || flywheelCfgGiven) && (MODE != PDT_MODE_POES || from_stdin || nOffsets > 1 || autoCarriers)) {
         printf("-W and -w need demodPOES, one channel and a capture taken in one piece: not a pipe, not several -t\n");
+        return 1;
+    }
+    if (repairName && (MODE != PDT_MODE_POES || !feedForward || !flywheelName)) {
+        printf("-Q needs demodPOES with -b -W <file>: the loop's bits carry no soft values\n");
         return 1;
     }
     if (flywheelCfgGiven && !flywheelName) {
@@ -1341,7 +1394,7 @@ int main(int argc, char **argv)
         ffIq = NULL;
     }
     const int flyBad = !flywheelName ? 0
-                       : feedForward ? write_flywheel_ffp(ctx, flywheelCfgGiven ? &flywheelCfg : NULL, flywheelName, ffpIq, ffFrames, rate, decim != 0, &flyFrames, &flyCount)
+                       : feedForward ? write_flywheel_ffp(ctx, flywheelCfgGiven ? &flywheelCfg : NULL, flywheelName, ffpIq, ffFrames, rate, decim != 0, repairName, &flyFrames, &flyCount)
                                      : write_flywheel(ctx, flywheelCfgGiven ? &flywheelCfg : NULL, flywheelName, &flyFrames, &flyCount);
     free(ffpIq);
     free(ffIq);
@@ -1389,8 +1442,9 @@ int main(int argc, char **argv)
             if (q.day >= 0) printf("Julean Day: %d \n", q.day);
         }
         if (flywheelName && pdt_tip_check_records(ctx, flyFrames, (uint64_t)flyCount, &q, NULL) == PDT_OK)
-            printf("\nFlywheel: %llu out of %llu Error Free Frames, %llu Good Chunks and %llu Bad Chunks\n", (unsigned long long)q.good_frames,
-                   (unsigned long long)q.frames_checked, (unsigned long long)q.good_chunks, (unsigned long long)q.bad_chunks);
+            printf("\nFlywheel: %llu out of %llu Error Free Frames, %llu Good Chunks and %llu Bad Chunks%s\n", (unsigned long long)q.good_frames,
+                   (unsigned long long)q.frames_checked, (unsigned long long)q.good_chunks, (unsigned long long)q.bad_chunks,
+                   repairName ? " (after -Q's repair every group passes by construction: its report is the parity record)" : "");
     }
 #else
     (void)quality;

@@ -21,6 +21,9 @@
  *             0001 0111, 1, the length code of N (N - 1 in three bits and an even-parity
  *             bit), a 20-bit ID, 32 N data bits, then carrier off; N = 1 + (burst + seed)
  *             mod 8, so eight consecutive bursts cover every length (360 .. 920 ms).
+ *  POES with parity (kind 3): a POES capture exactly as kind 0 except for byte 103 of every
+ *             minor frame: its bit 5 - g is the even parity of bytes 2 + 17 g .. 18 + 17 g, g = 0 .. 4
+ *             (the five TIP parity groups); bits 7, 6 and 0 come from the hash as before.
  *
  * A pass as a receiver sees it (round 6; every field 0 = off, the captures above unchanged): noise only before
  * `signal_start` (the receiver is on before the satellite rises) and from `signal_end` on (it stays on after it has set);
@@ -45,7 +48,7 @@
 #define PDT_SYNTH_TABLE_SIZE (1u << PDT_SYNTH_TABLE_BITS)
 
 typedef struct pdt_synth_params {
-    uint32_t kind;          /* 0 = POES, 1 = ARGOS, 2 = ARGOS with messages of 1 .. 8 blocks */
+    uint32_t kind;          /* 0 = POES, 1 = ARGOS, 2 = ARGOS with messages of 1 .. 8 blocks, 3 = POES with parity */
     uint32_t sample_rate;   /* Hz                                                         */
     uint32_t carrier_step;  /* round(f0 / Fs * 2^32)                                      */
     uint32_t phase0;        /* phi0 in turns * 2^32                                       */
@@ -80,6 +83,23 @@ PDT_SYNTH_FN uint32_t pdt_synth_poes_frame_byte(uint64_t seed, uint64_t fr, uint
     if (b == 1) return 0xE2u;
     uint32_t v = (uint32_t)(pdt_synth_mix(seed ^ (fr * 104u + b) * 0xD6E8FEB86659FD93ull) >> 24) & 0xFFu;
     return b == 2 ? (v & 0x1Fu) : v;
+}
+
+/* kind 3: the same, byte 103 carrying the even parity of the five TIP groups in its bits 5 .. 1 */
+PDT_SYNTH_FN uint32_t pdt_synth_poes_parity_byte(uint64_t seed, uint64_t fr, uint32_t b)
+{
+    uint32_t v = pdt_synth_poes_frame_byte(seed, fr, b);
+    if (b != 103) return v;
+    v &= 0xC1u;
+    for (uint32_t g = 0; g < 5; g++) {
+        uint32_t x = 0;
+        for (uint32_t t = 0; t < 17; t++) x ^= pdt_synth_poes_frame_byte(seed, fr, 2 + 17 * g + t);
+        x ^= x >> 4;
+        x ^= x >> 2;
+        x ^= x >> 1;
+        v |= (x & 1u) << (5 - g);
+    }
+    return v;
 }
 
 /* payload byte `b` (0..6) of ARGOS burst `burst` */
@@ -165,12 +185,12 @@ PDT_SYNTH_FN void pdt_synth_sample(const pdt_synth_params *p, const int16_t *sin
     }
     if (amp && p->fade_len && n >= p->fade_start && n - p->fade_start < p->fade_len)
         amp = (int32_t)(((uint64_t)amp * p->fade_q15 + 16384u) >> 15);
-    if (p->kind == 0) {
+    if (p->kind == 0 || p->kind == 3) {
         uint64_t k = (n * 16640ull) / p->sample_rate;     /* Manchester symbol index */
         uint64_t bit = k >> 1;
         uint64_t fr = bit / 832u;
         uint32_t j = (uint32_t)(bit % 832u);
-        uint32_t v = (pdt_synth_poes_frame_byte(p->seed, fr, j >> 3) >> (7 - (j & 7))) & 1u;
+        uint32_t v = ((p->kind == 3 && j >= 824 ? pdt_synth_poes_parity_byte(p->seed, fr, 103) : pdt_synth_poes_frame_byte(p->seed, fr, j >> 3)) >> (7 - (j & 7))) & 1u;
         int up = (v != 0) ^ (int)(k & 1);                 /* '1' -> +,-   '0' -> -,+ */
         theta += up ? p->mod_index : (uint32_t)(0u - p->mod_index);
     } else {

@@ -38,20 +38,21 @@ int tone_plan(const pdt_tone_cfg *cfg, double fs, double range_hz, uint64_t len,
 void tone_sums(int nfft, double *sw, double *sw2);
 void tones_derive(const void *raw, const pdt::TonePlan &p, double fs, double offset_hz, double sw, double sw2, pdt_tone *out);
 // pdt_argos_msg.hip
-hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, int rule, hipEvent_t mid);
+// (every *_launch below: `inner` is NULL, or the events recorded between its kernels -- CallTimer::inner)
+hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, int rule, hipEvent_t *inner);
 int argos_min_run(const pdt_argos_cfg *cfg, int *K, int *rule);
 // pdt_tip_sync.hip
 extern const char *const tip_sync_kernel_names[5];
-hipError_t tip_sync_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, pdt::TipSyncRule R, hipEvent_t *ev);
+hipError_t tip_sync_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, pdt::TipSyncRule R, hipEvent_t *inner);
 int tip_sync_rule(const pdt_tip_sync_cfg *cfg, pdt::TipSyncRule *R);
 // pdt_ff.hip
 hipError_t ff_launch(hipStream_t st, const void *table_dev, int nwin, long long mix_tiles, long long groups, const long long *periods_dev, int R,
-                     int H, long long pmax, const float *tab_dev, void *metric_dev, size_t metric_bytes, void *syncs_dev, hipEvent_t *ev);
+                     int H, long long pmax, const float *tab_dev, void *metric_dev, size_t metric_bytes, void *syncs_dev, hipEvent_t *inner);
 int ff_plan(const pdt_ff_cfg *cfg, uint32_t rate, int *H, int *R, double *ppm, int *given, double *residual);
 // pdt_ffp.hip
 int ffp_plan(const pdt_ffp_cfg *cfg, uint32_t rate, uint64_t n, pdt::FfpRule *r, int *given, double *residual);
 int ffp_run_device(hipStream_t st, const float *y, const pdt::FfpRule &r, const pdt::FfpSync &head, const std::vector<uint32_t> &steps,
-                   const std::vector<uint32_t> &starts, const float *tab_dev, void *work, const pdt::FfpOutPtrs &out, uint64_t bit_cap, hipEvent_t *ev);
+                   const std::vector<uint32_t> &starts, const float *tab_dev, void *work, const pdt::FfpOutPtrs &out, uint64_t bit_cap, hipEvent_t *inner);
 uint64_t ffp_bit_cap(const pdt::FfpRule &r);
 size_t ffp_work_bytes(const pdt::FfpRule &r, size_t nent);
 void ffp_steps(const pdt_tone *tones, uint64_t nseg, int nfft, const pdt::FfpRule &r, int given, double residual, std::vector<uint32_t> &steps,
@@ -604,8 +605,8 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->avgph, &ctx->term_ap, &ctx->seams_q, &ctx->chunkinfo, &ctx->an_tab, &ctx->analytic, &ctx->halo.buf[0], &ctx->halo.buf[1],
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
-                       &ctx->argos_work, &ctx->argos_bits, &ctx->ff_work, &ctx->ff_in, &ctx->ff_out, &ctx->ffp_work, &ctx->ffp_in, &ctx->ffp_out,
-                       &ctx->tip_sync_work, &ctx->tip_sync_bits, &ctx->tip_recs, &ctx->tip_repair_work, &ctx->tip_repair_soft };
+                       &ctx->staged_bits, &ctx->staged_iq, &ctx->argos_work, &ctx->ff_work, &ctx->ff_out, &ctx->ffp_work, &ctx->ffp_out,
+                       &ctx->tip_sync_work, &ctx->tip_recs, &ctx->tip_repair_work, &ctx->tip_repair_soft };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1325,27 +1326,174 @@ int pdt_bursts_shape(const pdt_ctx *ctx, int *nfft, int *rows_per, uint64_t *nro
     return PDT_OK;
 }
 
+// ---------------------------------------------------------------- second-pass entries: what they share
+// Calls that read what a demodulation left on the device and run a few kernels of their own.  Their kernel times: CallTimer (pdt_rt.h);
+// where their buffers' regions lie: pdt_work_layout.h; the rest is here.
+enum { MODE_ANY = -1 };
+
+// Context i of a call's list against those in front of it: there, of the mode asked for, on the first one's device (same_rate: and at
+// its sample rate), and not in the list twice.  What fails here is PDT_ERR_ARG.
+static bool list_arg_ok(pdt_ctx *const *ctxs, int i, int mode, bool same_rate)
+{
+    const pdt_ctx *c = ctxs[i];
+    if (!c || (mode != MODE_ANY && c->cfg.mode != mode)) return false;
+    if (c->cfg.device != ctxs[0]->cfg.device || (same_rate && c->cfg.sample_rate != ctxs[0]->cfg.sample_rate)) return false;
+    for (int j = 0; j < i; j++)
+        if (ctxs[j] == c) return false;
+    return true;
+}
+
+// a whole-capture call has left a channel stream on the device
+static bool channel_resident(const pdt_ctx *c) { return !c->stream_open && c->stage_len[PDT_ST_CHANNEL] && c->channel.p; }
+
+// the whole capture's bits are on the device: a whole-capture call in one piece was the last to write them (stage-level calls and
+// pdt_stream_begin zero every stage length; a piece of a capture or of a stream clears bits_whole)
+static bool bits_resident(const pdt_ctx *c) { return c->bits_whole && !c->stream_open && c->stage_len[PDT_ST_FIR] != 0 && c->bit_time; }
+
+// `count` elements of the host's in a buffer of the context's own, their count in front of them and the data 16 bytes in: nothing the
+// context's results live in is touched.  Both copies are synchronous (the count is a local).
+static int stage_counted(pdt_ctx *ctx, DevBuf &b, const void *host, uint64_t count, size_t elem_bytes)
+{
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    const int rc = b.ensure(16 + (size_t)count * elem_bytes);
+    if (rc) return rc;
+    const unsigned long long n = count;
+    HIP_TRY(hipMemcpy(b.p, &n, sizeof n, hipMemcpyHostToDevice));
+    if (count) HIP_TRY(hipMemcpy((unsigned char *)b.p + 16, host, (size_t)count * elem_bytes, hipMemcpyHostToDevice));
+    return PDT_OK;
+}
+
+// ... and n I,Q pairs of the host's, likewise
+static int stage_iq(pdt_ctx *ctx, DevBuf &b, const float *iq_host, uint64_t n)
+{
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    const int rc = b.ensure((size_t)n * 8 + 16);
+    if (rc) return rc;
+    if (n) HIP_TRY(hipMemcpy(b.p, iq_host, (size_t)n * 8, hipMemcpyHostToDevice));
+    return PDT_OK;
+}
+
+// One bit stream of a call: where it is, where its count is (both on the device), what its buffers hold, how many records are wanted
+struct BitJob {
+    const unsigned char *bits;
+    const unsigned long long *nbits_dev;
+    const unsigned *bitsym;
+    const long long *symidx;
+    long long bit_cap;
+    int cap;
+};
+
+// ... the bits a context's demodulation left (bits_resident)
+static BitJob job_resident(const pdt_ctx *c, int cap)
+{
+    const uint64_t nb = c->stage_len[PDT_ST_BITS];              // (what the host read back; the kernels read the device's own count)
+    return BitJob{ (const unsigned char *)c->bits.p, &((const DevScalars *)c->scal.p)->nbits, (const unsigned *)c->bitsym.p, (const long long *)c->symidx.p,
+                   nb && c->bits.p && c->scal.p ? (long long)nb : 0, cap };
+}
+
+// ... the bits of a feed-forward result buffer (FfOut, FfpOut: the count in front, the tail t), on the device's own count
+static BitJob job_result(const void *buf, const BitsTail &t, uint64_t bit_cap, int cap)
+{
+    const unsigned char *p = (const unsigned char *)buf;
+    return BitJob{ p + t.o_bits, (const unsigned long long *)p, (const unsigned *)(p + t.o_sym), (const long long *)(p + t.o_idx), (long long)bit_cap, cap };
+}
+
+// ... a string that stage_counted has brought up
+static BitJob job_staged(const DevBuf &b, uint64_t nbits, int cap)
+{
+    return BitJob{ (const unsigned char *)b.p + 16, (const unsigned long long *)b.p, nullptr, nullptr, (long long)nbits, cap };
+}
+
+// The room every stream's records take -- at most one per min_gap bits, at most the cap: stream i's from at[i] on -- and its tiles;
+// the sum of the tiles
+static long long job_rooms(const std::vector<BitJob> &jobs, long long min_gap, long long tile, std::vector<size_t> &at, std::vector<long long> &tiles)
+{
+    at.assign(jobs.size() + 1, 0);
+    tiles.resize(jobs.size());
+    long long ntiles = 0;
+    for (size_t i = 0; i < jobs.size(); i++) {
+        at[i + 1] = at[i] + (size_t)std::min<long long>(jobs[i].cap, jobs[i].bit_cap / min_gap + 1);
+        ntiles += tiles[i] = (jobs[i].bit_cap + tile - 1) / tile;
+    }
+    return ntiles;
+}
+
+extern "C++" {      // (templates: this part of the file lies inside extern "C")
+// What a run read back in one copy (`back`: the records of all streams side by side at o_rec, their counts at o_cnt) into the
+// run's results: recs holds stream i's records from at[i] on, found[i] of them counted, min(found[i], room) present
+template <typename Rec> static void unpack_back(const unsigned char *back, size_t o_rec, size_t o_cnt, size_t nrec, size_t n, std::vector<Rec> &recs,
+                                                std::vector<unsigned> &found)
+{
+    recs.resize(nrec);
+    if (nrec) memcpy(recs.data(), back + o_rec, nrec * sizeof(Rec));
+    found.resize(n);
+    if (n) memcpy(found.data(), back + o_cnt, n * sizeof(unsigned));
+}
+
+// the time stamp of stream i's source index; an empty one leaves the records' time as the kernels wrote it (the stage entries)
+typedef std::function<double(size_t, long long)> TimeOf;
+
+// Stream i's records of a run to the caller (out, and info_out where both it and infos are there: room for the stream's cap), stamped;
+// returns the number found, which may exceed the number present
+template <typename Rec, typename Info = char>
+static int deliver(const std::vector<Rec> &recs, const std::vector<size_t> &at, const std::vector<unsigned> &found, size_t i, const TimeOf &time_of, void *out,
+                   const std::vector<Info> *infos = nullptr, void *info_out = nullptr)
+{
+    const size_t have = std::min<size_t>(found[i], at[i + 1] - at[i]);
+    for (size_t k = 0; k < have; k++) {
+        Rec m = recs[at[i] + k];
+        if (time_of) m.time = time_of(i, m.time_src);
+        memcpy((unsigned char *)out + k * sizeof m, &m, sizeof m);
+        if (infos && info_out) memcpy((unsigned char *)info_out + k * sizeof(Info), &(*infos)[at[i] + k], sizeof(Info));
+    }
+    return (int)found[i];
+}
+}  // extern "C++"
+
 // ---------------------------------------------------------------- carrier measurement (pdt_tone.h)
+// k_tones over a table of segments that share p's geometry (nfft, the noise bins), through c0's tables, buffers and stream: the table
+// up, one launch, the raw records back, one synchronize (the table of the previous call is no longer read: every call ends with one);
+// then the window's sums, once per context and NFFT.  timer (may be NULL): a profiled c0's kernel times gain k_tones.
+static int tones_measure(pdt_ctx *c0, const TonePlan &p, const std::vector<ToneSeg> &table, std::vector<ToneRaw> &raw, CallTimer *timer)
+{
+    raw.resize(table.size());
+    if (!table.empty()) {
+        int rc = survey_tables(c0, p.nfft);
+        if (!rc) rc = c0->tone_table.ensure(table.size() * sizeof(ToneSeg));
+        if (!rc) rc = c0->tone_out.ensure(table.size() * sizeof(ToneRaw));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(c0->tone_table.p, table.data(), table.size() * sizeof(ToneSeg), hipMemcpyHostToDevice));
+        if (timer) HIP_TRY(timer->begin());
+        HIP_TRY(tones_launch(c0->stream, p.nfft, c0->tone_table.p, table.size(), p.noise_lo, p.noise_hi, (const float *)c0->survey_win.p,
+                             (const float *)c0->survey_tw.p, c0->tone_out.p));
+        if (timer) HIP_TRY(timer->end());
+        HIP_TRY(hipMemcpyAsync(raw.data(), c0->tone_out.p, raw.size() * sizeof(ToneRaw), hipMemcpyDeviceToHost, c0->stream));
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        if (timer) timer->commit();
+    }
+    if (c0->tone_sum_nfft != p.nfft) {
+        tone_sums(p.nfft, &c0->tone_sw, &c0->tone_sw2);
+        c0->tone_sum_nfft = p.nfft;
+    }
+    return PDT_OK;
+}
+
 // The segments of all contexts of a call in one launch over a table on the device, as the windows of a call are converted
 // (ddc_windows_launch): the first context supplies stream, tables and the two device buffers.  Every context is checked before
 // anything runs.  Nothing of any context's demodulation state is touched; a profiled first context's kernel times gain k_tones.
-static int tones_each(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, pdt_tone *out, int cap_each, int *counts)
+int pdt_tones_batch(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, pdt_tone *out, int cap_each, int *counts)
 {
     if (count < 0 || (count && (!ctxs || !out || !counts))) return PDT_ERR_ARG;
     std::vector<TonePlan> plans((size_t)count);
     for (int i = 0; i < count; i++) {
+        if (!list_arg_ok(ctxs, i, MODE_ANY, true)) return PDT_ERR_ARG;
         const pdt_ctx *c = ctxs[i];
-        if (!c) return PDT_ERR_ARG;
-        if (c->cfg.device != ctxs[0]->cfg.device || c->cfg.sample_rate != ctxs[0]->cfg.sample_rate) return PDT_ERR_ARG;
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == c) return PDT_ERR_ARG;
-        if (c->stream_open || !c->stage_len[PDT_ST_CHANNEL] || !c->channel.p) return PDT_ERR_STATE;
+        if (!channel_resident(c)) return PDT_ERR_STATE;
         const int rc = tone_plan(cfg, (double)c->cfg.sample_rate, search_range_hz(c), c->stage_len[PDT_ST_CHANNEL], cap_each, &plans[(size_t)i]);
         if (rc) return rc;
     }
     if (!count) return PDT_OK;
     pdt_ctx *c0 = ctxs[0];
-    const int nfft = plans[0].nfft;
     std::vector<ToneSeg> table;
     for (int i = 0; i < count; i++) {
         const TonePlan &p = plans[(size_t)i];
@@ -1353,45 +1501,12 @@ static int tones_each(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, 
             table.push_back(ToneSeg{ ctxs[i]->channel.p, (long long)(p.first + k * p.stride), (int32_t)table.size(), p.kmax });
     }
     if (table.size() > 0x7fffffffu) return PDT_ERR_ARG;
-    std::vector<ToneRaw> raw(table.size());
-    if (!table.empty()) {
-        HIP_TRY(hipSetDevice(c0->cfg.device));
-        int rc = survey_tables(c0, nfft);
-        if (!rc) rc = c0->tone_table.ensure(table.size() * sizeof(ToneSeg));
-        if (!rc) rc = c0->tone_out.ensure(table.size() * sizeof(ToneRaw));
-        if (rc) return rc;
-        // (the table of the previous call is no longer read: every call ends with a synchronize)
-        HIP_TRY(hipMemcpy(c0->tone_table.p, table.data(), table.size() * sizeof(ToneSeg), hipMemcpyHostToDevice));
-        hipEvent_t ea = nullptr, eb = nullptr;
-        if (c0->cfg.profile) {
-            HIP_TRY(hipEventCreate(&ea));
-            HIP_TRY(hipEventCreate(&eb));
-            HIP_TRY(hipEventRecord(ea, c0->stream));
-        }
-        HIP_TRY(tones_launch(c0->stream, nfft, c0->tone_table.p, table.size(), plans[0].noise_lo, plans[0].noise_hi, (const float *)c0->survey_win.p,
-                             (const float *)c0->survey_tw.p, c0->tone_out.p));
-        if (c0->cfg.profile) HIP_TRY(hipEventRecord(eb, c0->stream));
-        HIP_TRY(hipMemcpyAsync(raw.data(), c0->tone_out.p, raw.size() * sizeof(ToneRaw), hipMemcpyDeviceToHost, c0->stream));
-        HIP_TRY(hipStreamSynchronize(c0->stream));
-        if (c0->cfg.profile) {
-            pdt_kernel_time k;
-            memset(&k, 0, sizeof k);
-            snprintf(k.name, sizeof k.name, "k_tones");
-            k.launches = 1;
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ea, eb);
-            k.total_ms = ms;
-            (void)hipEventDestroy(ea);
-            (void)hipEventDestroy(eb);
-            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [](const pdt_kernel_time &o) { return !strcmp(o.name, "k_tones"); }),
-                             c0->ktimes.end());
-            c0->ktimes.push_back(k);
-        }
-    }
-    if (c0->tone_sum_nfft != nfft) {                                       // (the window's sums, once per context and NFFT)
-        tone_sums(nfft, &c0->tone_sw, &c0->tone_sw2);
-        c0->tone_sum_nfft = nfft;
-    }
+    if (!table.empty()) HIP_TRY(hipSetDevice(c0->cfg.device));
+    static const char *const names[1] = { "k_tones" };
+    CallTimer timer(c0, c0->stream, names, nullptr, 1);
+    std::vector<ToneRaw> raw;
+    const int rc = tones_measure(c0, plans[0], table, raw, &timer);
+    if (rc) return rc;
     size_t at = 0;
     for (int i = 0; i < count; i++) {
         const TonePlan &p = plans[(size_t)i];
@@ -1402,52 +1517,29 @@ static int tones_each(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, 
     return PDT_OK;
 }
 
-int pdt_tones_batch(pdt_ctx *const *ctxs, int count, const pdt_tone_cfg *cfg, pdt_tone *out, int cap_each, int *counts)
-{
-    return tones_each(ctxs, count, cfg, out, cap_each, counts);
-}
-
 int pdt_tones(pdt_ctx *ctx, const pdt_tone_cfg *cfg, pdt_tone *out, int cap, int *count)
 {
     if (!ctx || !out || !count) return PDT_ERR_ARG;
-    return tones_each(&ctx, 1, cfg, out, cap, count);
+    return pdt_tones_batch(&ctx, 1, cfg, out, cap, count);
 }
 
 // ---------------------------------------------------------------- ARGOS messages (pdt_argos_msg.h)
-// One bit stream of a call: where it is, where its count is (both on the device), what its buffers hold, how many records are wanted
-struct ArgosJob {
-    const unsigned char *bits;
-    const unsigned long long *nbits_dev;
-    const unsigned *bitsym;
-    const long long *symidx;
-    long long bit_cap;
-    int cap;
-};
-
 // The streams of a call through one launch of each kernel over a table on the device, as the segments of pdt_tones are measured: the first
-// context supplies stream and work buffer -- the records and counts of all streams (read back in one copy), the table, every stream's
-// tile counts and candidate bitmap.  recs: stream i's records from at[i] on, found[i] of them counted, min(found[i], room) present.
-static int argos_run(pdt_ctx *c0, const std::vector<ArgosJob> &jobs, int K, int rule, std::vector<ArgosMsg> &recs, std::vector<size_t> &at,
+// context supplies stream and work buffer (ArgosWork).  recs: stream i's records from at[i] on, found[i] of them counted, min(found[i],
+// room) present.
+static int argos_run(pdt_ctx *c0, const std::vector<BitJob> &jobs, int K, int rule, std::vector<ArgosMsg> &recs, std::vector<size_t> &at,
                      std::vector<unsigned> &found)
 {
     const size_t n = jobs.size();
     std::vector<ArgosCtx> table(n);
-    std::vector<long long> tiles(n);
-    at.assign(n + 1, 0);
-    long long ntiles = 0;
-    for (size_t i = 0; i < n; i++) {
-        // accepted messages lie at least 65 bits apart (a head's first bit behind a body of 52 bits or more; rule 1: spans do not overlap)
-        const long long room = std::min<long long>(jobs[i].cap, jobs[i].bit_cap / 65 + 1);
-        at[i + 1] = at[i] + (size_t)room;
-        tiles[i] = (jobs[i].bit_cap + ARGOS_MSG_TILE - 1) / ARGOS_MSG_TILE;
-        ntiles += tiles[i];
-    }
+    std::vector<long long> tiles;
+    // accepted messages lie at least 65 bits apart (a head's first bit behind a body of 52 bits or more; rule 1: spans do not overlap)
+    const long long ntiles = job_rooms(jobs, 65, ARGOS_MSG_TILE, at, tiles);
     if (ntiles > 0x7fffffffll) return PDT_ERR_ARG;
-    const size_t o_cnt = at[n] * sizeof(ArgosMsg), o_tab = o_cnt + ((n * sizeof(unsigned) + 15) & ~(size_t)15), o_any = o_tab + n * sizeof(ArgosCtx),
-                 o_cand = o_any + (((size_t)ntiles * sizeof(unsigned) + 15) & ~(size_t)15), total = o_cand + (size_t)ntiles * ARGOS_MSG_WORDS * 8;
+    const ArgosWork L = argos_work_layout(n, at[n], (size_t)ntiles, sizeof(ArgosMsg), sizeof(ArgosCtx), ARGOS_MSG_WORDS * 8);
     HIP_TRY(hipSetDevice(c0->cfg.device));
     int rc;
-    if ((rc = c0->argos_work.ensure(total))) return rc;
+    if ((rc = c0->argos_work.ensure(L.total))) return rc;
     unsigned char *w = (unsigned char *)c0->argos_work.p;
     long long t0 = 0;
     for (size_t i = 0; i < n; i++) {
@@ -1456,102 +1548,62 @@ static int argos_run(pdt_ctx *c0, const std::vector<ArgosJob> &jobs, int K, int 
         r.nbits = jobs[i].nbits_dev;
         r.bitsym = jobs[i].bitsym;
         r.symidx = jobs[i].symidx;
-        r.cand = (unsigned long long *)(w + o_cand) + (size_t)t0 * ARGOS_MSG_WORDS;
-        r.tile_any = (unsigned *)(w + o_any) + t0;
-        r.out = (ArgosMsg *)w + at[i];
-        r.count = (unsigned *)(w + o_cnt) + i;
+        r.cand = (unsigned long long *)(w + L.o_cand) + (size_t)t0 * ARGOS_MSG_WORDS;
+        r.tile_any = (unsigned *)(w + L.o_any) + t0;
+        r.out = (ArgosMsg *)(w + L.o_rec) + at[i];
+        r.count = (unsigned *)(w + L.o_cnt) + i;
         r.bit_cap = jobs[i].bit_cap;
         r.cap = (int)(at[i + 1] - at[i]);
         r.first_tile = (int)t0;
         t0 += tiles[i];
     }
     // (the table of the previous call is no longer read: every call ends with a synchronize)
-    HIP_TRY(hipMemcpy(w + o_tab, table.data(), n * sizeof(ArgosCtx), hipMemcpyHostToDevice));
-    hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
-    if (c0->cfg.profile) {
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(ev[0], c0->stream));
-    }
-    HIP_TRY(argos_msgs_launch(c0->stream, w + o_tab, (int)n, ntiles, K, rule, ev[1]));
-    if (c0->cfg.profile) HIP_TRY(hipEventRecord(ev[2], c0->stream));
-    std::vector<unsigned char> back(o_tab);
-    HIP_TRY(hipMemcpyAsync(back.data(), w, o_tab, hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipMemcpy(w + L.o_tab, table.data(), n * sizeof(ArgosCtx), hipMemcpyHostToDevice));
+    static const char *const names[2][2] = { { "k_argos_msgs", "k_argos_finish" }, { "k_argos_heads", "k_argos_pick" } };
+    CallTimer timer(c0, c0->stream, names[rule == ARGOS_RULE_BEST], nullptr, 2);
+    HIP_TRY(timer.begin());
+    HIP_TRY(argos_msgs_launch(c0->stream, w + L.o_tab, (int)n, ntiles, K, rule, timer.inner()));
+    HIP_TRY(timer.end());
+    std::vector<unsigned char> back(L.o_tab);
+    HIP_TRY(hipMemcpyAsync(back.data(), w, L.o_tab, hipMemcpyDeviceToHost, c0->stream));
     HIP_TRY(hipStreamSynchronize(c0->stream));
-    if (c0->cfg.profile) {
-        const char *names[2] = { rule == ARGOS_RULE_BEST ? "k_argos_heads" : "k_argos_msgs", rule == ARGOS_RULE_BEST ? "k_argos_pick" : "k_argos_finish" };
-        for (int k = 0; k < 2; k++) {
-            pdt_kernel_time kt;
-            memset(&kt, 0, sizeof kt);
-            snprintf(kt.name, sizeof kt.name, "%s", names[k]);
-            kt.launches = 1;
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-            kt.total_ms = ms;
-            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [&](const pdt_kernel_time &o) { return !strcmp(o.name, names[k]); }),
-                             c0->ktimes.end());
-            c0->ktimes.push_back(kt);
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    recs.resize(at[n]);
-    if (at[n]) memcpy(recs.data(), back.data(), at[n] * sizeof(ArgosMsg));
-    found.resize(n);
-    if (n) memcpy(found.data(), back.data() + o_cnt, n * sizeof(unsigned));
+    timer.commit();
+    unpack_back(back.data(), L.o_rec, L.o_cnt, at[n], n, recs, found);
     return PDT_OK;
 }
 
-// the whole capture's bits are on the device: a whole-capture call in one piece was the last to write them (stage-level calls and
-// pdt_stream_begin zero every stage length; a piece of a capture or of a stream clears bits_whole)
-static bool bits_resident(const pdt_ctx *c) { return c->bits_whole && !c->stream_open && c->stage_len[PDT_ST_FIR] != 0 && c->bit_time; }
-
-static int argos_each(pdt_ctx *const *ctxs, int count, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap_each, int *counts)
+// the jobs through argos_run; stream i's records to out + i * cap_each, its count to counts[i]
+static int argos_deliver(pdt_ctx *c0, const std::vector<BitJob> &jobs, int K, int rule, const TimeOf &time_of, pdt_argos_msg *out, int cap_each, int *counts)
 {
-    int K, rule;
-    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || argos_min_run(cfg, &K, &rule)) return PDT_ERR_ARG;
-    for (int i = 0; i < count; i++) {
-        const pdt_ctx *c = ctxs[i];
-        if (!c || c->cfg.mode != PDT_MODE_ARGOS || c->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == c) return PDT_ERR_ARG;
-    }
-    for (int i = 0; i < count; i++)
-        if (!bits_resident(ctxs[i])) return PDT_ERR_STATE;
-    if (!count) return PDT_OK;
-    try {
-        std::vector<ArgosJob> jobs((size_t)count);
-        for (int i = 0; i < count; i++) {
-            const pdt_ctx *c = ctxs[i];
-            const uint64_t nb = c->stage_len[PDT_ST_BITS];              // (what the host read back; the kernels read the device's own count)
-            jobs[(size_t)i] = ArgosJob{ (const unsigned char *)c->bits.p, &((const DevScalars *)c->scal.p)->nbits, (const unsigned *)c->bitsym.p,
-                                        (const long long *)c->symidx.p, nb && c->bits.p && c->scal.p ? (long long)nb : 0, cap_each };
-        }
-        std::vector<ArgosMsg> recs;
-        std::vector<size_t> at;
-        std::vector<unsigned> found;
-        const int rc = argos_run(ctxs[0], jobs, K, rule, recs, at, found);
-        if (rc) return rc;
-        for (int i = 0; i < count; i++) {
-            const size_t have = std::min<size_t>(found[(size_t)i], at[(size_t)i + 1] - at[(size_t)i]);
-            for (size_t k = 0; k < have; k++) {
-                ArgosMsg m = recs[at[(size_t)i] + k];
-                m.time = ctxs[i]->bit_time(m.time_src);
-                memcpy(&out[(size_t)i * (size_t)cap_each + k], &m, sizeof m);
-            }
-            counts[i] = (int)found[(size_t)i];
-        }
-    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    std::vector<ArgosMsg> recs;
+    std::vector<size_t> at;
+    std::vector<unsigned> found;
+    const int rc = argos_run(c0, jobs, K, rule, recs, at, found);
+    if (rc) return rc;
+    for (size_t i = 0; i < jobs.size(); i++) counts[i] = deliver(recs, at, found, i, time_of, out + i * (size_t)cap_each);
     return PDT_OK;
 }
 
 int pdt_argos_messages_batch(pdt_ctx *const *ctxs, int count, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap_each, int *counts)
 {
-    return argos_each(ctxs, count, cfg, out, cap_each, counts);
+    int K, rule;
+    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || argos_min_run(cfg, &K, &rule)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++)
+        if (!list_arg_ok(ctxs, i, PDT_MODE_ARGOS, false)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++)
+        if (!bits_resident(ctxs[i])) return PDT_ERR_STATE;
+    if (!count) return PDT_OK;
+    try {
+        std::vector<BitJob> jobs;
+        for (int i = 0; i < count; i++) jobs.push_back(job_resident(ctxs[i], cap_each));
+        return argos_deliver(ctxs[0], jobs, K, rule, [&](size_t i, long long src) { return ctxs[i]->bit_time(src); }, out, cap_each, counts);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
 }
 
 int pdt_argos_messages(pdt_ctx *ctx, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count)
 {
     if (!ctx || !count) return PDT_ERR_ARG;
-    return argos_each(&ctx, 1, cfg, out, cap, count);
+    return pdt_argos_messages_batch(&ctx, 1, cfg, out, cap, count);
 }
 
 int pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, const pdt_argos_cfg *cfg, pdt_argos_msg *out, int cap, int *count)
@@ -1560,69 +1612,34 @@ int pdt_stage_argos_messages(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nb
     if (!ctx || (!bits_host && nbits) || nbits >= (1ull << 31) || cap < 0 || (!out && cap) || !count || argos_min_run(cfg, &K, &rule)) return PDT_ERR_ARG;
     if (ctx->cfg.mode != PDT_MODE_ARGOS) return PDT_ERR_ARG;
     if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    // the string in a buffer of its own, its count in front of it: nothing the context's results live in is touched
-    int rc;
-    if ((rc = ctx->argos_bits.ensure(16 + (size_t)nbits))) return rc;
-    const unsigned long long nb = nbits;
-    HIP_TRY(hipMemcpy(ctx->argos_bits.p, &nb, sizeof nb, hipMemcpyHostToDevice));
-    if (nbits) HIP_TRY(hipMemcpy((unsigned char *)ctx->argos_bits.p + 16, bits_host, (size_t)nbits, hipMemcpyHostToDevice));
+    const int rc = stage_counted(ctx, ctx->staged_bits, bits_host, nbits, 1);
+    if (rc) return rc;
     try {
-        const std::vector<ArgosJob> jobs(1, ArgosJob{ (const unsigned char *)ctx->argos_bits.p + 16, (const unsigned long long *)ctx->argos_bits.p, nullptr,
-                                                      nullptr, (long long)nbits, cap });
-        std::vector<ArgosMsg> recs;
-        std::vector<size_t> at;
-        std::vector<unsigned> found;
-        if ((rc = argos_run(ctx, jobs, K, rule, recs, at, found))) return rc;
-        const size_t have = std::min<size_t>(found[0], at[1]);
-        if (have) memcpy(out, recs.data(), have * sizeof(ArgosMsg));
-        *count = (int)found[0];
+        return argos_deliver(ctx, std::vector<BitJob>(1, job_staged(ctx->staged_bits, nbits, cap)), K, rule, TimeOf(), out, cap, count);
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
-    return PDT_OK;
 }
 
 // ---------------------------------------------------------------- flywheel frame synchroniser (pdt_tip_sync.h)
-// One bit stream of a call, as an ArgosJob describes one
-struct TipSyncJob {
-    const unsigned char *bits;
-    const unsigned long long *nbits_dev;
-    const unsigned *bitsym;
-    const long long *symidx;
-    long long bit_cap;
-    int cap;
-};
-
 // The streams of a call through one launch of each kernel over a table on the device, as argos_run does it: the first context supplies
-// stream and work buffer -- the records, info records and counts of all streams (read back in one copy), the table, every stream's tile
-// counts, offsets and six bitmaps.  recs / infos: stream i's records from at[i] on, found[i] of them counted, min(found[i], room) present.
-static int tip_sync_run(pdt_ctx *c0, const std::vector<TipSyncJob> &jobs, TipSyncRule R, std::vector<TipSyncRec> &recs, std::vector<TipSyncInfo> &infos,
+// stream and work buffer (TipSyncWork).  recs / infos: stream i's records from at[i] on, found[i] of them counted, min(found[i], room)
+// present.
+static int tip_sync_run(pdt_ctx *c0, const std::vector<BitJob> &jobs, TipSyncRule R, std::vector<TipSyncRec> &recs, std::vector<TipSyncInfo> &infos,
                         std::vector<size_t> &at, std::vector<unsigned> &found)
 {
     const size_t n = jobs.size();
     std::vector<TipSyncCtx> table(n);
-    std::vector<long long> tiles(n);
-    at.assign(n + 1, 0);
-    long long ntiles = 0;
-    for (size_t i = 0; i < n; i++) {
-        // emitted heads lie at least 829 bits apart
-        const long long room = std::min<long long>(jobs[i].cap, jobs[i].bit_cap / TIP_SYNC_MIN_GAP + 1);
-        at[i + 1] = at[i] + (size_t)room;
-        tiles[i] = (jobs[i].bit_cap + TIP_SYNC_TILE - 1) / TIP_SYNC_TILE;
-        ntiles += tiles[i];
-    }
+    std::vector<long long> tiles;
+    const long long ntiles = job_rooms(jobs, TIP_SYNC_MIN_GAP, TIP_SYNC_TILE, at, tiles);        // (emitted heads lie at least 829 bits apart)
     if (ntiles > 0x7fffffffll) return PDT_ERR_ARG;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_info = up16(at[n] * sizeof(TipSyncRec)), o_cnt = o_info + up16(at[n] * sizeof(TipSyncInfo)), o_tab = o_cnt + up16(n * sizeof(unsigned)),
-                 o_tcnt = o_tab + up16(n * sizeof(TipSyncCtx)), o_toff = o_tcnt + up16((size_t)ntiles * sizeof(unsigned)),
-                 o_maps = o_toff + up16((size_t)ntiles * sizeof(unsigned)), map_bytes = (size_t)ntiles * TIP_SYNC_WORDS * 8, total = o_maps + 6 * map_bytes;
+    const TipSyncWork L = tip_sync_work_layout(n, at[n], (size_t)ntiles, sizeof(TipSyncRec), sizeof(TipSyncInfo), sizeof(TipSyncCtx), TIP_SYNC_WORDS * 8);
     HIP_TRY(hipSetDevice(c0->cfg.device));
     int rc;
-    if ((rc = c0->tip_sync_work.ensure(total))) return rc;
+    if ((rc = c0->tip_sync_work.ensure(L.total))) return rc;
     unsigned char *w = (unsigned char *)c0->tip_sync_work.p;
     long long t0 = 0;
     for (size_t i = 0; i < n; i++) {
         TipSyncCtx &r = table[i];
-        auto map = [&](int k) { return (unsigned long long *)(w + o_maps + (size_t)k * map_bytes) + (size_t)t0 * TIP_SYNC_WORDS; };
+        auto map = [&](int k) { return (unsigned long long *)(w + L.o_maps + (size_t)k * L.map_bytes) + (size_t)t0 * TIP_SYNC_WORDS; };
         r.bits = jobs[i].bits;
         r.nbits = jobs[i].nbits_dev;
         r.bitsym = jobs[i].bitsym;
@@ -1633,102 +1650,68 @@ static int tip_sync_run(pdt_ctx *c0, const std::vector<TipSyncJob> &jobs, TipSyn
         r.head[0] = map(3);
         r.head[1] = map(4);
         r.emit = map(5);
-        r.tile_cnt = (unsigned *)(w + o_tcnt) + t0;
-        r.tile_off = (unsigned *)(w + o_toff) + t0;
-        r.out = (TipSyncRec *)w + at[i];
-        r.info = (TipSyncInfo *)(w + o_info) + at[i];
-        r.count = (unsigned *)(w + o_cnt) + i;
+        r.tile_cnt = (unsigned *)(w + L.o_tcnt) + t0;
+        r.tile_off = (unsigned *)(w + L.o_toff) + t0;
+        r.out = (TipSyncRec *)(w + L.o_rec) + at[i];
+        r.info = (TipSyncInfo *)(w + L.o_info) + at[i];
+        r.count = (unsigned *)(w + L.o_cnt) + i;
         r.bit_cap = jobs[i].bit_cap;
         r.cap = (int)(at[i + 1] - at[i]);
         r.first_tile = (int)t0;
         t0 += tiles[i];
     }
     // (the table of the previous call is no longer read: every call ends with a synchronize)
-    HIP_TRY(hipMemcpy(w + o_tab, table.data(), n * sizeof(TipSyncCtx), hipMemcpyHostToDevice));
-    hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    if (c0->cfg.profile)
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(tip_sync_launch(c0->stream, w + o_tab, (int)n, ntiles, R, c0->cfg.profile ? ev : nullptr));
-    std::vector<unsigned char> back(o_tab);
-    HIP_TRY(hipMemcpyAsync(back.data(), w, o_tab, hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipMemcpy(w + L.o_tab, table.data(), n * sizeof(TipSyncCtx), hipMemcpyHostToDevice));
+    CallTimer timer(c0, c0->stream, tip_sync_kernel_names, nullptr, 5);
+    HIP_TRY(timer.begin());
+    HIP_TRY(tip_sync_launch(c0->stream, w + L.o_tab, (int)n, ntiles, R, timer.inner()));
+    HIP_TRY(timer.end());
+    std::vector<unsigned char> back(L.o_tab);
+    HIP_TRY(hipMemcpyAsync(back.data(), w, L.o_tab, hipMemcpyDeviceToHost, c0->stream));
     HIP_TRY(hipStreamSynchronize(c0->stream));
-    if (c0->cfg.profile) {
-        for (int k = 0; k < 5; k++) {
-            const char *name = tip_sync_kernel_names[k];
-            pdt_kernel_time kt;
-            memset(&kt, 0, sizeof kt);
-            snprintf(kt.name, sizeof kt.name, "%s", name);
-            kt.launches = 1;
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-            kt.total_ms = ms;
-            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [&](const pdt_kernel_time &o) { return !strcmp(o.name, name); }),
-                             c0->ktimes.end());
-            c0->ktimes.push_back(kt);
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    recs.resize(at[n]);
+    timer.commit();
+    unpack_back(back.data(), L.o_rec, L.o_cnt, at[n], n, recs, found);
     infos.resize(at[n]);
-    if (at[n]) {
-        memcpy(recs.data(), back.data(), at[n] * sizeof(TipSyncRec));
-        memcpy(infos.data(), back.data() + o_info, at[n] * sizeof(TipSyncInfo));
-    }
-    found.resize(n);
-    if (n) memcpy(found.data(), back.data() + o_cnt, n * sizeof(unsigned));
+    if (at[n]) memcpy(infos.data(), back.data() + L.o_info, at[n] * sizeof(TipSyncInfo));
     return PDT_OK;
 }
 
-static int tip_sync_each(pdt_ctx *const *ctxs, int count, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap_each, int *counts)
+// the jobs through tip_sync_run; stream i's records to out + i * cap_each (its info records to info + i * cap_each where info is
+// there), its count to counts[i]
+static int tip_sync_deliver(pdt_ctx *c0, const std::vector<BitJob> &jobs, TipSyncRule R, const TimeOf &time_of, pdt_frame *out, pdt_tip_sync_info *info,
+                            int cap_each, int *counts)
 {
-    TipSyncRule R;
-    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || tip_sync_rule(cfg, &R)) return PDT_ERR_ARG;
-    for (int i = 0; i < count; i++) {
-        const pdt_ctx *c = ctxs[i];
-        if (!c || c->cfg.mode != PDT_MODE_POES || c->cfg.device != ctxs[0]->cfg.device) return PDT_ERR_ARG;
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == c) return PDT_ERR_ARG;
-    }
-    for (int i = 0; i < count; i++)
-        if (!bits_resident(ctxs[i])) return PDT_ERR_STATE;
-    if (!count) return PDT_OK;
-    try {
-        std::vector<TipSyncJob> jobs((size_t)count);
-        for (int i = 0; i < count; i++) {
-            const pdt_ctx *c = ctxs[i];
-            const uint64_t nb = c->stage_len[PDT_ST_BITS];              // (what the host read back; the kernels read the device's own count)
-            jobs[(size_t)i] = TipSyncJob{ (const unsigned char *)c->bits.p, &((const DevScalars *)c->scal.p)->nbits, (const unsigned *)c->bitsym.p,
-                                          (const long long *)c->symidx.p, nb && c->bits.p && c->scal.p ? (long long)nb : 0, cap_each };
-        }
-        std::vector<TipSyncRec> recs;
-        std::vector<TipSyncInfo> infos;
-        std::vector<size_t> at;
-        std::vector<unsigned> found;
-        const int rc = tip_sync_run(ctxs[0], jobs, R, recs, infos, at, found);
-        if (rc) return rc;
-        for (int i = 0; i < count; i++) {
-            const size_t have = std::min<size_t>(found[(size_t)i], at[(size_t)i + 1] - at[(size_t)i]);
-            for (size_t k = 0; k < have; k++) {
-                TipSyncRec m = recs[at[(size_t)i] + k];
-                m.time = ctxs[i]->bit_time(m.time_src);
-                memcpy(&out[(size_t)i * (size_t)cap_each + k], &m, sizeof m);
-                if (info) memcpy(&info[(size_t)i * (size_t)cap_each + k], &infos[at[(size_t)i] + k], sizeof(TipSyncInfo));
-            }
-            counts[i] = (int)found[(size_t)i];
-        }
-    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    std::vector<TipSyncRec> recs;
+    std::vector<TipSyncInfo> infos;
+    std::vector<size_t> at;
+    std::vector<unsigned> found;
+    const int rc = tip_sync_run(c0, jobs, R, recs, infos, at, found);
+    if (rc) return rc;
+    for (size_t i = 0; i < jobs.size(); i++)
+        counts[i] = deliver(recs, at, found, i, time_of, out + i * (size_t)cap_each, &infos, info ? info + i * (size_t)cap_each : nullptr);
     return PDT_OK;
 }
 
 int pdt_tip_sync_batch(pdt_ctx *const *ctxs, int count, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap_each, int *counts)
 {
-    return tip_sync_each(ctxs, count, cfg, out, info, cap_each, counts);
+    TipSyncRule R;
+    if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || tip_sync_rule(cfg, &R)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++)
+        if (!list_arg_ok(ctxs, i, PDT_MODE_POES, false)) return PDT_ERR_ARG;
+    for (int i = 0; i < count; i++)
+        if (!bits_resident(ctxs[i])) return PDT_ERR_STATE;
+    if (!count) return PDT_OK;
+    try {
+        std::vector<BitJob> jobs;
+        for (int i = 0; i < count; i++) jobs.push_back(job_resident(ctxs[i], cap_each));
+        return tip_sync_deliver(ctxs[0], jobs, R, [&](size_t i, long long src) { return ctxs[i]->bit_time(src); }, out, info, cap_each, counts);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
 }
 
 int pdt_tip_sync(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count)
 {
     if (!ctx || !count) return PDT_ERR_ARG;
-    return tip_sync_each(&ctx, 1, cfg, out, info, cap, count);
+    return pdt_tip_sync_batch(&ctx, 1, cfg, out, info, cap, count);
 }
 
 int pdt_stage_tip_sync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, const pdt_tip_sync_cfg *cfg, pdt_frame *out, pdt_tip_sync_info *info,
@@ -1738,27 +1721,11 @@ int pdt_stage_tip_sync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits, c
     if (!ctx || (!bits_host && nbits) || nbits >= (1ull << 31) || cap < 0 || (!out && cap) || !count || tip_sync_rule(cfg, &R)) return PDT_ERR_ARG;
     if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;
     if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    // the string in a buffer of its own, its count in front of it: nothing the context's results live in is touched
-    int rc;
-    if ((rc = ctx->tip_sync_bits.ensure(16 + (size_t)nbits))) return rc;
-    const unsigned long long nb = nbits;
-    HIP_TRY(hipMemcpy(ctx->tip_sync_bits.p, &nb, sizeof nb, hipMemcpyHostToDevice));
-    if (nbits) HIP_TRY(hipMemcpy((unsigned char *)ctx->tip_sync_bits.p + 16, bits_host, (size_t)nbits, hipMemcpyHostToDevice));
+    const int rc = stage_counted(ctx, ctx->staged_bits, bits_host, nbits, 1);
+    if (rc) return rc;
     try {
-        const std::vector<TipSyncJob> jobs(1, TipSyncJob{ (const unsigned char *)ctx->tip_sync_bits.p + 16, (const unsigned long long *)ctx->tip_sync_bits.p,
-                                                          nullptr, nullptr, (long long)nbits, cap });
-        std::vector<TipSyncRec> recs;
-        std::vector<TipSyncInfo> infos;
-        std::vector<size_t> at;
-        std::vector<unsigned> found;
-        if ((rc = tip_sync_run(ctx, jobs, R, recs, infos, at, found))) return rc;
-        const size_t have = std::min<size_t>(found[0], at[1]);
-        if (have) memcpy(out, recs.data(), have * sizeof(TipSyncRec));
-        if (have && info) memcpy(info, infos.data(), have * sizeof(TipSyncInfo));
-        *count = (int)found[0];
+        return tip_sync_deliver(ctx, std::vector<BitJob>(1, job_staged(ctx->staged_bits, nbits, cap)), R, TimeOf(), out, info, cap, count);
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
-    return PDT_OK;
 }
 
 // ---------------------------------------------------------------- feed-forward bits (pdt_ff.h)
@@ -1770,23 +1737,9 @@ struct FfJob {
     double range_hz;
 };
 
-// a context's result buffer: the count, the record, then the time source, soft values, bit -> symbol map and characters of `cap` bits
-struct FfOut {
-    size_t o_idx, o_soft, o_sym, o_bits, total;
-    explicit FfOut(uint64_t cap)
-    {
-        const size_t c = ((size_t)cap + 15) & ~(size_t)15;
-        o_idx = 64;
-        o_soft = o_idx + 8 * c;
-        o_sym = o_soft + 4 * c;
-        o_bits = o_sym + 4 * c;
-        total = o_bits + c;
-    }
-};
-
 // The carrier of every stream: the first segment of pdt_tones at its defaults, all streams in one launch of k_tones through the first
-// context's tables and buffers; the frequency is derived here, on the host, in double.  A stream without a whole segment, a rate without
-// an allowed segment length and a record that is not valid leave residual 0 and valid 0.
+// context's tables and buffers (tones_measure); the frequency is derived here, on the host, in double.  A stream without a whole
+// segment, a rate without an allowed segment length and a record that is not valid leave residual 0 and valid 0.
 static int ff_tones(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, std::vector<double> &residual, std::vector<int> &valid)
 {
     const size_t n = jobs.size();
@@ -1802,20 +1755,9 @@ static int ff_tones(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, 
         plan = p;
     }
     if (table.empty()) return PDT_OK;
-    int rc = survey_tables(c0, plan.nfft);
-    if (!rc) rc = c0->tone_table.ensure(table.size() * sizeof(ToneSeg));
-    if (!rc) rc = c0->tone_out.ensure(table.size() * sizeof(ToneRaw));
+    std::vector<ToneRaw> raw;
+    const int rc = tones_measure(c0, plan, table, raw, nullptr);
     if (rc) return rc;
-    std::vector<ToneRaw> raw(table.size());
-    HIP_TRY(hipMemcpy(c0->tone_table.p, table.data(), table.size() * sizeof(ToneSeg), hipMemcpyHostToDevice));
-    HIP_TRY(tones_launch(c0->stream, plan.nfft, c0->tone_table.p, table.size(), plan.noise_lo, plan.noise_hi, (const float *)c0->survey_win.p,
-                         (const float *)c0->survey_tw.p, c0->tone_out.p));
-    HIP_TRY(hipMemcpyAsync(raw.data(), c0->tone_out.p, raw.size() * sizeof(ToneRaw), hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
-    if (c0->tone_sum_nfft != plan.nfft) {
-        tone_sums(plan.nfft, &c0->tone_sw, &c0->tone_sw2);
-        c0->tone_sum_nfft = plan.nfft;
-    }
     plan.nseg = 1;
     for (size_t i = 0; i < n; i++) {
         if (rec[i] < 0) continue;
@@ -1830,9 +1772,9 @@ static int ff_tones(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, 
 }
 
 // The streams of a call through one launch of each kernel over a table on the device: the first context supplies stream, rotation table
-// and the work buffer (table, periods, the mixed streams, the metrics); every stream's bits, count and record go to its owner's buffer
-// and stay there.  syncs (may be NULL): the records, which k_ff_pick also leaves side by side in the work buffer, read back in one copy
-// before the one synchronize that ends the call.
+// and the work buffer (FfWork); every stream's bits, count and record go to its owner's buffer (FfOut) and stay there.  syncs (may be
+// NULL): the records, which k_ff_pick also leaves side by side in the work buffer, read back in one copy before the one synchronize
+// that ends the call.
 static int ff_run(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, const pdt_ff_cfg *cfg, pdt_ff_sync *syncs)
 {
     int H, R, given;
@@ -1850,33 +1792,30 @@ static int ff_run(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, co
     std::vector<long long> periods((size_t)nr);
     for (int r = -R; r <= R; r++) periods[(size_t)(r + R)] = ff_period(H, r, ppm);
     const long long pmin = periods.front(), pmax = periods.back();
-    const size_t o_per = n * sizeof(FfWin), o_v = o_per + (((size_t)nr * 8 + 15) & ~(size_t)15), metric_each = (size_t)nr * (size_t)(2 * H) * 8;
-    std::vector<unsigned char> head(o_v);
-    FfWin *table = (FfWin *)head.data();
-    memcpy(head.data() + o_per, periods.data(), (size_t)nr * 8);
-    std::vector<size_t> at_v(n);
-    size_t at = o_v;
+    std::vector<long long> len(n);
+    for (size_t i = 0; i < n; i++) len[i] = (long long)std::min<uint64_t>(jobs[i].n, 2ull * rate);
+    const FfWork W(len, (size_t)nr, (size_t)H, sizeof(FfWin), sizeof(FfSync));
+    std::vector<unsigned char> head(W.o_v);
+    FfWin *table = (FfWin *)(head.data() + W.o_tab);
+    memcpy(head.data() + W.o_per, periods.data(), (size_t)nr * 8);
     long long tiles = 0, groups = 0;
     for (size_t i = 0; i < n; i++) {
-        const long long L = (long long)std::min<uint64_t>(jobs[i].n, 2ull * rate);
-        const uint64_t cap = (uint64_t)(ff_halves(L, 0, pmin) >> 1);
-        const FfOut o(cap);
+        const uint64_t cap = (uint64_t)(ff_halves(len[i], 0, pmin) >> 1);
+        const FfOut o = ff_out_layout(cap);
         pdt_ctx *own = jobs[i].owner;
         own->ff_rate = 0;
         if ((rc = own->ff_out.ensure(o.total))) return rc;
         own->ff_cap = cap;
-        at_v[i] = at;
-        at += ((size_t)L * 8 + 15) & ~(size_t)15;
         FfWin &w = table[i];
         unsigned char *p = (unsigned char *)own->ff_out.p;
         w.y = jobs[i].y;
-        w.bits = p + o.o_bits;
-        w.soft = (float *)(p + o.o_soft);
-        w.symidx = (long long *)(p + o.o_idx);
-        w.bitsym = (unsigned *)(p + o.o_sym);
+        w.bits = p + o.t.o_bits;
+        w.soft = (float *)(p + o.t.o_soft);
+        w.symidx = (long long *)(p + o.t.o_idx);
+        w.bitsym = (unsigned *)(p + o.t.o_sym);
         w.nbits = (unsigned long long *)p;
         w.sync = (FfSync *)(p + 16);
-        w.L = L;
+        w.L = len[i];
         w.residual_hz = residual[i];
         w.step = ddc_step((double)rate, residual[i]);
         w.tone_valid = valid[i];
@@ -1884,46 +1823,28 @@ static int ff_run(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, co
         w.group0 = (int32_t)groups;
         w.segs = (int32_t)((cap + FF_SEARCH_BITS - 1) / FF_SEARCH_BITS);
         w.reserved_ = 0;
-        tiles += (L + FF_MIX_TILE - 1) / FF_MIX_TILE;
+        tiles += (len[i] + FF_MIX_TILE - 1) / FF_MIX_TILE;
         groups += (long long)nr * w.segs;
         if (tiles > 0x7fffffffll || groups > 0x7fffffffll) return PDT_ERR_ARG;
     }
-    const size_t o_metric = at, o_syncs = o_metric + n * metric_each, total = o_syncs + n * sizeof(FfSync);
-    if ((rc = c0->ff_work.ensure(total))) return rc;
+    if ((rc = c0->ff_work.ensure(W.total))) return rc;
     unsigned char *wk = (unsigned char *)c0->ff_work.p;
     for (size_t i = 0; i < n; i++) {
-        table[i].v = (float *)(wk + at_v[i]);
-        table[i].metric = (unsigned long long *)(wk + o_metric + i * metric_each);
+        table[i].v = (float *)(wk + W.v[i]);
+        table[i].metric = (unsigned long long *)(wk + W.o_metric + i * W.metric_each);
     }
     // (the table of the previous call is no longer read: every call ends with a synchronize)
-    HIP_TRY(hipMemcpy(wk, head.data(), o_v, hipMemcpyHostToDevice));
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    if (c0->cfg.profile) {
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(ev[0], c0->stream));
-    }
-    HIP_TRY(ff_launch(c0->stream, wk, (int)n, tiles, groups, (const long long *)(wk + o_per), R, H, pmax, (const float *)c0->an_tab.p, wk + o_metric,
-                      n * metric_each, wk + o_syncs, c0->cfg.profile ? ev + 1 : nullptr));
-    if (c0->cfg.profile) HIP_TRY(hipEventRecord(ev[3], c0->stream));
+    HIP_TRY(hipMemcpy(wk, head.data(), W.o_v, hipMemcpyHostToDevice));
+    static const char *const names[3] = { "k_ff_mix", "k_ff_search", "k_ff_pick" };
+    CallTimer timer(c0, c0->stream, names, nullptr, 3);
+    HIP_TRY(timer.begin());
+    HIP_TRY(ff_launch(c0->stream, wk + W.o_tab, (int)n, tiles, groups, (const long long *)(wk + W.o_per), R, H, pmax, (const float *)c0->an_tab.p,
+                      wk + W.o_metric, n * W.metric_each, wk + W.o_syncs, timer.inner()));
+    HIP_TRY(timer.end());
     std::vector<FfSync> back(n);
-    HIP_TRY(hipMemcpyAsync(back.data(), wk + o_syncs, n * sizeof(FfSync), hipMemcpyDeviceToHost, c0->stream));
+    HIP_TRY(hipMemcpyAsync(back.data(), wk + W.o_syncs, n * sizeof(FfSync), hipMemcpyDeviceToHost, c0->stream));
     HIP_TRY(hipStreamSynchronize(c0->stream));
-    if (c0->cfg.profile) {
-        const char *names[3] = { "k_ff_mix", "k_ff_search", "k_ff_pick" };
-        for (int k = 0; k < 3; k++) {
-            pdt_kernel_time kt;
-            memset(&kt, 0, sizeof kt);
-            snprintf(kt.name, sizeof kt.name, "%s", names[k]);
-            kt.launches = 1;
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-            kt.total_ms = ms;
-            c0->ktimes.erase(std::remove_if(c0->ktimes.begin(), c0->ktimes.end(), [&](const pdt_kernel_time &o) { return !strcmp(o.name, names[k]); }),
-                             c0->ktimes.end());
-            c0->ktimes.push_back(kt);
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
+    timer.commit();
     for (size_t i = 0; i < n; i++) {
         jobs[i].owner->ff_rate = rate;
         if (syncs) memcpy(&syncs[i], &back[i], sizeof(pdt_ff_sync));
@@ -1935,18 +1856,13 @@ static int ff_run(pdt_ctx *c0, const std::vector<FfJob> &jobs, uint32_t rate, co
 static int ff_check(pdt_ctx *const *ctxs, int count)
 {
     if (count < 0 || (count && !ctxs)) return PDT_ERR_ARG;
-    for (int i = 0; i < count; i++) {
-        const pdt_ctx *c = ctxs[i];
-        if (!c || c->cfg.mode != PDT_MODE_ARGOS) return PDT_ERR_ARG;
-        if (c->cfg.device != ctxs[0]->cfg.device || c->cfg.sample_rate != ctxs[0]->cfg.sample_rate) return PDT_ERR_ARG;
-        for (int j = 0; j < i; j++)
-            if (ctxs[j] == c) return PDT_ERR_ARG;
-    }
+    for (int i = 0; i < count; i++)
+        if (!list_arg_ok(ctxs, i, PDT_MODE_ARGOS, true)) return PDT_ERR_ARG;
     int H, R, given;
     double ppm, res;
     if (count && ff_plan(nullptr, ctxs[0]->cfg.sample_rate, &H, &R, &ppm, &given, &res)) return PDT_ERR_ARG;
     for (int i = 0; i < count; i++)
-        if (ctxs[i]->stream_open || !ctxs[i]->stage_len[PDT_ST_CHANNEL] || !ctxs[i]->channel.p) return PDT_ERR_STATE;
+        if (!channel_resident(ctxs[i])) return PDT_ERR_STATE;
     return PDT_OK;
 }
 
@@ -1980,106 +1896,74 @@ int pdt_stage_ff_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_
     double ppm, res;
     if (!ctx || !sync || (!iq_host && n) || ctx->cfg.mode != PDT_MODE_ARGOS || ff_plan(cfg, rate, &H, &R, &ppm, &given, &res)) return PDT_ERR_ARG;
     if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    // the stream in a buffer of its own (the first 2 Fs samples are all that is read, the tone's segment lies inside them): nothing
-    // the context's results live in is touched
+    // (the first 2 Fs samples are all that is read, the tone's segment lies inside them)
     const uint64_t keep = std::min<uint64_t>(n, 2ull * rate);
-    int rc;
-    if ((rc = ctx->ff_in.ensure((size_t)keep * 8 + 16))) return rc;
-    if (keep) HIP_TRY(hipMemcpy(ctx->ff_in.p, iq_host, (size_t)keep * 8, hipMemcpyHostToDevice));
+    const int rc = stage_iq(ctx, ctx->staged_iq, iq_host, keep);
+    if (rc) return rc;
     try {
-        const std::vector<FfJob> jobs(1, FfJob{ ctx, (const float *)ctx->ff_in.p, keep, -1.0 });
+        const std::vector<FfJob> jobs(1, FfJob{ ctx, (const float *)ctx->staged_iq.p, keep, -1.0 });
         return ff_run(ctx, jobs, rate, cfg, sync);
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+// What pdt_ff_read and pdt_ffp_read answer from a result buffer (FfOut, FfpOut: `head` bytes with the count and, at 16, the record;
+// the tail t of bit_cap bits): the record, the count, and the first min(cap, count) bits, soft values and time sources
+static int read_bits_result(pdt_ctx *ctx, const DevBuf &buf, size_t head_bytes, const BitsTail &t, uint64_t bit_cap, void *sync, size_t sync_bytes,
+                            uint8_t *bits, float *soft, int64_t *index, uint64_t cap, uint64_t *count)
+{
+    HIP_TRY(hipSetDevice(ctx->cfg.device));
+    unsigned char head[128];
+    if (head_bytes > sizeof head) return PDT_ERR_ARG;
+    HIP_TRY(hipMemcpy(head, buf.p, head_bytes, hipMemcpyDeviceToHost));
+    unsigned long long nb;
+    memcpy(&nb, head, sizeof nb);
+    nb = std::min<unsigned long long>(nb, bit_cap);
+    if (sync) memcpy(sync, head + 16, sync_bytes);
+    const unsigned char *p = (const unsigned char *)buf.p;
+    const size_t k = (size_t)std::min<uint64_t>(cap, nb);
+    if (bits && k) HIP_TRY(hipMemcpy(bits, p + t.o_bits, k, hipMemcpyDeviceToHost));
+    if (soft && k) HIP_TRY(hipMemcpy(soft, p + t.o_soft, k * 4, hipMemcpyDeviceToHost));
+    if (index && k) HIP_TRY(hipMemcpy(index, p + t.o_idx, k * 8, hipMemcpyDeviceToHost));
+    *count = nb;
+    return PDT_OK;
 }
 
 int pdt_ff_read(pdt_ctx *ctx, pdt_ff_sync *sync, uint8_t *bits, float *soft, int64_t *index, uint64_t cap, uint64_t *count)
 {
     if (!ctx || !count) return PDT_ERR_ARG;
     if (!ctx->ff_rate || !ctx->ff_out.p) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    unsigned char head[64];
-    HIP_TRY(hipMemcpy(head, ctx->ff_out.p, sizeof head, hipMemcpyDeviceToHost));
-    unsigned long long nb;
-    memcpy(&nb, head, sizeof nb);
-    nb = std::min<unsigned long long>(nb, ctx->ff_cap);
-    if (sync) memcpy(sync, head + 16, sizeof *sync);
-    const FfOut o(ctx->ff_cap);
-    const unsigned char *p = (const unsigned char *)ctx->ff_out.p;
-    const size_t k = (size_t)std::min<uint64_t>(cap, nb);
-    if (bits && k) HIP_TRY(hipMemcpy(bits, p + o.o_bits, k, hipMemcpyDeviceToHost));
-    if (soft && k) HIP_TRY(hipMemcpy(soft, p + o.o_soft, k * 4, hipMemcpyDeviceToHost));
-    if (index && k) HIP_TRY(hipMemcpy(index, p + o.o_idx, k * 8, hipMemcpyDeviceToHost));
-    *count = nb;
-    return PDT_OK;
+    const FfOut o = ff_out_layout(ctx->ff_cap);
+    return read_bits_result(ctx, ctx->ff_out, o.head, o.t, ctx->ff_cap, sync, sizeof *sync, bits, soft, index, cap, count);
 }
 
-static int ff_messages_each(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule_cfg, pdt_ff_sync *syncs, pdt_argos_msg *out,
-                            int cap_each, int *counts)
+int pdt_ff_messages_batch(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule_cfg, pdt_ff_sync *syncs, pdt_argos_msg *out,
+                          int cap_each, int *counts)
 {
     int K, rule;
     if (count < 0 || cap_each < 0 || (count && (!ctxs || !counts || (!out && cap_each))) || argos_min_run(rule_cfg, &K, &rule)) return PDT_ERR_ARG;
-    int rc = ff_each(ctxs, count, cfg, syncs);
+    const int rc = ff_each(ctxs, count, cfg, syncs);
     if (rc || !count) return rc;
     try {
-        std::vector<ArgosJob> jobs((size_t)count);
-        for (int i = 0; i < count; i++) {
-            const pdt_ctx *c = ctxs[i];
-            const FfOut o(c->ff_cap);
-            const unsigned char *p = (const unsigned char *)c->ff_out.p;
-            jobs[(size_t)i] = ArgosJob{ p + o.o_bits, (const unsigned long long *)p, (const unsigned *)(p + o.o_sym), (const long long *)(p + o.o_idx),
-                                        (long long)c->ff_cap, cap_each };
-        }
-        std::vector<ArgosMsg> recs;
-        std::vector<size_t> at;
-        std::vector<unsigned> found;
-        if ((rc = argos_run(ctxs[0], jobs, K, rule, recs, at, found))) return rc;
+        std::vector<BitJob> jobs;
+        for (int i = 0; i < count; i++) jobs.push_back(job_result(ctxs[i]->ff_out.p, ff_out_layout(ctxs[i]->ff_cap).t, ctxs[i]->ff_cap, cap_each));
         const double fs = (double)ctxs[0]->cfg.sample_rate;
-        for (int i = 0; i < count; i++) {
-            const size_t have = std::min<size_t>(found[(size_t)i], at[(size_t)i + 1] - at[(size_t)i]);
-            for (size_t k = 0; k < have; k++) {
-                ArgosMsg m = recs[at[(size_t)i] + k];
-                m.time = (double)m.time_src / fs;
-                memcpy(&out[(size_t)i * (size_t)cap_each + k], &m, sizeof m);
-            }
-            counts[i] = (int)found[(size_t)i];
-        }
+        return argos_deliver(ctxs[0], jobs, K, rule, [fs](size_t, long long src) { return (double)src / fs; }, out, cap_each, counts);
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
-    return PDT_OK;
-}
-
-int pdt_ff_messages_batch(pdt_ctx *const *ctxs, int count, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule, pdt_ff_sync *syncs, pdt_argos_msg *out,
-                          int cap_each, int *counts)
-{
-    return ff_messages_each(ctxs, count, cfg, rule, syncs, out, cap_each, counts);
 }
 
 int pdt_ff_messages(pdt_ctx *ctx, const pdt_ff_cfg *cfg, const pdt_argos_cfg *rule, pdt_ff_sync *sync, pdt_argos_msg *out, int cap, int *count)
 {
     if (!ctx || !count) return PDT_ERR_ARG;
-    return ff_messages_each(&ctx, 1, cfg, rule, sync, out, cap, count);
+    return pdt_ff_messages_batch(&ctx, 1, cfg, rule, sync, out, cap, count);
 }
 
 // ---------------------------------------------------------------- feed-forward POES bits (pdt_ffp.h)
-// a context's result buffer: the count, the record, then the per-block table, the positions, and the time source, soft values, bit ->
-// symbol map and characters of `cap` bits
-struct FfpOut {
-    size_t o_blocks, o_pos, o_idx, o_soft, o_sym, o_bits, total;
-    FfpOut(uint64_t nb, uint64_t cap)
-    {
-        const size_t c = ((size_t)cap + 15) & ~(size_t)15;
-        o_blocks = 128;
-        o_pos = o_blocks + (((size_t)nb * sizeof(FfpBlock) + 15) & ~(size_t)15);
-        o_idx = o_pos + ((((size_t)nb + 1) * 8 + 15) & ~(size_t)15);
-        o_soft = o_idx + 8 * c;
-        o_sym = o_soft + 4 * c;
-        o_bits = o_sym + 4 * c;
-        total = o_bits + c + 16;
-    }
-};
+// where the regions of a context's result buffer lie
+static FfpOut ffp_out_of(const pdt_ctx *c) { return ffp_out_layout((size_t)c->ffp_blocks, (size_t)c->ffp_cap, sizeof(FfpBlock)); }
 
 // The carrier of the stream y (device, n samples): every segment of pdt_tones at its defaults and stride nfft, in one launch of k_tones
-// through the context's tables and buffers; the frequencies are derived here, on the host, in double.  tones: one record per segment.
+// through the context's tables and buffers (tones_measure); the frequencies are derived here, on the host, in double.  tones: one record
+// per segment.
 static int ffp_tones(pdt_ctx *c, const float *y, uint64_t n, uint32_t rate, double range_hz, std::vector<pdt_tone> &tones, int *nfft)
 {
     tones.clear();
@@ -2091,20 +1975,9 @@ static int ffp_tones(pdt_ctx *c, const float *y, uint64_t n, uint32_t rate, doub
     if (tone_plan(nullptr, (double)rate, range_hz, n, (int)want, &plan) != PDT_OK || !plan.nseg) return PDT_OK;
     std::vector<ToneSeg> table((size_t)plan.nseg);
     for (uint64_t j = 0; j < plan.nseg; j++) table[(size_t)j] = ToneSeg{ y, (long long)(plan.first + j * plan.stride), (int32_t)j, plan.kmax };
-    int rc = survey_tables(c, plan.nfft);
-    if (!rc) rc = c->tone_table.ensure(table.size() * sizeof(ToneSeg));
-    if (!rc) rc = c->tone_out.ensure(table.size() * sizeof(ToneRaw));
+    std::vector<ToneRaw> raw;
+    const int rc = tones_measure(c, plan, table, raw, nullptr);
     if (rc) return rc;
-    std::vector<ToneRaw> raw(table.size());
-    HIP_TRY(hipMemcpy(c->tone_table.p, table.data(), table.size() * sizeof(ToneSeg), hipMemcpyHostToDevice));
-    HIP_TRY(tones_launch(c->stream, plan.nfft, c->tone_table.p, table.size(), plan.noise_lo, plan.noise_hi, (const float *)c->survey_win.p,
-                         (const float *)c->survey_tw.p, c->tone_out.p));
-    HIP_TRY(hipMemcpyAsync(raw.data(), c->tone_out.p, raw.size() * sizeof(ToneRaw), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->tone_sum_nfft != plan.nfft) {
-        tone_sums(plan.nfft, &c->tone_sw, &c->tone_sw2);
-        c->tone_sum_nfft = plan.nfft;
-    }
     tones.resize(table.size());
     tones_derive(raw.data(), plan, (double)rate, 0.0, c->tone_sw, c->tone_sw2, tones.data());
     return PDT_OK;
@@ -2129,43 +2002,25 @@ static int ffp_run(pdt_ctx *c, const float *y, uint64_t n, uint32_t rate, double
     ffp_steps(tones.data(), tones.size(), nfft, r, given, residual, steps, starts, &head);
     const uint64_t cap = ffp_bit_cap(r);
     if (cap >= (1ull << 31)) return PDT_ERR_ARG;
-    const FfpOut o((uint64_t)r.nb, cap);
+    const FfpOut o = ffp_out_layout((size_t)r.nb, (size_t)cap, sizeof(FfpBlock));
     c->ffp_rate = 0;
     if ((rc = c->ffp_out.ensure(o.total))) return rc;
     if ((rc = c->ffp_work.ensure(ffp_work_bytes(r, steps.size())))) return rc;
     c->ffp_cap = cap;
     c->ffp_blocks = (uint64_t)r.nb;
-    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    if (c->cfg.profile) {
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(ev[0], c->stream));
-    }
+    static const char *const names[4] = { "k_ffp_mix", "k_ffp_search", "k_ffp_track", "k_ffp_bits" };
+    static const int launches[4] = { 1, 1, 2, 1 };
+    CallTimer timer(c, c->stream, names, launches, 4);
+    HIP_TRY(timer.begin());                                                // (in front of ffp_run_device's uploads)
     unsigned char *p = (unsigned char *)c->ffp_out.p;
     const FfpOutPtrs ptrs{ (unsigned long long *)p, (FfpSync *)(p + 16), (FfpBlock *)(p + o.o_blocks), (unsigned long long *)(p + o.o_pos),
-                           (long long *)(p + o.o_idx), (float *)(p + o.o_soft), (unsigned *)(p + o.o_sym), p + o.o_bits };
-    if ((rc = ffp_run_device(c->stream, y, r, head, steps, starts, (const float *)c->an_tab.p, c->ffp_work.p, ptrs, cap,
-                             c->cfg.profile ? ev + 1 : nullptr)))
-        return rc;
-    if (c->cfg.profile) HIP_TRY(hipEventRecord(ev[4], c->stream));
+                           (long long *)(p + o.t.o_idx), (float *)(p + o.t.o_soft), (unsigned *)(p + o.t.o_sym), p + o.t.o_bits };
+    if ((rc = ffp_run_device(c->stream, y, r, head, steps, starts, (const float *)c->an_tab.p, c->ffp_work.p, ptrs, cap, timer.inner()))) return rc;
+    HIP_TRY(timer.end());
     FfpSync back;
-    HIP_TRY(hipMemcpyAsync(&back, (unsigned char *)c->ffp_out.p + 16, sizeof back, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&back, p + 16, sizeof back, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->cfg.profile) {
-        const char *names[4] = { "k_ffp_mix", "k_ffp_search", "k_ffp_track", "k_ffp_bits" };
-        for (int k = 0; k < 4; k++) {
-            pdt_kernel_time kt;
-            memset(&kt, 0, sizeof kt);
-            snprintf(kt.name, sizeof kt.name, "%s", names[k]);
-            kt.launches = k == 2 ? 2 : 1;
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-            kt.total_ms = ms;
-            c->ktimes.erase(std::remove_if(c->ktimes.begin(), c->ktimes.end(), [&](const pdt_kernel_time &x) { return !strcmp(x.name, names[k]); }),
-                            c->ktimes.end());
-            c->ktimes.push_back(kt);
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
+    timer.commit();
     c->ffp_rate = rate;
     if (sync) memcpy(sync, &back, sizeof back);
     return PDT_OK;
@@ -2179,7 +2034,7 @@ static int ffp_check(const pdt_ctx *c, const pdt_ffp_cfg *cfg)
     int given;
     double res;
     if (ffp_plan(cfg, c->cfg.sample_rate, 0, &r, &given, &res)) return PDT_ERR_ARG;
-    if (c->stream_open || !c->stage_len[PDT_ST_CHANNEL] || !c->channel.p) return PDT_ERR_STATE;
+    if (!channel_resident(c)) return PDT_ERR_STATE;
     return PDT_OK;
 }
 
@@ -2201,11 +2056,7 @@ static int ffp_stage_in(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint6
     double res;
     if (!ctx || (!iq_host && n) || ctx->cfg.mode != PDT_MODE_POES || ffp_plan(cfg, rate, n, &r, &given, &res)) return PDT_ERR_ARG;
     if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    int rc;
-    if ((rc = ctx->ffp_in.ensure((size_t)n * 8 + 16))) return rc;
-    if (n) HIP_TRY(hipMemcpy(ctx->ffp_in.p, iq_host, (size_t)n * 8, hipMemcpyHostToDevice));
-    return PDT_OK;
+    return stage_iq(ctx, ctx->staged_iq, iq_host, n);
 }
 
 int pdt_stage_ffp_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ffp_cfg *cfg, pdt_ffp_sync *sync)
@@ -2214,7 +2065,7 @@ int pdt_stage_ffp_bits(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64
     const int rc = ffp_stage_in(ctx, rate, iq_host, n, cfg);
     if (rc) return rc;
     try {
-        return ffp_run(ctx, (const float *)ctx->ffp_in.p, n, rate, -1.0, cfg, sync);
+        return ffp_run(ctx, (const float *)ctx->staged_iq.p, n, rate, -1.0, cfg, sync);
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
 }
 
@@ -2222,21 +2073,8 @@ int pdt_ffp_read(pdt_ctx *ctx, pdt_ffp_sync *sync, uint8_t *bits, float *soft, i
 {
     if (!ctx || !count) return PDT_ERR_ARG;
     if (!ctx->ffp_rate || !ctx->ffp_out.p) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    unsigned char head[128];
-    HIP_TRY(hipMemcpy(head, ctx->ffp_out.p, sizeof head, hipMemcpyDeviceToHost));
-    unsigned long long nb;
-    memcpy(&nb, head, sizeof nb);
-    nb = std::min<unsigned long long>(nb, ctx->ffp_cap);
-    if (sync) memcpy(sync, head + 16, sizeof *sync);
-    const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
-    const unsigned char *p = (const unsigned char *)ctx->ffp_out.p;
-    const size_t k = (size_t)std::min<uint64_t>(cap, nb);
-    if (bits && k) HIP_TRY(hipMemcpy(bits, p + o.o_bits, k, hipMemcpyDeviceToHost));
-    if (soft && k) HIP_TRY(hipMemcpy(soft, p + o.o_soft, k * 4, hipMemcpyDeviceToHost));
-    if (index && k) HIP_TRY(hipMemcpy(index, p + o.o_idx, k * 8, hipMemcpyDeviceToHost));
-    *count = nb;
-    return PDT_OK;
+    const FfpOut o = ffp_out_of(ctx);
+    return read_bits_result(ctx, ctx->ffp_out, o.head, o.t, ctx->ffp_cap, sync, sizeof *sync, bits, soft, index, cap, count);
 }
 
 int pdt_ffp_blocks(pdt_ctx *ctx, pdt_ffp_block *out, uint64_t cap, uint64_t *count)
@@ -2244,103 +2082,68 @@ int pdt_ffp_blocks(pdt_ctx *ctx, pdt_ffp_block *out, uint64_t cap, uint64_t *cou
     if (!ctx || !count || (!out && cap)) return PDT_ERR_ARG;
     if (!ctx->ffp_rate || !ctx->ffp_out.p) return PDT_ERR_STATE;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
-    const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
     const size_t k = (size_t)std::min<uint64_t>(cap, ctx->ffp_blocks);
-    if (k) HIP_TRY(hipMemcpy(out, (const unsigned char *)ctx->ffp_out.p + o.o_blocks, k * sizeof(pdt_ffp_block), hipMemcpyDeviceToHost));
+    if (k) HIP_TRY(hipMemcpy(out, (const unsigned char *)ctx->ffp_out.p + ffp_out_of(ctx).o_blocks, k * sizeof(pdt_ffp_block), hipMemcpyDeviceToHost));
     *count = ctx->ffp_blocks;
     return PDT_OK;
 }
 
-// the flywheel's kernels on the bits the last ffp_run left in the context's buffer, on the device's own count
-static int ffp_frames_of(pdt_ctx *ctx, TipSyncRule R, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count)
+// The feed-forward bits by bits_call, then the flywheel's kernels on the bits it left in the context's buffer, on the device's own count
+extern "C++" template <typename Bits>
+int ffp_frames_after(pdt_ctx *ctx, Bits bits_call, const pdt_tip_sync_cfg *tip_cfg, pdt_ffp_sync *sync, pdt_frame *out, pdt_tip_sync_info *info, int cap,
+                     int *count)
 {
+    TipSyncRule R;
+    if (!ctx || !count || cap < 0 || (!out && cap) || tip_sync_rule(tip_cfg, &R)) return PDT_ERR_ARG;
+    pdt_ffp_sync s;
+    const int rc = bits_call(&s);
+    if (rc) return rc;
+    if (sync) *sync = s;
     try {
-        const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
-        const unsigned char *p = (const unsigned char *)ctx->ffp_out.p;
-        const std::vector<TipSyncJob> jobs(1, TipSyncJob{ p + o.o_bits, (const unsigned long long *)p, (const unsigned *)(p + o.o_sym),
-                                                          (const long long *)(p + o.o_idx), (long long)ctx->ffp_cap, cap });
-        std::vector<TipSyncRec> recs;
-        std::vector<TipSyncInfo> infos;
-        std::vector<size_t> at;
-        std::vector<unsigned> found;
-        const int rc = tip_sync_run(ctx, jobs, R, recs, infos, at, found);
-        if (rc) return rc;
-        const size_t have = std::min<size_t>(found[0], at[1]);
         const double fs = (double)ctx->ffp_rate;
-        for (size_t k = 0; k < have; k++) {
-            TipSyncRec m = recs[k];
-            m.time = (double)m.time_src / fs;
-            memcpy(&out[k], &m, sizeof m);
-            if (info) memcpy(&info[k], &infos[k], sizeof(TipSyncInfo));
-        }
-        *count = (int)found[0];
+        return tip_sync_deliver(ctx, std::vector<BitJob>(1, job_result(ctx->ffp_out.p, ffp_out_of(ctx).t, ctx->ffp_cap, cap)), R,
+                                [fs](size_t, long long src) { return (double)src / fs; }, out, info, cap, count);
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
-    return PDT_OK;
 }
 
 int pdt_ffp_frames(pdt_ctx *ctx, const pdt_ffp_cfg *cfg, const pdt_tip_sync_cfg *tip_cfg, pdt_ffp_sync *sync, pdt_frame *out, pdt_tip_sync_info *info,
                    int cap, int *count)
 {
-    TipSyncRule R;
-    if (!ctx || !count || cap < 0 || (!out && cap) || tip_sync_rule(tip_cfg, &R)) return PDT_ERR_ARG;
-    pdt_ffp_sync s;
-    int rc = pdt_ffp_bits(ctx, cfg, &s);
-    if (rc) return rc;
-    if (sync) *sync = s;
-    return ffp_frames_of(ctx, R, out, info, cap, count);
+    return ffp_frames_after(ctx, [&](pdt_ffp_sync *s) { return pdt_ffp_bits(ctx, cfg, s); }, tip_cfg, sync, out, info, cap, count);
 }
 
 int pdt_stage_ffp_frames(pdt_ctx *ctx, uint32_t rate, const float *iq_host, uint64_t n, const pdt_ffp_cfg *cfg, const pdt_tip_sync_cfg *tip_cfg,
                          pdt_ffp_sync *sync, pdt_frame *out, pdt_tip_sync_info *info, int cap, int *count)
 {
-    TipSyncRule R;
-    if (!ctx || !count || cap < 0 || (!out && cap) || tip_sync_rule(tip_cfg, &R)) return PDT_ERR_ARG;
-    pdt_ffp_sync s;
-    int rc = pdt_stage_ffp_bits(ctx, rate, iq_host, n, cfg, &s);
-    if (rc) return rc;
-    if (sync) *sync = s;
-    return ffp_frames_of(ctx, R, out, info, cap, count);
+    return ffp_frames_after(ctx, [&](pdt_ffp_sync *s) { return pdt_stage_ffp_bits(ctx, rate, iq_host, n, cfg, s); }, tip_cfg, sync, out, info, cap, count);
 }
 
 // ---------------------------------------------------------------- parity repair from the soft values (pdt_tip_repair.h)
 // k_tip_repair on the caller's records against soft values that are on the device (their count too: read as min(*nbits_dev, bit_cap)).
-// The records go up as they are, into a buffer of their own beside their info records and the counters; one synchronize ends the call.
+// The records go up as they are, into a buffer of their own beside their info records and the counters (RepairWork); one synchronize
+// ends the call.
 static int tip_repair_run(pdt_ctx *c, const float *soft_dev, const unsigned long long *nbits_dev, long long bit_cap, pdt_frame *frames, uint64_t n,
                           pdt_tip_repair_info *info, pdt_tip_repair_summary *summary)
 {
     memset(summary, 0, sizeof *summary);
     if (n == 0) return PDT_OK;
-    const size_t o_rec = 64, o_info = o_rec + (((size_t)n * sizeof(pdt_frame) + 15) & ~(size_t)15);
+    const RepairWork L = repair_work_layout((size_t)n, sizeof(pdt_frame), sizeof(pdt_tip_repair_info));
     int rc;
-    if ((rc = c->tip_repair_work.ensure(o_info + (size_t)n * sizeof(pdt_tip_repair_info)))) return rc;
+    if ((rc = c->tip_repair_work.ensure(L.total))) return rc;
     unsigned char *w = (unsigned char *)c->tip_repair_work.p;
     hipStream_t st = c->stream;
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    HIP_TRY(hipMemsetAsync(w, 0, o_rec, st));
-    HIP_TRY(hipMemcpyAsync(w + o_rec, frames, (size_t)n * sizeof(pdt_frame), hipMemcpyHostToDevice, st));
-    if (c->cfg.profile) {
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(ev[0], st));
-    }
-    HIP_TRY(tip_repair_launch(st, w + o_rec, (unsigned)n, soft_dev, nbits_dev, bit_cap, w + o_info, w));
-    if (c->cfg.profile) HIP_TRY(hipEventRecord(ev[1], st));
-    HIP_TRY(hipMemcpyAsync(frames, w + o_rec, (size_t)n * sizeof(pdt_frame), hipMemcpyDeviceToHost, st));
-    if (info) HIP_TRY(hipMemcpyAsync(info, w + o_info, (size_t)n * sizeof(pdt_tip_repair_info), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(summary, w, sizeof *summary, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(w + L.o_sum, 0, 64, st));
+    HIP_TRY(hipMemcpyAsync(w + L.o_rec, frames, (size_t)n * sizeof(pdt_frame), hipMemcpyHostToDevice, st));
+    static const char *const names[1] = { "k_tip_repair" };
+    CallTimer timer(c, st, names, nullptr, 1);
+    HIP_TRY(timer.begin());
+    HIP_TRY(tip_repair_launch(st, w + L.o_rec, (unsigned)n, soft_dev, nbits_dev, bit_cap, w + L.o_info, w + L.o_sum));
+    HIP_TRY(timer.end());
+    HIP_TRY(hipMemcpyAsync(frames, w + L.o_rec, (size_t)n * sizeof(pdt_frame), hipMemcpyDeviceToHost, st));
+    if (info) HIP_TRY(hipMemcpyAsync(info, w + L.o_info, (size_t)n * sizeof(pdt_tip_repair_info), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(summary, w + L.o_sum, sizeof *summary, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (c->cfg.profile) {
-        pdt_kernel_time kt;
-        memset(&kt, 0, sizeof kt);
-        snprintf(kt.name, sizeof kt.name, "%s", "k_tip_repair");
-        kt.launches = 1;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-        kt.total_ms = ms;
-        c->ktimes.erase(std::remove_if(c->ktimes.begin(), c->ktimes.end(), [&](const pdt_kernel_time &x) { return !strcmp(x.name, kt.name); }),
-                        c->ktimes.end());
-        c->ktimes.push_back(kt);
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
+    timer.commit();
     return PDT_OK;
 }
 
@@ -2350,11 +2153,8 @@ int pdt_tip_repair(pdt_ctx *ctx, pdt_frame *frames, uint64_t n, pdt_tip_repair_i
     if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;             // TIP minor frames only
     if (ctx->stream_open || !ctx->ffp_rate || !ctx->ffp_out.p) return PDT_ERR_STATE;
     HIP_TRY(hipSetDevice(ctx->cfg.device));
-    try {
-        const FfpOut o(ctx->ffp_blocks, ctx->ffp_cap);
-        const unsigned char *p = (const unsigned char *)ctx->ffp_out.p;
-        return tip_repair_run(ctx, (const float *)(p + o.o_soft), (const unsigned long long *)p, (long long)ctx->ffp_cap, frames, n, info, summary);
-    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    const unsigned char *p = (const unsigned char *)ctx->ffp_out.p;
+    return tip_repair_run(ctx, (const float *)(p + ffp_out_of(ctx).t.o_soft), (const unsigned long long *)p, (long long)ctx->ffp_cap, frames, n, info, summary);
 }
 
 int pdt_stage_tip_repair(pdt_ctx *ctx, const float *soft_host, uint64_t nbits, pdt_frame *frames, uint64_t n, pdt_tip_repair_info *info,
@@ -2363,17 +2163,10 @@ int pdt_stage_tip_repair(pdt_ctx *ctx, const float *soft_host, uint64_t nbits, p
     if (!ctx || !summary || (!frames && n) || n >= (1ull << 31) || (!soft_host && nbits) || nbits >= (1ull << 31)) return PDT_ERR_ARG;
     if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;
     if (ctx->stream_open) return PDT_ERR_STATE;
-    HIP_TRY(hipSetDevice(ctx->cfg.device));
-    try {
-        int rc;
-        if ((rc = ctx->tip_repair_soft.ensure(16 + (size_t)nbits * 4))) return rc;      // the count, then the values
-        unsigned char *p = (unsigned char *)ctx->tip_repair_soft.p;
-        const unsigned long long count = nbits;
-        HIP_TRY(hipMemcpyAsync(p, &count, sizeof count, hipMemcpyHostToDevice, ctx->stream));
-        if (nbits) HIP_TRY(hipMemcpyAsync(p + 16, soft_host, (size_t)nbits * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                                     // (`count` leaves scope)
-        return tip_repair_run(ctx, (const float *)(p + 16), (const unsigned long long *)p, (long long)nbits, frames, n, info, summary);
-    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+    const int rc = stage_counted(ctx, ctx->tip_repair_soft, soft_host, nbits, sizeof(float));
+    if (rc) return rc;
+    const unsigned char *p = (const unsigned char *)ctx->tip_repair_soft.p;
+    return tip_repair_run(ctx, (const float *)(p + 16), (const unsigned long long *)p, (long long)nbits, frames, n, info, summary);
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

@@ -360,9 +360,9 @@ using namespace pdt;
 namespace pdtrt {
 
 // the two kernels over the nctx records of a table that is on the device; tiles: the grid of the first (the sum of the contexts' tiles).
-// mid: recorded between the two when not NULL (a profiled context times them apart).  rule 0: k_argos_msgs and k_argos_finish; rule 1:
-// k_argos_heads and k_argos_pick
-hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, int rule, hipEvent_t mid)
+// inner: NULL, or the one event recorded between the two (a profiled context times them apart: CallTimer; the caller records the
+// first and the last).  rule 0: k_argos_msgs and k_argos_finish; rule 1: k_argos_heads and k_argos_pick
+hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, int K, int rule, hipEvent_t *inner)
 {
     if (nctx < 1 || tiles < 0 || tiles > 0x7fffffffll || K < 0 || K > ARGOS_MSG_RUN_MAX) return hipErrorInvalidValue;
     if (rule != ARGOS_RULE_FIRST && rule != ARGOS_RULE_BEST) return hipErrorInvalidValue;
@@ -371,7 +371,7 @@ hipError_t argos_msgs_launch(hipStream_t st, const void *table_dev, int nctx, lo
     if (tiles) hipLaunchKernelGGL(best ? k_argos_heads : k_argos_msgs, dim3((unsigned)tiles), dim3(256), 0, st, table, nctx, K);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (mid && (e = hipEventRecord(mid, st)) != hipSuccess) return e;
+    if (inner && (e = hipEventRecord(inner[0], st)) != hipSuccess) return e;
     hipLaunchKernelGGL(best ? k_argos_pick : k_argos_finish, dim3((unsigned)nctx), dim3(64), 0, st, table, K);
     return hipGetLastError();
 }

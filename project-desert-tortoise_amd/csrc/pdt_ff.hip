@@ -200,10 +200,10 @@ namespace pdtrt {
 int ff_tile_len(int H, long long pmax) { return (int)((2ll * FF_SEARCH_BITS * pmax + 65535) >> 16) + 2 * H + 1; }
 
 // the three kernels over the nwin records of a table that is on the device.  mix_tiles, groups: the grids of k_ff_mix and k_ff_search
-// (the sums over the windows); periods_dev: P_r, r = -R .. R; metric: the windows' M, zeroed here.  ev[0 .. 1]: recorded between the
-// kernels when not NULL (a profiled context times them apart); syncs_dev: room for nwin records, the copy the host reads
+// (the sums over the windows); periods_dev: P_r, r = -R .. R; metric: the windows' M, zeroed here.  inner: NULL, or the two events recorded between
+// the kernels (a profiled context times them apart: CallTimer); syncs_dev: room for nwin records, the copy the host reads
 hipError_t ff_launch(hipStream_t st, const void *table_dev, int nwin, long long mix_tiles, long long groups, const long long *periods_dev, int R,
-                     int H, long long pmax, const float *tab_dev, void *metric_dev, size_t metric_bytes, void *syncs_dev, hipEvent_t *ev)
+                     int H, long long pmax, const float *tab_dev, void *metric_dev, size_t metric_bytes, void *syncs_dev, hipEvent_t *inner)
 {
     if (nwin < 1 || mix_tiles < 0 || mix_tiles > 0x7fffffffll || groups < 0 || groups > 0x7fffffffll || R < 0 || R > FF_RATE_STEPS_MAX || H < FF_MIN_H ||
         H > FF_MAX_H)
@@ -213,11 +213,11 @@ hipError_t ff_launch(hipStream_t st, const void *table_dev, int nwin, long long 
     if (metric_bytes && (e = hipMemsetAsync(metric_dev, 0, metric_bytes, st)) != hipSuccess) return e;
     if (mix_tiles) hipLaunchKernelGGL(k_ff_mix, dim3((unsigned)mix_tiles), dim3(256), 0, st, table, nwin, tab_dev);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev && (e = hipEventRecord(ev[0], st)) != hipSuccess) return e;
+    if (inner && (e = hipEventRecord(inner[0], st)) != hipSuccess) return e;
     const int tile_len = ff_tile_len(H, pmax), lanes = 64 * ((2 * H + 63) / 64);
     if (groups) hipLaunchKernelGGL(k_ff_search, dim3((unsigned)groups), dim3((unsigned)lanes), (size_t)tile_len * sizeof(float2), st, table, nwin, periods_dev, H, tile_len);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev && (e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
+    if (inner && (e = hipEventRecord(inner[1], st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ff_pick, dim3((unsigned)nwin), dim3(64), 0, st, table, periods_dev, R, H, (FfSync *)syncs_dev);
     return hipGetLastError();
 }

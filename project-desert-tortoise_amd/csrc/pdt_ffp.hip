@@ -486,8 +486,9 @@ void ffp_tiling(const FfpRule &r, int *S, int *TG, int *chunks, int *groups, siz
     *lds = ffp_tile_bytes(tg, s + 2 * r.W);
 }
 
-// the four kernels of a call whose table entries are filled but for the tiling; ev[0 .. 2]: recorded between the kernels when not NULL
-hipError_t ffp_launch(hipStream_t st, FfpCall c, const float *tab_dev, size_t metric_bytes, hipEvent_t *ev)
+// the four kernels of a call whose table entries are filled but for the tiling; inner: NULL, or the three events recorded between the
+// kernels (CallTimer)
+hipError_t ffp_launch(hipStream_t st, FfpCall c, const float *tab_dev, size_t metric_bytes, hipEvent_t *inner)
 {
     const FfpRule &r = c.r;
     size_t lds;
@@ -498,14 +499,14 @@ hipError_t ffp_launch(hipStream_t st, FfpCall c, const float *tab_dev, size_t me
     if (metric_bytes && (e = hipMemsetAsync(c.metric, 0, metric_bytes, st)) != hipSuccess) return e;
     if (tiles) hipLaunchKernelGGL(k_ffp_mix, dim3((unsigned)tiles), dim3(256), 0, st, c, tab_dev);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev && (e = hipEventRecord(ev[0], st)) != hipSuccess) return e;
+    if (inner && (e = hipEventRecord(inner[0], st)) != hipSuccess) return e;
     if (groups) hipLaunchKernelGGL(k_ffp_search, dim3((unsigned)groups), dim3(256), lds, st, c);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev && (e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
+    if (inner && (e = hipEventRecord(inner[1], st)) != hipSuccess) return e;
     if (r.nb) hipLaunchKernelGGL(k_ffp_track, dim3((unsigned)((r.nb + 255) / 256)), dim3(256), 0, st, c, 0);
     hipLaunchKernelGGL(k_ffp_track, dim3(1), dim3(256), 0, st, c, 1);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev && (e = hipEventRecord(ev[2], st)) != hipSuccess) return e;
+    if (inner && (e = hipEventRecord(inner[2], st)) != hipSuccess) return e;
     if (r.nb) hipLaunchKernelGGL(k_ffp_bits, dim3((unsigned)r.nb), dim3(256), ffp_tile_bytes(1, FFP_BITS_CHUNK + 2 * r.W), st, c);
     return hipGetLastError();
 }
@@ -520,7 +521,7 @@ size_t ffp_work_bytes(const FfpRule &r, size_t nent)
 // One call: the mixer's table to the device, then the kernels.  The caller ends it with a synchronize (the table of the previous call is
 // no longer read: every call ends with one).  hipError as PDT_ERR_NOGPU
 int ffp_run_device(hipStream_t st, const float *y, const FfpRule &r, const FfpSync &head, const std::vector<uint32_t> &steps, const std::vector<uint32_t> &starts,
-                   const float *tab_dev, void *work, const FfpOutPtrs &out, uint64_t bit_cap, hipEvent_t *ev)
+                   const float *tab_dev, void *work, const FfpOutPtrs &out, uint64_t bit_cap, hipEvent_t *inner)
 {
     unsigned char *wk = (unsigned char *)work;
     const size_t nent = steps.size(), o_starts = ffp_up16(nent * 4), o_v = 2 * o_starts, o_metric = o_v + ffp_up16((size_t)r.n * 8 + 16),
@@ -548,7 +549,7 @@ int ffp_run_device(hipStream_t st, const float *y, const FfpRule &r, const FfpSy
     c.head = head;
     c.r = r;
     c.bit_cap = (long long)bit_cap;
-    return ffp_launch(st, c, tab_dev, metric_bytes, ev) == hipSuccess ? PDT_OK : PDT_ERR_NOGPU;
+    return ffp_launch(st, c, tab_dev, metric_bytes, inner) == hipSuccess ? PDT_OK : PDT_ERR_NOGPU;
 }
 
 }  // namespace pdtrt

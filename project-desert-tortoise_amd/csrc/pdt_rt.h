@@ -34,6 +34,7 @@
 #include "pdt_kernels_front.h"
 #include "pdt_timeaxis.h"
 #include "pdt_ingest.h"
+#include "pdt_work_layout.h"
 
 using namespace pdt;
 
@@ -469,25 +470,30 @@ struct pdt_ctx {
     DevBuf tone_table, tone_out;
     int tone_sum_nfft = 0;              // the window's sums below are those of this many points (0 = none yet)
     double tone_sw = 0, tone_sw2 = 0;
-    // ARGOS messages (pdt_argos_msg.h): the launch's table, bitmaps and records on the device (first context of a call), the string of
-    // the stage entry; whether the last call left the whole capture's bits resident, and the time stamp of one of them as a frame's is formed
-    DevBuf argos_work, argos_bits;
+    // what the stage entries of the second-pass features bring up from the host, nothing a result lives in: a bit string behind its
+    // count (pdt_stage_argos_messages on an ARGOS context, pdt_stage_tip_sync on a POES one: stage_counted), a channel stream
+    // (pdt_stage_ff_bits resp. pdt_stage_ffp_*: stage_iq).  A context has one mode, so each is one buffer.
+    DevBuf staged_bits, staged_iq;
+    // ARGOS messages (pdt_argos_msg.h): the launch's table, bitmaps and records on the device (first context of a call: ArgosWork);
+    // whether the last call left the whole capture's bits resident, and the time stamp of one of them as a frame's is formed
+    DevBuf argos_work;
     bool bits_whole = false;
     std::function<double(long long)> bit_time;
-    // flywheel frame synchroniser (pdt_tip_sync.h): the launch's table, bitmaps and records on the device (first context of a call), the
-    // string of the stage entry; the records, counters and results of pdt_tip_check_records
-    DevBuf tip_sync_work, tip_sync_bits, tip_recs;
-    // feed-forward bits (pdt_ff.h): the launch's table, periods, mixed streams and metrics on the device (first context of a call), the
-    // stream of the stage entry, and this context's own results -- count, record, time source, soft values, characters -- of ff_cap bits
-    DevBuf ff_work, ff_in, ff_out;
+    // flywheel frame synchroniser (pdt_tip_sync.h): the launch's table, bitmaps and records on the device (first context of a call:
+    // TipSyncWork); the records, counters and results of pdt_tip_check_records
+    DevBuf tip_sync_work, tip_recs;
+    // feed-forward bits (pdt_ff.h): the launch's table, periods, mixed streams and metrics on the device (first context of a call:
+    // FfWork), and this context's own results -- count, record, time source, soft values, characters (FfOut) -- of ff_cap bits
+    DevBuf ff_work, ff_out;
     uint64_t ff_cap = 0;
     uint32_t ff_rate = 0;               // 0 = no feed-forward call yet
-    // feed-forward POES bits (pdt_ffp.h): the call's work buffer -- the mixer's table, the mixed stream, the metrics --, the stream of the
-    // stage entries, and this context's own results -- count, record, per-block table, positions, time source, soft values, characters
-    DevBuf ffp_work, ffp_in, ffp_out;
+    // feed-forward POES bits (pdt_ffp.h): the call's work buffer -- the mixer's table, the mixed stream, the metrics (ffp_work_bytes) --
+    // and this context's own results -- count, record, per-block table, positions, time source, soft values, characters (FfpOut)
+    DevBuf ffp_work, ffp_out;
     uint64_t ffp_cap = 0, ffp_blocks = 0;
     uint32_t ffp_rate = 0;              // 0 = no such call yet
-    // parity repair (pdt_tip_repair.h): the caller's records, their info records and the counters; the soft values of the stage entry
+    // parity repair (pdt_tip_repair.h): the counters, the caller's records and their info records (RepairWork); the soft values of the
+    // stage entry behind their count (stage_counted)
     DevBuf tip_repair_work, tip_repair_soft;
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
@@ -606,6 +612,58 @@ class Launcher {
     hipEvent_t last_b = nullptr;
     bool have_last = false;
     size_t open_idx = 0;
+};
+
+// The kernel times of a call that runs K kernels of its own on one stream and waits for them (the second-pass entries: pdt_tones,
+// pdt_argos_messages, pdt_tip_sync, pdt_ff_bits, pdt_ffp_bits, pdt_tip_repair).  On a context that is not profiled every member does
+// nothing and no event exists.  On a profiled one begin() creates K + 1 events and records the first, the launcher records the K - 1 of
+// inner() between its kernels, end() records the last, and commit() -- behind the call's synchronize -- replaces the context's entries of
+// these names.  The events are destroyed with the object, whichever way the call returns.  names and launches (NULL: 1 each) outlive it.
+class CallTimer {
+  public:
+    enum { MAX_KERNELS = 7 };
+    CallTimer(pdt_ctx *c, hipStream_t s, const char *const *names_, const int *launches_, int K_)
+        : ctx(c), st(s), names(names_), launches(launches_), K(c->cfg.profile ? K_ : 0) {}
+    CallTimer(const CallTimer &) = delete;
+    CallTimer &operator=(const CallTimer &) = delete;
+    ~CallTimer()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t begin()
+    {
+        if (!K) return hipSuccess;
+        if (K > MAX_KERNELS) return hipErrorInvalidValue;
+        for (int k = 0; k <= K; k++)
+            if (hipError_t e = hipEventCreate(&ev[k])) return e;
+        return hipEventRecord(ev[0], st);
+    }
+    hipEvent_t *inner() { return K ? ev + 1 : nullptr; }      // (what every *_launch takes: NULL, or the boundaries between its kernels)
+    hipError_t end() { return K ? hipEventRecord(ev[K], st) : hipSuccess; }
+    void commit()
+    {
+        for (int k = 0; k < K; k++) {
+            pdt_kernel_time kt;
+            memset(&kt, 0, sizeof kt);
+            snprintf(kt.name, sizeof kt.name, "%s", names[k]);
+            kt.launches = launches ? launches[k] : 1;
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            kt.total_ms = ms;
+            ctx->ktimes.erase(std::remove_if(ctx->ktimes.begin(), ctx->ktimes.end(), [&](const pdt_kernel_time &o) { return !strcmp(o.name, kt.name); }),
+                              ctx->ktimes.end());
+            ctx->ktimes.push_back(kt);
+        }
+    }
+
+  private:
+    pdt_ctx *ctx;
+    hipStream_t st;
+    const char *const *names;
+    const int *launches;
+    int K;
+    hipEvent_t ev[MAX_KERNELS + 1] = {};
 };
 
 // run_capture records its timer groups into the plan; the Launcher above turns them into events when the plan runs

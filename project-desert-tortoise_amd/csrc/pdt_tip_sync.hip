@@ -280,25 +280,24 @@ namespace pdtrt {
 extern const char *const tip_sync_kernel_names[5] = { "k_tip_cand", "k_tip_heads", "k_tip_pick", "k_tip_scan", "k_tip_pack" };
 
 // the five kernels over the nctx records of a table that is on the device; tiles: the grid of the tiled ones (the sum of the contexts'
-// tiles).  ev: NULL, or six events recorded around and between the kernels (a profiled context times them apart)
-hipError_t tip_sync_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, TipSyncRule R, hipEvent_t *ev)
+// tiles).  inner: NULL, or the four events recorded between the kernels (a profiled context times them apart under
+// tip_sync_kernel_names: CallTimer; the caller records the first and the last)
+hipError_t tip_sync_launch(hipStream_t st, const void *table_dev, int nctx, long long tiles, TipSyncRule R, hipEvent_t *inner)
 {
     if (nctx < 1 || tiles < 0 || tiles > 0x7fffffffll) return hipErrorInvalidValue;
     const TipSyncCtx *table = (const TipSyncCtx *)table_dev;
     hipError_t e;
-    auto mark = [&](int k) -> hipError_t { return ev ? hipEventRecord(ev[k], st) : hipSuccess; };
-    if ((e = mark(0)) != hipSuccess) return e;
+    auto mark = [&](int k) -> hipError_t { return inner ? hipEventRecord(inner[k], st) : hipSuccess; };
     if (tiles) hipLaunchKernelGGL(k_tip_cand, dim3((unsigned)tiles), dim3(256), 0, st, table, nctx, R);
-    if ((e = hipGetLastError()) != hipSuccess || (e = mark(1)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess || (e = mark(0)) != hipSuccess) return e;
     if (tiles) hipLaunchKernelGGL(k_tip_heads, dim3((unsigned)tiles), dim3(64), 0, st, table, nctx, R);
-    if ((e = hipGetLastError()) != hipSuccess || (e = mark(2)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess || (e = mark(1)) != hipSuccess) return e;
     if (tiles) hipLaunchKernelGGL(k_tip_pick, dim3((unsigned)tiles), dim3(64), 0, st, table, nctx, R);
-    if ((e = hipGetLastError()) != hipSuccess || (e = mark(3)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess || (e = mark(2)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_tip_scan, dim3((unsigned)nctx), dim3(256), 0, st, table);
-    if ((e = hipGetLastError()) != hipSuccess || (e = mark(4)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess || (e = mark(3)) != hipSuccess) return e;
     if (tiles) hipLaunchKernelGGL(k_tip_pack, dim3((unsigned)tiles), dim3(128), 0, st, table, nctx, R);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return mark(5);
+    return hipGetLastError();
 }
 
 // cfg (NULL = the defaults) -> E, W, G; PDT_ERR_ARG for a value out of range

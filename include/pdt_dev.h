@@ -25,6 +25,11 @@ unsigned long long pdt_dev_span_rows(const struct pdt_ctx *ctx, unsigned *n_exit
  * last run had no re-key point (PDT_GSPAN_REKEY=0, a short row), or the row was left untabulated or had too many exits to
  * deduplicate and went through all its chunks in stage 1. */
 unsigned long long pdt_dev_span_rekey(const struct pdt_ctx *ctx, unsigned *out, unsigned long long max);
+/* Which low-pass filter kernel the last demodulation took (the last segment of a stream): 0 none (no output samples), 1 k_fir_plain
+ * (ARGOS), 2 k_mix_fir (mix and filter in one kernel), 3 the register-tiled interpolating form, 4 the generic interpolating
+ * form.  *fused_tiles_out (may be NULL): the tile or run maps that kernel wrote for the AGC, 0 when the AGC built its own.  The
+ * profile's group is called "fir" whatever was launched; this is how tests/test_gpu_interp.py sees the dispatch. */
+unsigned pdt_dev_fir_form(const struct pdt_ctx *ctx, unsigned long long *fused_tiles_out);
 /* The down-converter's kernel on ONE record, as a piece of a stream hands it over (csrc/pdt_ddc.h): x_dev is the address of input
  * sample 0 in device memory, the samples lo <= i < hi are present and zeros lie elsewhere, g0 is the global index of input 0
  * (the phase of input i is (g0 + i) step), and outputs 0 <= m < n_out, each centred on input m decim, go to out_dev as float32

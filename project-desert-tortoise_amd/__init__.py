@@ -649,7 +649,7 @@ ABI_SYMBOLS = [
     "pdt_tip_sync", "pdt_tip_sync_batch", "pdt_stage_tip_sync", "pdt_host_tip_sync", "pdt_tip_sync_tile", "pdt_tip_check_records",
     "pdt_tip_repair", "pdt_stage_tip_repair", "pdt_host_tip_repair",
 ]
-DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
+DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_fir_form", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
 
 _lib = None
 
@@ -764,6 +764,8 @@ def lib():
     L.pdt_write_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_write_records.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_dev_set.argtypes = [C.c_char_p, C.c_char_p]
+    L.pdt_dev_fir_form.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    L.pdt_dev_fir_form.restype = C.c_uint
     L.pdt_set_loop_params.argtypes = [C.c_void_p, C.POINTER(LoopParams)]
     L.pdt_demod_file.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_set_real_input.argtypes = [C.c_void_p, C.c_double]
@@ -1428,6 +1430,13 @@ class Demodulator:
         assert a.size == l.size
         _check(self._L.pdt_stage_squelch(self._h, a.ctypes.data, l.ctypes.data, a.size, float(threshold)), "pdt_stage_squelch")
         return a
+
+    def fir_form(self) -> "tuple[int, int]":
+        """pdt_dev_fir_form (test-only, include/pdt_dev.h): (the filter kernel the last run took -- 0 none, 1 k_fir_plain, 2 k_mix_fir,
+        3 register-tiled, 4 generic --, the AGC tile or run maps it wrote; 0: the AGC built its own)"""
+        tiles = C.c_ulonglong(0)
+        form = self._L.pdt_dev_fir_form(self._h, C.byref(tiles))
+        return int(form), int(tiles.value)
 
     def stats_interp(self) -> int:
         taps, interp = make_lpf(self.mode, self.sample_rate)

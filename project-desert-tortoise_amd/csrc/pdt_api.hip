@@ -364,6 +364,13 @@ unsigned long long pdt_dev_span_rekey(const pdt_ctx *ctx, unsigned *out, unsigne
     return n;
 }
 
+// test-only (include/pdt_dev.h): which filter kernel the last run took, and how many AGC maps it wrote
+unsigned pdt_dev_fir_form(const pdt_ctx *ctx, unsigned long long *fused_tiles_out)
+{
+    if (fused_tiles_out) *fused_tiles_out = ctx ? (unsigned long long)ctx->fir_fused_tiles : 0ull;
+    return ctx ? (unsigned)ctx->fir_form : 0u;
+}
+
 // test-only (include/pdt_dev.h): the down-converter on exactly this record, one launch by value; no context
 int pdt_dev_ddc(int device, uint32_t in_rate, int decim, double offset_hz, int sample_format, const void *x_dev, long long lo, long long hi,
                 uint64_t n_out, uint64_t g0, void *out_dev)

@@ -1177,6 +1177,7 @@ template <typename T> struct Chain {
         int rc = PDT_OK;
         (void)rc;
         // ---- FIR
+        ctx->fir_form = 0;                                     // (what pdt_dev_fir_form reports: set below, where a kernel is taken)
         if (n_out > 0) {
             L.begin(fuse_mix ? "mix_fir" : "fir");
             bool done = false;                                 // the kernel that writes the AGC's tile maps was taken
@@ -1218,8 +1219,10 @@ template <typename T> struct Chain {
             }
             if (!done) done = rec_fir_unfused<T>(ctx, PL, st, (const T *)d_pll, N, d_fir, fir_tile_maps, AP.decay);
             if (!done) fused_tiles = 0;
+            ctx->fir_form = fuse_mix ? 2 : done ? 3 : argos ? 1 : 4;
             L.end();
         }
+        ctx->fir_fused_tiles = fused_tiles;
 
         return PDT_OK;
     }

@@ -406,6 +406,8 @@ struct pdt_ctx {
     int gardner_mode = 0;              // 0 sequential, 1 state table (last run)
     long long gspan_nrows = 0;         // table rows of several chunks in the last run (0: none) -- pdt_dev_span_rows
     int gspan_rekey = 0;               // chunks its span walk went before the re-key (0: single stage) -- pdt_dev_span_rekey
+    int fir_form = 0;                  // the filter kernel of the last run: 0 none, 1 k_fir_plain, 2 k_mix_fir, 3 register-tiled, 4 generic -- pdt_dev_fir_form
+    long long fir_fused_tiles = 0;     // the AGC tile / run maps that kernel wrote (0: the AGC built its own)
     const void *pcm_dev = nullptr;     // input actually used (own copy or caller's buffer)
     int pcm_fmt = 0;                   // 0 = int16 pairs, 1 = float32 pairs (InFmt::pcm_fmt)
 

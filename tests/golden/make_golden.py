@@ -25,7 +25,7 @@ REF_ARGOS = os.path.join(ROOT, "oracle/_ref/ref_demodARGOS")
 STAGES = ["iq", "time", "pll", "lock", "fir", "agc", "sym", "symt", "bits", "bitt", "taps"]
 REAL_STAGES = ["pll", "lock", "fir", "agc", "agcraw", "sym", "symt", "bits", "bitt", "avg"]
 
-POES_RATES = [18750, 32000, 50000, 100000, 250000]
+POES_RATES = [17000, 18750, 20000, 22050, 25000, 32000, 37500, 50000, 60000, 100000, 250000]      # interpolation factors 9 ... 1
 POES_SECONDS = 3.0
 ARGOS_SECONDS = 13.0
 

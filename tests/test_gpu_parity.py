@@ -70,7 +70,7 @@ def test_clip_norm_override(pdt, orc, clip):
         assert d.text() == golden_text("clip.n12.txt")
 
 
-@pytest.mark.parametrize("fs", [18750, 32000, 50000, 100000, 250000])
+@pytest.mark.parametrize("fs", [17000, 18750, 20000, 22050, 25000, 32000, 37500, 50000, 60000, 100000, 250000])
 def test_synthetic_rates_golden(pdt, orc, golden, fs):
     p = golden["params"]
     iq = pdt.synth_capture(0, fs, p["poes_seconds"], seed=p["poes_seed"])

@@ -48,9 +48,13 @@ def test_oracle_norm_override(orc, clip):
     assert o.text() == golden_text("clip.n12.txt")
 
 
-@pytest.mark.parametrize("fs", [18750, 32000, 50000, 100000, 250000])
+POES_RATES = [17000, 18750, 20000, 22050, 25000, 32000, 37500, 50000, 60000, 100000, 250000]      # interpolation factors 9 ... 1
+
+
+@pytest.mark.parametrize("fs", POES_RATES)
 def test_oracle_synthetic_poes(orc, pdt, golden, fs):
     p = golden["params"]
+    assert p["poes_rates"] == POES_RATES
     iq = pdt.synth_capture(0, fs, p["poes_seconds"], seed=p["poes_seed"])
     assert hashlib.sha256(iq.tobytes()).hexdigest() == golden["synth"][f"poes_{fs}"], "generator is not bit-reproducible"
     o = orc.Oracle(orc.POES, fs, iq)

@@ -45,7 +45,10 @@ def test_clip_all_stages(orc, clip, tmp_path, chunk):
     assert o.text() == text
 
 
-@pytest.mark.parametrize("fs,seed,f0", [(50000, 5, -2300.0), (250000, 6, 3100.0), (32000, 7, 400.0)])
+@pytest.mark.parametrize("fs,seed,f0", [(50000, 5, -2300.0), (250000, 6, 3100.0), (32000, 7, 400.0),
+                                        # interpolation factors 4, 6, 7 and 9, and the two half-way rates (2.5 and 7.5 round to even)
+                                        (37500, 8, -1900.0), (25000, 9, 700.0), (22050, 10, -350.0), (17000, 11, 200.0),
+                                        (60000, 12, 2500.0), (20000, 13, -600.0)])
 def test_synthetic_poes_all_stages(orc, pdt, tmp_path, fs, seed, f0):
     iq = pdt.synth_capture(0, fs, 4.0, f0_hz=f0, seed=seed)
     wav = tmp_path / "s.wav"

@@ -358,7 +358,8 @@ int  pdt_demod_batch_device(pdt_ctx *const *ctxs, const void *const *iq_device, 
 
 /* RAW input of demodPOES (".raw": interleaved IEEE float32 I,Q used as they are, no normalisation;
  * GetComplexRawChunk, wave.c:413-540, POESTIPdemod/main.c:313-339; the sample rate comes from -s).
- * POES only -- ARGOSdemod/main.c:238-241 refuses RAW files.                                       */
+ * POES only -- ARGOSdemod/main.c:238-241 refuses RAW files.  Non-finite samples (NaN, +-infinity) are
+ * taken as the reference takes them: every stream, the norm factor and the frames are the reference's.  */
 int  pdt_demod_f32(pdt_ctx *ctx, const float *iq_host, uint64_t nframes);
 int  pdt_demod_device_f32(pdt_ctx *ctx, const void *iq_device, uint64_t nframes);
 

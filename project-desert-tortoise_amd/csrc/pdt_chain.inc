@@ -1621,7 +1621,8 @@ template <typename T> struct Chain {
                     PDT_LAUNCH(64, (k_gardner_emit_first<PDT_GEMIT_SUB_WIN>), dim3((unsigned)((n_tab - g_first + 3) / 4)), dim3(64), 0, st_emit, (const float *)d_agc, GP, GD,
                                        n_tab, (const GardnerEntry<float> *)ctx->gentries.p, (const unsigned *)ctx->gspan_keys.p,
                                        (const GardnerSpanRow *)ctx->gspan_rows.p, (const GardnerSpanRec *)ctx->gspan_recs.p,
-                                       (GardnerEntry<float> *)ctx->gcentries.p, (unsigned char *)ctx->gflags.p, (float *)d_sym, d_symidx, sym_cap, g_first);
+                                       (GardnerEntry<float> *)ctx->gcentries.p, (unsigned char *)ctx->gflags.p, (float *)d_sym, d_symidx, sym_cap, g_first,
+                                       (const unsigned *)ctx->gspan_tails.p);
                     PDT_LAUNCH(64, (k_gardner_emit_rest<PDT_GEMIT_SUB_WIN>), dim3((unsigned)(((n_tab - g_first) * (GD.span - 1) + 3) / 4)), dim3(64), 0, st_emit,
                                        (const float *)d_agc, GP, GD, n_tab, (const GardnerEntry<float> *)ctx->gcentries.p,
                                        (const unsigned char *)ctx->gflags.p, (float *)d_sym, d_symidx, sym_cap, g_first);

@@ -82,6 +82,10 @@ template <> __device__ __forceinline__ unsigned uniform<unsigned>(unsigned v)
 // neither NaN nor infinity
 __device__ __forceinline__ bool is_finite_bits(float v) { return (__float_as_int(v) & 0x7f800000) != 0x7f800000; }
 __device__ __forceinline__ bool is_finite_bits(double v) { return (__double2hiint(v) & 0x7ff00000) != 0x7ff00000; }
+// poison <- poison + v * 0: stays +0.0 over finite values and turns into a NaN, for good, at the first NaN or infinity (one fused
+// multiply-add per staged value, on the lanes that stage)
+__device__ __forceinline__ void poison_with(float &poison, float v) { poison = __builtin_fmaf(v, 0.0f, poison); }
+__device__ __forceinline__ void poison_with(double &poison, double v) { poison = __builtin_fma(v, 0.0, poison); }
 // rint(x) as an integer, read out of the mantissa of x + 1.5 * 2^(mantissa bits): the addition rounds to nearest-even at the
 // integer position exactly as rint does (float: 0 <= x < 2^22; double: |x| < 2^31)
 __device__ __forceinline__ int rint_index(float x) { return __float_as_int(x + 12582912.0f) - 0x4B400000; }
@@ -131,12 +135,14 @@ __device__ __forceinline__ long long gardner_walk_chunk(const T *__restrict__ in
     const T nT = (T)n_cur;
     long long count = count0;
     unsigned wbase = 0;
-    bool chunk_done = false;
+    // a sampling instant that is a NaN (an earlier chunk held one) takes no symbol of this chunk either: nothing to stage
+    bool chunk_done = !uniform<int>((int)(Real<T>::rint(ns) < nT));
     while (!chunk_done) {
         // ---- stage the part of [wbase, wbase+LEN) the sampler can touch: chunk data with 8
         // independent loads in flight per lane, then the few past-the-end values (Q3/Q16)
         __syncthreads();
         int n_staged;
+        T poison = 0;                                  // a NaN once this thread has staged a NaN or an infinity (poison_with)
         {
             const unsigned avail = (n_cur > wbase) ? n_cur - wbase : 0u;
             const int n_data = (int)((avail < (unsigned)LEN) ? avail : (unsigned)LEN);
@@ -147,16 +153,28 @@ __device__ __forceinline__ long long gardner_walk_chunk(const T *__restrict__ in
 #pragma unroll
                 for (int u = 0; u < 8; u++) r[u] = src[t + u * NT];
 #pragma unroll
-                for (int u = 0; u < 8; u++) win[t + u * NT] = r[u];
+                for (int u = 0; u < 8; u++) {
+                    poison_with(poison, r[u]);
+                    win[t + u * NT] = r[u];
+                }
             }
-            for (; t < n_data; t += NT) win[t] = src[t];
+            for (; t < n_data; t += NT) {
+                const T v = src[t];
+                poison_with(poison, v);
+                win[t] = v;
+            }
             int n_tail = n_data + 2 * (int)step + 24;          // furthest look-ahead of the mid-point
             if (n_tail > LEN) n_tail = LEN;
-            for (int q = n_data + lane; q < n_tail; q += NT)
-                win[q] = gardner_beyond(in, lock, P, c, (long long)n_cur, (long long)(wbase + (unsigned)q));
+            for (int q = n_data + lane; q < n_tail; q += NT) {
+                const T v = gardner_beyond(in, lock, P, c, (long long)n_cur, (long long)(wbase + (unsigned)q));
+                poison_with(poison, v);
+                win[q] = v;
+            }
             n_staged = n_tail;
         }
-        __syncthreads();
+        // the check-free batch below counts on sampling instants that advance: with a NaN or an infinity in the window every step
+        // is the checked one, whose select returns a NaN error as the reference's does and whose test ends the chunk on a NaN instant
+        const bool wbad = __syncthreads_or((int)(poison != poison)) != 0;
         const unsigned wend = wbase + (unsigned)LEN;
         const unsigned lim_idx = (n_cur < wend) ? n_cur : wend;   // first index the batch must not reach
         int nout = 0;
@@ -191,7 +209,7 @@ __device__ __forceinline__ long long gardner_walk_chunk(const T *__restrict__ in
             }
             // ---- check-free batch
             const T room = (T)lim_idx - (T)2 - ns;
-            int K = (room > (T)0) ? (int)(room / adv) : 0;
+            int K = (room > (T)0 && !wbad) ? (int)(room / adv) : 0;
             K = uniform<int>(K);
             if (K > OUT - nout) K = OUT - nout;
             const T wb = (T)wbase;
@@ -709,7 +727,8 @@ __device__ __forceinline__ void k_gardner_ring(const T *__restrict__ in, const T
                 jn++;
                 while (__hip_atomic_load(&s_ready[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != use + 1) __builtin_amdgcn_s_sleep(1);
                 const T *w = win[s];
-                const bool exact = s_bad[s] != 0 || n_cur >= (1 << 22) - 4096;
+                const bool bad = s_bad[s] != 0;             // every step the checked one: its test ends the chunk on a NaN instant
+                const bool exact = bad || n_cur >= (1 << 22) - 4096;
                 int n_staged = n_cur + tail;
                 if (n_staged > LEN) n_staged = LEN;
                 for (;;) {
@@ -737,7 +756,7 @@ __device__ __forceinline__ void k_gardner_ring(const T *__restrict__ in, const T
                     }
                     // ---- check-free batch
                     const T room = (T)n_cur - (T)2 - ns;
-                    int K = (room > (T)0) ? (int)(room / adv) : 0;
+                    int K = (room > (T)0 && !bad) ? (int)(room / adv) : 0;
                     K = uniform<int>(K);
                     if (K > OUT - nout) K = OUT - nout;
                     T *ov = o_val + nout;
@@ -1228,11 +1247,15 @@ __device__ __forceinline__ void k_gardner_table_merge(const float *__restrict__ 
     if (tid == 0) { x_ns[0] = L[0].ns; x_prev[0] = L[0].prev; x_half[0] = L[0].half; }
     __syncthreads();
 #pragma unroll
-    for (int l = 0; l < 2; l++)
+    for (int l = 0; l < 2; l++) {
         if (tid + l * PDT_GTM_THREADS >= n_alive) { L[l].ns = x_ns[0]; L[l].prev = x_prev[0]; L[l].half = x_half[0]; }
+    }
 
     int wbase = 0;
     float enter_hi = step + 1.2f;                 // upper bound of ns when entering the window
+    // The walks below clip with the median, which gives a bound where the reference's select returns a NaN error: a NaN or an
+    // infinity among the staged samples, in a candidate's previous symbol or in its first mid-point leaves the slice's cells (the
+    // candidate's cell) untabulated -- the chain then walks the chunk with the select (gardner_walk_chunk)
     for (;;) {
         // ---- stage [wbase, wbase + WIN)
         __syncthreads();
@@ -1256,6 +1279,10 @@ __device__ __forceinline__ void k_gardner_table_merge(const float *__restrict__ 
             }
         }
         __syncthreads();
+        // (read back from LDS: folded into the staging loop above, the flag cost the kernel 14 registers and two of its 8 waves a SIMD)
+        float poison = 0;                         // (poison_with; it lives until the vote below, not across the walks)
+#pragma unroll 4
+        for (int t = tid; t < WIN; t += PDT_GTM_THREADS) poison_with(poison, win[t]);
         const int wend = wbase + WIN;
         const bool last_window = (wend - margin >= n_cur);
         const float stop = last_window ? nT : (float)(wend - margin);    // lanes leave the window at rint(ns) >= stop
@@ -1269,13 +1296,17 @@ __device__ __forceinline__ void k_gardner_table_merge(const float *__restrict__ 
                 for (int l = 0; l < 2; l++) {
                     const float rn = __builtin_rintf(L[l].ns);
                     if (rn < nT) {
+                        poison_with(poison, L[l].prev);
                         const unsigned i_cur = (unsigned)rn;
                         const unsigned i_half = (unsigned)__builtin_rintf(L[l].half);
                         const float cur = win[i_cur];
                         float mid;
                         if (i_half < (unsigned)WIN) mid = win[i_half];
-                        else mid = (i_half < (unsigned)n_cur) ? in[base + i_half]
-                                                              : gardner_beyond(in, (const float *)nullptr, P, c, (long long)n_cur, (long long)i_half);
+                        else {
+                            mid = (i_half < (unsigned)n_cur) ? in[base + i_half]
+                                                             : gardner_beyond(in, (const float *)nullptr, P, c, (long long)n_cur, (long long)i_half);
+                            poison_with(poison, mid);
+                        }
                         const float err = __builtin_amdgcn_fmed3f(kp * (cur - L[l].prev) * mid, -lim, lim);
                         L[l].ns = L[l].ns - err;
                         L[l].q_last = L[l].ns;
@@ -1287,6 +1318,10 @@ __device__ __forceinline__ void k_gardner_table_merge(const float *__restrict__ 
                     }
                 }
             }
+        }
+        if (poison != poison) my_k[0] |= (int)0x80000000;     // (the flag rides in a register that lives across the walks anyway: one
+                                                              // of its own cost the kernel a wave a SIMD, a scalar one too)
+        if (wave < waves_on) {
             if (L[0].count >= 1 && L[1].count >= 1) {
                 int k_min = (int)((stop - 4.0f - enter_hi) / (step + 0.101f)) - 1;
                 if (k_min < 0) k_min = 0;
@@ -1400,20 +1435,27 @@ __device__ __forceinline__ void k_gardner_table_merge(const float *__restrict__ 
     }
     // ---- exit states of the survivors, then one table cell per original candidate
     __syncthreads();
+    {
+        const unsigned long long any = __ballot(my_k[0] < 0);
+        if ((tid & 63) == 0) htab[wave] = any != 0ull ? 1u : 0u;   // (the window is dead: the waves' flags meet in its hash table's first words)
+        my_k[0] &= 0x7fffffff;
+    }
 #pragma unroll
     for (int l = 0; l < 2; l++) {
         const int p = tid + l * PDT_GTM_THREADS;
         if (p < n_alive) { x_q[p] = L[l].q_last; x_il[p] = L[l].i_last; x_cnt[p] = L[l].count; }
     }
     __syncthreads();
+    static_assert(PDT_GTM_THREADS == 128, "two wavefronts' flags");
+    const int nonfin = (int)(htab[0] | htab[1]);
 #pragma unroll
     for (int l = 0; l < 2; l++) {
         const int q = tid + l * PDT_GTM_THREADS;
         if (q < n_slots) {
             const unsigned o = own[q];
             const unsigned cnt = (unsigned)((int)x_cnt[o] + extra[q]);
-            const unsigned cell = gardner_encode_exit(D, x_q[o], x_il[o], cnt);
-            if (cell == PDT_GTAB_MISS) atomicAdd(&stats[0], 1u);  // exit outside the enumerated domain (never expected)
+            const unsigned cell = nonfin ? PDT_GTAB_MISS : gardner_encode_exit(D, x_q[o], x_il[o], cnt);
+            if (cell == PDT_GTAB_MISS && !nonfin) atomicAdd(&stats[0], 1u);  // exit outside the enumerated domain (never expected)
             row[my_k[l]] = cell;
         }
     }
@@ -1562,7 +1604,8 @@ template <int WIN, int NSUB, bool EMIT>
 __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__restrict__ in, const GardnerParams<float> &P,
                                                   const long long (&c_sub)[NSUB], GardnerLane &L, float *__restrict__ sym,
                                                   long long *__restrict__ symidx, long long sym_at, long long sym_cap,
-                                                  float *o_val = nullptr, unsigned *o_idx = nullptr /* EMIT: LDS, NSUB x GSUB_OUT each */)
+                                                  float *o_val = nullptr, unsigned *o_idx = nullptr /* EMIT: LDS, NSUB x GSUB_OUT each */,
+                                                  int *nonfin_out = nullptr /* set where this lane met an error that is a NaN or infinite */)
 {
     constexpr int SUBW = 64 / NSUB;
     const int lane = (int)threadIdx.x;
@@ -1609,6 +1652,11 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
     // fetch the next window's samples into registers before they walk the current one (round 20).  The emission has wavefronts
     // enough and keeps its registers.
     constexpr bool PREFETCH = !EMIT;
+    // The walks clip with the median, which is the reference's select wherever the unclipped error is not a NaN.  The walk that
+    // emits nothing folds every unclipped error into `poison` (poison_with: one multiply-add a symbol, beside the step's dependent
+    // chain, which leaves a lone wavefront issue slots to spare): a lane whose poison is a NaN at the end has a trajectory the
+    // reference does not have (or met an infinite error, which clips alike: a miss too many), every other lane has the reference's.
+    float poison = 0;
     struct __attribute__((packed, aligned(4))) Q { float v[4]; };
     Q pre[PREFETCH ? NSUB : 1][PREFETCH ? WIN / 256 : 1];
     bool have_pre = false;
@@ -1702,7 +1750,9 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
             else mid = (i_half < (unsigned)n_cur) ? in[my_base + i_half]
                                                   : gardner_beyond(in, (const float *)nullptr, P, my_base / C, (long long)n_cur, (long long)i_half);
             emit(cur, i_cur);
-            const float err = __builtin_amdgcn_fmed3f(kp * (cur - L.prev) * mid, -lim, lim);
+            const float raw = kp * (cur - L.prev) * mid;
+            if (!EMIT) poison_with(poison, raw);
+            const float err = __builtin_amdgcn_fmed3f(raw, -lim, lim);
             L.ns = L.ns - err;
             L.q_last = L.ns;
             L.half = L.ns + hs;
@@ -1726,8 +1776,17 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
                 L.ns = L.ns + step;
                 L.prev = cur;
                 L.count += 1;
-            } else
-                gardner_lane_step(L, wrel, kp, lim, hs, step);
+            } else {
+                const float cur = lds_rel_at(wrel, L.ns);
+                const float mid = lds_rel_at(wrel, L.half);
+                const float raw = kp * (cur - L.prev) * mid;
+                poison_with(poison, raw);
+                const float err = __builtin_amdgcn_fmed3f(raw, -lim, lim);
+                L.ns = L.ns - err;
+                L.half = L.ns + hs;
+                L.ns = L.ns + step;
+                L.prev = cur;
+            }
         }
         if (!EMIT) L.count += (unsigned)k_min;
         for (;;) {
@@ -1736,7 +1795,9 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
             const float cur = wrel[(int)rn];
             const float mid = wrel[rint_index(L.half)];
             emit(cur, (unsigned)rn);
-            const float err = __builtin_amdgcn_fmed3f(kp * (cur - L.prev) * mid, -lim, lim);
+            const float raw = kp * (cur - L.prev) * mid;
+            if (!EMIT) poison_with(poison, raw);
+            const float err = __builtin_amdgcn_fmed3f(raw, -lim, lim);
             L.ns = L.ns - err;
             L.q_last = L.ns;
             L.half = L.ns + hs;
@@ -1750,6 +1811,7 @@ __device__ __forceinline__ void gardner_sub_chunk(float *win, const float *__res
         enter_hi = stop + step + 1.2f;
         wbase = wend - margin - back;
     }
+    if (!EMIT && nonfin_out && poison != poison) *nonfin_out = 1;
 }
 
 
@@ -1821,6 +1883,7 @@ __device__ __forceinline__ void k_gardner_span_walk(const float *__restrict__ in
         // step +- 0.1, so they stay inside the staged windows like everybody else
         if (!L.active) { L.ns = s_ref[0]; L.prev = s_ref[1]; L.half = s_ref[2]; }
         GardnerSpanRec *my_recs = recs + (size_t)my_key * (size_t)(D.span - 1);
+        int nonfin = 0;                                  // this lane met an error the median does not clip as the select does: no tail, the chain walks the row
         for (int g = g_lo; g < g_hi; g++) {
             long long cc[NSUB];
 #pragma unroll
@@ -1830,16 +1893,18 @@ __device__ __forceinline__ void k_gardner_span_walk(const float *__restrict__ in
                 rc.ns = L.ns; rc.prev = L.prev; rc.half = L.half; rc.count = L.count;
                 my_recs[g - 1] = rc;
             }
-            gardner_sub_chunk<WIN, NSUB, false>(win, in, P, cc, L, nullptr, nullptr, 0, 0);
+            gardner_sub_chunk<WIN, NSUB, false>(win, in, P, cc, L, nullptr, nullptr, 0, 0, nullptr, nullptr, &nonfin);
             if (g + 1 < D.span) L.ns = L.ns - nT;                         // roll over; `half` is deliberately not (Q3)
         }
         if (L.active) {
             if (g_hi < D.span) {
                 GardnerSpanRec rc;                                       // stage 1 ends here: the state in front of chunk g_hi
                 rc.ns = L.ns; rc.prev = L.prev; rc.half = L.half; rc.count = L.count;
+                if (nonfin) rc.count |= 0x80000000u;                     // (the states stay finite; a count this large encodes as a miss at
+                                                                         // stage 2's end and in k_gardner_span_spread, whoever merged with whom)
                 my_recs[g_hi - 1] = rc;
             } else
-                tails[my_key] = gardner_encode_exit(D, L.q_last, L.i_last, L.count);
+                tails[my_key] = nonfin ? PDT_GTAB_MISS : gardner_encode_exit(D, L.q_last, L.i_last, L.count);
         }
     }
 }
@@ -1974,7 +2039,8 @@ __device__ __forceinline__ void k_gardner_emit_first(const float *__restrict__ i
                                                      const GardnerSpanRec *__restrict__ recs,
                                                      GardnerEntry<float> *__restrict__ centries, unsigned char *__restrict__ flags,
                                                      float *__restrict__ sym, long long *__restrict__ symidx, long long sym_cap,
-                                                     long long g_first = 0 /* a stream segment: the rows in front are history (no entry states) */)
+                                                     long long g_first /* a stream segment: the rows in front are history (no entry states) */,
+                                                     const unsigned *__restrict__ tails /* a key without a tail: a chunk of its row held a NaN or an infinity */)
 {
     __shared__ __attribute__((aligned(16))) float win[4 * WIN];
     const int lane = threadIdx.x;
@@ -1989,9 +2055,21 @@ __device__ __forceinline__ void k_gardner_emit_first(const float *__restrict__ i
     GardnerLane L;
     L.ns = e.ns; L.prev = e.prev; L.half = e.half; L.q_last = 0; L.i_last = 0; L.count = 0; L.k = 0;
     L.active = g0 + mysub < n_rows;
+    // These walks clip with the median and count their steps: they are the reference's only over finite data.  A group the chain
+    // entered with a state that is not finite (a NaN instant: the reference takes nothing more) is not walked here -- its lanes
+    // shadow a chunk's start state, all zero, and store nothing -- and stays flagged; so does a group whose key has no tail (its
+    // walk through the row met an error that is a NaN or infinite, k_gardner_span_walk): k_gardner takes flagged groups with the checked walker
+    // behind this launch and overwrites what this one stored for their first chunk.  What the median's walk may have stored
+    // past such a chunk's true count lies where later groups store: either they are flagged too and overwrite it, or -- the
+    // walks differ only where the reference's instant became a NaN -- it lies behind the capture's last symbol.
+    // (the sub-groups past the last row shadow group g0's entry state, active or not: the test is on the state)
+    const bool nonfin = !(is_finite_bits(e.ns) && is_finite_bits(e.half) && is_finite_bits(e.prev));
+    const bool dead = L.active && nonfin;
+    if (nonfin) { L.ns = L.prev = L.half = 0.0f; L.active = false; }
     __shared__ float o_val[4 * PDT_GSUB_OUT];
     __shared__ unsigned o_idx[4 * PDT_GSUB_OUT];
     gardner_sub_chunk<WIN, 4, true>(win, in, P, c_sub, L, sym, symidx, e.offset, sym_cap, o_val, o_idx);
+    if (dead && (lane & 15) == 0) flags[my_g] = 1;
     if (L.active && (lane & 15) == 0) {
         unsigned char flag = 1;
         const GardnerSpanRow rw = rows[my_g];
@@ -2004,7 +2082,7 @@ __device__ __forceinline__ void k_gardner_emit_first(const float *__restrict__ i
                 if (keys[rw.off + mid] < k1) lo = mid + 1;
                 else hi = mid;
             }
-            if (lo < rw.n && keys[rw.off + lo] == k1) {
+            if (lo < rw.n && keys[rw.off + lo] == k1 && tails[rw.off + lo] != PDT_GTAB_MISS) {
                 const GardnerSpanRec *rc = recs + (size_t)(rw.off + lo) * (size_t)(D.span - 1);
                 for (int q = 1; q < D.span; q++) {
                     GardnerEntry<float> ce;
@@ -2096,7 +2174,8 @@ __device__ __forceinline__ void k_gardner_span_join(GardnerDomain D, long long n
                 if (cnt < (1u << (32 - D.idx_bits)) - 1u) out = (tail & kmask) | (cnt << D.idx_bits);
             }
         }
-        if (out == PDT_GTAB_MISS) atomicAdd(&stats[0], 1u);
+        if (out == PDT_GTAB_MISS) atomicAdd(&stats[0], 1u);       // (a tail left out on purpose -- an error that was a NaN or infinite -- counts here too,
+                                                                  // unlike k_gardner_table_merge's slices: the join cannot tell the two; nobody reads the counter)
         row[k] = out;
     }
 }

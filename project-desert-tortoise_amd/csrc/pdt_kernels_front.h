@@ -2585,7 +2585,9 @@ __device__ __forceinline__ void k_static_gain(IqSrc pcm, long long n0, T *__rest
     // monotone map of avg (rounding is monotone), while avg always lies in [0, max m].  So two chains
     // over the last TAIL magnitudes, started from 0 and from the chunk's largest magnitude, bracket
     // the true chain; when they end on the same float -- they always do -- that float IS the
-    // reference's result, whatever came before.  Otherwise the full chain below runs.
+    // reference's result, whatever came before.  Otherwise the full chain below runs.  (A NaN magnitude is never forgotten: it is
+    // kept as the maximum, the chain started from it ends on a NaN, the one from 0 does not unless the tail holds one too -- where
+    // both do, NaN is the reference's result -- and the full chain below gives the reference's NaN.)
     constexpr int TAIL = 192;
     constexpr int CAP = 16384;
     __shared__ T s_mag[CAP];
@@ -2596,13 +2598,13 @@ __device__ __forceinline__ void k_static_gain(IqSrc pcm, long long n0, T *__rest
             T a, b;
             IqSample<T>::get(pcm, i, a, b);
             const T m = Real<T>::hypot(a, b);
-            mx = (m > mx) ? m : mx;
+            mx = (m > mx || m != m) ? m : mx;                     // (false for every m once mx is a NaN)
             if (i >= n0 - TAIL) s_mag[i - (n0 - TAIL)] = m;
         }
         s_red[threadIdx.x] = mx;
         __syncthreads();
         for (int w = 128; w >= 1; w >>= 1) {
-            if ((int)threadIdx.x < w) s_red[threadIdx.x] = (s_red[threadIdx.x + w] > s_red[threadIdx.x]) ? s_red[threadIdx.x + w] : s_red[threadIdx.x];
+            if ((int)threadIdx.x < w) s_red[threadIdx.x] = (s_red[threadIdx.x + w] > s_red[threadIdx.x] || s_red[threadIdx.x + w] != s_red[threadIdx.x + w]) ? s_red[threadIdx.x + w] : s_red[threadIdx.x];
             __syncthreads();
         }
         T a = (threadIdx.x == 0) ? (T)0 : s_red[0];

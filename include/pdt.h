@@ -60,7 +60,10 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 23): POES frames' failed parity groups repaired from the soft bit values -- pdt_tip_repair_info,
+/* 4, additions without a bump (round 27): the DCS-2 platform messages that TIP minor frames relay -- pdt_dcs_cfg, pdt_dcs_packet,
+ * pdt_dcs_summary, pdt_tip_dcs, pdt_tip_dcs_records, pdt_host_tip_dcs, pdt_format_dcs_packets, pdt_write_dcs_packets, pdt_tip_dcs_tile: a
+ * result beside the frames, which stay as they are.
+ * 4, additions without a bump (round 23): POES frames' failed parity groups repaired from the soft bit values -- pdt_tip_repair_info,
  * pdt_tip_repair_summary, pdt_tip_repair, pdt_stage_tip_repair, pdt_host_tip_repair: opt-in, beside everything else.
  * 4, additions without a bump (round 22): POES bits without a loop -- pdt_ffp_cfg, pdt_ffp_sync, pdt_ffp_block, pdt_ffp_bits, pdt_ffp_read,
  * pdt_ffp_blocks, pdt_ffp_frames, pdt_stage_ffp_bits, pdt_stage_ffp_frames, pdt_host_ffp_bits, pdt_host_ffp_mix: a second, opt-in source
@@ -1020,6 +1023,74 @@ int  pdt_stage_tip_repair(pdt_ctx *ctx, const float *soft_host, uint64_t nbits, 
                           pdt_tip_repair_summary *summary);
 int  pdt_host_tip_repair(const float *soft, uint64_t nbits, pdt_frame *frames, uint64_t n, pdt_tip_repair_info *info,
                          pdt_tip_repair_summary *summary);
+
+/* POES frames: the DCS-2 platform messages they relay (POES contexts).  The satellite receives the ARGOS platforms on
+ * 401.65 MHz and relays each message -- platform ID, sensor data, its own time code, the measured Doppler word -- in 32 bytes of every TIP
+ * minor frame (standalone_matlab/Functionized/POES.m:868-1311).  These entries are opt-in and stand BESIDE everything else; the rule is
+ * fixed in csrc/pdt_tip_dcs.h and pdt_host_tip_dcs restates it on the host:
+ *   input     pdt_frame records from any source, repaired or not.  A record is ELIGIBLE <=> complete == 1 and nbytes == 104; `inverted`
+ *             plays no part
+ *   SLOTS     the DCS bytes of a frame are bytes[b] for b = 18 19 24 25 28 29 32 33 40 41 44 45 52 53 56 57 60 61 64 65 68 69 72 73 76 77
+ *             86 87 90 91 94 95 (POES.m:869-932, 0-based here): 32 slots; the time of slot byte b is time + b * (0.1 / 104) (POES.m:257)
+ *   SEGMENTS  record i+1 continues record i <=> both are eligible and bit_index[i+1] - bit_index[i] == 832.  A segment is a maximal run of
+ *             such records, its stream S the concatenation of their slots.  An ineligible record belongs to no segment and is counted as
+ *             skipped.  Nothing is joined across a gap (the reference concatenates whatever frames it has)
+ *   HEAD      position k of a segment is a head <=> k + 2 lies inside the segment, S[k] == 0xD6, S[k+1] < channel_max (0 means 8; the
+ *             reference uses 9 for NOAA-19, POES.m:942-946; 1 .. 16) and the high nibble c of S[k+2] is a valid length code: with
+ *             n1 = c >> 1, (c & 1) == ((n1 >> 2) ^ (n1 >> 1) ^ n1) & 1 -- the codes 0 3 5 6 9 A C F of POES.m:1195-1214.  Then
+ *             blocks = n1 + 1 and L = 12 + 4 blocks.  A D6 with a good channel byte and an invalid code is counted (bad_code) and is no
+ *             head (the reference takes 44 bytes).  A D6 that is a segment's first byte is a head like any other (the reference never sees
+ *             the stream's first byte)
+ *   ACCEPTED  within a segment, in ascending order, a head is accepted <=> k >= the end k' + L' of the previously accepted one; any other
+ *             head is SHADOWED and counted (the reference cuts a packet wherever a data byte pair looks like a head)
+ *   PACKET    of an accepted head: nbytes = min(L, segment_len - k), complete = (nbytes == L), bytes[0 .. nbytes) from the stream, the rest
+ *             zero; channel = S[k+1]; time_code = (S[k+3] & 31) << 16 | S[k+4] << 8 | S[k+5] (nbytes >= 6, else 0); id = big-endian
+ *             S[k+6 .. k+9] (nbytes >= 10, else 0; the reference's TXID, POES.m:1184); when complete, w = the last three bytes, big-endian,
+ *             doppler_ok = 1 when w has an even number of ones, doppler_raw = (int32)(w >> 1) - (1 << 22) (the reference prints
+ *             doppler_raw / 32.0, POES.m:1261-1271), both 0 otherwise; frame and slot = the record and the slot 0 .. 31 that hold the D6;
+ *             stream_index = that byte's position when every eligible record's slots are counted in record order; time = the time of the
+ *             D6 byte ITSELF (the reference stamps a packet with the time of the byte in front of its D6)
+ *   SUMMARY   totals over the call: records used, records skipped, segments, stream bytes, heads, shadowed, bad_code, packets, complete,
+ *             doppler_bad (complete packets whose Doppler word has odd parity)
+ * Packets come out in ascending record order.  *count = the packets found; at most cap are written (cap = 0 with out = NULL only counts);
+ * the summary is always complete.
+ *   pdt_tip_dcs             the frames of the context's last pdt_demod_* call, which are still in device memory (as pdt_tip_check).
+ *                           PDT_ERR_STATE when nothing has been demodulated or a stream is open; PDT_ERR_ARG for an ARGOS context, a null
+ *                           count or summary, cap < 0, a null out with cap > 0, channel_max > 16.  No other result of the context changes (a
+ *                           profiled context's pdt_kernel_times gain the entries k_dcs_gather, k_dcs_maps, k_dcs_scan and k_dcs_pack)
+ *   pdt_tip_dcs_records     a caller's records (uploaded to a buffer of their own, as pdt_tip_check_records uploads its); n >= 2^31 or a
+ *                           null pointer with n > 0: PDT_ERR_ARG
+ *   pdt_host_tip_dcs        host only, no GPU: the same packets and summary, `time` included, bit for bit
+ *   pdt_tip_dcs_tile        the stream bytes one tile covers (tests place packets at its seams)
+ *   pdt_format_dcs_packets  the packets' text; returns the bytes needed, writes at most cap.  One line per packet:
+ *                             "%.5f %u %u %07u %08X %s " (time, channel, blocks, time_code, id, Doppler), "%02X " per byte, "\n"
+ *                           where the Doppler is "%.5f" of doppler_raw / 32.0 for a complete packet with even parity, the same behind a '*'
+ *                           when the parity is odd, and "-" for a packet that is cut off
+ *   pdt_write_dcs_packets   the same text to a file descriptor; PDT_ERR_IO when a write fails                                            */
+typedef struct pdt_dcs_cfg {
+    uint32_t channel_max;  /* the channel byte's bound, 1 .. 16; 0 = 8                                                       */
+    uint32_t reserved;
+} pdt_dcs_cfg;             /* NULL or zeroed = default                                                                       */
+typedef struct pdt_dcs_packet {
+    double   time;         /* of the D6 byte                                                                                 */
+    int64_t  stream_index; /* of the D6 byte, over the slots of every eligible record                                        */
+    uint32_t frame;        /* the record that holds the D6                                                                   */
+    uint32_t time_code, id;
+    int32_t  doppler_raw;
+    uint8_t  slot, channel, blocks, nbytes, complete, doppler_ok, pad[2];
+    uint8_t  bytes[44];
+} pdt_dcs_packet;
+typedef struct pdt_dcs_summary {
+    uint64_t used, skipped, segments, stream_bytes, heads, shadowed, bad_code, packets, complete, doppler_bad;
+} pdt_dcs_summary;
+int      pdt_tip_dcs(pdt_ctx *ctx, const pdt_dcs_cfg *cfg, pdt_dcs_packet *out, int cap, int *count, pdt_dcs_summary *summary);
+int      pdt_tip_dcs_records(pdt_ctx *ctx, const pdt_frame *frames, uint64_t n, const pdt_dcs_cfg *cfg, pdt_dcs_packet *out, int cap, int *count,
+                             pdt_dcs_summary *summary);
+int      pdt_host_tip_dcs(const pdt_frame *frames, uint64_t n, const pdt_dcs_cfg *cfg, pdt_dcs_packet *out, int cap, int *count,
+                          pdt_dcs_summary *summary);
+uint64_t pdt_format_dcs_packets(const pdt_dcs_packet *packets, uint64_t n, char *buf, uint64_t cap);
+int      pdt_write_dcs_packets(const pdt_dcs_packet *packets, uint64_t n, int fd, uint64_t *bytes_written);
+int      pdt_tip_dcs_tile(void);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

@@ -455,6 +455,59 @@ def host_tip_repair(soft, frames):
     return _tip_repair_result(a, info, sm)
 
 
+# pdt_dcs_packet as a numpy record, pdt_dcs_cfg and pdt_dcs_summary
+DCS_PACKET_DTYPE = np.dtype([("time", "<f8"), ("stream_index", "<i8"), ("frame", "<u4"), ("time_code", "<u4"), ("id", "<u4"), ("doppler_raw", "<i4"),
+                             ("slot", "u1"), ("channel", "u1"), ("blocks", "u1"), ("nbytes", "u1"), ("complete", "u1"), ("doppler_ok", "u1"),
+                             ("pad", "u1", (2,)), ("bytes", "u1", (44,)), ("_tail", "u1", (4,))])     # the C struct is padded to 88
+assert DCS_PACKET_DTYPE.itemsize == 88
+
+
+class DcsCfg(C.Structure):
+    _fields_ = [("channel_max", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DcsSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("used", "skipped", "segments", "stream_bytes", "heads", "shadowed", "bad_code", "packets", "complete",
+                                          "doppler_bad")]
+
+
+def _dcs_result(out, count: int, cap: int, sm):
+    return out[:min(count, cap)], count, {k: int(getattr(sm, k)) for k, _ in DcsSummary._fields_}
+
+
+def tip_dcs_tile() -> int:
+    """pdt_tip_dcs_tile: the stream bytes one tile of the DCS kernels covers (tests place packets at its seams)"""
+    return int(lib().pdt_tip_dcs_tile())
+
+
+def host_tip_dcs(frames, channel_max: int = 0, cap: int = 65536):
+    """pdt_host_tip_dcs: the DCS-2 platform messages that FRAME_DTYPE records of TIP minor frames relay, restated on the host (no GPU).
+    channel_max: the channel byte's bound (0 = 8; 9 for NOAA-19).  Returns (DCS_PACKET_DTYPE[min(found, cap)], found, summary dict)."""
+    a = np.ascontiguousarray(frames, dtype=FRAME_DTYPE).reshape(-1)
+    c = DcsCfg(channel_max, 0)
+    out, count, sm = np.zeros(max(cap, 1), dtype=DCS_PACKET_DTYPE), C.c_int(0), DcsSummary()
+    _check(lib().pdt_host_tip_dcs(a.ctypes.data, len(a), C.byref(c), out.ctypes.data if cap else None, cap, C.byref(count), C.byref(sm)), "pdt_host_tip_dcs")
+    return _dcs_result(out, count.value, cap, sm)
+
+
+def format_dcs_packets(packets: np.ndarray) -> bytes:
+    """pdt_format_dcs_packets: one line per packet (host-only C, no GPU needed)"""
+    a = np.ascontiguousarray(packets, dtype=DCS_PACKET_DTYPE).reshape(-1)
+    L = lib()
+    n = L.pdt_format_dcs_packets(a.ctypes.data, len(a), None, 0)
+    buf = C.create_string_buffer(n + 1)
+    L.pdt_format_dcs_packets(a.ctypes.data, len(a), buf, n)
+    return buf.raw[:n]
+
+
+def write_dcs_packets(packets: np.ndarray, fd: int) -> int:
+    """pdt_write_dcs_packets: the same text to an open file descriptor; returns the bytes written"""
+    a = np.ascontiguousarray(packets, dtype=DCS_PACKET_DTYPE).reshape(-1)
+    w = C.c_uint64(0)
+    _check(lib().pdt_write_dcs_packets(a.ctypes.data, len(a), fd, C.byref(w)), "pdt_write_dcs_packets")
+    return int(w.value)
+
+
 class FfCfg(C.Structure):
     """pdt_ff_cfg: a zero means the default; rate_steps 0 with FF_ZERO_RATE_STEPS in zero_mask asks for the nominal rate alone;
     FF_RESIDUAL_GIVEN in flags: residual_hz is the caller's, otherwise the carrier is measured"""
@@ -648,6 +701,7 @@ ABI_SYMBOLS = [
     "pdt_host_ffp_mix",
     "pdt_tip_sync", "pdt_tip_sync_batch", "pdt_stage_tip_sync", "pdt_host_tip_sync", "pdt_tip_sync_tile", "pdt_tip_check_records",
     "pdt_tip_repair", "pdt_stage_tip_repair", "pdt_host_tip_repair",
+    "pdt_tip_dcs", "pdt_tip_dcs_records", "pdt_host_tip_dcs", "pdt_format_dcs_packets", "pdt_write_dcs_packets", "pdt_tip_dcs_tile",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_fir_form", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
 
@@ -813,6 +867,12 @@ def lib():
     L.pdt_tip_repair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TipRepairSummary)]
     L.pdt_stage_tip_repair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TipRepairSummary)]
     L.pdt_host_tip_repair.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TipRepairSummary)]
+    L.pdt_tip_dcs.argtypes = [C.c_void_p, C.POINTER(DcsCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(DcsSummary)]
+    L.pdt_tip_dcs_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DcsCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(DcsSummary)]
+    L.pdt_host_tip_dcs.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DcsCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(DcsSummary)]
+    L.pdt_format_dcs_packets.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
+    L.pdt_format_dcs_packets.restype = C.c_uint64
+    L.pdt_write_dcs_packets.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_format_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.pdt_format_argos_messages.restype = C.c_uint64
     L.pdt_write_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
@@ -1588,6 +1648,23 @@ class Demodulator:
                "pdt_stage_tip_repair")
         return _tip_repair_result(a, info, sm)
 
+    def tip_dcs(self, channel_max: int = 0, cap: int = 65536):
+        """pdt_tip_dcs: the DCS-2 platform messages in the minor frames of this context's last demodulation, which are still on the device:
+        (DCS_PACKET_DTYPE[min(found, cap)], found, summary dict).  The context's own results stay as they were."""
+        c = DcsCfg(channel_max, 0)
+        out, count, sm = np.zeros(max(cap, 1), dtype=DCS_PACKET_DTYPE), C.c_int(0), DcsSummary()
+        _check(self._L.pdt_tip_dcs(self._h, C.byref(c), out.ctypes.data if cap else None, cap, C.byref(count), C.byref(sm)), "pdt_tip_dcs")
+        return _dcs_result(out, count.value, cap, sm)
+
+    def tip_dcs_records(self, frames, channel_max: int = 0, cap: int = 65536):
+        """pdt_tip_dcs_records: the same kernels on a caller's FRAME_DTYPE records (those of tip_sync() or ffp_frames(), repaired or not)"""
+        a = np.ascontiguousarray(frames, dtype=FRAME_DTYPE).reshape(-1)
+        c = DcsCfg(channel_max, 0)
+        out, count, sm = np.zeros(max(cap, 1), dtype=DCS_PACKET_DTYPE), C.c_int(0), DcsSummary()
+        _check(self._L.pdt_tip_dcs_records(self._h, a.ctypes.data, len(a), C.byref(c), out.ctypes.data if cap else None, cap, C.byref(count), C.byref(sm)),
+               "pdt_tip_dcs_records")
+        return _dcs_result(out, count.value, cap, sm)
+
     def tip_sync(self, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False, with_count: bool = False):
         """pdt_tip_sync: the POES minor frames a flywheel synchroniser finds in the bits of this context's last whole-capture call -- a
         sync word with up to max_errors wrong bits (None = 2) counts when a neighbouring slot within `window` frames (None = 2) has one
@@ -1713,6 +1790,8 @@ def synth_lib():
         S.pdt_synth_argos_payload.restype = None
         S.pdt_synth_argos_message.argtypes = [C.POINTER(SynthParams), C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_void_p]
         S.pdt_synth_argos_message.restype = None
+        S.pdt_synth_dcs_packet.argtypes = [C.POINTER(SynthParams), C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        S.pdt_synth_dcs_packet.restype = None
         S.pdt_synth_sine_table.restype = C.POINTER(C.c_int16)
         S.pdt_synth_wav_header.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
         S.pdt_synth_wav_header.restype = None
@@ -1730,7 +1809,7 @@ def synth_capture(kind: int, sample_rate: int, seconds: float, f0_hz: float | No
                   start: int = 0) -> np.ndarray:
     """int16[n,2] synthetic POES (kind 0) / ARGOS (kind 1; kind 2: messages of 1 .. 8 blocks) capture; bit-reproducible everywhere."""
     if f0_hz is None:
-        f0_hz = 1000.0 if kind in (0, 3) else 120.0            # (kind 3: POES frames that carry their parity)
+        f0_hz = 1000.0 if kind in (0, 3, 4) else 120.0         # (kind 3: POES frames that carry their parity; kind 4: and a DCS stream)
     p = synth_params(kind, sample_rate, f0_hz, seed)
     n = int(round(seconds * sample_rate))
     out = np.zeros((n, 2), dtype="<i2")
@@ -1755,6 +1834,13 @@ def synth_argos_message(p: SynthParams, burst: int) -> tuple[int, int, np.ndarra
     blocks, ident, data = C.c_int(0), C.c_uint32(0), np.zeros(32, dtype=np.uint8)
     synth_lib().pdt_synth_argos_message(C.byref(p), burst, C.byref(blocks), C.byref(ident), data.ctypes.data)
     return blocks.value, ident.value, data[:4 * blocks.value]
+
+
+def synth_dcs_packet(p: SynthParams, s: int, which: int) -> np.ndarray:
+    """kind 4: the bytes of DCS packet `which` (0 = A, 1 = B) of slot group s as transmitted"""
+    out, n = np.zeros(44, dtype=np.uint8), C.c_int(0)
+    synth_lib().pdt_synth_dcs_packet(C.byref(p), s, which, out.ctypes.data, C.byref(n))
+    return out[:n.value]
 
 
 def write_wav(path: str, sample_rate: int, iq: np.ndarray):

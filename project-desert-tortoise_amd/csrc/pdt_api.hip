@@ -11,6 +11,7 @@
 #include "pdt_tip_sync.h"
 #include "pdt_ff.h"
 #include "pdt_ffp.h"
+#include "pdt_tip_dcs.h"
 
 #include <sys/stat.h>
 
@@ -60,6 +61,15 @@ void ffp_steps(const pdt_tone *tones, uint64_t nseg, int nfft, const pdt::FfpRul
 // pdt_tip_repair.hip
 hipError_t tip_repair_launch(hipStream_t st, void *recs_dev, unsigned nrec, const float *soft_dev, const unsigned long long *nbits_dev, long long bit_cap,
                              void *info_dev, void *sum_dev);
+// pdt_tip_dcs.hip
+extern const char *const tip_dcs_kernel_names[4];
+size_t tip_dcs_map_bytes();
+size_t tip_dcs_entry_bytes();
+hipError_t tip_dcs_launch(hipStream_t st, const void *recs_dev, bool chain_layout, const void *times_dev, unsigned long long n, unsigned channel_max,
+                          void *sum_dev, void *flags_dev, void *stream_dev, void *head_dev, void *bad_dev, void *maps_dev, void *entry_dev, void *out_dev,
+                          unsigned long long cap, hipEvent_t *inner);
+void tip_dcs_summary(const unsigned long long *c, unsigned long long n, pdt_dcs_summary *s);
+int tip_dcs_rule(const pdt_dcs_cfg *cfg, unsigned *channel_max);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -613,7 +623,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
                        &ctx->staged_bits, &ctx->staged_iq, &ctx->argos_work, &ctx->ff_work, &ctx->ff_out, &ctx->ffp_work, &ctx->ffp_out,
-                       &ctx->tip_sync_work, &ctx->tip_recs, &ctx->tip_repair_work, &ctx->tip_repair_soft };
+                       &ctx->tip_sync_work, &ctx->tip_recs, &ctx->tip_repair_work, &ctx->tip_repair_soft, &ctx->tip_dcs_work };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -2174,6 +2184,75 @@ int pdt_stage_tip_repair(pdt_ctx *ctx, const float *soft_host, uint64_t nbits, p
     if (rc) return rc;
     const unsigned char *p = (const unsigned char *)ctx->tip_repair_soft.p;
     return tip_repair_run(ctx, (const float *)(p + 16), (const unsigned long long *)p, (long long)nbits, frames, n, info, summary);
+}
+
+// ---------------------------------------------------------------- DCS packets of TIP minor frames (pdt_tip_dcs.h)
+// The four kernels on n records: the caller's (uploaded into the work buffer as they are) or, with frames == NULL, the chain's own in
+// ctx->frames, whose time stamps go up from frames_host beside them.  The counters come back first -- the packet count has stayed on the
+// device until then --, then as many packets as were found and fit.
+static_assert(sizeof(FrameRec) == sizeof(pdt::TipDcsChainRec) && offsetof(FrameRec, nbytes) == offsetof(pdt::TipDcsChainRec, nbytes) &&
+              offsetof(FrameRec, complete) == offsetof(pdt::TipDcsChainRec, complete) && offsetof(FrameRec, bytes) == offsetof(pdt::TipDcsChainRec, bytes), "FrameRec");
+static int tip_dcs_run(pdt_ctx *c, const pdt_frame *frames, uint64_t n, unsigned channel_max, pdt_dcs_packet *out, int cap, int *count, pdt_dcs_summary *summary)
+{
+    memset(summary, 0, sizeof *summary);
+    *count = 0;
+    if (n == 0) return PDT_OK;
+    const size_t tiles = ((size_t)n + pdt::TIP_DCS_TILE_RECS - 1) / pdt::TIP_DCS_TILE_RECS;
+    const size_t room = (size_t)std::min<uint64_t>((uint64_t)cap, 3 * n);                       // (a record holds at most three heads' packets)
+    const DcsWork L = dcs_work_layout((size_t)n, tiles, pdt::TIP_DCS_TILE, tip_dcs_map_bytes(), tip_dcs_entry_bytes(),
+                                      (size_t)n * (frames ? sizeof(pdt_frame) : sizeof(double)), room * sizeof(pdt_dcs_packet));
+    int rc;
+    if ((rc = c->tip_dcs_work.ensure(L.total))) return rc;
+    unsigned char *w = (unsigned char *)c->tip_dcs_work.p;
+    hipStream_t st = c->stream;
+    std::vector<double> times;
+    HIP_TRY(hipMemsetAsync(w + L.o_sum, 0, L.o_stream - L.o_sum, st));                               // the counters and the flags
+    if (frames) HIP_TRY(hipMemcpyAsync(w + L.o_src, frames, (size_t)n * sizeof(pdt_frame), hipMemcpyHostToDevice, st));
+    else {
+        times.resize((size_t)n);
+        for (size_t f = 0; f < (size_t)n; f++) times[f] = c->frames_host[f].time;
+        HIP_TRY(hipMemcpyAsync(w + L.o_src, times.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    CallTimer timer(c, st, tip_dcs_kernel_names, nullptr, 4);
+    HIP_TRY(timer.begin());
+    HIP_TRY(tip_dcs_launch(st, frames ? (const void *)(w + L.o_src) : c->frames.p, !frames, w + L.o_src, n, channel_max, w + L.o_sum, w + L.o_flags, w + L.o_stream,
+                           w + L.o_head, w + L.o_bad, w + L.o_maps, w + L.o_entry, w + L.o_out, room, timer.inner()));
+    HIP_TRY(timer.end());
+    unsigned long long counters[16];
+    HIP_TRY(hipMemcpyAsync(counters, w + L.o_sum, sizeof counters, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    timer.commit();
+    tip_dcs_summary(counters, n, summary);
+    const size_t give = (size_t)std::min<uint64_t>(summary->packets, room);
+    if (give) HIP_TRY(hipMemcpy(out, w + L.o_out, give * sizeof(pdt_dcs_packet), hipMemcpyDeviceToHost));
+    *count = (int)std::min<uint64_t>(summary->packets, 0x7fffffffull);
+    return PDT_OK;
+}
+
+int pdt_tip_dcs(pdt_ctx *ctx, const pdt_dcs_cfg *cfg, pdt_dcs_packet *out, int cap, int *count, pdt_dcs_summary *summary)
+{
+    unsigned channel_max;
+    if (!ctx || !count || !summary || cap < 0 || (!out && cap) || tip_dcs_rule(cfg, &channel_max)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;             // TIP minor frames only
+    const unsigned nf = ctx->frames_on_device;
+    if (ctx->stream_open || !ctx->have_frames || nf != ctx->frames_host.size()) return PDT_ERR_STATE;
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;
+    try {
+        return tip_dcs_run(ctx, nullptr, nf, channel_max, out, cap, count, summary);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+int pdt_tip_dcs_records(pdt_ctx *ctx, const pdt_frame *frames, uint64_t n, const pdt_dcs_cfg *cfg, pdt_dcs_packet *out, int cap, int *count,
+                        pdt_dcs_summary *summary)
+{
+    unsigned channel_max;
+    if (!ctx || !count || !summary || (!frames && n) || n >= (1ull << 31) || cap < 0 || (!out && cap) || tip_dcs_rule(cfg, &channel_max)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;
+    try {
+        return tip_dcs_run(ctx, frames, n, channel_max, out, cap, count, summary);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
 }
 
 int pdt_stage_bytesync(pdt_ctx *ctx, const uint8_t *bits_host, uint64_t nbits)

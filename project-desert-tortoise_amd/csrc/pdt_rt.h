@@ -497,6 +497,8 @@ struct pdt_ctx {
     // parity repair (pdt_tip_repair.h): the counters, the caller's records and their info records (RepairWork); the soft values of the
     // stage entry behind their count (stage_counted)
     DevBuf tip_repair_work, tip_repair_soft;
+    // DCS packets (pdt_tip_dcs.h): counters, flags, stream, bitmaps, tile maps and entries, the records or their time stamps, the packets (DcsWork)
+    DevBuf tip_dcs_work;
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
     int held_fmt = 0;

@@ -67,6 +67,17 @@ inline RepairWork repair_work_layout(size_t recs, size_t rec_bytes, size_t info_
     return { c.take(64), c.take(recs * rec_bytes), c.take(recs * info_bytes), c.at };
 }
 
+// DCS packets (tip_dcs_run): the counters (128 bytes), the records' flags (two spare ones end them), the stream of 32 bytes per record
+// rounded up to whole tiles, the head and the bad-code bitmap (a bit per stream byte), every tile's map and entry, the records' time
+// stamps or the caller's records (`src_bytes`), the packets
+struct DcsWork { size_t o_sum, o_flags, o_stream, o_head, o_bad, o_maps, o_entry, o_src, o_out, total; };
+inline DcsWork dcs_work_layout(size_t recs, size_t tiles, size_t tile_bytes, size_t map_bytes, size_t entry_bytes, size_t src_bytes, size_t out_bytes)
+{
+    Carve c;
+    return { c.take(128), c.take(recs + 2), c.take(tiles * tile_bytes), c.take(tiles * tile_bytes / 8), c.take(tiles * tile_bytes / 8),
+             c.take(tiles * map_bytes), c.take(tiles * entry_bytes), c.take(src_bytes), c.take(out_bytes), c.at };
+}
+
 // what both feed-forward result buffers end with: time source, soft values, bit -> symbol map and characters of `cap` bits, each over
 // the capacity rounded up to 16
 struct BitsTail { size_t o_idx, o_soft, o_sym, o_bits; };

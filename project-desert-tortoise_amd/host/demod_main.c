@@ -88,6 +88,13 @@
  * least and next for each failing group --, and a summary line precedes the -W count.  After the repair every group
  * passes by construction: -q's flywheel line on these frames says nothing, the report is the parity record to keep.  -Q without -b (the
  * loop's bits carry no soft values) or for demodARGOS: a message, exit status 1.
+ * -C <file> (an addition, demodPOES): the DCS-2 platform messages the run's minor frames relay (pdt_tip_dcs), one line per
+ * packet -- "%.5f %u %u %07u %08X %s " of its time, channel, blocks, time code, ID and Doppler ("%.5f" of the word / 32, behind a '*' when
+ * the word's parity is odd, "-" for a packet that is cut off), "%02X " per byte --, then a blank line and the table the reference ends
+ * with (POES.m:1291-1307): "%08X %u" per platform ID, most frequent first, ties by ascending ID.  With -W the packets are those of -W's
+ * records (after -Q's repair when that is given), otherwise those of the minorFrames file's frames; a run without frames writes an empty
+ * file.  One console line reports packets, complete packets, Doppler parity failures and segments.  One channel of a capture taken in one
+ * piece, as -W: demodARGOS, a pipe, -l and several -t refuse it.
  * -W <file> (an addition, demodPOES): the minor frames a flywheel synchroniser finds in the bits of the capture (pdt_tip_sync, DESIGN
  * 4.18), in the minor-frame text format, beside the unchanged minorFrames file.  -w E,W,G sets its three constants (max_errors, window,
  * fly; default 2,2,3); with -q a second validation line, for these frames, follows the reference's.  One channel of a capture taken
@@ -108,14 +115,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:bW:w:Q:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:bW:w:Q:C:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:bW:w:Q:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:bW:w:Q:C:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -412,6 +419,79 @@ static int write_flywheel(pdt_ctx *ctx, const pdt_tip_sync_cfg *cfg, const char 
     printf("Flywheel frames: %d -> %s\n", n, name);
     *frames = fr;
     *count = n;
+    return 0;
+}
+
+/* -C: the DCS packets of -W's records, or (fr == NULL) of the frames of ctx's last capture, which are still on the device, one line each;
+ * a blank line; the per-ID table, built here from the packets.  Returns 0 when the file is written. */
+typedef struct { uint32_t id, count; } dcs_id_count;
+static int dcs_id_order(const void *a, const void *b)
+{
+    const dcs_id_count *x = (const dcs_id_count *)a, *y = (const dcs_id_count *)b;
+    if (x->count != y->count) return x->count > y->count ? -1 : 1;
+    return x->id < y->id ? -1 : x->id > y->id;
+}
+static int dcs_id_value(const void *a, const void *b)
+{
+    const uint32_t x = ((const dcs_id_count *)a)->id, y = ((const dcs_id_count *)b)->id;
+    return x < y ? -1 : x > y;
+}
+
+static int write_dcs(pdt_ctx *ctx, const pdt_frame *fr, int nfr, const char *name)
+{
+    pdt_dcs_summary sum;
+    int found = 0;
+    memset(&sum, 0, sizeof sum);
+    int rc = fr ? pdt_tip_dcs_records(ctx, fr, (uint64_t)nfr, NULL, NULL, 0, &found, &sum) : pdt_tip_dcs(ctx, NULL, NULL, 0, &found, &sum);
+    if (!fr && rc == PDT_ERR_STATE) {
+        if (pdt_num_frames(ctx)) {
+            printf("-C needs a capture taken in one piece: this one was demodulated in pieces and left its frames in no one place\n");
+            return 1;
+        }
+        rc = PDT_OK;                                                   /* (a run without frames: an empty file) */
+        found = 0;
+    }
+    pdt_dcs_packet *pk = (pdt_dcs_packet *)malloc((size_t)(found ? found : 1) * sizeof *pk);
+    dcs_id_count *ids = (dcs_id_count *)malloc((size_t)(found ? found : 1) * sizeof *ids);
+    if (rc == PDT_OK && (!pk || !ids)) rc = PDT_ERR_NOMEM;
+    if (rc == PDT_OK && found) {
+        const int cap = found;
+        rc = fr ? pdt_tip_dcs_records(ctx, fr, (uint64_t)nfr, NULL, pk, cap, &found, &sum) : pdt_tip_dcs(ctx, NULL, pk, cap, &found, &sum);
+        if (found > cap) found = cap;
+    }
+    if (rc != PDT_OK) printf("DCS decommutation failed: %s\n", pdt_strerror(rc));
+    FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !m) printf("Error opening %s\n", name);
+    if (!m) {
+        free(pk);
+        free(ids);
+        return 1;
+    }
+    int bad = 0;
+    if (found) {
+        fflush(m);
+        bad = pdt_write_dcs_packets(pk, (uint64_t)found, fileno(m), NULL) != PDT_OK;
+        fseek(m, 0, SEEK_END);
+        for (int k = 0; k < found; k++) ids[k].id = pk[k].id, ids[k].count = 1;
+        qsort(ids, (size_t)found, sizeof *ids, dcs_id_value);
+        int nid = 0;
+        for (int k = 0; k < found; k++) {
+            if (nid && ids[nid - 1].id == ids[k].id) ids[nid - 1].count++;
+            else ids[nid++] = ids[k];
+        }
+        qsort(ids, (size_t)nid, sizeof *ids, dcs_id_order);
+        fprintf(m, "\n");
+        for (int k = 0; k < nid; k++) fprintf(m, "%08X %u\n", (unsigned)ids[k].id, (unsigned)ids[k].count);
+    }
+    bad |= fclose(m) != 0;
+    free(pk);
+    free(ids);
+    if (bad) {
+        printf("Error writing %s\n", name);
+        return 1;
+    }
+    printf("DCS packets: %llu, %llu complete, %llu Doppler parity failures, %llu segments -> %s\n", (unsigned long long)sum.packets,
+           (unsigned long long)sum.complete, (unsigned long long)sum.doppler_bad, (unsigned long long)sum.segments, name);
     return 0;
 }
 
@@ -906,6 +986,7 @@ int main(int argc, char **argv)
     const char *messageName = NULL;                                                 /* -A: the ARGOS messages' file */
     const char *flywheelName = NULL;                                                /* -W: the flywheel synchroniser's frames' file */
     const char *repairName = NULL;                                                  /* -Q: the parity repair's report */
+    const char *dcsName = NULL;                                                     /* -C: the DCS packets' file */
     pdt_tip_sync_cfg flywheelCfg;                                                   /* -w E,W,G: its constants */
     int flywheelCfgGiven = 0;
     char outFileName[1100];
@@ -1031,6 +1112,9 @@ int main(int argc, char **argv)
         case 'Q':                                       /* -b -W: repair the frames' failed parity groups, the report to this file */
             repairName = optarg;
             break;
+        case 'C':                                       /* the DCS packets the minor frames relay, to this file */
+            dcsName = optarg;
+            break;
         case 'w': {                                     /* max_errors, window, fly of the flywheel's rule */
             int e = 0, w = 0, g = 0;
             char tail = 0;
@@ -1135,6 +1219,10 @@ int main(int argc, char **argv)
     }
     if (flywheelCfgGiven && !flywheelName) {
         printf("-w sets the constants of -W <file>\n");
+        return 1;
+    }
+    if (dcsName && (MODE != PDT_MODE_POES || from_stdin || live || nOffsets > 1 || autoCarriers)) {
+        printf("-C needs demodPOES, one channel and a capture taken in one piece: not a pipe, not -l, not several -t\n");
         return 1;
     }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
@@ -1399,6 +1487,11 @@ int main(int argc, char **argv)
     free(ffpIq);
     free(ffIq);
     if (flyBad) {
+        fclose(out);
+        remove(outFileName);
+        exit(1);
+    }
+    if (dcsName && write_dcs(ctx, flywheelName ? flyFrames : NULL, flyCount, dcsName)) {
         fclose(out);
         remove(outFileName);
         exit(1);

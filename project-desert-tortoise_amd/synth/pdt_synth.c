@@ -30,7 +30,7 @@ void pdt_synth_default_params(pdt_synth_params *p, int kind, uint32_t sample_rat
     p->carrier_step = (uint32_t)(int64_t)llrint(f0_hz / (double)sample_rate * 4294967296.0);
     p->phase0 = turns(0.3);
     p->amplitude = 9830;                                   /* 0.3 full scale */
-    if (kind == 0 || kind == 3) {
+    if (kind == 0 || kind == 3 || kind == 4) {
         p->mod_index = turns(1.06);
         p->noise_gain = 1204;                              /* sigma = A/10/sqrt2 per component: 20 dB */
     } else {
@@ -87,7 +87,8 @@ void pdt_synth_wav_header(uint8_t h[44], uint32_t sample_rate, uint64_t nframes)
 void pdt_synth_poes_frame(const pdt_synth_params *p, uint64_t fr, uint8_t out[104])
 {
     for (uint32_t b = 0; b < 104; b++)
-        out[b] = (uint8_t)(p->kind == 3 ? pdt_synth_poes_parity_byte(p->seed, fr, b) : pdt_synth_poes_frame_byte(p->seed, fr, b));
+        out[b] = (uint8_t)(p->kind == 4 ? pdt_synth_poes_dcs_byte(p->seed, fr, b)
+                           : p->kind == 3 ? pdt_synth_poes_parity_byte(p->seed, fr, b) : pdt_synth_poes_frame_byte(p->seed, fr, b));
 }
 
 void pdt_synth_argos_payload(const pdt_synth_params *p, uint64_t burst, uint8_t out[7])
@@ -105,19 +106,27 @@ void pdt_synth_argos_message(const pdt_synth_params *p, uint64_t burst, int *blo
         data[b] = b < 4 * n ? (uint8_t)pdt_synth_argos_data_byte(p->seed, burst, b) : 0;
 }
 
+void pdt_synth_dcs_packet(const pdt_synth_params *p, uint64_t s, int which, uint8_t out[44], int *len)
+{
+    const uint32_t L = 12u + 4u * pdt_synth_dcs_blocks(p->seed, s, which ? 1u : 0u);
+    *len = (int)L;
+    for (uint32_t j = 0; j < 44; j++)
+        out[j] = j < L ? (uint8_t)pdt_synth_dcs_packet_byte(p->seed, s, which ? 1u : 0u, j) : 0;
+}
+
 #ifdef PDT_SYNTH_MAIN
-/* synth_wav poes|poesp|argos|argosn <sample_rate> <seconds> <f0_hz> <seed> out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]
+/* synth_wav poes|poesp|poesd|argos|argosn <sample_rate> <seconds> <f0_hz> <seed> out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]
  * with the optional arguments: a pass -- lead_s / tail_s seconds of noise only at the ends, the carrier ramping from f0_hz to
  * f_end_hz in between, the amplitude envelope's floor (0 = flat), the noise amplitude multiplied by noise_x */
 #include <stdio.h>
 int main(int argc, char **argv)
 {
     if (argc < 7) {
-        fprintf(stderr, "usage: %s poes|poesp|argos|argosn sample_rate seconds f0_hz seed out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]\n", argv[0]);
+        fprintf(stderr, "usage: %s poes|poesp|poesd|argos|argosn sample_rate seconds f0_hz seed out.wav [lead_s tail_s f_end_hz env_floor [noise_x]]\n", argv[0]);
         return 2;
     }
-    /* argosn: messages of 1 .. 8 blocks (kind 2); poesp: POES frames that carry their parity (kind 3) */
-    int kind = strcmp(argv[1], "poesp") == 0 ? 3 : strcmp(argv[1], "argosn") == 0 ? 2 : strcmp(argv[1], "argos") == 0;
+    /* argosn: messages of 1 .. 8 blocks (kind 2); poesp: POES frames that carry their parity (kind 3); poesd: and a DCS stream (kind 4) */
+    int kind = strcmp(argv[1], "poesd") == 0 ? 4 : strcmp(argv[1], "poesp") == 0 ? 3 : strcmp(argv[1], "argosn") == 0 ? 2 : strcmp(argv[1], "argos") == 0;
     uint32_t fs = (uint32_t)strtoul(argv[2], NULL, 10);
     double secs = atof(argv[3]);
     pdt_synth_params p;

@@ -24,6 +24,9 @@
  *  POES with parity (kind 3): a POES capture exactly as kind 0 except for byte 103 of every
  *             minor frame: its bit 5 - g is the even parity of bytes 2 + 17 g .. 18 + 17 g, g = 0 .. 4
  *             (the five TIP parity groups); bits 7, 6 and 0 come from the hash as before.
+ *  POES with DCS (kind 4): a POES capture exactly as kind 3 except that byte 2 is 8 (NOAA-15), bytes 4 and 5 carry the 9-bit
+ *             minor-frame counter fr % 320, and the 32 DCS slots of every frame carry a stream of DCS-2 packets that is a pure
+ *             function of the stream byte index (pdt_synth_dcs_stream_byte); the parity bits cover the bytes as sent.
  *
  * A pass as a receiver sees it (round 6; every field 0 = off, the captures above unchanged): noise only before
  * `signal_start` (the receiver is on before the satellite rises) and from `signal_end` on (it stays on after it has set);
@@ -48,7 +51,7 @@
 #define PDT_SYNTH_TABLE_SIZE (1u << PDT_SYNTH_TABLE_BITS)
 
 typedef struct pdt_synth_params {
-    uint32_t kind;          /* 0 = POES, 1 = ARGOS, 2 = ARGOS with messages of 1 .. 8 blocks, 3 = POES with parity */
+    uint32_t kind;          /* 0 = POES, 1 = ARGOS, 2 = ARGOS with messages of 1 .. 8 blocks, 3 = POES with parity, 4 = POES with parity and DCS */
     uint32_t sample_rate;   /* Hz                                                         */
     uint32_t carrier_step;  /* round(f0 / Fs * 2^32)                                      */
     uint32_t phase0;        /* phi0 in turns * 2^32                                       */
@@ -94,6 +97,85 @@ PDT_SYNTH_FN uint32_t pdt_synth_poes_parity_byte(uint64_t seed, uint64_t fr, uin
     for (uint32_t g = 0; g < 5; g++) {
         uint32_t x = 0;
         for (uint32_t t = 0; t < 17; t++) x ^= pdt_synth_poes_frame_byte(seed, fr, 2 + 17 * g + t);
+        x ^= x >> 4;
+        x ^= x >> 2;
+        x ^= x >> 1;
+        v |= (x & 1u) << (5 - g);
+    }
+    return v;
+}
+
+/* kind 4: the DCS slot 0 .. 31 that frame byte b is (POES.m:869-932: sixteen byte pairs), or -1 */
+PDT_SYNTH_FN int pdt_synth_dcs_slot(uint32_t b)
+{
+    const uint32_t pair = b >> 1;        /* the pairs start at bytes 18 24 28 32 40 44 52 56 60 64 68 72 76 86 90 94 */
+    const uint64_t pairs = (1ull << 9) | (1ull << 12) | (1ull << 14) | (1ull << 16) | (1ull << 20) | (1ull << 22) | (1ull << 26) | (1ull << 28) |
+                           (1ull << 30) | (1ull << 32) | (1ull << 34) | (1ull << 36) | (1ull << 38) | (1ull << 43) | (1ull << 45) | (1ull << 47);
+    if (pair > 47 || !((pairs >> pair) & 1u)) return -1;
+    int before = 0;
+    for (uint32_t k = 0; k < pair; k++) before += (int)((pairs >> k) & 1u);
+    return 2 * before + (int)(b & 1u);
+}
+
+/* kind 4: slot group s (64 stream bytes, two frames) holds packet A (which = 0) of 1 + (s + seed) % 8 blocks at its start and packet B
+ * (which = 1) of 1 + ((s >> 3) & 1) blocks directly behind it; the rest of the group is zeros */
+PDT_SYNTH_FN uint32_t pdt_synth_dcs_blocks(uint64_t seed, uint64_t s, uint32_t which)
+{
+    return which ? 1u + (uint32_t)((s >> 3) & 1u) : 1u + (uint32_t)((s + seed) & 7u);
+}
+
+/* byte j (0 .. 11 + 4 blocks) of that packet: D6, the channel, the length code, the 21-bit time code 2 s + which, four ID bytes, the
+ * data, a hashed 23-bit Doppler value with its even-parity bit appended.  An ID or data byte that comes out D6 is sent as D7 */
+PDT_SYNTH_FN uint32_t pdt_synth_dcs_packet_byte(uint64_t seed, uint64_t s, uint32_t which, uint32_t j)
+{
+    const uint32_t n1 = pdt_synth_dcs_blocks(seed, s, which) - 1u, L = 16u + 4u * n1;
+    const uint32_t tc = (uint32_t)((2u * s + which) & 0x1FFFFFu);
+    if (j == 0) return 0xD6u;
+    if (j == 1) return (uint32_t)((s + (which ? 3u : 0u)) & 7u);
+    if (j == 2) return ((n1 << 1) | (((n1 >> 2) ^ (n1 >> 1) ^ n1) & 1u)) << 4;
+    if (j <= 5) return (tc >> (8u * (5u - j))) & 0xFFu;
+    if (j + 3 >= L) {
+        uint32_t v = (uint32_t)(pdt_synth_mix(seed ^ ((2u * s + which) * 64u + 63u) * 0x9FB21C651E98DF25ull) >> 24) & 0x7FFFFFu, x = v;
+        x ^= x >> 16;
+        x ^= x >> 8;
+        x ^= x >> 4;
+        x ^= x >> 2;
+        x ^= x >> 1;
+        return (((v << 1) | (x & 1u)) >> (8u * (L - 1u - j))) & 0xFFu;
+    }
+    const uint32_t v = (uint32_t)(pdt_synth_mix(seed ^ ((2u * s + which) * 64u + j) * 0xA24BAED4963EE407ull) >> 24) & 0xFFu;
+    return v == 0xD6u ? 0xD7u : v;
+}
+
+/* byte q of the DCS stream: a pure function of the stream byte index */
+PDT_SYNTH_FN uint32_t pdt_synth_dcs_stream_byte(uint64_t seed, uint64_t q)
+{
+    const uint64_t s = q >> 6;
+    const uint32_t o = (uint32_t)(q & 63u), la = 12u + 4u * pdt_synth_dcs_blocks(seed, s, 0), lb = 12u + 4u * pdt_synth_dcs_blocks(seed, s, 1);
+    if (o < la) return pdt_synth_dcs_packet_byte(seed, s, 0, o);
+    if (o < la + lb) return pdt_synth_dcs_packet_byte(seed, s, 1, o - la);
+    return 0;
+}
+
+/* kind 4: a POES capture as kind 3 whose frames carry a DCS stream: byte 2 is 8 (NOAA-15), bytes 4 and 5 the 9-bit minor-frame counter
+ * fr % 320 (byte 4's upper seven bits from the hash as before), the 32 DCS slots the stream above, byte 103 the parity of the bytes as sent */
+PDT_SYNTH_FN uint32_t pdt_synth_poes_dcs_data_byte(uint64_t seed, uint64_t fr, uint32_t b)
+{
+    const int slot = pdt_synth_dcs_slot(b);
+    if (slot >= 0) return pdt_synth_dcs_stream_byte(seed, fr * 32u + (uint32_t)slot);
+    if (b == 2) return 8u;
+    if (b == 4) return (pdt_synth_poes_frame_byte(seed, fr, 4) & 0xFEu) | (uint32_t)((fr % 320u) >> 8);
+    if (b == 5) return (uint32_t)((fr % 320u) & 0xFFu);
+    return pdt_synth_poes_frame_byte(seed, fr, b);
+}
+PDT_SYNTH_FN uint32_t pdt_synth_poes_dcs_byte(uint64_t seed, uint64_t fr, uint32_t b)
+{
+    uint32_t v = pdt_synth_poes_dcs_data_byte(seed, fr, b);
+    if (b != 103) return v;
+    v &= 0xC1u;
+    for (uint32_t g = 0; g < 5; g++) {
+        uint32_t x = 0;
+        for (uint32_t t = 0; t < 17; t++) x ^= pdt_synth_poes_dcs_data_byte(seed, fr, 2 + 17 * g + t);
         x ^= x >> 4;
         x ^= x >> 2;
         x ^= x >> 1;
@@ -185,12 +267,13 @@ PDT_SYNTH_FN void pdt_synth_sample(const pdt_synth_params *p, const int16_t *sin
     }
     if (amp && p->fade_len && n >= p->fade_start && n - p->fade_start < p->fade_len)
         amp = (int32_t)(((uint64_t)amp * p->fade_q15 + 16384u) >> 15);
-    if (p->kind == 0 || p->kind == 3) {
+    if (p->kind == 0 || p->kind == 3 || p->kind == 4) {
         uint64_t k = (n * 16640ull) / p->sample_rate;     /* Manchester symbol index */
         uint64_t bit = k >> 1;
         uint64_t fr = bit / 832u;
         uint32_t j = (uint32_t)(bit % 832u);
-        uint32_t v = ((p->kind == 3 && j >= 824 ? pdt_synth_poes_parity_byte(p->seed, fr, 103) : pdt_synth_poes_frame_byte(p->seed, fr, j >> 3)) >> (7 - (j & 7))) & 1u;
+        uint32_t v = ((p->kind == 4 ? pdt_synth_poes_dcs_byte(p->seed, fr, j >> 3)
+                                    : p->kind == 3 && j >= 824 ? pdt_synth_poes_parity_byte(p->seed, fr, 103) : pdt_synth_poes_frame_byte(p->seed, fr, j >> 3)) >> (7 - (j & 7))) & 1u;
         int up = (v != 0) ^ (int)(k & 1);                 /* '1' -> +,-   '0' -> -,+ */
         theta += up ? p->mod_index : (uint32_t)(0u - p->mod_index);
     } else {
@@ -242,6 +325,8 @@ void pdt_synth_poes_frame(const pdt_synth_params *p, uint64_t fr, uint8_t out[10
 void pdt_synth_argos_payload(const pdt_synth_params *p, uint64_t burst, uint8_t out[7]);
 /* kind 2: the message burst `burst` carries -- its blocks, its ID, its 4 N data bytes (the rest of data: 0) */
 void pdt_synth_argos_message(const pdt_synth_params *p, uint64_t burst, int *blocks, uint32_t *id, uint8_t data[32]);
+/* kind 4: the DCS packet `which` (0 = A, 1 = B) of slot group s as transmitted -- its *len bytes (the rest of out: 0) */
+void pdt_synth_dcs_packet(const pdt_synth_params *p, uint64_t s, int which, uint8_t out[44], int *len);
 #ifdef __cplusplus
 }
 #endif

@@ -18,15 +18,15 @@ LIBCOMPAT := $(CSRC)/libpdt_compat_poes.so $(CSRC)/libpdt_compat_argos.so
 
 all: $(LIBPDT) $(LIBSYNTH) $(LIBGATHER) $(LIBCOMPAT) bin/synth_wav bin/demodPOES bin/demodARGOS bin/demodMulti oracle
 
-# libpdt.so = eighteen translation units, compiled side by side (`make -j4`: two minutes; the device code of one unit is one single-threaded job
+# libpdt.so = nineteen translation units, compiled side by side (`make -j4`: two minutes; the device code of one unit is one single-threaded job
 # of the compiler: as ONE unit the library took six minutes): pdt_api (contexts, streaming, C ABI), the host -> HBM ingest (pdt_ingest: no kernels), the chain's launch
 # recording instantiated for float and for double with the kernels each launches, and the PLL kernels' slow-wrap variants,
-# the Hilbert front end of real captures (pdt_analytic) the down-converter of wideband captures (pdt_ddc) their carrier survey (pdt_survey) and burst search (pdt_bursts), the carrier measurement of channel streams (pdt_tone), the ARGOS messages of a bit stream (pdt_argos_msg), the flywheel frame synchroniser of POES bit streams (pdt_tip_sync), the feed-forward bits of burst windows (pdt_ff) and of POES streams (pdt_ffp), the repair of POES frames' failed parity groups from the soft bit values (pdt_tip_repair), the DCS-2 platform messages the minor frames relay (pdt_tip_dcs),
+# the Hilbert front end of real captures (pdt_analytic) the down-converter of wideband captures (pdt_ddc) their carrier survey (pdt_survey) and burst search (pdt_bursts), the carrier measurement of channel streams (pdt_tone), the ARGOS messages of a bit stream (pdt_argos_msg), the flywheel frame synchroniser of POES bit streams (pdt_tip_sync), the feed-forward bits of burst windows (pdt_ff) and of POES streams (pdt_ffp), the repair of POES frames' failed parity groups from the soft bit values (pdt_tip_repair), the DCS-2 platform messages the minor frames relay (pdt_tip_dcs) and their subcommutated bytes by table (pdt_tip_subcom),
 # and the test hook that runs the kernels' scalar primitives one by one on the device (pdt_probe: pdt_device_math).
 # Among the headers, pdt_work_layout.h (where the regions of the second-pass entries' device buffers lie) is free of HIP: tests/work_layout_main.cc
 # compiles it with g++; it is listed because the build tag hashes every file of LIBPDT_SRC
-LIBPDT_HDR := $(CSRC)/pdt_rt.h $(CSRC)/pdt_chain.inc $(CSRC)/pdt_kernels_front.h $(CSRC)/pdt_kernels_back.h $(CSRC)/pdt_device_math.h $(CSRC)/pdt_sincostab.h $(CSRC)/pdt_timeaxis.h $(CSRC)/pdt_analytic.h $(CSRC)/pdt_ddc.h $(CSRC)/pdt_survey.h $(CSRC)/pdt_bursts.h $(CSRC)/pdt_tone.h $(CSRC)/pdt_argos_msg.h $(CSRC)/pdt_tip_sync.h $(CSRC)/pdt_ff.h $(CSRC)/pdt_ffp.h $(CSRC)/pdt_tip_repair.h $(CSRC)/pdt_tip_dcs.h $(CSRC)/pdt_ingest.h $(CSRC)/pdt_work_layout.h include/pdt.h include/pdt_dev.h
-LIBPDT_UNITS := pdt_chain_f32 pdt_chain_f64 pdt_chain_wide_f32 pdt_chain_wide_f64 pdt_api pdt_ingest pdt_analytic pdt_ddc pdt_survey pdt_bursts pdt_tone pdt_argos_msg pdt_tip_sync pdt_ff pdt_ffp pdt_tip_repair pdt_tip_dcs pdt_probe
+LIBPDT_HDR := $(CSRC)/pdt_rt.h $(CSRC)/pdt_chain.inc $(CSRC)/pdt_kernels_front.h $(CSRC)/pdt_kernels_back.h $(CSRC)/pdt_device_math.h $(CSRC)/pdt_sincostab.h $(CSRC)/pdt_timeaxis.h $(CSRC)/pdt_analytic.h $(CSRC)/pdt_ddc.h $(CSRC)/pdt_survey.h $(CSRC)/pdt_bursts.h $(CSRC)/pdt_tone.h $(CSRC)/pdt_argos_msg.h $(CSRC)/pdt_tip_sync.h $(CSRC)/pdt_ff.h $(CSRC)/pdt_ffp.h $(CSRC)/pdt_tip_repair.h $(CSRC)/pdt_tip_dcs.h $(CSRC)/pdt_tip_subcom.h $(CSRC)/pdt_ingest.h $(CSRC)/pdt_work_layout.h include/pdt.h include/pdt_dev.h
+LIBPDT_UNITS := pdt_chain_f32 pdt_chain_f64 pdt_chain_wide_f32 pdt_chain_wide_f64 pdt_api pdt_ingest pdt_analytic pdt_ddc pdt_survey pdt_bursts pdt_tone pdt_argos_msg pdt_tip_sync pdt_ff pdt_ffp pdt_tip_repair pdt_tip_dcs pdt_tip_subcom pdt_probe
 LIBPDT_SRC := $(LIBPDT_UNITS:%=$(CSRC)/%.hip) $(LIBPDT_HDR)
 LIBPDT_OBJ := $(LIBPDT_UNITS:%=$(CSRC)/%.o)
 $(CSRC)/%.o: $(CSRC)/%.hip $(LIBPDT_HDR)
@@ -63,6 +63,12 @@ bin/demodARGOS: $(PKG)/host/demod_main.c include/pdt.h $(LIBPDT)
 bin/demodMulti: $(PKG)/host/demod_multi.c include/pdt.h include/pdt_gather.h $(LIBPDT) $(LIBGATHER)
 	mkdir -p bin
 	$(CC) $(CFLAGS) -Iinclude -o $@ $(PKG)/host/demod_multi.c -L$(CSRC) -lpdtgather -lpdt -lpthread -Wl,-rpath,'$$ORIGIN/../$(CSRC)'
+
+# the subcommutation rule's host statement (pdt_tip_subcom.h) under the address and undefined-behaviour sanitizers, in a program of its own: no
+# GPU, no libpdt (tests/test_tip_subcom.py builds the same program and feeds it its cases); not part of `all`
+bin/tip_subcom_host: tests/tip_subcom_host_main.cc $(CSRC)/pdt_tip_subcom.h $(CSRC)/pdt_tip_dcs.h $(CSRC)/pdt_tip_repair.h
+	mkdir -p bin
+	g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tests/tip_subcom_host_main.cc
 
 # (after the compat libraries: oracle/Makefile decides at start-up whether to link its compat_demod* drivers against them)
 oracle: $(LIBCOMPAT)

@@ -60,7 +60,11 @@
 extern "C" {
 #endif
 
-/* 4, additions without a bump (round 27): the DCS-2 platform messages that TIP minor frames relay -- pdt_dcs_cfg, pdt_dcs_packet,
+/* 4, additions without a bump (round 28): the subcommutated bytes of TIP minor frames by table, SEM-2 and the analogue housekeeping points
+ * built in -- pdt_subcom_entry, pdt_subcom_cfg, pdt_subcom_sample, pdt_subcom_summary, pdt_tip_subcom, pdt_tip_subcom_records,
+ * pdt_host_tip_subcom, pdt_subcom_table, pdt_subcom_name, pdt_tip_subcom_tile, pdt_format_subcom, pdt_write_subcom: a result beside the
+ * frames, which stay as they are.
+ * 4, additions without a bump (round 27): the DCS-2 platform messages that TIP minor frames relay -- pdt_dcs_cfg, pdt_dcs_packet,
  * pdt_dcs_summary, pdt_tip_dcs, pdt_tip_dcs_records, pdt_host_tip_dcs, pdt_format_dcs_packets, pdt_write_dcs_packets, pdt_tip_dcs_tile: a
  * result beside the frames, which stay as they are.
  * 4, additions without a bump (round 23): POES frames' failed parity groups repaired from the soft bit values -- pdt_tip_repair_info,
@@ -1091,6 +1095,101 @@ int      pdt_host_tip_dcs(const pdt_frame *frames, uint64_t n, const pdt_dcs_cfg
 uint64_t pdt_format_dcs_packets(const pdt_dcs_packet *packets, uint64_t n, char *buf, uint64_t cap);
 int      pdt_write_dcs_packets(const pdt_dcs_packet *packets, uint64_t n, int fd, uint64_t *bytes_written);
 int      pdt_tip_dcs_tile(void);
+
+/* POES frames: the subcommutated bytes (POES contexts).  A fixed byte of the minor frame belongs to a different measurement
+ * depending on the frame's 9-bit minor-frame counter: SEM-2, the space environment monitor, reads out 22 MEPED and 38 TED channels through
+ * bytes 20 and 21 (standalone_matlab/Functionized/POES.m:1314-1700), the 16-second analogue housekeeping points use bytes 11 and 14
+ * (POES.m:462-513).  One table-driven rule covers them; both tables are built in and any other is the caller's.  These entries are opt-in
+ * and stand BESIDE everything else; the rule is fixed in csrc/pdt_tip_subcom.h and pdt_host_tip_subcom restates it on the host:
+ *   input     pdt_frame records from any source, repaired or not.  A record is ELIGIBLE <=> complete == 1 and nbytes == 104.  Its
+ *             counter is id = (bytes[4] & 1) << 8 | bytes[5].  An eligible record with id >= 320 is counted bad_id and yields nothing; an
+ *             ineligible record is counted skipped; every other record is used
+ *   TABLE     1 .. 256 entries {channel, byte, period, phase, mask, shift, invert}: channel < 128, byte 0 .. 103, period divides 320,
+ *             phase < period, mask != 0, shift 0 .. 7, invert 0 or 1; any other table: PDT_ERR_ARG.  Entries need not be sorted; nchan =
+ *             the largest channel + 1, empty channels are allowed
+ *   FIRES     an entry fires in a used record <=> id % period == phase.  raw = bytes[byte], value = ((invert ? 255 - raw : raw) & mask) >> shift
+ *   SAMPLE    every firing is a sample: time = the frame byte's own, record's time + byte * (0.1 / 104); frame = the record's index;
+ *             minor_id = id; channel; entry = the entry's index; value; raw; flags:
+ *               PDT_SUBCOM_BYTE_PARITY (1)  the even-parity group that covers `byte` fails (pdt_tip_check's groups: group g = 0 .. 4 covers
+ *                                           bytes 2 + 17 g .. 18 + 17 g against bit 5 - g of byte 103)
+ *               PDT_SUBCOM_ID_PARITY   (2)  group 0 fails: it covers bytes 4 and 5, so the counter that chose the channel is in doubt
+ *               PDT_SUBCOM_UNCOVERED   (4)  `byte` lies in no group (0, 1, 87 .. 103)
+ *               PDT_SUBCOM_SPIKE       (8)  see below
+ *             With cfg.trusted_only a sample with bit 1 or bit 2 set is counted `dropped` and does not exist for anything that follows:
+ *             not for the order, the spike test or the counts samples, byte_parity, id_parity (both 0 then) and channels_hit
+ *   ORDER     channel-major: channel 0's samples, then channel 1's ...; within a channel ascending by (record, entry index).
+ *             offsets[0 .. nchan] (nchan + 1 values; NULL: not wanted) gives each channel's place and is always complete, whatever cap is
+ *   SPIKE     sample j of a channel is a spike <=> both neighbours j - 1 and j + 1 lie in the same channel and |v[j-1] - v[j]| > thr and
+ *             |v[j+1] - v[j]| > thr, on the values as decoded; thr = cfg.spike_threshold, 0 means 20 (the reference's FilterThreshold),
+ *             above 255: PDT_ERR_ARG
+ *   SUMMARY   used, skipped, bad_id, samples, dropped, byte_parity, id_parity, spikes, channels_hit (channels with a sample)
+ * Three departures from POES.m:1379-1490: the reference zeroes a spike in place, so its test of the next sample sees the zero -- a
+ * sequential dependence, and a lost value --, here a spike is flagged and keeps its value; the reference's series start with a dummy 0
+ * (X(1) = 0), here a channel's first and last sample never spike; neighbours are neighbours in the series whatever gap lies between them,
+ * as in the reference.
+ * *count = the samples found; at most cap are written, the first cap of the order above (cap = 0 with out = NULL only counts); the summary
+ * and offsets are always complete.  A call whose records could give 2^31 samples or more (n times the most entries that fire in one
+ * record): PDT_ERR_ARG.
+ *   pdt_tip_subcom          the frames of the context's last pdt_demod_* call, which are still in device memory (as pdt_tip_dcs).
+ *                           PDT_ERR_STATE when nothing has been demodulated or a stream is open; PDT_ERR_ARG for an ARGOS context, a table
+ *                           or cfg that is not allowed, a null count or summary, cap < 0, a null out with cap > 0.  No other result of the
+ *                           context changes (a profiled context's pdt_kernel_times gain the entries k_subcom_mark, k_subcom_count,
+ *                           k_subcom_scan, k_subcom_place and k_subcom_spikes)
+ *   pdt_tip_subcom_records  a caller's records (uploaded to a buffer of their own); n >= 2^31 or a null pointer with n > 0: PDT_ERR_ARG
+ *   pdt_host_tip_subcom     host only, no GPU: the same samples, offsets and summary, `time` included, bit for bit
+ *   pdt_subcom_table        a built-in table: returns its number of entries (0: there is no such table), writes at most cap.
+ *                           PDT_SUBCOM_SEM: 76 entries, 60 channels, bytes 20 and 21, every entry inverted (the data is sent complemented,
+ *                           POES.m:1317-1318) -- MEPED 0P1 .. 0P6 0E1 .. 0E3 9P1 .. 9P6 9E1 .. 9E3 P6 .. P9 (POES.m:1340-1377), TED 0EFL 3EFL
+ *                           0PFL 3PFL 0EFH 3EFH 0PFH 3PFH 0EM 0PM 0DEM 0DPM 3EM 3PM 3DEM 3DPM 0DE1 0DE2 3DE1 3DE2 0DP1 0DP2 3DP1 3DP2 0EBKL
+ *                           0EBKH 3PBKL 0DE3 0DE4 3DE3 3DE4 0DP3 0DP4 3DP3 3DP4 0PBKL 0PBKH 3PBKH (POES.m:1561-1621), channels numbered in
+ *                           this order.  PDT_SUBCOM_HK: 5 entries, not inverted -- byte 11 every 80 frames: STX1 at 48, STX2 at 50, STX3 at
+ *                           40; byte 14 every 160: SARR-A at 114, SARR-B at 2 (POES.m:492-508; line 506 names the wrong array, the counter
+ *                           is the same)
+ *   pdt_subcom_name         a built-in table's name of a channel, or NULL
+ *   pdt_tip_subcom_tile     the records one tile of the kernels covers (tests place samples at its seams)
+ *   pdt_format_subcom       the samples' text; returns the bytes needed, writes at most cap.  One line per sample, "%.5f %s %u %u %s\n":
+ *                           the time, the channel's name in table `which` (c<channel> where that has none: PDT_SUBCOM_CUSTOM), the
+ *                           counter, the value and the flags as a subset of the letters b i u s in that order, or "-"
+ *   pdt_write_subcom        the same text to a file descriptor; PDT_ERR_IO when a write fails                                           */
+#define PDT_SUBCOM_BYTE_PARITY 1
+#define PDT_SUBCOM_ID_PARITY 2
+#define PDT_SUBCOM_UNCOVERED 4
+#define PDT_SUBCOM_SPIKE 8
+#define PDT_SUBCOM_SEM 0
+#define PDT_SUBCOM_HK 1
+#define PDT_SUBCOM_CUSTOM (-1)
+typedef struct pdt_subcom_entry {
+    uint8_t  channel;      /* < 128                                                                                          */
+    uint8_t  byte;         /* of the frame, 0 .. 103                                                                         */
+    uint16_t period;       /* divides 320                                                                                    */
+    uint16_t phase;        /* < period: the entry fires when id % period == phase                                            */
+    uint8_t  mask, shift;  /* value = ((invert ? 255 - raw : raw) & mask) >> shift                                           */
+    uint8_t  invert, pad;
+} pdt_subcom_entry;
+typedef struct pdt_subcom_cfg {
+    uint32_t trusted_only;    /* nonzero: samples whose byte's or whose counter's parity group fails are dropped             */
+    uint32_t spike_threshold; /* 1 .. 255; 0 = 20                                                                            */
+} pdt_subcom_cfg;             /* NULL or zeroed = default                                                                    */
+typedef struct pdt_subcom_sample {
+    double   time;         /* of the frame byte                                                                              */
+    uint32_t frame;        /* the record                                                                                     */
+    uint16_t minor_id;
+    uint8_t  channel, entry, value, raw, flags, pad[5];
+} pdt_subcom_sample;
+typedef struct pdt_subcom_summary {
+    uint64_t used, skipped, bad_id, samples, dropped, byte_parity, id_parity, spikes, channels_hit;
+} pdt_subcom_summary;
+int      pdt_tip_subcom(pdt_ctx *ctx, const pdt_subcom_entry *entries, uint64_t nentries, const pdt_subcom_cfg *cfg, pdt_subcom_sample *out, int cap,
+                        int *count, uint64_t *offsets, pdt_subcom_summary *summary);
+int      pdt_tip_subcom_records(pdt_ctx *ctx, const pdt_frame *frames, uint64_t n, const pdt_subcom_entry *entries, uint64_t nentries,
+                                const pdt_subcom_cfg *cfg, pdt_subcom_sample *out, int cap, int *count, uint64_t *offsets, pdt_subcom_summary *summary);
+int      pdt_host_tip_subcom(const pdt_frame *frames, uint64_t n, const pdt_subcom_entry *entries, uint64_t nentries, const pdt_subcom_cfg *cfg,
+                             pdt_subcom_sample *out, int cap, int *count, uint64_t *offsets, pdt_subcom_summary *summary);
+int      pdt_subcom_table(int which, pdt_subcom_entry *entries, int cap);
+const char *pdt_subcom_name(int which, int channel);
+int      pdt_tip_subcom_tile(void);
+uint64_t pdt_format_subcom(const pdt_subcom_sample *samples, uint64_t n, int which, char *buf, uint64_t cap);
+int      pdt_write_subcom(const pdt_subcom_sample *samples, uint64_t n, int which, int fd, uint64_t *bytes_written);
 
 /* Results of the last pdt_demod_* call. */
 uint64_t pdt_num_frames(const pdt_ctx *ctx);

@@ -508,6 +508,81 @@ def write_dcs_packets(packets: np.ndarray, fd: int) -> int:
     return int(w.value)
 
 
+# pdt_subcom_entry and pdt_subcom_sample as numpy records, pdt_subcom_cfg and pdt_subcom_summary
+SUBCOM_ENTRY_DTYPE = np.dtype([("channel", "u1"), ("byte", "u1"), ("period", "<u2"), ("phase", "<u2"), ("mask", "u1"), ("shift", "u1"), ("invert", "u1"),
+                               ("pad", "u1")])
+SUBCOM_SAMPLE_DTYPE = np.dtype([("time", "<f8"), ("frame", "<u4"), ("minor_id", "<u2"), ("channel", "u1"), ("entry", "u1"), ("value", "u1"), ("raw", "u1"),
+                                ("flags", "u1"), ("pad", "u1", (5,))])
+assert SUBCOM_ENTRY_DTYPE.itemsize == 10 and SUBCOM_SAMPLE_DTYPE.itemsize == 24
+SUBCOM_BYTE_PARITY, SUBCOM_ID_PARITY, SUBCOM_UNCOVERED, SUBCOM_SPIKE = 1, 2, 4, 8
+SUBCOM_SEM, SUBCOM_HK, SUBCOM_CUSTOM = 0, 1, -1
+
+
+class SubcomCfg(C.Structure):
+    _fields_ = [("trusted_only", C.c_uint32), ("spike_threshold", C.c_uint32)]
+
+
+class SubcomSummary(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("used", "skipped", "bad_id", "samples", "dropped", "byte_parity", "id_parity", "spikes", "channels_hit")]
+
+
+def tip_subcom_tile() -> int:
+    """pdt_tip_subcom_tile: the records one tile of the subcommutation kernels covers (tests place samples at its seams)"""
+    return int(lib().pdt_tip_subcom_tile())
+
+
+def subcom_table(which: int) -> np.ndarray:
+    """pdt_subcom_table: a built-in table (SUBCOM_SEM, SUBCOM_HK) as SUBCOM_ENTRY_DTYPE records; empty where there is no such table"""
+    t = np.zeros(256, dtype=SUBCOM_ENTRY_DTYPE)
+    return t[:int(lib().pdt_subcom_table(which, t.ctypes.data, 256))].copy()
+
+
+def subcom_name(which: int, channel: int):
+    """pdt_subcom_name: a built-in table's name of a channel, or None"""
+    s = lib().pdt_subcom_name(which, channel)
+    return s.decode() if s else None
+
+
+def _subcom_table(table):
+    return subcom_table(table) if isinstance(table, int) else np.ascontiguousarray(table, dtype=SUBCOM_ENTRY_DTYPE).reshape(-1)
+
+
+def _subcom_call(fn, what, head, table, trusted_only, spike_threshold, cap):
+    """what every subcommutation entry shares: (SUBCOM_SAMPLE_DTYPE[min(found, cap)], found, offsets uint64[nchan + 1], summary dict)"""
+    t = _subcom_table(table)
+    c = SubcomCfg(int(trusted_only), spike_threshold)
+    out, count, sm, off = np.zeros(max(cap, 1), dtype=SUBCOM_SAMPLE_DTYPE), C.c_int(0), SubcomSummary(), np.zeros(129, dtype=np.uint64)
+    _check(fn(*head, t.ctypes.data, len(t), C.byref(c), out.ctypes.data if cap else None, cap, C.byref(count), off.ctypes.data, C.byref(sm)), what)
+    nchan = int(t["channel"].max()) + 1 if len(t) else 0
+    return out[:min(count.value, cap)], count.value, off[:nchan + 1].copy(), {k: int(getattr(sm, k)) for k, _ in SubcomSummary._fields_}
+
+
+def host_tip_subcom(frames, table=SUBCOM_SEM, trusted_only: bool = False, spike_threshold: int = 0, cap: int = 65536):
+    """pdt_host_tip_subcom: the subcommutated bytes of FRAME_DTYPE records of TIP minor frames by `table` (SUBCOM_SEM, SUBCOM_HK or
+    SUBCOM_ENTRY_DTYPE records), restated on the host (no GPU).  Returns (SUBCOM_SAMPLE_DTYPE[min(found, cap)], found, offsets, summary dict):
+    the samples channel-major, offsets[c] .. offsets[c + 1] the samples of channel c."""
+    a = np.ascontiguousarray(frames, dtype=FRAME_DTYPE).reshape(-1)
+    return _subcom_call(lib().pdt_host_tip_subcom, "pdt_host_tip_subcom", (a.ctypes.data, len(a)), table, trusted_only, spike_threshold, cap)
+
+
+def format_subcom(samples: np.ndarray, which: int = SUBCOM_CUSTOM) -> bytes:
+    """pdt_format_subcom: one line per sample, the channels named as table `which` names them (host-only C, no GPU needed)"""
+    a = np.ascontiguousarray(samples, dtype=SUBCOM_SAMPLE_DTYPE).reshape(-1)
+    L = lib()
+    n = L.pdt_format_subcom(a.ctypes.data, len(a), which, None, 0)
+    buf = C.create_string_buffer(n + 1)
+    L.pdt_format_subcom(a.ctypes.data, len(a), which, buf, n)
+    return buf.raw[:n]
+
+
+def write_subcom(samples: np.ndarray, fd: int, which: int = SUBCOM_CUSTOM) -> int:
+    """pdt_write_subcom: the same text to an open file descriptor; returns the bytes written"""
+    a = np.ascontiguousarray(samples, dtype=SUBCOM_SAMPLE_DTYPE).reshape(-1)
+    w = C.c_uint64(0)
+    _check(lib().pdt_write_subcom(a.ctypes.data, len(a), which, fd, C.byref(w)), "pdt_write_subcom")
+    return int(w.value)
+
+
 class FfCfg(C.Structure):
     """pdt_ff_cfg: a zero means the default; rate_steps 0 with FF_ZERO_RATE_STEPS in zero_mask asks for the nominal rate alone;
     FF_RESIDUAL_GIVEN in flags: residual_hz is the caller's, otherwise the carrier is measured"""
@@ -702,6 +777,8 @@ ABI_SYMBOLS = [
     "pdt_tip_sync", "pdt_tip_sync_batch", "pdt_stage_tip_sync", "pdt_host_tip_sync", "pdt_tip_sync_tile", "pdt_tip_check_records",
     "pdt_tip_repair", "pdt_stage_tip_repair", "pdt_host_tip_repair",
     "pdt_tip_dcs", "pdt_tip_dcs_records", "pdt_host_tip_dcs", "pdt_format_dcs_packets", "pdt_write_dcs_packets", "pdt_tip_dcs_tile",
+    "pdt_tip_subcom", "pdt_tip_subcom_records", "pdt_host_tip_subcom", "pdt_subcom_table", "pdt_subcom_name", "pdt_tip_subcom_tile", "pdt_format_subcom",
+    "pdt_write_subcom",
 ]
 DEV_SYMBOLS = ["pdt_dev_set", "pdt_dev_span_rows", "pdt_dev_span_rekey", "pdt_dev_fir_form", "pdt_dev_ddc"]       # include/pdt_dev.h (test-only)
 
@@ -873,6 +950,16 @@ def lib():
     L.pdt_format_dcs_packets.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.pdt_format_dcs_packets.restype = C.c_uint64
     L.pdt_write_dcs_packets.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    subcom_tail = [C.c_void_p, C.c_uint64, C.POINTER(SubcomCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(SubcomSummary)]
+    L.pdt_tip_subcom.argtypes = [C.c_void_p] + subcom_tail
+    L.pdt_tip_subcom_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + subcom_tail
+    L.pdt_host_tip_subcom.argtypes = [C.c_void_p, C.c_uint64] + subcom_tail
+    L.pdt_subcom_table.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    L.pdt_subcom_name.argtypes = [C.c_int, C.c_int]
+    L.pdt_subcom_name.restype = C.c_char_p
+    L.pdt_format_subcom.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64]
+    L.pdt_format_subcom.restype = C.c_uint64
+    L.pdt_write_subcom.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
     L.pdt_format_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.pdt_format_argos_messages.restype = C.c_uint64
     L.pdt_write_argos_messages.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
@@ -1664,6 +1751,16 @@ class Demodulator:
         _check(self._L.pdt_tip_dcs_records(self._h, a.ctypes.data, len(a), C.byref(c), out.ctypes.data if cap else None, cap, C.byref(count), C.byref(sm)),
                "pdt_tip_dcs_records")
         return _dcs_result(out, count.value, cap, sm)
+
+    def tip_subcom(self, table=SUBCOM_SEM, trusted_only: bool = False, spike_threshold: int = 0, cap: int = 65536):
+        """pdt_tip_subcom: the subcommutated bytes, by `table`, of the minor frames of this context's last demodulation, which are still on the
+        device: (SUBCOM_SAMPLE_DTYPE[min(found, cap)], found, offsets, summary dict).  The context's own results stay as they were."""
+        return _subcom_call(self._L.pdt_tip_subcom, "pdt_tip_subcom", (self._h,), table, trusted_only, spike_threshold, cap)
+
+    def tip_subcom_records(self, frames, table=SUBCOM_SEM, trusted_only: bool = False, spike_threshold: int = 0, cap: int = 65536):
+        """pdt_tip_subcom_records: the same kernels on a caller's FRAME_DTYPE records (those of tip_sync() or ffp_frames(), repaired or not)"""
+        a = np.ascontiguousarray(frames, dtype=FRAME_DTYPE).reshape(-1)
+        return _subcom_call(self._L.pdt_tip_subcom_records, "pdt_tip_subcom_records", (self._h, a.ctypes.data, len(a)), table, trusted_only, spike_threshold, cap)
 
     def tip_sync(self, max_errors=None, window=None, fly=None, cap: int = 65536, with_info: bool = False, with_count: bool = False):
         """pdt_tip_sync: the POES minor frames a flywheel synchroniser finds in the bits of this context's last whole-capture call -- a

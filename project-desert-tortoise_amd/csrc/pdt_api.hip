@@ -12,6 +12,7 @@
 #include "pdt_ff.h"
 #include "pdt_ffp.h"
 #include "pdt_tip_dcs.h"
+#include "pdt_tip_subcom.h"
 
 #include <sys/stat.h>
 
@@ -70,6 +71,13 @@ hipError_t tip_dcs_launch(hipStream_t st, const void *recs_dev, bool chain_layou
                           unsigned long long cap, hipEvent_t *inner);
 void tip_dcs_summary(const unsigned long long *c, unsigned long long n, pdt_dcs_summary *s);
 int tip_dcs_rule(const pdt_dcs_cfg *cfg, unsigned *channel_max);
+// pdt_tip_subcom.hip
+extern const char *const tip_subcom_kernel_names[5];
+hipError_t tip_subcom_launch(hipStream_t st, const void *recs_dev, bool chain_layout, const void *times_dev, unsigned long long n, const void *table_dev, int ne,
+                             int nchan, int trusted_only, int thr, void *sum_dev, void *marks_dev, void *cnt_dev, void *offsets_dev, void *vals_dev,
+                             unsigned long long limit, void *out_dev, unsigned long long cap, hipEvent_t *inner);
+void tip_subcom_summary(const unsigned long long *c, pdt_subcom_summary *s);
+int tip_subcom_rule(const pdt_subcom_entry *entries, uint64_t nentries, const pdt_subcom_cfg *cfg, uint64_t n, int *nchan, int *max_fire, int *trusted_only, int *thr);
 // pdt_ddc.hip
 long long ddc_windows_table(int decim, pdt::DdcWindow *win, int count, std::vector<unsigned char> &table);
 hipError_t ddc_windows_launch(hipStream_t st, int fmt, int decim, const float *taps_dev, const float *tab_dev, const void *table_dev, int count,
@@ -623,7 +631,7 @@ void pdt_close(pdt_ctx *ctx)
                        &ctx->ddc_taps, &ctx->channel, &ctx->survey_win, &ctx->survey_tw, &ctx->survey_part, &ctx->survey_out,
                        &ctx->bursts_rows, &ctx->bursts_peaks, &ctx->bursts_counts, &ctx->win_table, &ctx->tone_table, &ctx->tone_out,
                        &ctx->staged_bits, &ctx->staged_iq, &ctx->argos_work, &ctx->ff_work, &ctx->ff_out, &ctx->ffp_work, &ctx->ffp_out,
-                       &ctx->tip_sync_work, &ctx->tip_recs, &ctx->tip_repair_work, &ctx->tip_repair_soft, &ctx->tip_dcs_work };
+                       &ctx->tip_sync_work, &ctx->tip_recs, &ctx->tip_repair_work, &ctx->tip_repair_soft, &ctx->tip_dcs_work, &ctx->tip_subcom_work };
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -2252,6 +2260,82 @@ int pdt_tip_dcs_records(pdt_ctx *ctx, const pdt_frame *frames, uint64_t n, const
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;
     try {
         return tip_dcs_run(ctx, frames, n, channel_max, out, cap, count, summary);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+// ---------------------------------------------------------------- subcommutated bytes of TIP minor frames (pdt_tip_subcom.h)
+// The five kernels on n records: the caller's (uploaded into the work buffer as they are) or, with frames == NULL, the chain's own in
+// ctx->frames, whose time stamps go up from frames_host beside them.  The counters and offsets come back first -- the sample count has
+// stayed on the device until then --, then as many samples as were found and fit.
+struct SubcomRuleHost { int nchan, max_fire, trusted_only, thr; };
+static int tip_subcom_run(pdt_ctx *c, const pdt_frame *frames, uint64_t n, const pdt_subcom_entry *entries, int ne, const SubcomRuleHost &R, pdt_subcom_sample *out,
+                          int cap, int *count, uint64_t *offsets, pdt_subcom_summary *summary)
+{
+    memset(summary, 0, sizeof *summary);
+    *count = 0;
+    if (offsets) memset(offsets, 0, ((size_t)R.nchan + 1) * sizeof *offsets);
+    if (n == 0) return PDT_OK;
+    const size_t tiles = ((size_t)n + pdt::TIP_SUBCOM_TILE - 1) / pdt::TIP_SUBCOM_TILE;
+    const size_t limit = (size_t)n * (size_t)R.max_fire, room = std::min((size_t)cap, limit);
+    const SubcomWork L = subcom_work_layout((size_t)n, tiles, (size_t)R.nchan, (size_t)ne * sizeof(pdt_subcom_entry),
+                                            (size_t)n * (frames ? sizeof(pdt_frame) : sizeof(double)), limit, room * sizeof(pdt_subcom_sample));
+    int rc;
+    if ((rc = c->tip_subcom_work.ensure(L.total))) return rc;
+    unsigned char *w = (unsigned char *)c->tip_subcom_work.p;
+    hipStream_t st = c->stream;
+    std::vector<double> times;
+    HIP_TRY(hipMemsetAsync(w + L.o_sum, 0, L.o_table - L.o_sum, st));                                // the counters and the offsets
+    HIP_TRY(hipMemcpyAsync(w + L.o_table, entries, (size_t)ne * sizeof(pdt_subcom_entry), hipMemcpyHostToDevice, st));
+    if (frames) HIP_TRY(hipMemcpyAsync(w + L.o_src, frames, (size_t)n * sizeof(pdt_frame), hipMemcpyHostToDevice, st));
+    else {
+        times.resize((size_t)n);
+        for (size_t f = 0; f < (size_t)n; f++) times[f] = c->frames_host[f].time;
+        HIP_TRY(hipMemcpyAsync(w + L.o_src, times.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    CallTimer timer(c, st, tip_subcom_kernel_names, nullptr, 5);
+    HIP_TRY(timer.begin());
+    HIP_TRY(tip_subcom_launch(st, frames ? (const void *)(w + L.o_src) : c->frames.p, !frames, w + L.o_src, n, w + L.o_table, ne, R.nchan, R.trusted_only, R.thr,
+                              w + L.o_sum, w + L.o_marks, w + L.o_cnt, w + L.o_offsets, w + L.o_vals, limit, w + L.o_out, room, timer.inner()));
+    HIP_TRY(timer.end());
+    unsigned long long head[16 + 129];
+    HIP_TRY(hipMemcpyAsync(head, w + L.o_sum, sizeof head, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    timer.commit();
+    tip_subcom_summary(head, summary);
+    if (offsets)
+        for (int k = 0; k <= R.nchan; k++) offsets[k] = head[16 + k];
+    const size_t give = (size_t)std::min<uint64_t>(summary->samples, room);
+    if (give) HIP_TRY(hipMemcpy(out, w + L.o_out, give * sizeof(pdt_subcom_sample), hipMemcpyDeviceToHost));
+    *count = (int)std::min<uint64_t>(summary->samples, 0x7fffffffull);
+    return PDT_OK;
+}
+
+int pdt_tip_subcom(pdt_ctx *ctx, const pdt_subcom_entry *entries, uint64_t nentries, const pdt_subcom_cfg *cfg, pdt_subcom_sample *out, int cap, int *count,
+                   uint64_t *offsets, pdt_subcom_summary *summary)
+{
+    SubcomRuleHost R;
+    if (!ctx || !count || !summary || cap < 0 || (!out && cap)) return PDT_ERR_ARG;
+    if (tip_subcom_rule(entries, nentries, cfg, ctx->frames_on_device, &R.nchan, &R.max_fire, &R.trusted_only, &R.thr)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;             // TIP minor frames only
+    const unsigned nf = ctx->frames_on_device;
+    if (ctx->stream_open || !ctx->have_frames || nf != ctx->frames_host.size()) return PDT_ERR_STATE;
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;
+    try {
+        return tip_subcom_run(ctx, nullptr, nf, entries, (int)nentries, R, out, cap, count, offsets, summary);
+    } catch (const std::exception &) { return PDT_ERR_NOMEM; }
+}
+
+int pdt_tip_subcom_records(pdt_ctx *ctx, const pdt_frame *frames, uint64_t n, const pdt_subcom_entry *entries, uint64_t nentries, const pdt_subcom_cfg *cfg,
+                           pdt_subcom_sample *out, int cap, int *count, uint64_t *offsets, pdt_subcom_summary *summary)
+{
+    SubcomRuleHost R;
+    if (!ctx || !count || !summary || (!frames && n) || n >= (1ull << 31) || cap < 0 || (!out && cap)) return PDT_ERR_ARG;
+    if (tip_subcom_rule(entries, nentries, cfg, n, &R.nchan, &R.max_fire, &R.trusted_only, &R.thr)) return PDT_ERR_ARG;
+    if (ctx->cfg.mode != PDT_MODE_POES) return PDT_ERR_ARG;
+    if (ctx->stream_open) return PDT_ERR_STATE;
+    if (hipSetDevice(ctx->cfg.device) != hipSuccess) return PDT_ERR_NOGPU;
+    try {
+        return tip_subcom_run(ctx, frames, n, entries, (int)nentries, R, out, cap, count, offsets, summary);
     } catch (const std::exception &) { return PDT_ERR_NOMEM; }
 }
 

@@ -499,6 +499,8 @@ struct pdt_ctx {
     DevBuf tip_repair_work, tip_repair_soft;
     // DCS packets (pdt_tip_dcs.h): counters, flags, stream, bitmaps, tile maps and entries, the records or their time stamps, the packets (DcsWork)
     DevBuf tip_dcs_work;
+    // subcommutated bytes (pdt_tip_subcom.h): counters, offsets, table, marks, tile counts, the records or their time stamps, values, samples (SubcomWork)
+    DevBuf tip_subcom_work;
     const void *held_src = nullptr;
     uint64_t held_frames = 0;
     int held_fmt = 0;

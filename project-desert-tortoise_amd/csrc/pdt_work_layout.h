@@ -78,6 +78,17 @@ inline DcsWork dcs_work_layout(size_t recs, size_t tiles, size_t tile_bytes, siz
              c.take(tiles * map_bytes), c.take(tiles * entry_bytes), c.take(src_bytes), c.take(out_bytes), c.at };
 }
 
+// subcommutated bytes (tip_subcom_run): the counters (128 bytes) and offsets[0 .. 128] -- [0, o_table) is read back in one copy --, the
+// table, a mark per record, every tile's count per channel (channel-major), the records' time stamps or the caller's records
+// (`src_bytes`), every possible sample's value (`limit` bytes), the samples
+struct SubcomWork { size_t o_sum, o_offsets, o_table, o_marks, o_cnt, o_src, o_vals, o_out, total; };
+inline SubcomWork subcom_work_layout(size_t recs, size_t tiles, size_t channels, size_t table_bytes, size_t src_bytes, size_t limit, size_t out_bytes)
+{
+    Carve c;
+    return { c.take(128), c.take(129 * 8), c.take(table_bytes), c.take(recs * sizeof(unsigned)), c.take(channels * tiles * sizeof(unsigned)), c.take(src_bytes),
+             c.take(limit), c.take(out_bytes), c.at };
+}
+
 // what both feed-forward result buffers end with: time source, soft values, bit -> symbol map and characters of `cap` bits, each over
 // the capacity rounded up to 16
 struct BitsTail { size_t o_idx, o_soft, o_sym, o_bits; };

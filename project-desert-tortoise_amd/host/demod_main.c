@@ -95,6 +95,12 @@
  * records (after -Q's repair when that is given), otherwise those of the minorFrames file's frames; a run without frames writes an empty
  * file.  One console line reports packets, complete packets, Doppler parity failures and segments.  One channel of a capture taken in one
  * piece, as -W: demodARGOS, a pipe, -l and several -t refuse it.
+ * -E <file>, -H <file> (additions, demodPOES): the subcommutated bytes of the run's minor frames (pdt_tip_subcom) -- -E the 60
+ * SEM-2 channels of bytes 20 and 21, -H the five analogue housekeeping points of bytes 11 and 14 --, one line per sample, channel by
+ * channel: "%.5f %s %u %u %s" of the frame byte's time, the channel's name, the minor-frame counter, the value and the flags (a subset of
+ * the letters b i u s: the byte's parity group fails, the counter's group fails, the byte lies in no group, a spike; or "-").  The frames
+ * are those -C takes: -W's records (after -Q's repair) where -W is given, otherwise the minorFrames file's; a run without frames writes an
+ * empty file.  One console line each reports samples, channels, parity flags and spikes.  The same runs as -C refuse them.
  * -W <file> (an addition, demodPOES): the minor frames a flywheel synchroniser finds in the bits of the capture (pdt_tip_sync, DESIGN
  * 4.18), in the minor-frame text format, beside the unchanged minorFrames file.  -w E,W,G sets its three constants (max_errors, window,
  * fly; default 2,2,3); with -q a second validation line, for these frames, follows the reference's.  One channel of a capture taken
@@ -115,14 +121,14 @@
 #ifdef PDT_ARGOS
 #define MODE PDT_MODE_ARGOS
 #define DEFAULT_CHUNKSIZE 2400
-#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:bW:w:Q:C:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
+#define OPTS "s:rn:c:o:d:mlPTD:f:x:t:F:B:M:A:R:bW:w:Q:C:E:H:" /* -l (round 4): the sound-card twin's chain, -s its rate in kHz when the samples come from a pipe */
 #define BANNER "Project Desert Tortoise: Wave file ARGOS Demodulator (MI355X build)\n"
 #define PREFIX "packets"
 #define UNIT "Packets"
 #else
 #define MODE PDT_MODE_POES
 #define DEFAULT_CHUNKSIZE 10000
-#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:bW:w:Q:C:"
+#define OPTS "s:rn:c:o:d:qmlPTD:f:x:t:F:B:M:A:bW:w:Q:C:E:H:"
 #define BANNER "Project Desert Tortoise: Wave file NOAA TIP Demodulator (MI355X build)\n"
 #define PREFIX "minorFrames"
 #define UNIT "Frames"
@@ -492,6 +498,57 @@ static int write_dcs(pdt_ctx *ctx, const pdt_frame *fr, int nfr, const char *nam
     }
     printf("DCS packets: %llu, %llu complete, %llu Doppler parity failures, %llu segments -> %s\n", (unsigned long long)sum.packets,
            (unsigned long long)sum.complete, (unsigned long long)sum.doppler_bad, (unsigned long long)sum.segments, name);
+    return 0;
+}
+
+/* -E, -H: the samples of built-in table `which` in -W's records, or (fr == NULL) in the frames of ctx's last capture, which are still on
+ * the device, one line each.  Returns 0 when the file is written. */
+static int write_subcom(pdt_ctx *ctx, const pdt_frame *fr, int nfr, int which, const char *what, const char *name)
+{
+    pdt_subcom_entry table[256];
+    pdt_subcom_summary sum;
+    int found = 0;
+    const int ne = pdt_subcom_table(which, table, 256);
+    memset(&sum, 0, sizeof sum);
+    int rc = fr ? pdt_tip_subcom_records(ctx, fr, (uint64_t)nfr, table, (uint64_t)ne, NULL, NULL, 0, &found, NULL, &sum)
+                : pdt_tip_subcom(ctx, table, (uint64_t)ne, NULL, NULL, 0, &found, NULL, &sum);
+    if (!fr && rc == PDT_ERR_STATE) {
+        if (pdt_num_frames(ctx)) {
+            printf("%s needs a capture taken in one piece: this one was demodulated in pieces and left its frames in no one place\n", what);
+            return 1;
+        }
+        rc = PDT_OK;                                                   /* (a run without frames: an empty file) */
+        found = 0;
+    }
+    pdt_subcom_sample *sm = (pdt_subcom_sample *)malloc((size_t)(found ? found : 1) * sizeof *sm);
+    if (rc == PDT_OK && !sm) rc = PDT_ERR_NOMEM;
+    if (rc == PDT_OK && found) {
+        const int cap = found;
+        rc = fr ? pdt_tip_subcom_records(ctx, fr, (uint64_t)nfr, table, (uint64_t)ne, NULL, sm, cap, &found, NULL, &sum)
+                : pdt_tip_subcom(ctx, table, (uint64_t)ne, NULL, sm, cap, &found, NULL, &sum);
+        if (found > cap) found = cap;
+    }
+    if (rc != PDT_OK) printf("Decommutation (%s) failed: %s\n", what, pdt_strerror(rc));
+    FILE *m = rc == PDT_OK ? fopen(name, "w") : NULL;
+    if (rc == PDT_OK && !m) printf("Error opening %s\n", name);
+    if (!m) {
+        free(sm);
+        return 1;
+    }
+    int bad = 0;
+    if (found) {
+        fflush(m);
+        bad = pdt_write_subcom(sm, (uint64_t)found, which, fileno(m), NULL) != PDT_OK;
+    }
+    bad |= fclose(m) != 0;
+    free(sm);
+    if (bad) {
+        printf("Error writing %s\n", name);
+        return 1;
+    }
+    printf("%s samples: %llu in %llu channels, %llu byte parity, %llu counter parity, %llu spikes -> %s\n", which == PDT_SUBCOM_SEM ? "SEM" : "Housekeeping",
+           (unsigned long long)sum.samples, (unsigned long long)sum.channels_hit, (unsigned long long)sum.byte_parity, (unsigned long long)sum.id_parity,
+           (unsigned long long)sum.spikes, name);
     return 0;
 }
 
@@ -987,6 +1044,7 @@ int main(int argc, char **argv)
     const char *flywheelName = NULL;                                                /* -W: the flywheel synchroniser's frames' file */
     const char *repairName = NULL;                                                  /* -Q: the parity repair's report */
     const char *dcsName = NULL;                                                     /* -C: the DCS packets' file */
+    const char *semName = NULL, *hkName = NULL;                                     /* -E, -H: the SEM and the housekeeping samples' files */
     pdt_tip_sync_cfg flywheelCfg;                                                   /* -w E,W,G: its constants */
     int flywheelCfgGiven = 0;
     char outFileName[1100];
@@ -1115,6 +1173,12 @@ int main(int argc, char **argv)
         case 'C':                                       /* the DCS packets the minor frames relay, to this file */
             dcsName = optarg;
             break;
+        case 'E':                                       /* the SEM-2 samples the minor frames carry, to this file */
+            semName = optarg;
+            break;
+        case 'H':                                       /* the analogue housekeeping samples, to this file */
+            hkName = optarg;
+            break;
         case 'w': {                                     /* max_errors, window, fly of the flywheel's rule */
             int e = 0, w = 0, g = 0;
             char tail = 0;
@@ -1223,6 +1287,10 @@ int main(int argc, char **argv)
     }
     if (dcsName && (MODE != PDT_MODE_POES || from_stdin || live || nOffsets > 1 || autoCarriers)) {
         printf("-C needs demodPOES, one channel and a capture taken in one piece: not a pipe, not -l, not several -t\n");
+        return 1;
+    }
+    if ((semName || hkName) && (MODE != PDT_MODE_POES || from_stdin || live || nOffsets > 1 || autoCarriers)) {
+        printf("%s needs demodPOES, one channel and a capture taken in one piece: not a pipe, not -l, not several -t\n", semName ? "-E" : "-H");
         return 1;
     }
     FILE *in = from_stdin ? stdin : fopen(inFileName, "rb");
@@ -1492,6 +1560,12 @@ int main(int argc, char **argv)
         exit(1);
     }
     if (dcsName && write_dcs(ctx, flywheelName ? flyFrames : NULL, flyCount, dcsName)) {
+        fclose(out);
+        remove(outFileName);
+        exit(1);
+    }
+    if ((semName && write_subcom(ctx, flywheelName ? flyFrames : NULL, flyCount, PDT_SUBCOM_SEM, "-E", semName)) ||
+        (hkName && write_subcom(ctx, flywheelName ? flyFrames : NULL, flyCount, PDT_SUBCOM_HK, "-H", hkName))) {
         fclose(out);
         remove(outFileName);
         exit(1);
